@@ -11,10 +11,20 @@ points, 352x1216 image, 10 agent steps, fp32.  Inputs are resident in HBM before
       them itself (cmr_agent_amd/utils/launch.py).  `--dist-backend gloo --share-gpu` puts every rank on device 0: a rehearsal
       of the launcher, the barrier / MAX protocol and the bucket all-reduce on a one-GPU box (not a scaling number).
 
-Prints ONE JSON line (rank 0).  `roofline` = the dominant kernel (stride-1 3x3 NHWC convolution on
-fp32 MFMA): algorithmic FLOPs of its launches / their HIP-event time inside the timed region, against
-the 157.3 TFLOP/s fp32 matrix peak.  `cpu_baseline` = the oracle (CPU restatement pinned to the
-reference) on a bounded sample of the same workload on this box's host cores (rank 0, N=1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`) and nothing else is measured.
+
+  --full: everything beside the headline figure, as one line: `roofline` = the dominant kernel (stride-1 3x3
+      NHWC convolution on fp32 MFMA): algorithmic FLOPs of its launches / their HIP-event time in separate
+      eager passes, against the 157.3 TFLOP/s fp32 matrix peak; `pipelined`; `cpu_baseline` = the oracle (CPU
+      restatement pinned to the reference) on a bounded sample of the same workload on the host cores (rank 0,
+      N=1 only); and at N=1 the other BASELINE configurations as sub-objects (`c3`, `c1_bf16`, `train`,
+      `train_geo`, `train_geo_160x512`).  In the --mode train / train-geo / iter lines: their roofline pass and
+      CPU baseline.
+  --dump-outputs DIR: after the timed steps, rank 0 writes what the timed path returned in its LAST step as
+      DIR/<name>.npy (float32; integer outputs as float64; a fixed seeded sample of anything larger than 2**20
+      elements), for output-for-output comparison of two builds (inputs and weights are seeded: identical from
+      run to run with the same arguments).
 """
 import argparse
 import json
@@ -77,18 +87,55 @@ def load_models(cfg, dev):
     return geo.to(dev).eval(), agent.to(dev).eval(), spec
 
 
-def registration_step(geo, agent, cfg, batch):
-    """Test_Agent.py:150-187 for one batch (inputs already on the device)."""
+def registration_step(geo, agent, cfg, batch, last=None):
+    """Test_Agent.py:150-187 for one batch (inputs already on the device).  `last` (a list), when given, receives the logits / value of
+    the last agent step, as RegistrationGraph.static_last holds them."""
     data = dict(batch)
     geo(data)
     pose, target = env.init(data)
     target = env.to_disentangled(target, data['pc'], data=data)
     for _ in range(cfg.action_num):
         s2, s3 = env.observation_from_a_pose(data, pose, materialize_state_2d=False)
-        r, t, _ = agent(s2, s3)
+        r, t, v = agent(s2, s3)
         ar, at = agent.action_from_logits(r, t, deterministic=True)
         pose = env.step(ar, at, pose, cfg)
+    if last is not None:
+        last[:] = [r, t, v]
     return pose.cpu()                                   # final pose D2H (Test_Agent.py:185)
+
+
+DUMP_SAMPLE = 1 << 20                   # elements kept of an output larger than this (fixed, seeded sample)
+
+
+def host_arrays(prefix, obj, out=None):
+    """Tensors / arrays / numbers in `obj` (nested dicts, lists, tuples) -> {name: numpy array} on the host, float32 (float64 for integer
+    and float64 outputs), copied now: the device buffers they come from may be overwritten by what runs next."""
+    out = {} if out is None else out
+    if isinstance(obj, dict):
+        for k, v in obj.items():
+            host_arrays("%s_%s" % (prefix, k) if prefix else str(k), v, out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            host_arrays("%s_%d" % (prefix, i), v, out)
+    elif torch.is_tensor(obj) or isinstance(obj, (np.ndarray, float, int)):
+        a = obj.detach().cpu().numpy() if torch.is_tensor(obj) else np.asarray(obj)
+        wide = a.dtype.kind in "iub" or a.dtype == np.float64
+        out[prefix] = np.ascontiguousarray(a, dtype=np.float64 if wide else np.float32)
+    return out
+
+
+def dump_outputs(dirname, arrays):
+    """arrays ({name: ndarray}) -> dirname/<name>.npy; an array of more than DUMP_SAMPLE elements is replaced by a fixed seeded sample of
+    its flattened values (the same positions in every run of the same shape), so that the total stays far below 64 MB."""
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(20231016).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[idx]
+        total += a.nbytes
+        assert total <= 64 << 20, "--dump-outputs: more than 64 MB"
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def _cpu_model():
@@ -295,7 +342,7 @@ def agent_update_cpu_baseline(spec, w, MB, budget_s=14.0):
                        % (len(times), MB, ", ".join("%.2f" % t for t in times)))
 
 
-def train_main(args, ctx=None, with_cpu=False):
+def train_main(args, ctx=None, with_cpu=False, dump=None):
     """--mode train: the agent update of Train_Agent.py:263-305 at the headline map size.  One STEP =
     one minibatch of 10 buffered observations per GPU (the reference's PPO minibatch, Train_Agent.py:260) through
     cmr_agent_amd.train.AgentUpdate: train-mode forward, BC + PPO loss, HIP backward into the flat gradient bucket, ONE
@@ -317,9 +364,11 @@ def train_main(args, ctx=None, with_cpu=False):
     batch = agent_update_batch(MB, h, wd, w["N"], cfg.num_steps, g, dev)
     info = dist_info(ranks, args)
     up.step(batch)                          # untimed: first launches load code objects
-    with CallTimer() as ct:                 # eager, before the graph is captured: every C-ABI call of one update with its work
-        up.step(batch)
-        torch.cuda.synchronize()
+    ct = None
+    if args.full:
+        with CallTimer() as ct:             # eager, before the graph is captured: every C-ABI call of one update with its work
+            up.step(batch)
+            torch.cuda.synchronize()
     if not args.eager:
         up.enable_graph(batch)          # forward + backward replayed from a hipGraph; all-reduce and Adam launched per step
     for _ in range(args.warmup):
@@ -332,6 +381,8 @@ def train_main(args, ctx=None, with_cpu=False):
             ar_ms += up.allreduce_ms()
     ranks.barrier()
     elapsed = ranks.max_over_ranks(time.perf_counter() - t0)
+    if dump and ranks.rank == 0:
+        dump_outputs(dump, host_arrays("", {"losses": losses, "gradient_bucket": up.bucket.grads}))
     info.update(rank_facts(ranks, cfg.seed))
     assert torch.isfinite(losses).all()
     bucket_sum = float(up.bucket.grads.double().sum())     # identical on every rank after the all-reduce
@@ -375,14 +426,15 @@ def train_main(args, ctx=None, with_cpu=False):
             "allreduce_ms_per_step": ar_ms / args.steps if ranks.dist is not None else 0.0,
             "gradient_bucket_sum_min_max_over_ranks": sums, "gradient_buckets_identical": sums[0] == sums[-1],
             "conv_tflops_algorithmic": flops / (elapsed / args.steps) / 1e12,
-            "launches_per_step": sum(d["calls"] for d in ct.table()),
             "launch_mode": "eager" if args.eager else "hipGraph replay of forward + backward",
-            # every modelled entry point of the step competes for `dominant`: the named families above, and each remaining entry point on its own
-            "roofline": train_roofline(ct.table(), 1, families + [("%s (entry point)" % d["name"], (d["name"],),
-                                                                     BF16_MFMA_PEAK_TFLOPS if "bf16" in d["name"] else FP32_MFMA_PEAK_TFLOPS)
-                                                                    for d in ct.table() if d["modelled"] and not any(d["name"] in f[1] for f in families)],
-                                       1e3 * elapsed / args.steps, traffic_profile=_latest_profile("pmc_train.json")),
             "loss": float(losses[0]), **info}
+        if ct is not None:
+            line["launches_per_step"] = sum(d["calls"] for d in ct.table())
+            # every modelled entry point of the step competes for `dominant`: the named families above, and each remaining entry point on its own
+            line["roofline"] = train_roofline(ct.table(), 1, families + [("%s (entry point)" % d["name"], (d["name"],),
+                                                                            BF16_MFMA_PEAK_TFLOPS if "bf16" in d["name"] else FP32_MFMA_PEAK_TFLOPS)
+                                                                           for d in ct.table() if d["modelled"] and not any(d["name"] in f[1] for f in families)],
+                                              1e3 * elapsed / args.steps, traffic_profile=_latest_profile("pmc_train.json"))
         if with_cpu and world == 1:
             line["cpu_baseline"] = agent_update_cpu_baseline(spec, w, MB)
     return line
@@ -441,7 +493,7 @@ class GeoPrologue:
         return self.ev[0].elapsed_time(self.ev[1])
 
 
-def geo_train_main(args, ctx=None, with_cpu=False):
+def geo_train_main(args, ctx=None, with_cpu=False, dump=None):
     """--mode train-geo: the geometric-model update of Train_Geo.py:166-174.  Default shape = the reference's training
     configuration (KittiConfig: 160x512 crop, 40 960 points, batch 8 per GPU); `--img 352x1216 --num-pt 65536 --prologue` = SURVEY.md
     8d's C5 / BASELINE configs[4] with the on-device node sampling, nearest-node assignment and a ball query inside the timed step.
@@ -468,11 +520,13 @@ def geo_train_main(args, ctx=None, with_cpu=False):
         prologue(batch)
     info = dist_info(ranks, args)
     up.step(batch)                          # untimed: first launches load code objects
-    with CallTimer() as ct:                 # eager, before the graph is captured: every C-ABI call of one step with its work
-        if prologue is not None:
-            prologue(batch)
-        up.step(batch)
-        torch.cuda.synchronize()
+    ct = None
+    if args.full:
+        with CallTimer() as ct:             # eager, before the graph is captured: every C-ABI call of one step with its work
+            if prologue is not None:
+                prologue(batch)
+            up.step(batch)
+            torch.cuda.synchronize()
     if not args.eager:
         up.enable_graph(batch)          # forward + backward replayed from a hipGraph; all-reduce and Adam launched per step
     ahead = prologue is not None and getattr(args, "prologue_ahead", False)
@@ -511,21 +565,13 @@ def geo_train_main(args, ctx=None, with_cpu=False):
             ar_ms += up.allreduce_ms()
     ranks.barrier()
     elapsed = ranks.max_over_ranks(time.perf_counter() - t0)
+    if dump and ranks.rank == 0:
+        dump_outputs(dump, host_arrays("", {"losses": losses, "gradient_bucket": up.bucket.grads}))
     info.update(rank_facts(ranks, cfg.seed))
     loss = float(losses["loss"])
     assert loss == loss
     line = None
     if ranks.rank == 0:
-        table = ct.table()
-        # entry points that launch the same kernel count as one candidate (the Winograd convolution with and without the BatchNorm sums)
-        same = [("cmr_conv3x3_wino_nhwc_f32", "cmr_conv3x3_wino_stats_nhwc_f32", "cmr_conv3x3_wino_bnbwd_nhwc_f32")]
-        group = lambda n: next((g for g in same if n in g), (n,))
-        tot = {}
-        for d in table:
-            if d["modelled"]:
-                tot[group(d["name"])] = tot.get(group(d["name"]), 0.0) + d["ms"]
-        dom_names = max(tot, key=tot.get)
-        dom = {"name": " / ".join(n for n in dom_names if any(d["name"] == n for d in table))}
         line = {
             "metric": "geometric-model update pairs/sec (Train_Geo.py step, %dx%d image, %d points%s)" % (
                 H, W, cfg.num_pt, ", node sampling + nearest node + ball query on the device inside the step" if prologue is not None else ""),
@@ -541,13 +587,24 @@ def geo_train_main(args, ctx=None, with_cpu=False):
                        "batch_per_gpu": B,
                        "parallelism": "data parallel: one flat-bucket RCCL all-reduce (%d floats) per optimizer step" % up.bucket.numel},
             "allreduce_ms_per_step": ar_ms / args.steps if ranks.dist is not None else 0.0,
-            "launches_per_step": sum(d["calls"] for d in table),
-            "roofline": train_roofline(table, 1, [("%s (the entry point with the largest summed time of the step)" % dom["name"],
-                                                   dom_names, FP32_MFMA_PEAK_TFLOPS)], 1e3 * elapsed / args.steps,
-                                       traffic_profile=_latest_profile("pmc_train_geo.json") if (H, W, cfg.num_pt) == (160, 512, 65536) else
-                                       (_latest_profile("pmc_train_geo_c5.json") if (H, W, cfg.num_pt) == (352, 1216, 65536) else None)),
             "launch_mode": "eager" if args.eager else "hipGraph replay of forward + backward",
             "loss": loss, **info}
+        if ct is not None:
+            table = ct.table()
+            # entry points that launch the same kernel count as one candidate (the Winograd convolution with and without the BatchNorm sums)
+            same = [("cmr_conv3x3_wino_nhwc_f32", "cmr_conv3x3_wino_stats_nhwc_f32", "cmr_conv3x3_wino_bnbwd_nhwc_f32")]
+            group = lambda n: next((g for g in same if n in g), (n,))
+            tot = {}
+            for d in table:
+                if d["modelled"]:
+                    tot[group(d["name"])] = tot.get(group(d["name"]), 0.0) + d["ms"]
+            dom_names = max(tot, key=tot.get)
+            dom = {"name": " / ".join(n for n in dom_names if any(d["name"] == n for d in table))}
+            line["launches_per_step"] = sum(d["calls"] for d in table)
+            line["roofline"] = train_roofline(table, 1, [("%s (the entry point with the largest summed time of the step)" % dom["name"],
+                                                          dom_names, FP32_MFMA_PEAK_TFLOPS)], 1e3 * elapsed / args.steps,
+                                              traffic_profile=_latest_profile("pmc_train_geo.json") if (H, W, cfg.num_pt) == (160, 512, 65536) else
+                                              (_latest_profile("pmc_train_geo_c5.json") if (H, W, cfg.num_pt) == (352, 1216, 65536) else None))
         if prologue is not None:
             line["prologue_ms"] = pro_ms / args.steps
             line["prologue"] = ("HIP events around planar_to_rows + fps + gather + nearest + ball_query + transpose of every timed step (inside ms_per_step)" +
@@ -561,7 +618,7 @@ def geo_train_main(args, ctx=None, with_cpu=False):
     return line
 
 
-def iter_main(args, ctx=None):
+def iter_main(args, ctx=None, dump=None):
     """--mode iter: one IterModel forward (models/IterModel.py:250-475) on the pair it is written for: 160x512 image (40x128
     maps), 729 sampled poses, BASELINE configs[1]'s 16 384 points.  One STEP = one forward on a batch dict as MultiHeadModel leaves it
     (synthetic features, hash-filled weights).  Replicas only across GPUs (the model handles one pair)."""
@@ -575,31 +632,41 @@ def iter_main(args, ctx=None):
     model = model.to(dev).eval()
     N = args.num_pt or 16384
     base = {k: v.to(dev) for k, v in synthetic.make_iter_batch("bench", N, 9, 0.2, 2.0).items()}
-    run = lambda: model(dict(base))
+
+    def run():
+        data = dict(base)
+        model(data)                 # returns 0 and leaves its outputs in the batch dict, as the reference's forward does
+        return data
     with torch.no_grad():
         for _ in range(args.warmup):
             run()
         ranks.barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            run()
+            out = run()
         ranks.barrier()
         elapsed = ranks.max_over_ranks(time.perf_counter() - t0)
-        with CallTimer() as ct:
-            run()
-            torch.cuda.synchronize()
+        if dump and ranks.rank == 0:
+            dump_outputs(dump, host_arrays("", {k: v for k, v in out.items() if base.get(k) is not v}))
+        ct = None
+        if args.full:
+            with CallTimer() as ct:
+                run()
+                torch.cuda.synchronize()
     line = None
     if ranks.rank == 0:
-        table = ct.table()
-        conv = [d for d in table if d["name"].startswith("cmr_conv3x3")]
-        cms, cfl = sum(d["ms"] for d in conv), sum(d["issued_flops"] for d in conv)
-        stages = {d["name"]: round(d["ms"], 3) for d in table}
-        line = ({
+        line = {
             "metric": "IterModel forwards/sec (729 sampled poses, 40x128 maps, %d points)" % N, "value": world * args.steps / elapsed,
             "unit": "cost-volume forwards/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
             "config": {"workload": "IterModel.forward on one pair: 160x512 image, %d points (60 %% selected), nlabel 9; hash-filled weights" % N,
-                       "parallelism": "replicas only (the model is written for one pair)"},
+                       "parallelism": "replicas only (the model is written for one pair)"}}
+    if ranks.rank == 0 and ct is not None:
+        table = ct.table()
+        conv = [d for d in table if d["name"].startswith("cmr_conv3x3")]
+        cms, cfl = sum(d["ms"] for d in conv), sum(d["issued_flops"] for d in conv)
+        stages = {d["name"]: round(d["ms"], 3) for d in table}
+        line.update({
             "roofline": {"kernel": "the nine 3x3 convolutions of cost_volume_convs as a batch of 729 maps (Winograd fp32 / bf16 two-team kernel)",
                          "bound": "mfma", "achieved": cfl / (cms * 1e-3) / 1e12, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": cfl / (cms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS, "traffic": None,
@@ -609,8 +676,9 @@ def iter_main(args, ctx=None):
     return line
 
 
-def register_main(args, ctx, workload="c1", dtype=None, with_cpu=True, with_pipeline=True, with_alone=True):
-    """The registration iteration of one workload (WORKLOADS) -> the JSON line (rank 0; None elsewhere)."""
+def register_main(args, ctx, workload="c1", dtype=None, with_cpu=True, with_pipeline=True, with_alone=True, full=True, dump=None):
+    """The registration iteration of one workload (WORKLOADS) -> the JSON line (rank 0; None elsewhere).  full=False: the headline only
+    (no pipelined line, no eager roofline passes, no CPU baseline).  dump: directory for the last timed step's outputs (rank 0)."""
     dev, ranks, world = ctx
     rank = ranks.rank
 
@@ -630,8 +698,9 @@ def register_main(args, ctx, workload="c1", dtype=None, with_cpu=True, with_pipe
     # The loop body is captured once into a hipGraph (cmr_agent_amd/runtime.py) and replayed per step;
     # --eager issues the same ~1000 launches from Python.  The conv timing events are recorded eagerly
     # in a separate (untimed) pass so that they do not sit inside the timed region's graph.
+    last = []                                           # logits / value of the last agent step of the last step run
     if args.eager:
-        run_step = lambda: registration_step(geo, agent, cfg, batch)
+        run_step = lambda: registration_step(geo, agent, cfg, batch, last)
     else:
         rg = (PipelinedRegistrationGraph if args.pipeline else RegistrationGraph)(geo, agent, cfg, batch)
         run_step = lambda: rg.run().cpu()
@@ -644,6 +713,11 @@ def register_main(args, ctx, workload="c1", dtype=None, with_cpu=True, with_pipe
             pose = run_step()
         barrier()
         elapsed = time.perf_counter() - t0
+        if dump and rank == 0:
+            # what the caller of the timed path receives from its last step: the final poses [B, 4, 4], and the rotation / translation
+            # logits and the value of the last agent step (static outputs of the replayed graph)
+            r, t, v = last if args.eager else rg.static_last
+            dump_outputs(dump, host_arrays("", {"pose": pose, "last_step_logits_r": r, "last_step_logits_t": t, "last_step_value": v}))
         # the same K steps through the two-stage software pipeline over consecutive batches (geo forward of batch i concurrently with
         # the agent loop of batch i - 1, one hipGraph): a throughput mode, reported BESIDE the headline (whose step is one batch's
         # geo forward + agent loop back to back)
@@ -655,7 +729,8 @@ def register_main(args, ctx, workload="c1", dtype=None, with_cpu=True, with_pipe
             return {"metric": "registration iters/sec (replay-only profiling run)", "value": ranks.aggregate_rate(w["B"] * args.steps, elapsed),
                     "unit": "registration iters/s", "ms_per_step": 1e3 * elapsed / args.steps, "steps": args.steps, "warmup": args.warmup,
                     "n_gpus": world, "dtype": dtype, "launch_mode": "hipGraph replay only"} if rank == 0 else None
-        if not args.eager and not args.pipeline and with_pipeline:
+        ct = ct1 = None
+        if full and not args.eager and not args.pipeline and with_pipeline:
             rgp = PipelinedRegistrationGraph(geo, agent, cfg, batch)
             for _ in range(args.warmup):
                 rgp.run().cpu()
@@ -666,14 +741,14 @@ def register_main(args, ctx, workload="c1", dtype=None, with_cpu=True, with_pipe
             barrier()
             pipe = (ranks.max_over_ranks(time.perf_counter() - t1), bool(torch.equal(pose_p, pose)))
             del rgp
-        with CallTimer() as ct:                          # HIP events around EVERY C-ABI call, with its algorithmic work
-            for _ in range(args.steps):
-                registration_step(geo, agent, cfg, batch)
-            torch.cuda.synchronize()
+        if full:
+            with CallTimer() as ct:                      # HIP events around EVERY C-ABI call, with its algorithmic work
+                for _ in range(args.steps):
+                    registration_step(geo, agent, cfg, batch)
+                torch.cuda.synchronize()
         # the same pass with every branch on ONE stream: each kernel's duration alone on the device (the pass above times a side-stream
         # kernel from its launch to its end, including the time it waits for CUs the concurrent convolution holds)
-        ct1 = None
-        if with_alone and not args.eager:
+        if full and with_alone and not args.eager:
             from cmr_agent_amd.utils import streams
             streams.ENABLED = False
             try:
@@ -688,8 +763,9 @@ def register_main(args, ctx, workload="c1", dtype=None, with_cpu=True, with_pipe
     info = dist_info(ranks, args)
     info.update(rank_facts(ranks, cfg.seed))
     line = None
+    iters = world * w["B"] * args.steps
 
-    if rank == 0:
+    if rank == 0 and ct is not None:
         table = ct.table()
         dom_names = ("cmr_conv3x3_bf16_nhwc_f32", "cmr_conv3x3_bf16io_nhwc") if dtype == "bf16" else ("cmr_conv3x3_wino_nhwc_f32",)
         doms = [d for d in table if d["name"] in dom_names]
@@ -735,7 +811,6 @@ def register_main(args, ctx, workload="c1", dtype=None, with_cpu=True, with_pipe
             else:
                 traffic_note = "stale profile, not reported (%s)" % why
         achieved = conv["flops"] / (conv["ms"] * 1e-3) / 1e12
-        iters = world * w["B"] * args.steps
         # the dominant kernel INSIDE the timed hipGraph replay: launch-weighted mean duration of the Winograd kernels in the committed
         # `rocprofv3 --kernel-trace --stats` summary of `bench.py --replay-only` (tools/r06_final.sh), priced with this run's FLOPs per launch.
         # This is the headline `roofline.frac` -- while the profile is fresh; otherwise the eager figure leads and says so.
@@ -833,6 +908,7 @@ def register_main(args, ctx, workload="c1", dtype=None, with_cpu=True, with_pipe
                                            "profiles/, fresh by content hash), not a counter read in this run", **common)
             if in_graph is not None:
                 roofline["avg_launch_us"] = in_graph["us"]          # the duration `frac` is computed from; the eager mean is avg_launch_us_eager
+    if rank == 0:
         line = {
             "metric": "registration iters/sec (%s %dx%d img + %d pts, 1 geo forward + %d agent steps)" % (
                 "KITTI" if w["cfg"] == "kitti" else "nuScenes", w["H"], w["W"], w["N"], w["steps"]),
@@ -842,7 +918,7 @@ def register_main(args, ctx, workload="c1", dtype=None, with_cpu=True, with_pipe
             "config": {"workload": w["name"] + (", fp32" if dtype == "f32" else ", bf16 3x3 convolutions (fp32 accumulate and storage, "
                                                 "everything else fp32)") + ", hash-filled weights", "batch_per_gpu": w["B"],
                        "parallelism": "batch sharding, no data-path collective"},
-            "agent_steps_per_s": iters * w["steps"] / elapsed, "roofline": roofline,
+            "agent_steps_per_s": iters * w["steps"] / elapsed, **({"roofline": roofline} if ct is not None else {}),
             "launch_mode": "eager" if args.eager else ("hipGraph replay, 2-stage software pipeline over consecutive batches (geo forward of "
                            "batch i || agent loop of batch i - 1)" if args.pipeline else "hipGraph replay"), **info,
         }
@@ -887,7 +963,7 @@ def geo_lines_in_child(args):
     env_c = dict(os.environ, ROC_CPU_WAIT_FOR_SIGNAL="0")
     for k in ("MASTER_ADDR", "MASTER_PORT", "RANK", "LOCAL_RANK", "WORLD_SIZE", "GROUP_RANK", "LOCAL_WORLD_SIZE"):
         env_c.pop(k, None)                        # world size 1: the child brings its own one-rank process group up (--force-dist)
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "train-geo", "--num-pt", "65536", "--steps", "5", "--warmup", "2"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "train-geo", "--num-pt", "65536", "--steps", "5", "--warmup", "2", "--full"]
     if args.dist_backend == "nccl" and not args.no_force_dist:
         base.append("--force-dist")
     out = []
@@ -916,6 +992,10 @@ def main():
     ap.add_argument("--mode", choices=("register", "train", "train-geo", "iter"), default="register",
                     help="register (default): the headline registration iteration; train: the agent's minibatch update; "
                          "train-geo: the geometric model's training step")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure: roofline passes, pipelined line, CPU baseline "
+                    "and (register mode at 1 GPU) the other BASELINE configurations as sub-objects; a plain run times the steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the outputs of the last timed step as "
+                    "DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--replay-only", action="store_true", help="register mode: warm-up and the timed hipGraph replays only (no pipelined line, no "
                     "eager HIP-event passes, no roofline): the command `rocprofv3 --kernel-trace --stats` is run on for roofline.frac_in_graph")
@@ -949,7 +1029,8 @@ def main():
     if args.mode != "register":
         fn = {"train": train_main, "train-geo": geo_train_main, "iter": iter_main}[args.mode]
         ctx = setup_ranks(args)
-        line = fn(args, ctx, with_cpu=not args.no_cpu_baseline) if args.mode != "iter" else iter_main(args, ctx)
+        line = (fn(args, ctx, with_cpu=args.full and not args.no_cpu_baseline, dump=args.dump_outputs) if args.mode != "iter" else
+                iter_main(args, ctx, dump=args.dump_outputs))
         if line is not None:
             print(json.dumps(line), flush=True)
         ctx[1].close()
@@ -958,9 +1039,10 @@ def main():
     ctx = setup_ranks(args)          # RCCL: timing barrier / MAX only, no data-path collective
     dev, ranks, world = ctx
     rank = ranks.rank
-    line = register_main(args, ctx, args.workload, args.dtype, with_cpu=not args.no_cpu_baseline, with_pipeline=not args.no_pipeline_line,
-                         with_alone=not args.no_alone_pass)
-    if world == 1 and args.workload == "c1" and not args.no_train_lines and not args.replay_only and args.dtype is None:
+    line = register_main(args, ctx, args.workload, args.dtype, with_cpu=args.full and not args.no_cpu_baseline,
+                         with_pipeline=not args.no_pipeline_line, with_alone=not args.no_alone_pass, full=args.full, dump=args.dump_outputs)
+    if (args.full and world == 1 and args.workload == "c1" and not args.no_train_lines and not args.replay_only
+            and args.dtype is None):
         # The other BASELINE.json configurations at 1 GPU, each with its own roofline, folded into the default line so that the driver's
         # record carries them: configs[3] (`c3`: nuScenes shape, bf16), configs[2] (`train`: per-GPU bf16 agent update), configs[4] as
         # SURVEY.md 8d's C5 (`train_geo`: Train_Geo step at 352x1216 / 65 536 points with the point prologue inside the step) and the same

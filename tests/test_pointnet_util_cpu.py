@@ -1,16 +1,15 @@
 """CPU tier: the host-side / view-only members of models/pointnet_util.py that the package exports by the reference's names
-(pc_normalize :12-17, sample_and_group_all :136-153) -- against the imported reference where /root/reference exists (authoring container),
-against their definitions everywhere."""
+(pc_normalize :12-17, sample_and_group_all :136-153) -- against their definitions and against the reference's own outputs on the same
+inputs (tests/golden/pointnet_util_host.npz, tests/golden/make_golden_pointnet_util_host.py)."""
 import os
 import sys
 
 import numpy as np
-import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from cmr_agent_amd.models import pointnet_util as PU  # noqa: E402
 
@@ -39,20 +38,16 @@ def test_pc_normalize_and_sample_and_group_all_by_definition():
 
 
 def test_against_the_imported_reference():
-    import ref_harness
-    if not ref_harness.reference_available():
-        pytest.skip("/root/reference is not on this box")
-    ref_harness.install_stubs() if hasattr(ref_harness, "install_stubs") else None
-    sys.path.insert(0, ref_harness.REF_ROOT)
-    try:
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("_ref_pointnet_util", os.path.join(ref_harness.REF_ROOT, "models", "pointnet_util.py"))
-        R = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(R)
-    finally:
-        sys.path.remove(ref_harness.REF_ROOT)
+    """The reference's own pc_normalize / sample_and_group_all on the same inputs, as tests/golden/make_golden_pointnet_util_host.py
+    recorded them (pointnet_util_host.npz): bit for bit."""
+    import golden_util as G
+    fx = G.load_case("pointnet_util_host")
     xyz, pts = _inputs()
-    assert np.array_equal(PU.pc_normalize(xyz[1].numpy()), R.pc_normalize(xyz[1].numpy()))
-    for p in (pts, None):
-        a, b = PU.sample_and_group_all(xyz, p), R.sample_and_group_all(xyz, p)
-        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    got = {"pc_normalize": PU.pc_normalize(xyz[1].numpy())}
+    for tag, p in (("pts", pts), ("none", None)):
+        got["sample_and_group_all_%s_xyz" % tag], got["sample_and_group_all_%s_points" % tag] = PU.sample_and_group_all(xyz, p)
+    assert sorted(got) == sorted(fx)
+    for name, a in got.items():
+        a = a.numpy() if torch.is_tensor(a) else np.asarray(a)
+        assert tuple(fx[name]["shape"]) == a.shape and fx[name]["stride"] == 1, name
+        assert fx[name]["sample"].dtype == a.dtype and np.array_equal(fx[name]["sample"], a.reshape(-1)), name

@@ -2,7 +2,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/ab2d; rm -rf $O; mkdir -p $O
 for v in 0 1; do
   export CMR_AGENT_LAZY_2D=$v
-  rocprofv3 --kernel-trace --stats -d $O/v$v --output-format csv -- python3 $R/bench.py --mode train --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline > $O/v$v.json 2> $O/v$v.err
+  rocprofv3 --kernel-trace --stats -d $O/v$v --output-format csv -- python3 $R/bench.py --full --mode train --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline > $O/v$v.json 2> $O/v$v.err
   cp $O/v$v/*/*kernel_stats.csv $O/stats_$v.csv
 done
 python3 - <<PY

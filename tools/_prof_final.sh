@@ -5,9 +5,9 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_final
 rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats -d $O/f32 --output-format csv -- python3 $R/bench.py --no-cpu-baseline > $O/bench_f32_under_rocprof.json 2> $O/f32.err
+rocprofv3 --kernel-trace --stats -d $O/f32 --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline > $O/bench_f32_under_rocprof.json 2> $O/f32.err
 echo f32 done
-rocprofv3 --kernel-trace --stats -d $O/bf16 --output-format csv -- python3 $R/bench.py --dtype bf16 --no-cpu-baseline > $O/bench_bf16_under_rocprof.json 2> $O/bf16.err
+rocprofv3 --kernel-trace --stats -d $O/bf16 --output-format csv -- python3 $R/bench.py --full --dtype bf16 --no-cpu-baseline > $O/bench_bf16_under_rocprof.json 2> $O/bf16.err
 echo bf16 done
 cp $O/f32/*/*kernel_stats.csv $O/kernel_stats_f32.csv
 cp $O/bf16/*/*kernel_stats.csv $O/kernel_stats_bf16.csv

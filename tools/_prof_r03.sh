@@ -6,9 +6,9 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_r03
 rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats -d $O/reg --output-format csv -- python3 $R/bench.py --no-train-lines --no-pipeline-line --no-cpu-baseline > $O/bench_register_only_under_rocprof.json 2> $O/reg.err
+rocprofv3 --kernel-trace --stats -d $O/reg --output-format csv -- python3 $R/bench.py --full --no-train-lines --no-pipeline-line --no-cpu-baseline > $O/bench_register_only_under_rocprof.json 2> $O/reg.err
 echo reg done
-rocprofv3 --kernel-trace --stats -d $O/full --output-format csv -- python3 $R/bench.py > $O/bench_default_under_rocprof.json 2> $O/full.err
+rocprofv3 --kernel-trace --stats -d $O/full --output-format csv -- python3 $R/bench.py --full > $O/bench_default_under_rocprof.json 2> $O/full.err
 echo full done
 cp $O/reg/*/*kernel_stats.csv $O/kernel_stats_register_only.csv
 cp $O/full/*/*kernel_stats.csv $O/kernel_stats_default_command.csv

@@ -2,10 +2,11 @@
 # round 3: secondary bench lines (bf16 mode, configs[3] shape, train modes, iter) -> gpurun_out/r03_bench_*.json
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
-run() { name=$1; shift; timeout -k 10 400 python bench.py "$@" > gpurun_out/r03_bench_$name.json 2> gpurun_out/r03_bench_$name.err; echo "$name rc=$?"; python - <<EOF2
+OUT=${OUT:-out}; mkdir -p "$OUT"
+run() { name=$1; shift; timeout -k 10 400 python bench.py --full "$@" > "$OUT"/r03_bench_$name.json 2> "$OUT"/r03_bench_$name.err; echo "$name rc=$?"; python - <<EOF2
 import json
 try:
-    d=json.loads(open("gpurun_out/r03_bench_$name.json").read().strip().splitlines()[-1]); r=d.get("roofline",{})
+    d=json.loads(open("$OUT/r03_bench_$name.json").read().strip().splitlines()[-1]); r=d.get("roofline",{})
     print("   ", round(d["value"],1), d["unit"], round(d["ms_per_step"],3), "ms; frac", round(r.get("frac",0),3), r.get("bound"), "path", round(r.get("path",0),3), "pipelined", (d.get("pipelined") or {}).get("value"))
 except Exception as e: print("   ERR", e)
 EOF2

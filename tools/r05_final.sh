@@ -11,7 +11,7 @@ rm -rf $O; mkdir -p $O
 SECONDS=0
 prof() {   # prof <tag> <bench args...>
   tag=$1; shift
-  ( cd /tmp && rocprofv3 --kernel-trace --stats -d $O/$tag --output-format csv -- python3 $R/bench.py "$@" > $O/bench_${tag}_under_rocprof.json 2> $O/$tag.err ) && echo "$tag done at ${SECONDS}s"
+  ( cd /tmp && rocprofv3 --kernel-trace --stats -d $O/$tag --output-format csv -- python3 $R/bench.py --full "$@" > $O/bench_${tag}_under_rocprof.json 2> $O/$tag.err ) && echo "$tag done at ${SECONDS}s"
   cp $O/$tag/*/*kernel_stats.csv $O/kernel_stats_$tag.csv && rm -rf $O/$tag
 }
 prof replay_only --replay-only --no-cpu-baseline
@@ -23,5 +23,6 @@ timeout -k 10 300 python tools/phases.py sub > gpurun_out/r05_phases_f32.txt 2> 
 cat gpurun_out/r05_phases_f32.txt
 # the default line LAST: it reads profiles/r05_kernel_stats_replay_only.csv (copied there by the author from the run above) for frac_in_graph
 cp $O/kernel_stats_replay_only.csv profiles/r05_kernel_stats_replay_only.csv 2> /dev/null
-timeout -k 10 500 python bench.py > gpurun_out/r05_bench_default.json 2> gpurun_out/r05_bench_default.err; echo "default rc=$? at ${SECONDS}s"
+OUT=${OUT:-out}; mkdir -p "$OUT"
+timeout -k 10 500 python bench.py --full > "$OUT"/r05_bench_default.json 2> "$OUT"/r05_bench_default.err; echo "default rc=$? at ${SECONDS}s"
 ls -la $O

@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 6: final artefacts, part 2 (in the container, after `gpurun -- bash tools/r06_final.sh` merged its files into gpurun_out/): copy
 # them to profiles/r06_* and write the freshness sidecars bench.py checks (tools/profile_meta.py: content hashes of the sources each
-# profile depends on).  Then part 3: gpurun -- 'python bench.py > gpurun_out/r06_bench_default.json 2> gpurun_out/r06_bench_default.err'.
+# profile depends on).  Then part 3, on the GPU box: python bench.py --full > <output directory>/r06_bench_default.json.
 cd "$(dirname "$0")/.."
 G=gpurun_out; P=profiles
 for t in replay_only register_only; do

@@ -3,7 +3,7 @@
 # (b) the registration part of the default command, (c) the agent update, (d) the geometric update (160x512 and the C5 shape); phases; the
 # PMC passes (FETCH_SIZE / WRITE_SIZE, separate runs) behind every roofline.traffic of the driver line.  Everything lands in gpurun_out/;
 # tools/r06_collect.sh (part 2, here in the container) copies it to profiles/r06_* and writes the freshness sidecars; part 3 is the
-# default line: gpurun -- 'python bench.py > gpurun_out/r06_bench_default.json'.
+# default line, on the GPU box: python bench.py --full > <output directory>/r06_bench_default.json.
 #   gpurun --timeout 1200 -- 'bash tools/r06_final.sh'
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
@@ -14,7 +14,7 @@ rm -rf $O; mkdir -p $O
 SECONDS=0
 prof() {   # prof <tag> <bench args...>
   tag=$1; shift
-  ( cd /tmp && rocprofv3 --kernel-trace --stats -d $O/$tag --output-format csv -- python3 $R/bench.py "$@" > $O/bench_${tag}_under_rocprof.json 2> $O/$tag.err ) && echo "$tag done at ${SECONDS}s"
+  ( cd /tmp && rocprofv3 --kernel-trace --stats -d $O/$tag --output-format csv -- python3 $R/bench.py --full "$@" > $O/bench_${tag}_under_rocprof.json 2> $O/$tag.err ) && echo "$tag done at ${SECONDS}s"
   cp $O/$tag/*/*kernel_stats.csv $O/kernel_stats_$tag.csv && rm -rf $O/$tag
 }
 prof replay_only --replay-only --no-cpu-baseline &&
