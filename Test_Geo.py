@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Evaluation of the geometric model with the reference's structure and output (Test_Geo.py:29-132: `python Test_Geo.py --dataset
+kitti|nuscenes`), running the HIP path.
+
+Per pair: the overlap head's precision / recall against pc_mask (computed by forward when the batch carries labels), the inlier ratio of
+the nearest-feature matches of the ground-truth overlap points (IR, cal_match_accuracy), of the predicted overlap points (IR1) and of
+those predicted points whose matched pixel is predicted to overlap too (IR2); a match is an inlier within 3 px of the projected point at
+1/4 scale.  All three come from one cmr_feat_match_f32 launch per batch and ratio (per sample, then averaged over the pairs as the
+reference's lists are).  The last line is the reference's: pc_overlap_precision pc_overlap_recall IR IR1 IR2.
+
+Left out: the reference's IterModel call (:56-62, 79).  No number printed depends on it, and it needs label keys (R_amplitude,
+label_R, ...) that no loader emits.
+
+Pairs come from the synthetic generator (cmr_agent_amd.utils.synthetic) unless --data-root names a dataset in the reference's layout
+(its 'test' split), and the weights are the deterministic hash fill unless --geo-ckpt points at a reference-format state_dict."""
+import argparse
+import itertools
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from cmr_agent_amd import ops  # noqa: E402
+from cmr_agent_amd.config import KittiConfiguration, NuScenesConfiguration  # noqa: E402
+from cmr_agent_amd.dataset.sampling import hip_fps, hip_nearest  # noqa: E402
+from cmr_agent_amd.models import MultiHeadModel  # noqa: E402
+from cmr_agent_amd.models.MultiHeadModel import match_features  # noqa: E402
+from cmr_agent_amd.utils import hashfill, synthetic  # noqa: E402
+from cmr_agent_amd.utils.checkpoint import load_checked  # noqa: E402
+
+
+def _ratios(counts):
+    c = counts.double().cpu().numpy()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return c[:, 1] / c[:, 0], c[:, 3] / c[:, 2]              # IR1, IR2 per sample (0 / 0 = NaN, as torch)
+
+
+def main():
+    ap = argparse.ArgumentParser(description='Image to point Registration: geometric model matching (MI355X HIP path)')
+    ap.add_argument('--dataset', type=str, default='kitti', help=" 'kitti' or 'nuscenes' ")
+    ap.add_argument('--pairs', type=int, default=4, help="number of (image, cloud) pairs")
+    ap.add_argument('--batch-size', type=int, default=1)
+    ap.add_argument('--num-pt', type=int, default=None)
+    ap.add_argument('--img', type=str, default=None, help="HxW network input size (multiples of 32), default from the config")
+    ap.add_argument('--geo-ckpt', default=None)
+    ap.add_argument('--data-root', default=None, help="dataset root in the reference's on-disk layout (cmr_agent_amd/dataset/loader.py): the 'test' split; "
+                    "default: the synthetic generator")
+    args = ap.parse_args()
+    dev = torch.device("cuda")
+    Cfg = {"kitti": KittiConfiguration, "nuscenes": NuScenesConfiguration}[args.dataset]
+    kw = {}
+    if args.img:
+        kw["cropped_img_H"], kw["cropped_img_W"] = (int(v) for v in args.img.lower().split("x"))
+    config = Cfg(num_pt=args.num_pt, device=dev, data_root=args.data_root, **kw)
+    spec = json.load(open(os.path.join(ROOT, "tests", "golden", "specs.json")))
+    geo_model = MultiHeadModel(config)
+    load_checked(geo_model, torch.load(args.geo_ckpt) if args.geo_ckpt else hashfill.make_state_dict(spec["geo"], "geo4/"))
+    geo_model = geo_model.to(dev).eval()
+
+    bs, nbatch = args.batch_size, (args.pairs + args.batch_size - 1) // args.batch_size
+    prec, rec, ir, ir1, ir2 = [], [], [], [], []
+    with torch.no_grad():
+        if args.data_root:
+            from cmr_agent_amd.dataset import FrameDataset, FrameLoader
+            batches = itertools.islice(iter(FrameLoader(FrameDataset(args.data_root, config, 'test', device=dev), bs, shuffle=False)), nbatch)
+        else:
+            batches = (synthetic.make_batch(bs, config.num_pt, config.cropped_img_H, config.cropped_img_W, config.num_node, hip_fps(dev),
+                                            hip_nearest(dev), seed=config.seed + i, n_circle=16, device=dev) for i in range(nbatch))
+        for data in batches:
+            geo_model(data)
+            if 'pc_overlap_precision' in data:
+                prec.append(float(data['pc_overlap_precision']))
+                rec.append(float(data['pc_overlap_recall']))
+            geo_model.geo_head.cal_match_accuracy(data)
+            ir.extend(data['matching_ir_per_sample'].double().cpu().numpy().tolist())
+            img_overlap = ops.softmax2(data['_cmr']["img_overlap_logits"])[1]           # img_overlap_logits.argmax(0), Test_Geo.py:88
+            _, _, counts, _ = match_features(data, data['pc_overlap_pred'], img_overlap=img_overlap)
+            r1, r2 = _ratios(counts)
+            ir1.extend(r1.tolist())
+            ir2.extend(r2.tolist())
+            print(np.mean(r1), np.mean(r2))
+
+    mean = lambda v: float(np.mean(v)) if v else float("nan")
+    print(mean(prec), mean(rec), mean(ir), mean(ir1), mean(ir2))
+
+
+if __name__ == '__main__':
+    main()

@@ -84,6 +84,50 @@ class OverlapDetectionHead(_Head):
         return self.finish_cl(cl, *self.trunk_cl(cl))
 
 
+MATCH_INLIER_THRES = 3.0       # pixels at 1/4 scale (MultiHeadModel.py:212, 313; Test_Geo.py:75)
+
+
+def point_xy_float_all(K, pc_in_cam_space):
+    """Projected point coordinates [B, 2, N] at 1/4 scale, before rounding (KittiDataset.py:313-316: (K pc)[0:2] / (K pc)[2]), for batches
+    that do not carry 'point_xy_float_all' (no loader emits it).  K [B, 3, 3] or [3, 3], pc_in_cam_space [B, 3, N]; any device.  Points
+    at or behind the camera (z <= 0) divide like the reference: their coordinates are far off or non-finite and never score an inlier."""
+    K = K.float()
+    pc_ = torch.matmul(K if K.dim() == 3 else K.unsqueeze(0), pc_in_cam_space.float())
+    return (pc_[:, 0:2, :] / pc_[:, 2:3, :]).contiguous()
+
+
+def _gt_xy(data_batch, dev):
+    xy = data_batch.get('point_xy_float_all')
+    if xy is None:
+        xy = point_xy_float_all(data_batch['K'].to(dev), data_batch['pc_in_cam_space'].to(dev))
+    return xy.to(dev, torch.float32).contiguous()
+
+
+def match_features(data_batch, mask, img_overlap=None, want_dist=False):
+    """ops.feat_match on the batch's geometric features: the '_cmr' rows of the last forward when present (no transpose copy), else the
+    public [B,64,N] / [B,64,h,w] tensors; ground-truth xy from 'point_xy_float_all' or derived from K and pc_in_cam_space.
+    -> (idx int32 [B, N], dist or None, counts int32 [B, 4], w)."""
+    cl = data_batch.get('_cmr')
+    if cl is not None and 'pc_geo_feat' in cl and 'img_geo_feat' in cl:
+        pc, img = cl['pc_geo_feat'].contiguous(), cl['img_geo_feat'].contiguous()
+    else:
+        pcb, imb = data_batch['pc_geo_feat'], data_batch['img_geo_feat']
+        pc = pcb.permute(0, 2, 1).reshape(-1, pcb.shape[1]).contiguous()
+        img = imb.permute(0, 2, 3, 1).contiguous()
+    B, h, w, _ = img.shape
+    N = pc.shape[0] // B
+    dev = pc.device
+    xy = _gt_xy(data_batch, dev)
+    idx, dist, counts = ops.feat_match(pc, img, mask.to(dev).contiguous(), gt_xy=xy, thr=MATCH_INLIER_THRES, img_overlap=img_overlap,
+                                       want_dist=want_dist)
+    return idx.view(B, N), dist, counts, w
+
+
+def _ratio(counts, num, den):
+    c = counts.float()
+    return c[:, num] / c[:, den]                                 # 0 / 0 = NaN, as right.sum() / right.shape[0] on an empty selection
+
+
 class GeometricDistanceHead(_Head):
     def __init__(self, config):
         f = config.embed_dim
@@ -97,6 +141,16 @@ class GeometricDistanceHead(_Head):
 
     def forward_cl(self, cl):
         return self.finish_cl(cl, *self.trunk_cl(cl))
+
+    def cal_match_accuracy(self, data_batch):
+        """MultiHeadModel.py:180-216: inlier ratio of the nearest-feature matches of the ground-truth overlap points (pc_mask), threshold
+        3 px.  Sets 'matching_ir' (0-d, sample 0, as the reference) and -- port extension, one launch scores the whole batch --
+        'matching_ir_per_sample' [B].  Not called by forward (the reference's call site, :270, is commented out)."""
+        with torch.no_grad():
+            _, _, counts, _ = match_features(data_batch, data_batch['pc_mask'])
+            ir = _ratio(counts, 1, 0)
+            data_batch['matching_ir_per_sample'] = ir
+            data_batch['matching_ir'] = ir[0]
 
 
 _EYE4 = {}
@@ -120,6 +174,23 @@ class MultiHeadModel(Planned):
 
     def _build_plan(self):
         return {}
+
+    def cal_matcning_ground_truth(self, data_batch):
+        """MultiHeadModel.py:285-315 (the name is the reference's): nearest-feature matches of the predicted overlap points
+        ('pc_overlap_pred').  Sets, for sample 0, 'feat_matching_centers' [2, n_sel] (x, y of the matched pixels) and
+        'inlier_matching_ground_truth' [n_sel] bool (within 3 px of the projected point); port extension: 'matching_ir_per_sample' [B]
+        for this mask.  Not called by forward, as in the reference."""
+        with torch.no_grad():
+            mask = data_batch['pc_overlap_pred']
+            idx, _, counts, w = match_features(data_batch, mask)
+            dev = idx.device
+            sel = mask[0].to(dev).bool()
+            p = idx[0][sel].long()
+            centers = torch.stack([p % w, torch.div(p, w, rounding_mode='floor')]).float()
+            gt = _gt_xy(data_batch, dev)[0][:, sel]
+            data_batch['feat_matching_centers'] = centers
+            data_batch['inlier_matching_ground_truth'] = torch.sqrt(torch.sum((centers - gt) ** 2, dim=0)) <= MATCH_INLIER_THRES
+            data_batch['matching_ir_per_sample'] = _ratio(counts, 1, 0)
 
     def forward_cl(self, data_batch):
         cl = self.encoder_decoder.forward_cl(data_batch)

@@ -893,6 +893,50 @@ def circle_loss(pc_feat_rows, img_feat_nhwc, pc_idx, xy_int, xy_float, B, N, dis
     return out
 
 
+def feat_match(pc_feat_rows, img_feat_nhwc, mask, gt_xy=None, thr=3.0, img_overlap=None, want_dist=False):
+    """Nearest pixel feature of every selected point (include/cmr_hip.h cmr_feat_match_f32): pc_feat rows [B*N, 64], img_feat NHWC
+    [B, h, w, 64] (both contiguous float32), mask [B, N] / [B*N] of bool / uint8 / int64 (non-zero = selected); optional gt_xy float32
+    [B, 2, N] with threshold thr, optional img_overlap bool / uint8 [B, h, w] / [B*h*w].
+    -> (idx int32 [B*N]: pixel p = y * w + x or -1, dist float32 [B*N] or None, counts int32 [B, 4] = (selected, inliers, selected whose
+    pixel is in img_overlap, both))."""
+    if pc_feat_rows.dim() != 2 or img_feat_nhwc.dim() != 4:
+        raise ValueError("feat_match: point rows must be 2-D [B*N, C] and pixel features 4-D [B, h, w, C], got %s / %s" % (
+            tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
+    B, h, w, C = img_feat_nhwc.shape
+    if C != 64 or pc_feat_rows.shape[1] != 64:
+        raise ValueError("feat_match: feature width must be 64, got %d / %d" % (pc_feat_rows.shape[1], C))
+    if pc_feat_rows.dtype != f32 or img_feat_nhwc.dtype != f32:
+        raise ValueError("feat_match: features must be float32, got %s / %s" % (pc_feat_rows.dtype, img_feat_nhwc.dtype))
+    if B < 1 or B > GRID_Y_MAX or pc_feat_rows.shape[0] % B:
+        raise ValueError("feat_match: %d point rows do not split into %d samples (1 <= B <= %d)" % (pc_feat_rows.shape[0], B, GRID_Y_MAX))
+    N = pc_feat_rows.shape[0] // B
+    if mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N:
+        raise ValueError("feat_match: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (B * N, mask.dtype, tuple(mask.shape)))
+    if gt_xy is not None and (gt_xy.dtype != f32 or tuple(gt_xy.shape) != (B, 2, N)):
+        raise ValueError("feat_match: gt_xy must be float32 [%d, 2, %d], got %s %s" % (B, N, gt_xy.dtype, tuple(gt_xy.shape)))
+    if img_overlap is not None and (img_overlap.dtype not in (torch.bool, torch.uint8) or img_overlap.numel() != B * h * w):
+        raise ValueError("feat_match: img_overlap must be bool / uint8 with %d elements, got %s %s" % (
+            B * h * w, img_overlap.dtype, tuple(img_overlap.shape)))
+    ts = [t for t in (pc_feat_rows, img_feat_nhwc, mask, gt_xy, img_overlap) if t is not None]
+    if not all(t.is_cuda and t.is_contiguous() and t.device == pc_feat_rows.device for t in ts):
+        raise ValueError("feat_match: every tensor must be a contiguous tensor on the same GPU")
+    if pc_feat_rows.data_ptr() % 16 or img_feat_nhwc.data_ptr() % 16:
+        raise ValueError("feat_match: feature rows must be 16-byte aligned")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    if img_overlap is not None and img_overlap.dtype == torch.bool:
+        img_overlap = img_overlap.view(torch.uint8)
+    dev = pc_feat_rows.device
+    idx = torch.empty((B * N,), dtype=torch.int32, device=dev)
+    dist = torch.empty((B * N,), dtype=f32, device=dev) if want_dist else None
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    nb = _lib.load().cmr_feat_match_workspace_bytes(B, N)
+    ws = _ws(nb, dev)
+    _lib.call("cmr_feat_match_f32", _p(pc_feat_rows), _p(img_feat_nhwc), C, B, N, h, w, _p(mask), mask.element_size(), _p(gt_xy),
+              float(thr), _p(img_overlap), _p(idx), _p(dist), _p(counts), _p(ws), nb, _stream())
+    return idx, dist, counts
+
+
 def expert_action(pose_source, pose_target, r_steps, t_steps, six_dof):
     """-> (action_r int64 [B, 1|3], action_t int64 [B, 2|3]); the step tables are float64 device tensors."""
     B = pose_source.shape[0]

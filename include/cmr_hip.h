@@ -334,6 +334,18 @@ int cmr_circle_loss_f32(const float* pc_feat, const float* img_feat, const int64
                         float neg_margin, float log_scale, float lambda, float* out, void* workspace, int64_t workspace_bytes,
                         hipStream_t stream);
 
+/* Match evaluation of the geometric features (MultiHeadModel.py:180-216 cal_match_accuracy, :285-315 cal_matcning_ground_truth,
+ * Test_Geo.py:91-122): for every selected point the nearest pixel feature in L2, argmin over the sample's h*w pixels, ties to the lower
+ * pixel index (torch.argmin).  pc_feat rows [B*N][C], img_feat [B][h*w][C] (NHWC), C must be 64; mask [B*N] with mask_bytes 1 (u8 /
+ * bool) or 8 (int64), non-zero = selected.  idx int32 [B*N] = pixel p (x = p % w, y = p / w) or -1 on unselected rows; dist (optional)
+ * f32 [B*N] = the minimum distance (NaN on unselected rows).  counts int32 [B][4] = {selected, selected with |xy(p) - gt_xy| <= thr,
+ * selected whose pixel has img_overlap != 0, both}; gt_xy (optional) f32 [B][2][N] (x row, y row; non-finite is never an inlier),
+ * img_overlap (optional) u8 [B*h*w].  Workspace: cmr_feat_match_workspace_bytes(B, N). */
+int64_t cmr_feat_match_workspace_bytes(int B, int N);
+int cmr_feat_match_f32(const float* pc_feat, const float* img_feat, int C, int B, int N, int h, int w, const void* mask, int mask_bytes,
+                       const float* gt_xy, float thr, const uint8_t* img_overlap, int32_t* idx, float* dist, int32_t* counts,
+                       void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 /* ---- rollout ops of the training loop ---------------------------------------- */
 
 /* environment.py:143-176 (expert): residual pose target * source^-1 -> extrinsic-xyz Euler angles (folded back when the
