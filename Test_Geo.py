@@ -11,6 +11,11 @@ reference's lists are).  The last line is the reference's: pc_overlap_precision 
 Left out: the reference's IterModel call (:56-62, 79).  No number printed depends on it, and it needs label keys (R_amplitude,
 label_R, ...) that no loader emits.
 
+--pnp (port extension): also the camera pose from those IR2 matches alone, PnP inside RANSAC
+(MultiHeadModel.pose_from_matches), scored per pair like Test_Agent.py (both poses through env.to_disentangled, get_P_diff; one line
+"RTE RRE" per pair), then Test_Agent.py's closing lines: registration recall (RTE < 5 and RRE < 10) and the RTE / RRE mean and std of the
+recalled pairs.  Without the flag the output is unchanged.
+
 Pairs come from the synthetic generator (cmr_agent_amd.utils.synthetic) unless --data-root names a dataset in the reference's layout
 (its 'test' split), and the weights are the deterministic hash fill unless --geo-ckpt points at a reference-format state_dict."""
 import argparse
@@ -28,6 +33,7 @@ import torch  # noqa: E402
 from cmr_agent_amd import ops  # noqa: E402
 from cmr_agent_amd.config import KittiConfiguration, NuScenesConfiguration  # noqa: E402
 from cmr_agent_amd.dataset.sampling import hip_fps, hip_nearest  # noqa: E402
+from cmr_agent_amd.environment import environment as env  # noqa: E402
 from cmr_agent_amd.models import MultiHeadModel  # noqa: E402
 from cmr_agent_amd.models.MultiHeadModel import match_features  # noqa: E402
 from cmr_agent_amd.utils import hashfill, synthetic  # noqa: E402
@@ -40,6 +46,13 @@ def _ratios(counts):
         return c[:, 1] / c[:, 0], c[:, 3] / c[:, 2]              # IR1, IR2 per sample (0 / 0 = NaN, as torch)
 
 
+def get_P_diff(P_pred, P_gt):
+    """Test_Agent.py:99-105 (scipy Euler 'XYZ' in degrees, summed absolute angles)."""
+    from scipy.spatial.transform import Rotation
+    r = Rotation.from_matrix(np.dot(P_pred[0:3, 0:3], P_gt[0:3, 0:3].T)).as_euler('XYZ', degrees=True)
+    return np.linalg.norm(P_pred[0:3, 3] - P_gt[0:3, 3]), np.sum(np.abs(r))
+
+
 def main():
     ap = argparse.ArgumentParser(description='Image to point Registration: geometric model matching (MI355X HIP path)')
     ap.add_argument('--dataset', type=str, default='kitti', help=" 'kitti' or 'nuscenes' ")
@@ -50,6 +63,8 @@ def main():
     ap.add_argument('--geo-ckpt', default=None)
     ap.add_argument('--data-root', default=None, help="dataset root in the reference's on-disk layout (cmr_agent_amd/dataset/loader.py): the 'test' split; "
                     "default: the synthetic generator")
+    ap.add_argument('--pnp', action='store_true', help="also register each pair from the IR2 matches alone (PnP-RANSAC) and print "
+                    "Test_Agent.py's RTE / RRE and registration recall")
     args = ap.parse_args()
     dev = torch.device("cuda")
     Cfg = {"kitti": KittiConfiguration, "nuscenes": NuScenesConfiguration}[args.dataset]
@@ -64,6 +79,7 @@ def main():
 
     bs, nbatch = args.batch_size, (args.pairs + args.batch_size - 1) // args.batch_size
     prec, rec, ir, ir1, ir2 = [], [], [], [], []
+    rte, rre = [], []
     with torch.no_grad():
         if args.data_root:
             from cmr_agent_amd.dataset import FrameDataset, FrameLoader
@@ -84,9 +100,25 @@ def main():
             ir1.extend(r1.tolist())
             ir2.extend(r2.tolist())
             print(np.mean(r1), np.mean(r2))
+            if args.pnp:
+                geo_model.pose_from_matches(data, img_overlap=img_overlap)
+                pred = env.to_disentangled(data['pnp_pose'].clone(), data['pc'])
+                gt = env.to_disentangled(data['P'].to(dev).float().clone(), data['pc'])
+                for b in range(pred.shape[0]):
+                    t_diff, r_diff = get_P_diff(pred[b].cpu().numpy(), gt[b].cpu().numpy())
+                    print(t_diff, r_diff)
+                    rte.append(t_diff)
+                    rre.append(r_diff)
 
     mean = lambda v: float(np.mean(v)) if v else float("nan")
     print(mean(prec), mean(rec), mean(ir), mean(ir1), mean(ir2))
+    if args.pnp:
+        rte, rre = np.array(rte), np.array(rre)
+        mask = (rte < 5) & (rre < 10)
+        print("Registration Recall:", mask.sum() / mask.shape[0])
+        if mask.any():
+            print('RTE Mean:', rte[mask].mean(), 'RTE Std:', rte[mask].std())
+            print('RRE Mean:', rre[mask].mean(), 'RRE Std:', rre[mask].std())
 
 
 if __name__ == '__main__':

@@ -192,6 +192,38 @@ class MultiHeadModel(Planned):
             data_batch['inlier_matching_ground_truth'] = torch.sqrt(torch.sum((centers - gt) ** 2, dim=0)) <= MATCH_INLIER_THRES
             data_batch['matching_ir_per_sample'] = _ratio(counts, 1, 0)
 
+    def pose_from_matches(self, data_batch, img_overlap=None, n_hyp=1024, thr=1.0, seed=0, refine_iters=10):
+        """Port extension (no counterpart in the reference): the camera pose from the geometric model's own matches, PnP
+        inside RANSAC (ops.pnp_ransac).  Correspondences: the points of 'pc_overlap_pred', each with its nearest pixel feature
+        (match_features), kept only where that pixel lies inside the predicted image overlap (Test_Geo.py's IR2 set); the pixel p gives
+        u = p % w, v = p // w on the h x w map 'K' refers to.  img_overlap: bool / uint8 [B, h, w]; default the argmax of the last
+        forward's image-overlap logits.  Sets 'pnp_pose' [B, 4, 4] (maps 'pc' into the camera frame, as 'P'), 'pnp_inliers' [B] and
+        'pnp_status' [B] (0 ok, 1 fewer than 4 correspondences, 2 no valid hypothesis).  Not called by forward."""
+        with torch.no_grad():
+            pc = data_batch['pc']
+            dev = pc.device
+            if img_overlap is None:
+                cl = data_batch.get('_cmr')
+                if cl is not None and 'img_overlap_logits' in cl:
+                    img_overlap = ops.softmax2(cl['img_overlap_logits'])[1]
+                else:
+                    lg = data_batch['img_overlap_logits']
+                    img_overlap = lg[:, 1] > lg[:, 0]
+            mask = data_batch['pc_overlap_pred'].to(dev)
+            idx, _, _, w = match_features(data_batch, mask)
+            B, N = idx.shape
+            ov = img_overlap.to(dev).reshape(B, -1).bool()
+            p = idx.long().clamp(min=0)
+            use = (idx >= 0) & mask.bool().view(B, N) & torch.gather(ov, 1, p)
+            uv = torch.stack([p % w, torch.div(p, w, rounding_mode='floor')], 1).float().contiguous()
+            K = data_batch['K'].to(dev).float()
+            K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3).contiguous()
+            pose, inliers, status = ops.pnp_ransac(pc.float().contiguous(), uv, use.contiguous(), K, n_hyp=n_hyp, thr=thr, seed=seed,
+                                                   refine_iters=refine_iters)
+            data_batch['pnp_pose'] = pose
+            data_batch['pnp_inliers'] = inliers
+            data_batch['pnp_status'] = status
+
     def forward_cl(self, data_batch):
         cl = self.encoder_decoder.forward_cl(data_batch)
         # four independent branches (2 heads x {points, pixels}): one flat fork, the pixel convolutions of the

@@ -937,6 +937,51 @@ def feat_match(pc_feat_rows, img_feat_nhwc, mask, gt_xy=None, thr=3.0, img_overl
     return idx, dist, counts
 
 
+def pnp_ransac(pts, uv, mask, K, n_hyp=1024, thr=1.0, seed=0, refine_iters=10, want_hyp_inliers=False):
+    """Camera pose from 2-D/3-D correspondences, PnP inside RANSAC (include/cmr_hip.h cmr_pnp_ransac_f32): pts float32 [B, 3, N]
+    (data['pc'] layout), uv float32 [B, 2, N] pixel coordinates on the map K refers to, mask [B, N] / [B*N] of bool / uint8 / int64
+    (non-zero = use), K float32 [B, 3, 3]; n_hyp hypotheses, inlier threshold thr pixels, hash seed, up to refine_iters Gauss-Newton steps.
+    -> (pose float32 [B, 4, 4] mapping pts into the camera frame, inliers int32 [B], status int32 [B] (0 ok, 1 fewer than 4
+    correspondences, 2 no valid hypothesis)[, hyp_inliers int32 [B, n_hyp], -1 = invalid hypothesis])."""
+    if pts.dim() != 3 or pts.shape[1] != 3:
+        raise ValueError("pnp_ransac: pts must be [B, 3, N], got %s" % (tuple(pts.shape),))
+    B, _, N = pts.shape
+    if tuple(uv.shape) != (B, 2, N):
+        raise ValueError("pnp_ransac: uv must be [%d, 2, %d], got %s" % (B, N, tuple(uv.shape)))
+    if tuple(K.shape) != (B, 3, 3):
+        raise ValueError("pnp_ransac: K must be [%d, 3, 3], got %s" % (B, tuple(K.shape)))
+    if pts.dtype != f32 or uv.dtype != f32 or K.dtype != f32:
+        raise ValueError("pnp_ransac: pts, uv and K must be float32, got %s / %s / %s" % (pts.dtype, uv.dtype, K.dtype))
+    if mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N:
+        raise ValueError("pnp_ransac: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (B * N, mask.dtype, tuple(mask.shape)))
+    if B < 1 or B > GRID_Y_MAX or N < 1 or N > GRID_Y_MAX * 512:
+        raise ValueError("pnp_ransac: need 1 <= B <= %d and 1 <= N <= %d, got B=%d N=%d" % (GRID_Y_MAX, GRID_Y_MAX * 512, B, N))
+    if int(n_hyp) != n_hyp or not 1 <= n_hyp <= 1 << 20:
+        raise ValueError("pnp_ransac: n_hyp must be an integer in [1, 2^20], got %r" % (n_hyp,))
+    if not (float(thr) > 0.0 and float(thr) < float("inf")):
+        raise ValueError("pnp_ransac: thr must be a finite positive number, got %r" % (thr,))
+    if int(refine_iters) != refine_iters or refine_iters < 0:
+        raise ValueError("pnp_ransac: refine_iters must be a non-negative integer, got %r" % (refine_iters,))
+    if int(seed) != seed or not 0 <= seed < 1 << 32:
+        raise ValueError("pnp_ransac: seed must be an unsigned 32-bit integer, got %r" % (seed,))
+    ts = (pts, uv, mask, K)
+    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
+        raise ValueError("pnp_ransac: every tensor must be a contiguous tensor on the same GPU")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    dev = pts.device
+    n_hyp, refine_iters, seed = int(n_hyp), int(refine_iters), int(seed)
+    pose = torch.empty((B, 4, 4), dtype=f32, device=dev)
+    inliers = torch.empty((B,), dtype=torch.int32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    hyp = torch.empty((B, n_hyp), dtype=torch.int32, device=dev) if want_hyp_inliers else None
+    nb = _lib.load().cmr_pnp_ransac_workspace_bytes(B, N, n_hyp)
+    ws = _ws(nb, dev)
+    _lib.call("cmr_pnp_ransac_f32", _p(pts), _p(uv), _p(mask), mask.element_size(), _p(K), B, N, n_hyp, float(thr), seed, refine_iters,
+              _p(pose), _p(inliers), _p(status), _p(hyp), _p(ws), nb, _stream())
+    return (pose, inliers, status, hyp) if want_hyp_inliers else (pose, inliers, status)
+
+
 def expert_action(pose_source, pose_target, r_steps, t_steps, six_dof):
     """-> (action_r int64 [B, 1|3], action_t int64 [B, 2|3]); the step tables are float64 device tensors."""
     B = pose_source.shape[0]

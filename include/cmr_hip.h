@@ -346,6 +346,21 @@ int cmr_feat_match_f32(const float* pc_feat, const float* img_feat, int C, int B
                        const float* gt_xy, float thr, const uint8_t* img_overlap, int32_t* idx, float* dist, int32_t* counts,
                        void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+/* Camera pose from 2-D/3-D correspondences, PnP inside RANSAC (port extension; MultiHeadModel.pose_from_matches,
+ * Test_Geo.py --pnp).  pts f32 [B][3][N] (planar, data['pc']), uv f32 [B][2][N] pixel coordinates on the map K refers to, mask [B*N]
+ * with mask_bytes 1 (u8 / bool) or 8 (int64), non-zero = use; K f32 [B][3][3].  Per sample: the selected rows in row order; n_hyp
+ * hypotheses, each from 4 distinct list positions drawn by a 32-bit hash of (seed, sample, hypothesis, counter), Lambda Twist P3P in
+ * float64 on three, the fourth choosing among the solutions; a correspondence is an inlier of K[R|t] when z > 0 and its reprojection
+ * error is <= thr (fp32); the hypothesis with most inliers (ties to the lowest index) is refined by up to refine_iters Gauss-Newton
+ * steps on its inlier set and kept refined if the inliers do not drop.  pose f32 [B][4][4] maps pts into the camera frame (data['P']);
+ * inliers int32 [B]; status int32 [B] = 0 ok, 1 fewer than 4 correspondences, 2 no valid hypothesis (both: identity pose, 0 inliers);
+ * hyp_inliers (optional) int32 [B][n_hyp] = inliers per hypothesis, -1 for an invalid one.  Deterministic: a sample's outputs depend
+ * only on its own inputs, its index b and seed.  Workspace: cmr_pnp_ransac_workspace_bytes(B, N, n_hyp), 8-byte aligned. */
+int64_t cmr_pnp_ransac_workspace_bytes(int B, int N, int n_hyp);
+int cmr_pnp_ransac_f32(const float* pts, const float* uv, const void* mask, int mask_bytes, const float* K, int B, int N, int n_hyp,
+                       float thr, uint32_t seed, int refine_iters, float* pose, int32_t* inliers, int32_t* status, int32_t* hyp_inliers,
+                       void* ws, int64_t ws_bytes, hipStream_t stream);
+
 /* ---- rollout ops of the training loop ---------------------------------------- */
 
 /* environment.py:143-176 (expert): residual pose target * source^-1 -> extrinsic-xyz Euler angles (folded back when the
