@@ -16,6 +16,11 @@ label_R, ...) that no loader emits.
 "RTE RRE" per pair), then Test_Agent.py's closing lines: registration recall (RTE < 5 and RRE < 10) and the RTE / RRE mean and std of the
 recalled pairs.  Without the flag the output is unchanged.
 
+--mutual / --ratio R / --excl-radius K (with --pnp): the matches are filtered before PnP -- mutual nearest neighbours and
+/ or Lowe's ratio test d1 <= R * d2 with d2 taken outside the (2K + 1)^2 window of the best pixel (cmr_feat_match_filter_f32) -- and each
+batch prints one extra line "kept <kept> of <selected> IR <unfiltered> -> <kept>": the predicted-overlap matches that pass and their
+inlier ratio beside the unfiltered one.  Without these flags the output is unchanged.
+
 Pairs come from the synthetic generator (cmr_agent_amd.utils.synthetic) unless --data-root names a dataset in the reference's layout
 (its 'test' split), and the weights are the deterministic hash fill unless --geo-ckpt points at a reference-format state_dict."""
 import argparse
@@ -65,7 +70,17 @@ def main():
                     "default: the synthetic generator")
     ap.add_argument('--pnp', action='store_true', help="also register each pair from the IR2 matches alone (PnP-RANSAC) and print "
                     "Test_Agent.py's RTE / RRE and registration recall")
+    ap.add_argument('--mutual', action='store_true', help="with --pnp: keep only mutual nearest-neighbour matches")
+    ap.add_argument('--ratio', type=float, default=None, help="with --pnp: Lowe's ratio test, keep a match when d1 <= RATIO * d2 (0 < RATIO <= 1)")
+    ap.add_argument('--excl-radius', type=int, default=2, help="with --ratio: d2 is the best distance outside the (2K + 1)^2 window of the best pixel")
     args = ap.parse_args()
+    filtered = args.mutual or args.ratio is not None
+    if filtered and not args.pnp:
+        ap.error("--mutual / --ratio filter the matches that go into PnP: give --pnp as well")
+    if args.ratio is not None and not 0.0 < args.ratio <= 1.0:
+        ap.error("--ratio must lie in (0, 1]")
+    if args.excl_radius < 0:
+        ap.error("--excl-radius must be >= 0")
     dev = torch.device("cuda")
     Cfg = {"kitti": KittiConfiguration, "nuscenes": NuScenesConfiguration}[args.dataset]
     kw = {}
@@ -101,7 +116,12 @@ def main():
             ir2.extend(r2.tolist())
             print(np.mean(r1), np.mean(r2))
             if args.pnp:
-                geo_model.pose_from_matches(data, img_overlap=img_overlap)
+                geo_model.pose_from_matches(data, img_overlap=img_overlap, mutual=args.mutual, ratio=args.ratio,
+                                            excl_radius=args.excl_radius)
+                if filtered:
+                    fc = data['pnp_filter_counts'].double().cpu().numpy().sum(0)
+                    with np.errstate(invalid="ignore", divide="ignore"):
+                        print("kept", int(fc[1]), "of", int(fc[0]), "IR", fc[3] / fc[0], "->", fc[2] / fc[1])
                 pred = env.to_disentangled(data['pnp_pose'].clone(), data['pc'])
                 gt = env.to_disentangled(data['P'].to(dev).float().clone(), data['pc'])
                 for b in range(pred.shape[0]):

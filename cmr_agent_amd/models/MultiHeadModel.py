@@ -103,17 +103,21 @@ def _gt_xy(data_batch, dev):
     return xy.to(dev, torch.float32).contiguous()
 
 
+def _geo_rows(data_batch):
+    """The batch's geometric features in the matcher's layout: the '_cmr' rows of the last forward when present (no transpose copy), else
+    the public [B,64,N] / [B,64,h,w] tensors -> (point rows [B*N, 64], pixel features NHWC [B, h, w, 64])."""
+    cl = data_batch.get('_cmr')
+    if cl is not None and 'pc_geo_feat' in cl and 'img_geo_feat' in cl:
+        return cl['pc_geo_feat'].contiguous(), cl['img_geo_feat'].contiguous()
+    pcb, imb = data_batch['pc_geo_feat'], data_batch['img_geo_feat']
+    return pcb.permute(0, 2, 1).reshape(-1, pcb.shape[1]).contiguous(), imb.permute(0, 2, 3, 1).contiguous()
+
+
 def match_features(data_batch, mask, img_overlap=None, want_dist=False):
     """ops.feat_match on the batch's geometric features: the '_cmr' rows of the last forward when present (no transpose copy), else the
     public [B,64,N] / [B,64,h,w] tensors; ground-truth xy from 'point_xy_float_all' or derived from K and pc_in_cam_space.
     -> (idx int32 [B, N], dist or None, counts int32 [B, 4], w)."""
-    cl = data_batch.get('_cmr')
-    if cl is not None and 'pc_geo_feat' in cl and 'img_geo_feat' in cl:
-        pc, img = cl['pc_geo_feat'].contiguous(), cl['img_geo_feat'].contiguous()
-    else:
-        pcb, imb = data_batch['pc_geo_feat'], data_batch['img_geo_feat']
-        pc = pcb.permute(0, 2, 1).reshape(-1, pcb.shape[1]).contiguous()
-        img = imb.permute(0, 2, 3, 1).contiguous()
+    pc, img = _geo_rows(data_batch)
     B, h, w, _ = img.shape
     N = pc.shape[0] // B
     dev = pc.device
@@ -121,6 +125,20 @@ def match_features(data_batch, mask, img_overlap=None, want_dist=False):
     idx, dist, counts = ops.feat_match(pc, img, mask.to(dev).contiguous(), gt_xy=xy, thr=MATCH_INLIER_THRES, img_overlap=img_overlap,
                                        want_dist=want_dist)
     return idx.view(B, N), dist, counts, w
+
+
+def match_features_filtered(data_batch, mask, mutual=True, ratio=0.0, excl_radius=2, max_dist=0.0):
+    """ops.feat_match_filter on the batch's geometric features (as match_features): the nearest pixel of every selected point and which
+    of those matches pass the mutual check / ratio test / distance bound.
+    -> (idx int32 [B, N], keep bool [B, N], counts int32 [B, 4] = (selected, kept, kept inliers, selected inliers), w)."""
+    pc, img = _geo_rows(data_batch)
+    B, h, w, _ = img.shape
+    N = pc.shape[0] // B
+    dev = pc.device
+    idx, keep, counts, _, _, _ = ops.feat_match_filter(pc, img, mask.to(dev).contiguous(), mutual=mutual, ratio=ratio,
+                                                       excl_radius=excl_radius, max_dist=max_dist, gt_xy=_gt_xy(data_batch, dev),
+                                                       thr=MATCH_INLIER_THRES)
+    return idx.view(B, N), keep.view(B, N), counts, w
 
 
 def _ratio(counts, num, den):
@@ -192,13 +210,19 @@ class MultiHeadModel(Planned):
             data_batch['inlier_matching_ground_truth'] = torch.sqrt(torch.sum((centers - gt) ** 2, dim=0)) <= MATCH_INLIER_THRES
             data_batch['matching_ir_per_sample'] = _ratio(counts, 1, 0)
 
-    def pose_from_matches(self, data_batch, img_overlap=None, n_hyp=1024, thr=1.0, seed=0, refine_iters=10):
+    def pose_from_matches(self, data_batch, img_overlap=None, n_hyp=1024, thr=1.0, seed=0, refine_iters=10, mutual=False, ratio=None,
+                          excl_radius=2, max_dist=None):
         """Port extension (no counterpart in the reference): the camera pose from the geometric model's own matches, PnP
         inside RANSAC (ops.pnp_ransac).  Correspondences: the points of 'pc_overlap_pred', each with its nearest pixel feature
         (match_features), kept only where that pixel lies inside the predicted image overlap (Test_Geo.py's IR2 set); the pixel p gives
         u = p % w, v = p // w on the h x w map 'K' refers to.  img_overlap: bool / uint8 [B, h, w]; default the argmax of the last
         forward's image-overlap logits.  Sets 'pnp_pose' [B, 4, 4] (maps 'pc' into the camera frame, as 'P'), 'pnp_inliers' [B] and
-        'pnp_status' [B] (0 ok, 1 fewer than 4 correspondences, 2 no valid hypothesis).  Not called by forward."""
+        'pnp_status' [B] (0 ok, 1 fewer than 4 correspondences, 2 no valid hypothesis).  Not called by forward.
+        mutual / ratio / max_dist (off by default, and then this is the unfiltered path exactly): the matches come from
+        match_features_filtered and only the kept ones go on -- mutual nearest neighbours, d1 <= ratio * d2 with d2 taken outside the
+        (2 excl_radius + 1)^2 window of the best pixel, d1 <= max_dist -- and 'pnp_used' int [B] is the number of correspondences handed
+        to PnP, 'pnp_filter_counts' int32 [B, 4] the filter's (selected, kept, kept inliers, selected inliers) before the image-overlap
+        mask."""
         with torch.no_grad():
             pc = data_batch['pc']
             dev = pc.device
@@ -210,11 +234,20 @@ class MultiHeadModel(Planned):
                     lg = data_batch['img_overlap_logits']
                     img_overlap = lg[:, 1] > lg[:, 0]
             mask = data_batch['pc_overlap_pred'].to(dev)
-            idx, _, _, w = match_features(data_batch, mask)
+            filtered = bool(mutual) or bool(ratio) or bool(max_dist)
+            if filtered:
+                idx, keep, fcounts, w = match_features_filtered(data_batch, mask, mutual=bool(mutual), ratio=ratio or 0.0,
+                                                                excl_radius=excl_radius, max_dist=max_dist or 0.0)
+            else:
+                idx, _, _, w = match_features(data_batch, mask)
             B, N = idx.shape
             ov = img_overlap.to(dev).reshape(B, -1).bool()
             p = idx.long().clamp(min=0)
             use = (idx >= 0) & mask.bool().view(B, N) & torch.gather(ov, 1, p)
+            if filtered:
+                use = use & keep
+                data_batch['pnp_used'] = use.sum(1)
+                data_batch['pnp_filter_counts'] = fcounts
             uv = torch.stack([p % w, torch.div(p, w, rounding_mode='floor')], 1).float().contiguous()
             K = data_batch['K'].to(dev).float()
             K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3).contiguous()

@@ -937,6 +937,61 @@ def feat_match(pc_feat_rows, img_feat_nhwc, mask, gt_xy=None, thr=3.0, img_overl
     return idx, dist, counts
 
 
+def feat_match_filter(pc_feat_rows, img_feat_nhwc, mask, mutual=True, ratio=0.0, excl_radius=2, max_dist=0.0, gt_xy=None, thr=3.0,
+                      want_dist=False, want_rev=False):
+    """Nearest pixel feature of every selected point plus the filters that go ahead of PnP-RANSAC (include/cmr_hip.h
+    cmr_feat_match_filter_f32); tensors as feat_match.  mutual: keep a row only when its pixel's nearest selected point is
+    that row; ratio in [0, 1] (0 = off): keep when d1 <= ratio * d2, d2 = the best distance outside the (2 excl_radius + 1)^2 window of
+    the best pixel; max_dist >= 0 (0 = off): keep when d1 <= max_dist.
+    -> (idx int32 [B*N] as feat_match, keep bool [B*N], counts int32 [B, 4] = (selected, kept, kept inliers, selected inliers),
+    d1 / d2 float32 [B*N] or None (want_dist), rev int32 [B*h*w]: the nearest selected row of every pixel, or None (want_rev))."""
+    if pc_feat_rows.dim() != 2 or img_feat_nhwc.dim() != 4:
+        raise ValueError("feat_match_filter: point rows must be 2-D [B*N, C] and pixel features 4-D [B, h, w, C], got %s / %s" % (
+            tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
+    B, h, w, C = img_feat_nhwc.shape
+    if C != 64 or pc_feat_rows.shape[1] != 64:
+        raise ValueError("feat_match_filter: feature width must be 64, got %d / %d" % (pc_feat_rows.shape[1], C))
+    if pc_feat_rows.dtype != f32 or img_feat_nhwc.dtype != f32:
+        raise ValueError("feat_match_filter: features must be float32, got %s / %s" % (pc_feat_rows.dtype, img_feat_nhwc.dtype))
+    if B < 1 or B > GRID_Y_MAX or pc_feat_rows.shape[0] % B or h < 1 or w < 1 or h * w > 1 << 30:
+        raise ValueError("feat_match_filter: %d point rows do not split into %d samples (1 <= B <= %d) or the map %d x %d is empty / "
+                         "over 2^30 pixels" % (pc_feat_rows.shape[0], B, GRID_Y_MAX, h, w))
+    N = pc_feat_rows.shape[0] // B
+    if N < 1 or N > GRID_Y_MAX * 256:
+        raise ValueError("feat_match_filter: need 1 <= N <= %d rows per sample, got %d" % (GRID_Y_MAX * 256, N))
+    if mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N:
+        raise ValueError("feat_match_filter: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (
+            B * N, mask.dtype, tuple(mask.shape)))
+    if gt_xy is not None and (gt_xy.dtype != f32 or tuple(gt_xy.shape) != (B, 2, N)):
+        raise ValueError("feat_match_filter: gt_xy must be float32 [%d, 2, %d], got %s %s" % (B, N, gt_xy.dtype, tuple(gt_xy.shape)))
+    if isinstance(excl_radius, bool) or int(excl_radius) != excl_radius or not 0 <= excl_radius < 1 << 31:
+        raise ValueError("feat_match_filter: excl_radius must be a non-negative integer, got %r" % (excl_radius,))
+    if not 0.0 <= float(ratio) <= 1.0:
+        raise ValueError("feat_match_filter: ratio must lie in [0, 1] (0 = no ratio test), got %r" % (ratio,))
+    if not 0.0 <= float(max_dist) < float("inf"):
+        raise ValueError("feat_match_filter: max_dist must be finite and >= 0 (0 = no bound), got %r" % (max_dist,))
+    ts = [t for t in (pc_feat_rows, img_feat_nhwc, mask, gt_xy) if t is not None]
+    if not all(t.is_cuda and t.is_contiguous() and t.device == pc_feat_rows.device for t in ts):
+        raise ValueError("feat_match_filter: every tensor must be a contiguous tensor on the same GPU")
+    if pc_feat_rows.data_ptr() % 16 or img_feat_nhwc.data_ptr() % 16:
+        raise ValueError("feat_match_filter: feature rows must be 16-byte aligned")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    dev = pc_feat_rows.device
+    idx = torch.empty((B * N,), dtype=torch.int32, device=dev)
+    keep = torch.empty((B * N,), dtype=torch.uint8, device=dev)
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    d1 = torch.empty((B * N,), dtype=f32, device=dev) if want_dist else None
+    d2 = torch.empty((B * N,), dtype=f32, device=dev) if want_dist else None
+    rev = torch.empty((B * h * w,), dtype=torch.int32, device=dev) if want_rev else None
+    nb = _lib.load().cmr_feat_match_filter_workspace_bytes(B, N, h, w)
+    ws = _ws(nb, dev)
+    _lib.call("cmr_feat_match_filter_f32", _p(pc_feat_rows), _p(img_feat_nhwc), C, B, N, h, w, _p(mask), mask.element_size(),
+              1 if mutual else 0, float(ratio), int(excl_radius), float(max_dist), _p(gt_xy), float(thr), _p(idx), _p(keep), _p(counts),
+              _p(d1), _p(d2), _p(rev), _p(ws), nb, _stream())
+    return idx, keep.view(torch.bool), counts, d1, d2, rev
+
+
 def pnp_ransac(pts, uv, mask, K, n_hyp=1024, thr=1.0, seed=0, refine_iters=10, want_hyp_inliers=False):
     """Camera pose from 2-D/3-D correspondences, PnP inside RANSAC (include/cmr_hip.h cmr_pnp_ransac_f32): pts float32 [B, 3, N]
     (data['pc'] layout), uv float32 [B, 2, N] pixel coordinates on the map K refers to, mask [B, N] / [B*N] of bool / uint8 / int64

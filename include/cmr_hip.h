@@ -346,6 +346,28 @@ int cmr_feat_match_f32(const float* pc_feat, const float* img_feat, int C, int B
                        const float* gt_xy, float thr, const uint8_t* img_overlap, int32_t* idx, float* dist, int32_t* counts,
                        void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+/* Match filtering ahead of PnP-RANSAC (port extension; ops.feat_match_filter, MultiHeadModel.pose_from_matches,
+ * Test_Geo.py --mutual / --ratio).  Inputs as cmr_feat_match_f32: pc_feat rows [B*N][C], img_feat [B][h*w][C], C must be 64, mask [B*N]
+ * with mask_bytes 1 or 8.  Per sample, S = the selected rows, d(n, p) = the L2 distance of point n and pixel p:
+ *   idx int32 [B*N]    argmin_p d(n, p), ties to the lowest p: cmr_feat_match_f32's idx bit for bit (same arithmetic); -1 outside S;
+ *   d1 (optional) f32 [B*N]  that minimum; d2 (optional) f32 [B*N]  min of d(n, p) over the pixels OUTSIDE the window of the best pixel,
+ *                      max(|x_p - x_best|, |y_p - y_best|) > excl_radius (>= 0; 0 = the plain second nearest), +inf when there is none;
+ *                      both NaN outside S;
+ *   rev (optional) int32 [B*h*w]  argmin over n in S of d(n, p) as a row number, ties to the lowest n; -1 when S is empty;
+ *   keep u8 [B*N]      n in S and (!mutual or rev[idx[n]] == n) and (ratio <= 0 or d1 <= ratio * d2) and (max_dist <= 0 or
+ *                      d1 <= max_dist), on distances (not squares), in fp32; an infinite d2 passes;
+ *   counts int32 [B][4] = {|S|, kept, kept and inlier, selected and inlier}; inlier as cmr_feat_match_f32: gt_xy (optional, f32
+ *                      [B][2][N]) finite and within thr of the best pixel.
+ * The reverse sweep runs only with mutual or rev, the windowed one only with ratio > 0 or d2.  Everything is enqueued on the stream (no
+ * host round trip); every output is a plain store of the workgroup that owns the row / pixel and the counts are integer atomics, so
+ * two calls agree bit for bit and a sample depends on its own rows only.  Workspace: cmr_feat_match_filter_workspace_bytes(B, N, h, w),
+ * 16-byte aligned. */
+int64_t cmr_feat_match_filter_workspace_bytes(int B, int N, int h, int w);
+int cmr_feat_match_filter_f32(const float* pc_feat, const float* img_feat, int C, int B, int N, int h, int w, const void* mask,
+                              int mask_bytes, int mutual, float ratio, int excl_radius, float max_dist, const float* gt_xy, float thr,
+                              int32_t* idx, uint8_t* keep, int32_t* counts, float* d1, float* d2, int32_t* rev, void* workspace,
+                              int64_t workspace_bytes, hipStream_t stream);
+
 /* Camera pose from 2-D/3-D correspondences, PnP inside RANSAC (port extension; MultiHeadModel.pose_from_matches,
  * Test_Geo.py --pnp).  pts f32 [B][3][N] (planar, data['pc']), uv f32 [B][2][N] pixel coordinates on the map K refers to, mask [B*N]
  * with mask_bytes 1 (u8 / bool) or 8 (int64), non-zero = use; K f32 [B][3][3].  Per sample: the selected rows in row order; n_hyp
