@@ -5,7 +5,13 @@
 There are no KITTI / nuScenes files and no checkpoints in this environment, so the loader is the
 synthetic generator (cmr_agent_amd.utils.synthetic) and the weights are the deterministic hash
 fill unless --geo-ckpt / --agent-ckpt point at reference-format state_dicts.  Metrics are the
-reference's: RTE / RRE per pair and registration recall (RTE < 5 m and RRE < 10 deg, :198)."""
+reference's: RTE / RRE per pair and registration recall (RTE < 5 m and RRE < 10 deg, :198).
+
+--refine R[,R...] (port extension; optional --guided-thr T[,T...], --guided-max-dist D): the agent's final pose, which sits on
+the lattice of its step tables, is polished against the geometric features -- a clone of it through env.from_disentangled, rounds of
+(guided match inside the (2R + 1)^2 window -> Gauss-Newton with inlier threshold T; MultiHeadModel.refine_pose_from_matches), back
+through env.to_disentangled.  Per pair one extra line "refined <RTE> <RRE>", and after the closing block the same three lines again with
+the prefix "Refined ".  Without the flag the output is unchanged."""
 import argparse
 import json
 import os
@@ -19,12 +25,14 @@ os.environ.setdefault("ROC_CPU_WAIT_FOR_SIGNAL", "1")        # HIP runtime: cros
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from cmr_agent_amd import ops  # noqa: E402
 from cmr_agent_amd.dataset.sampling import hip_fps, hip_nearest  # noqa: E402
 from cmr_agent_amd.config import KittiConfiguration, NuScenesConfiguration  # noqa: E402
 from cmr_agent_amd.environment import environment as env  # noqa: E402
 from cmr_agent_amd.models import CMRAgent, MultiHeadModel  # noqa: E402
 from cmr_agent_amd.utils import hashfill, synthetic  # noqa: E402
 from cmr_agent_amd.utils.checkpoint import load_checked  # noqa: E402
+from cmr_agent_amd.utils.evalcli import guided_rounds, print_recall  # noqa: E402
 
 
 def get_P_diff(P_pred, P_gt):
@@ -44,7 +52,15 @@ def main():
     ap.add_argument('--agent-ckpt', default=None)
     ap.add_argument('--data-root', default=None, help="dataset root in the reference's on-disk layout (cmr_agent_amd/dataset/loader.py): the 'test' split; "
                     "default: the synthetic generator")
+    ap.add_argument('--refine', type=str, default=None, help="refine the agent's final pose by guided matching, one round per window radius R[,R...]")
+    ap.add_argument('--guided-thr', type=str, default=None, help="with --refine: inlier threshold in pixels per round T[,T...] (default: R / 1.5 per round, at least 1)")
+    ap.add_argument('--guided-max-dist', type=float, default=None, help="with --refine: keep a guided match only when its feature distance is <= D")
     args = ap.parse_args()
+    radii = thrs = None
+    if args.refine is not None:
+        radii, thrs = guided_rounds(ap, args.refine, args.guided_thr, ops.GUIDED_MAX_RADIUS)
+    elif args.guided_thr is not None or args.guided_max_dist is not None:
+        ap.error("--guided-thr / --guided-max-dist belong to --refine")
     dev = torch.device("cuda")
     Cfg = {"kitti": KittiConfiguration, "nuscenes": NuScenesConfiguration}[args.dataset]
     kw = {}
@@ -57,7 +73,7 @@ def main():
     load_checked(agent, torch.load(args.agent_ckpt) if args.agent_ckpt else hashfill.make_state_dict(spec["agent"], "agent/"))
     geo_model, agent = geo_model.to(dev).eval(), agent.to(dev).eval()
 
-    rte, rre = [], []
+    rte, rre, rte_ref, rre_ref = [], [], [], []
     with torch.no_grad():
         if args.data_root:
             from cmr_agent_amd.dataset import FrameDataset, FrameLoader
@@ -79,12 +95,17 @@ def main():
             print(t_diff, r_diff)
             rte.append(t_diff)
             rre.append(r_diff)
-    rte, rre = np.array(rte), np.array(rre)
-    mask = (rte < 5) & (rre < 10)
-    print("Registration Recall:", mask.sum() / mask.shape[0])
-    if mask.any():
-        print('RTE Mean:', rte[mask].mean(), 'RTE Std:', rte[mask].std())
-        print('RRE Mean:', rre[mask].mean(), 'RRE Std:', rre[mask].std())
+            if radii is not None:
+                start = env.from_disentangled(pose_source.clone(), data['pc'], data=data)
+                geo_model.refine_pose_from_matches(data, pose=start, radii=radii, thrs=thrs, max_dist=args.guided_max_dist)
+                ref = env.to_disentangled(data['refined_pose'].clone(), data['pc'], data=data)
+                t_diff, r_diff = get_P_diff(ref[0].cpu().numpy(), pose_target[0].cpu().numpy())
+                print("refined", t_diff, r_diff)
+                rte_ref.append(t_diff)
+                rre_ref.append(r_diff)
+    print_recall(rte, rre)
+    if radii is not None:
+        print_recall(rte_ref, rre_ref, "Refined ")
 
 
 if __name__ == '__main__':

@@ -21,6 +21,11 @@ recalled pairs.  Without the flag the output is unchanged.
 batch prints one extra line "kept <kept> of <selected> IR <unfiltered> -> <kept>": the predicted-overlap matches that pass and their
 inlier ratio beside the unfiltered one.  Without these flags the output is unchanged.
 
+--guided R[,R...] (with --pnp; optional --guided-thr T[,T...], --guided-max-dist D): the PnP pose is refined by rounds of
+(guided match inside the (2R + 1)^2 window round every point's projection -> Gauss-Newton on the kept matches with inlier threshold T;
+MultiHeadModel.refine_pose_from_matches).  Per pair one extra line "refined <RTE> <RRE>" after the pair's "RTE RRE" line, and after the
+closing block the same three lines again with the prefix "Refined ".  Without the flag the output is unchanged.
+
 Pairs come from the synthetic generator (cmr_agent_amd.utils.synthetic) unless --data-root names a dataset in the reference's layout
 (its 'test' split), and the weights are the deterministic hash fill unless --geo-ckpt points at a reference-format state_dict."""
 import argparse
@@ -43,6 +48,7 @@ from cmr_agent_amd.models import MultiHeadModel  # noqa: E402
 from cmr_agent_amd.models.MultiHeadModel import match_features  # noqa: E402
 from cmr_agent_amd.utils import hashfill, synthetic  # noqa: E402
 from cmr_agent_amd.utils.checkpoint import load_checked  # noqa: E402
+from cmr_agent_amd.utils.evalcli import guided_rounds, print_recall  # noqa: E402
 
 
 def _ratios(counts):
@@ -73,6 +79,9 @@ def main():
     ap.add_argument('--mutual', action='store_true', help="with --pnp: keep only mutual nearest-neighbour matches")
     ap.add_argument('--ratio', type=float, default=None, help="with --pnp: Lowe's ratio test, keep a match when d1 <= RATIO * d2 (0 < RATIO <= 1)")
     ap.add_argument('--excl-radius', type=int, default=2, help="with --ratio: d2 is the best distance outside the (2K + 1)^2 window of the best pixel")
+    ap.add_argument('--guided', type=str, default=None, help="with --pnp: refine the PnP pose by guided matching, one round per window radius R[,R...]")
+    ap.add_argument('--guided-thr', type=str, default=None, help="with --guided: inlier threshold in pixels per round T[,T...] (default: R / 1.5 per round, at least 1)")
+    ap.add_argument('--guided-max-dist', type=float, default=None, help="with --guided: keep a guided match only when its feature distance is <= D")
     args = ap.parse_args()
     filtered = args.mutual or args.ratio is not None
     if filtered and not args.pnp:
@@ -81,6 +90,13 @@ def main():
         ap.error("--ratio must lie in (0, 1]")
     if args.excl_radius < 0:
         ap.error("--excl-radius must be >= 0")
+    radii = thrs = None
+    if args.guided is not None:
+        if not args.pnp:
+            ap.error("--guided refines the PnP pose: give --pnp as well")
+        radii, thrs = guided_rounds(ap, args.guided, args.guided_thr, ops.GUIDED_MAX_RADIUS)
+    elif args.guided_thr is not None or args.guided_max_dist is not None:
+        ap.error("--guided-thr / --guided-max-dist belong to --guided")
     dev = torch.device("cuda")
     Cfg = {"kitti": KittiConfiguration, "nuscenes": NuScenesConfiguration}[args.dataset]
     kw = {}
@@ -94,7 +110,7 @@ def main():
 
     bs, nbatch = args.batch_size, (args.pairs + args.batch_size - 1) // args.batch_size
     prec, rec, ir, ir1, ir2 = [], [], [], [], []
-    rte, rre = [], []
+    rte, rre, rte_ref, rre_ref = [], [], [], []
     with torch.no_grad():
         if args.data_root:
             from cmr_agent_amd.dataset import FrameDataset, FrameLoader
@@ -124,21 +140,26 @@ def main():
                         print("kept", int(fc[1]), "of", int(fc[0]), "IR", fc[3] / fc[0], "->", fc[2] / fc[1])
                 pred = env.to_disentangled(data['pnp_pose'].clone(), data['pc'])
                 gt = env.to_disentangled(data['P'].to(dev).float().clone(), data['pc'])
+                if radii is not None:
+                    geo_model.refine_pose_from_matches(data, radii=radii, thrs=thrs, max_dist=args.guided_max_dist, img_overlap=img_overlap)
+                    ref = env.to_disentangled(data['refined_pose'].clone(), data['pc'])
                 for b in range(pred.shape[0]):
                     t_diff, r_diff = get_P_diff(pred[b].cpu().numpy(), gt[b].cpu().numpy())
                     print(t_diff, r_diff)
                     rte.append(t_diff)
                     rre.append(r_diff)
+                    if radii is not None:
+                        t_diff, r_diff = get_P_diff(ref[b].cpu().numpy(), gt[b].cpu().numpy())
+                        print("refined", t_diff, r_diff)
+                        rte_ref.append(t_diff)
+                        rre_ref.append(r_diff)
 
     mean = lambda v: float(np.mean(v)) if v else float("nan")
     print(mean(prec), mean(rec), mean(ir), mean(ir1), mean(ir2))
     if args.pnp:
-        rte, rre = np.array(rte), np.array(rre)
-        mask = (rte < 5) & (rre < 10)
-        print("Registration Recall:", mask.sum() / mask.shape[0])
-        if mask.any():
-            print('RTE Mean:', rte[mask].mean(), 'RTE Std:', rte[mask].std())
-            print('RRE Mean:', rre[mask].mean(), 'RRE Std:', rre[mask].std())
+        print_recall(rte, rre)
+        if radii is not None:
+            print_recall(rte_ref, rre_ref, "Refined ")
 
 
 if __name__ == '__main__':

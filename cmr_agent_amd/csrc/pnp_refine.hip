@@ -1,0 +1,348 @@
+// Gauss-Newton pose refinement from a GIVEN pose (port extension): the refinement step of cmr_pnp_ransac_f32 (DESIGN.md
+// 4l, csrc/pnp.hip pnp_select_kernel) restated so that it starts from any pose, with the accumulation split over the correspondences
+// instead of running in one workgroup per sample.
+//
+// Launches, all on the caller's stream; the sequence depends on `iters` alone (3 + 2 (iters + 1) launches), a sample that has stopped
+// turns its remaining launches into early returns read from its state in the workspace:
+//   prf_init_kernel    per sample: pose_in -> the float64 working pose, K[R|t] of pose_in rounded to fp32 (the working set's predicate);
+//   for it = 0 .. iters:
+//     prf_accum_kernel   grid (slices, B), a slice = PRF_SLICE consecutive rows: the rows of the slice that are selected AND inliers of
+//                        pose_in (pnp.hip's fmaf sequence, copied) add their J^T J (21), J^T r (6) and cost (1) in float64 -- per
+//                        thread in row order (rows t, t + 256, ...), wave butterfly, the four waves in order -- into the slice's own
+//                        slot, with the integer size of the slice's share of the working set.  Rows need no compaction;
+//     prf_step_kernel    per sample: adds the slots IN SLICE ORDER, then the accept / undo logic of pnp_select_kernel: a cost that did
+//                        not drop undoes the last step and stops; otherwise 6x6 Cholesky, left increment X_c <- Exp(w) X_c + v;
+//   prf_count_kernel   grid (slices, B): inliers of the working pose over ALL selected rows, per slice (integers);
+//   prf_final_kernel   per sample: adds the slice counts, keeps the refined pose if the count is >= the working set's size.
+// No floating-point atomics, no atomics at all: every slot, state and output has one writer, and the slice size is a constant, so two
+// calls agree bit for bit and a sample depends on its own rows only.
+#include "cmr_common.h"
+
+namespace {
+
+constexpr int PRF_THREADS = 256;
+constexpr int PRF_SLICE = 1024;      // rows per accumulation workgroup: 4 per thread.  A constant: the summation order must not depend on B
+constexpr int PRF_NACC = 28;         // J^T J (21 upper-triangle entries), J^T r (6), cost
+constexpr double PRF_PIVOT_TOL = 1e-13;
+
+struct PrfState {
+  double cur[12];                    // the working pose: R row-major, t
+  double prev[12];
+  double cost_prev;
+  float Min[12];                     // K [R|t] of pose_in in fp32: the working set's predicate
+  int32_t stop, status, wcount, pad;
+};
+
+__device__ __forceinline__ bool prf_sel(const void* mask, int mask_bytes, int64_t g) {
+  return mask_bytes == 1 ? ((const uint8_t*)mask)[g] != 0 : ((const int64_t*)mask)[g] != 0;
+}
+
+// pnp.hip:pnp_inlier, the same operations in the same order
+__device__ __forceinline__ bool prf_inlier(const float* M, float X, float Y, float Z, float u, float v, float thr2) {
+  const float x = fmaf(M[0], X, fmaf(M[1], Y, fmaf(M[2], Z, M[3])));
+  const float y = fmaf(M[4], X, fmaf(M[5], Y, fmaf(M[6], Z, M[7])));
+  const float z = fmaf(M[8], X, fmaf(M[9], Y, fmaf(M[10], Z, M[11])));
+  const float ex = fmaf(-u, z, x), ey = fmaf(-v, z, y);
+  const float e2 = fmaf(ex, ex, ey * ey);
+  return z > 0.f && e2 <= thr2 * (z * z);
+}
+
+// pnp.hip:pnp_kmat: K [R | t] -> fp32 row-major 3x4 (pose = R row-major then t)
+__device__ __forceinline__ void prf_kmat(const double* K, const double* pose, float* M) {
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) M[4 * i + j] = (float)(K[3 * i] * pose[j] + K[3 * i + 1] * pose[3 + j] + K[3 * i + 2] * pose[6 + j]);
+    M[4 * i + 3] = (float)(K[3 * i] * pose[9] + K[3 * i + 1] * pose[10] + K[3 * i + 2] * pose[11]);
+  }
+}
+
+__device__ __forceinline__ double prf_wave_sum(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// Rodrigues: exp([w]x)  (pnp.hip:pnp_expso3)
+__device__ void prf_expso3(const double* w, double* E) {
+  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+  const double th = sqrt(th2);
+  double a, c;
+  if (th < 1e-8) { a = 1.0 - th2 / 6.0; c = 0.5 - th2 / 24.0; }
+  else { a = sin(th) / th; c = (1.0 - cos(th)) / th2; }
+  const double W[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      double ww = 0.0;
+      for (int k = 0; k < 3; ++k) ww += W[3 * i + k] * W[3 * k + j];
+      E[3 * i + j] = (i == j ? 1.0 : 0.0) + a * W[3 * i + j] + c * ww;
+    }
+}
+
+// Cholesky solve of the 6x6 H x = g (H from the 21 upper-triangle entries, row by row; pnp.hip:pnp_chol6); false if H is not positive
+// definite.  Unlike pnp_chol6 a pivot must also exceed PRF_PIVOT_TOL times its diagonal entry: a rank-deficient H (all rows on a
+// line) leaves a pivot of rounding noise, ~1e-16 of the diagonal with either sign, and "status 2" must not hang on that sign.
+__device__ bool prf_chol6(const double* Hu, const double* g, double* x) {
+  double L[36] = {};
+  double H[36];
+  int k = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) { H[6 * i + j] = Hu[k]; H[6 * j + i] = Hu[k]; ++k; }
+  for (int j = 0; j < 6; ++j) {
+    double d = H[6 * j + j];
+    for (int p = 0; p < j; ++p) d -= L[6 * j + p] * L[6 * j + p];
+    if (!(d > 0.0 && d > PRF_PIVOT_TOL * H[6 * j + j])) return false;
+    L[6 * j + j] = sqrt(d);
+    for (int i = j + 1; i < 6; ++i) {
+      double s = H[6 * i + j];
+      for (int p = 0; p < j; ++p) s -= L[6 * i + p] * L[6 * j + p];
+      L[6 * i + j] = s / L[6 * j + j];
+    }
+  }
+  double z[6];
+  for (int i = 0; i < 6; ++i) {
+    double s = g[i];
+    for (int p = 0; p < i; ++p) s -= L[6 * i + p] * z[p];
+    z[i] = s / L[6 * i + i];
+  }
+  for (int i = 5; i >= 0; --i) {
+    double s = z[i];
+    for (int p = i + 1; p < 6; ++p) s -= L[6 * p + i] * x[p];
+    x[i] = s / L[6 * i + i];
+  }
+  return true;
+}
+
+__global__ __launch_bounds__(64) void prf_init_kernel(const float* __restrict__ pose_in, const float* __restrict__ Kin,
+                                                      PrfState* __restrict__ state) {
+  const int b = blockIdx.x;
+  if (threadIdx.x != 0) return;
+  PrfState& st = state[b];
+  const float* P = pose_in + 16 * b;
+  double K[9];
+  for (int i = 0; i < 9; ++i) K[i] = (double)Kin[9 * b + i];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) st.cur[3 * i + j] = (double)P[4 * i + j];
+    st.cur[9 + i] = (double)P[4 * i + 3];
+  }
+  for (int i = 0; i < 12; ++i) st.prev[i] = st.cur[i];
+  st.cost_prev = 0.0;
+  prf_kmat(K, st.cur, st.Min);
+  st.stop = 0;
+  st.status = 0;
+  st.wcount = 0;
+  st.pad = 0;
+}
+
+__global__ __launch_bounds__(PRF_THREADS) void prf_accum_kernel(const float* __restrict__ pts, const float* __restrict__ uv,
+                                                                const void* __restrict__ mask, int mask_bytes,
+                                                                const float* __restrict__ Kin, int N, float thr2,
+                                                                const PrfState* __restrict__ state, double* __restrict__ slots,
+                                                                int32_t* __restrict__ cslots) {
+  __shared__ double acc[PRF_THREADS / 64][PRF_NACC];
+  __shared__ int cnt[PRF_THREADS / 64];
+  const int b = blockIdx.y, s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const PrfState& st = state[b];
+  if (st.stop) return;
+  double R[9], t[3], K[9];
+  float Min[12];
+  for (int i = 0; i < 9; ++i) R[i] = st.cur[i];
+  for (int i = 0; i < 3; ++i) t[i] = st.cur[9 + i];
+  for (int i = 0; i < 12; ++i) Min[i] = st.Min[i];
+  for (int i = 0; i < 9; ++i) K[i] = (double)Kin[9 * b + i];
+  const float* pb = pts + (int64_t)b * 3 * N;
+  const float* qb = uv + (int64_t)b * 2 * N;
+  const int end = (s + 1) * PRF_SLICE < N ? (s + 1) * PRF_SLICE : N;
+  double a[PRF_NACC] = {};
+  int c = 0;
+  for (int i = s * PRF_SLICE + tid; i < end; i += PRF_THREADS) {
+    if (!prf_sel(mask, mask_bytes, (int64_t)b * N + i)) continue;
+    const float X = pb[i], Y = pb[N + i], Z = pb[2 * N + i], u = qb[i], v = qb[N + i];
+    if (!prf_inlier(Min, X, Y, Z, u, v, thr2)) continue;
+    ++c;
+    const double xc0 = R[0] * X + R[1] * Y + R[2] * Z + t[0], xc1 = R[3] * X + R[4] * Y + R[5] * Z + t[1],
+                 xc2 = R[6] * X + R[7] * Y + R[8] * Z + t[2];
+    const double p0 = K[0] * xc0 + K[1] * xc1 + K[2] * xc2, p1 = K[3] * xc0 + K[4] * xc1 + K[5] * xc2,
+                 p2 = K[6] * xc0 + K[7] * xc1 + K[8] * xc2;
+    if (!(p2 > 0.0)) continue;
+    const double iz = 1.0 / p2, pu = p0 * iz, pv = p1 * iz;
+    const double ru = pu - u, rv = pv - v;
+    const double ga[3] = {(K[0] - K[6] * pu) * iz, (K[1] - K[7] * pu) * iz, (K[2] - K[8] * pu) * iz};     // d pu / d xc
+    const double gb[3] = {(K[3] - K[6] * pv) * iz, (K[4] - K[7] * pv) * iz, (K[5] - K[8] * pv) * iz};
+    // d / d omega (left increment): xc x g
+    const double ja[6] = {xc1 * ga[2] - xc2 * ga[1], xc2 * ga[0] - xc0 * ga[2], xc0 * ga[1] - xc1 * ga[0], ga[0], ga[1], ga[2]};
+    const double jb[6] = {xc1 * gb[2] - xc2 * gb[1], xc2 * gb[0] - xc0 * gb[2], xc0 * gb[1] - xc1 * gb[0], gb[0], gb[1], gb[2]};
+    int q = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int cc = r; cc < 6; ++cc) a[q++] += ja[r] * ja[cc] + jb[r] * jb[cc];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) a[21 + r] += ja[r] * ru + jb[r] * rv;
+    a[27] += ru * ru + rv * rv;
+  }
+#pragma unroll
+  for (int q = 0; q < PRF_NACC; ++q) {
+    const double v = prf_wave_sum(a[q]);
+    if (lane == 0) acc[wave][q] = v;
+  }
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+  if (lane == 0) cnt[wave] = c;
+  __syncthreads();
+  const int64_t slot = (int64_t)b * gridDim.x + s;
+  if (tid < PRF_NACC) {
+    double v = acc[0][tid];
+    for (int w = 1; w < PRF_THREADS / 64; ++w) v += acc[w][tid];
+    slots[slot * PRF_NACC + tid] = v;
+  }
+  if (tid == 64) cslots[slot] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+}
+
+__global__ __launch_bounds__(64) void prf_step_kernel(int it, int iters, int nslice, PrfState* __restrict__ state,
+                                                      const double* __restrict__ slots, const int32_t* __restrict__ cslots) {
+  __shared__ double tot[PRF_NACC];
+  __shared__ int wc;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  PrfState& st = state[b];
+  if (st.stop) return;
+  if (tid < PRF_NACC) {
+    double v = 0.0;
+    for (int s = 0; s < nslice; ++s) v += slots[((int64_t)b * nslice + s) * PRF_NACC + tid];       // slice order
+    tot[tid] = v;
+  } else if (tid == PRF_NACC) {
+    int c = 0;
+    for (int s = 0; s < nslice; ++s) c += cslots[(int64_t)b * nslice + s];
+    wc = c;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  if (it == 0) {
+    st.wcount = wc;
+    if (wc < 4) { st.status = 1; st.stop = 1; return; }
+    bool fin = true;
+    for (int q = 0; q < PRF_NACC; ++q) fin = fin && isfinite(tot[q]);
+    if (!fin) { st.status = 2; st.stop = 1; return; }
+  }
+  const double cost = tot[27];
+  if (it > 0 && !(cost < st.cost_prev)) {
+    for (int i = 0; i < 12; ++i) st.cur[i] = st.prev[i];                // the step did not lower the cost: undo it
+    st.stop = 1;
+    return;
+  }
+  if (it == iters) { st.stop = 1; return; }
+  double g[6], dx[6];
+  for (int r = 0; r < 6; ++r) g[r] = -tot[21 + r];
+  bool ok = prf_chol6(tot, g, dx);
+  double nw[12];
+  if (ok) {
+    double E[9];
+    prf_expso3(dx, E);
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) nw[3 * i + j] = E[3 * i] * st.cur[j] + E[3 * i + 1] * st.cur[3 + j] + E[3 * i + 2] * st.cur[6 + j];
+      nw[9 + i] = E[3 * i] * st.cur[9] + E[3 * i + 1] * st.cur[10] + E[3 * i + 2] * st.cur[11] + dx[3 + i];
+    }
+    for (int i = 0; i < 12; ++i) ok = ok && isfinite(nw[i]);
+  }
+  if (!ok) {
+    if (it == 0) st.status = 2;                                          // nothing to refine with: the call returns pose_in
+    st.stop = 1;
+    return;
+  }
+  for (int i = 0; i < 12; ++i) { st.prev[i] = st.cur[i]; st.cur[i] = nw[i]; }
+  st.cost_prev = cost;
+}
+
+__global__ __launch_bounds__(PRF_THREADS) void prf_count_kernel(const float* __restrict__ pts, const float* __restrict__ uv,
+                                                                const void* __restrict__ mask, int mask_bytes,
+                                                                const float* __restrict__ Kin, int N, float thr2,
+                                                                const PrfState* __restrict__ state, int32_t* __restrict__ cslots) {
+  __shared__ int cnt[PRF_THREADS / 64];
+  const int b = blockIdx.y, s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const PrfState& st = state[b];
+  if (st.status != 0) return;
+  double K[9];
+  for (int i = 0; i < 9; ++i) K[i] = (double)Kin[9 * b + i];
+  float M[12];
+  prf_kmat(K, st.cur, M);
+  const float* pb = pts + (int64_t)b * 3 * N;
+  const float* qb = uv + (int64_t)b * 2 * N;
+  const int end = (s + 1) * PRF_SLICE < N ? (s + 1) * PRF_SLICE : N;
+  int c = 0;
+  for (int i = s * PRF_SLICE + tid; i < end; i += PRF_THREADS)
+    if (prf_sel(mask, mask_bytes, (int64_t)b * N + i)) c += prf_inlier(M, pb[i], pb[N + i], pb[2 * N + i], qb[i], qb[N + i], thr2);
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+  if (lane == 0) cnt[wave] = c;
+  __syncthreads();
+  if (tid == 0) cslots[(int64_t)b * gridDim.x + s] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+}
+
+__global__ __launch_bounds__(64) void prf_final_kernel(const float* __restrict__ pose_in, int nslice, const PrfState* __restrict__ state,
+                                                       const int32_t* __restrict__ cslots, float* __restrict__ pose,
+                                                       int32_t* __restrict__ inliers, int32_t* __restrict__ status) {
+  __shared__ int sh_use, sh_rc;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const PrfState& st = state[b];
+  if (tid == 0) {
+    int rc = 0, use = 0;
+    if (st.status == 0) {
+      for (int s = 0; s < nslice; ++s) rc += cslots[(int64_t)b * nslice + s];
+      bool fin = true;
+      for (int i = 0; i < 12; ++i) fin = fin && isfinite(st.cur[i]);
+      use = fin && rc >= st.wcount;
+    }
+    sh_use = use;
+    sh_rc = rc;
+    inliers[b] = use ? rc : st.wcount;
+    status[b] = st.status != 0 ? st.status : (use ? 0 : 2);
+  }
+  __syncthreads();
+  if (tid < 16) {
+    const int r = tid >> 2, c = tid & 3;
+    float val = pose_in[16 * b + tid];
+    if (sh_use) val = r == 3 ? (c == 3 ? 1.f : 0.f) : (float)(c < 3 ? st.cur[3 * r + c] : st.cur[9 + r]);
+    pose[16 * b + tid] = val;
+  }
+}
+
+struct PrfWs { int64_t state, slots, cslots, total; };
+
+inline int64_t prf_up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+
+inline PrfWs prf_layout(int B, int N) {
+  PrfWs L;
+  const int64_t nslice = ((int64_t)N + PRF_SLICE - 1) / PRF_SLICE;
+  L.state = 0;
+  L.slots = L.state + prf_up16((int64_t)B * sizeof(PrfState));
+  L.cslots = L.slots + prf_up16((int64_t)B * nslice * PRF_NACC * 8);
+  L.total = L.cslots + prf_up16((int64_t)B * nslice * 4);
+  return L;
+}
+
+}  // namespace
+
+extern "C" int64_t cmr_pnp_refine_workspace_bytes(int B, int N) { return B <= 0 || N <= 0 ? 0 : prf_layout(B, N).total; }
+
+extern "C" int cmr_pnp_refine_f32(const float* pts, const float* uv, const void* mask, int mask_bytes, const float* K, const float* pose_in,
+                                  int B, int N, float thr, int iters, float* pose, int32_t* inliers, int32_t* status, void* ws,
+                                  int64_t ws_bytes, hipStream_t stream) {
+  CMR_REQUIRE(pts && uv && mask && K && pose_in && pose && inliers && status && ws);
+  CMR_REQUIRE(B > 0 && B <= 65535 && N > 0 && (int64_t)N <= (int64_t)65535 * PRF_SLICE && iters >= 0 && iters <= 1000);
+  CMR_REQUIRE(mask_bytes == 1 || mask_bytes == 8);
+  CMR_REQUIRE(thr > 0.f && __builtin_isfinite(thr));
+  CMR_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15u) == 0);
+  CMR_REQUIRE(ws_bytes >= cmr_pnp_refine_workspace_bytes(B, N));
+  const PrfWs L = prf_layout(B, N);
+  PrfState* state = (PrfState*)((char*)ws + L.state);
+  double* slots = (double*)((char*)ws + L.slots);
+  int32_t* cslots = (int32_t*)((char*)ws + L.cslots);
+  const int nslice = (N + PRF_SLICE - 1) / PRF_SLICE;
+  const float thr2 = thr * thr;
+  hipLaunchKernelGGL(prf_init_kernel, dim3(B), dim3(64), 0, stream, pose_in, K, state);
+  for (int it = 0; it <= iters; ++it) {
+    hipLaunchKernelGGL(prf_accum_kernel, dim3(nslice, B), dim3(PRF_THREADS), 0, stream, pts, uv, mask, mask_bytes, K, N, thr2,
+                       (const PrfState*)state, slots, cslots);
+    hipLaunchKernelGGL(prf_step_kernel, dim3(B), dim3(64), 0, stream, it, iters, nslice, state, (const double*)slots, (const int32_t*)cslots);
+  }
+  hipLaunchKernelGGL(prf_count_kernel, dim3(nslice, B), dim3(PRF_THREADS), 0, stream, pts, uv, mask, mask_bytes, K, N, thr2,
+                     (const PrfState*)state, cslots);
+  hipLaunchKernelGGL(prf_final_kernel, dim3(B), dim3(64), 0, stream, pose_in, nslice, (const PrfState*)state, (const int32_t*)cslots, pose,
+                     inliers, status);
+  return cmr_launch_status();
+}

@@ -85,6 +85,23 @@ def to_disentangled(poses, pcd, data=None):
 
 
 @torch.no_grad()
+def from_disentangled(poses, pcd, data=None):
+    """The inverse of to_disentangled (port extension, DESIGN.md 4n): t <- t + mu - R mu with mu the centroid to_disentangled uses;
+    mutates and returns `poses`.  data (optional): the centroid to_disentangled left in data['_cmr_centroid'] is reused when it
+    belongs to `pcd`.  Twelve numbers per sample: torch ops on the poses' device (CPU tensors work too)."""
+    cen = data.get('_cmr_centroid') if data is not None else None
+    if cen is not None and cen[0] is pcd and cen[1].device == poses.device:
+        mu = cen[1].view(poses.shape[0], -1)[:, 0:3]
+    elif pcd.is_cuda:
+        mu = _centroid(pcd).view(poses.shape[0], -1)[:, 0:3].to(poses.device)
+    else:
+        mu = pcd[:, 0:3, :].float().mean(2).to(poses.device)
+    mu = mu.to(poses.dtype)
+    poses[:, 0:3, 3] += mu - torch.matmul(poses[:, 0:3, 0:3], mu.unsqueeze(2)).squeeze(2)
+    return poses
+
+
+@torch.no_grad()
 def observation_from_a_pose(data, RT, materialize_state_2d=True):
     """-> (state_2d [B,128,h,w], state_3d [B,5,N]) as views of channels-last / row storage.
     New storage is returned on every call (the reference's replay buffer keeps them).

@@ -257,6 +257,47 @@ class MultiHeadModel(Planned):
             data_batch['pnp_inliers'] = inliers
             data_batch['pnp_status'] = status
 
+    def refine_pose_from_matches(self, data_batch, pose=None, radii=(6, 3, 2), thrs=(4.0, 2.0, 1.0), max_dist=None, iters=10, mask=None,
+                                 img_overlap=None):
+        """Port extension: polish a pose from anywhere -- pose_from_matches' 'pnp_pose' (the default) or the agent's final
+        pose through environment.from_disentangled -- against the geometric features.  For each (radius, thr) in turn: ops.guided_match
+        under the current pose (every point of `mask`, default 'pc_overlap_pred', is matched inside the (2 radius + 1)^2 window round its
+        projection), correspondences = the kept rows (and, when img_overlap bool / uint8 [B, h, w] is given, whose matched pixel lies
+        inside it), uv = (p % w, p // w), then ops.pnp_refine from the current pose with inlier threshold thr.  pose: float32 [B, 4, 4]
+        mapping 'pc' into the camera frame (as 'P').  Sets 'refined_pose' [B, 4, 4], 'refined_inliers' [B] and 'refined_status' [B] (of the
+        last round; ops.pnp_refine's codes) and 'guided_counts' int32 [rounds, B, 4] (selected, in view, kept, kept inliers per round).
+        Not called by forward."""
+        radii, thrs = tuple(radii), tuple(thrs)
+        if len(radii) != len(thrs) or not radii:
+            raise ValueError("refine_pose_from_matches: radii and thrs must be non-empty and of equal length, got %r / %r" % (radii, thrs))
+        with torch.no_grad():
+            pc = data_batch['pc'].float().contiguous()
+            dev = pc.device
+            feat, img = _geo_rows(data_batch)
+            B, h, w, _ = img.shape
+            N = pc.shape[2]
+            cur = (data_batch['pnp_pose'] if pose is None else pose).to(dev).float().contiguous()
+            sel = (data_batch['pc_overlap_pred'] if mask is None else mask).to(dev).contiguous()
+            K = data_batch['K'].to(dev).float()
+            K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3).contiguous()
+            xy = _gt_xy(data_batch, dev) if ('point_xy_float_all' in data_batch or 'pc_in_cam_space' in data_batch) else None
+            ov = None if img_overlap is None else img_overlap.to(dev).reshape(B, -1).bool()
+            counts, inliers, status = [], None, None
+            for radius, thr in zip(radii, thrs):
+                idx, keep, cnt, _, _ = ops.guided_match(pc, feat, img, sel, cur, K, radius, max_dist=max_dist or 0.0, gt_xy=xy,
+                                                        thr=MATCH_INLIER_THRES)
+                counts.append(cnt)
+                p = idx.view(B, N).long().clamp(min=0)
+                use = keep.view(B, N)
+                if ov is not None:
+                    use = use & torch.gather(ov, 1, p)
+                uv = torch.stack([p % w, torch.div(p, w, rounding_mode='floor')], 1).float().contiguous()
+                cur, inliers, status = ops.pnp_refine(pc, uv, use.contiguous(), K, cur, thr=thr, iters=iters)
+            data_batch['refined_pose'] = cur
+            data_batch['refined_inliers'] = inliers
+            data_batch['refined_status'] = status
+            data_batch['guided_counts'] = torch.stack(counts)
+
     def forward_cl(self, data_batch):
         cl = self.encoder_decoder.forward_cl(data_batch)
         # four independent branches (2 heads x {points, pixels}): one flat fork, the pixel convolutions of the

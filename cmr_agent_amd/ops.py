@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI (include/cmr_hip.h).  PyTorch is used for device
 memory and the current HIP stream only; every computation is a HIP kernel.  Arguments are
 2-D row views ([rows, C], unit inner stride, arbitrary row stride) unless stated otherwise."""
+import math
 import os
 
 import torch
@@ -1035,6 +1036,117 @@ def pnp_ransac(pts, uv, mask, K, n_hyp=1024, thr=1.0, seed=0, refine_iters=10, w
     _lib.call("cmr_pnp_ransac_f32", _p(pts), _p(uv), _p(mask), mask.element_size(), _p(K), B, N, n_hyp, float(thr), seed, refine_iters,
               _p(pose), _p(inliers), _p(status), _p(hyp), _p(ws), nb, _stream())
     return (pose, inliers, status, hyp) if want_hyp_inliers else (pose, inliers, status)
+
+
+GUIDED_MAX_RADIUS = 16      # csrc/guided_match.hip GM_MAX_RADIUS
+
+
+def _is_int(v):
+    """An integer-valued number that is not a bool; inf, NaN and non-numbers are simply not one (no OverflowError / TypeError)."""
+    try:
+        return not isinstance(v, bool) and math.isfinite(v) and int(v) == v
+    except (TypeError, ValueError, OverflowError):
+        return False
+
+
+def guided_match(pts, pc_feat_rows, img_feat_nhwc, mask, pose, K, radius, max_dist=0.0, gt_xy=None, thr=3.0, want_dist=False,
+                 want_proj=False):
+    """Nearest pixel feature of every selected point inside the (2 radius + 1)^2 window round its projection under `pose`
+    (include/cmr_hip.h cmr_guided_match_f32): pts float32 [B, 3, N] (data['pc']), pc_feat rows [B*N, 64], img_feat NHWC
+    [B, h, w, 64], mask [B, N] / [B*N] of bool / uint8 / int64, pose float32 [B, 4, 4] mapping pts into the camera frame, K float32
+    [B, 3, 3] for the h x w map, 0 <= radius <= GUIDED_MAX_RADIUS, max_dist >= 0 (0 = off), optional gt_xy float32 [B, 2, N] with thr.
+    -> (idx int32 [B*N]: pixel p = y * w + x or -1 (unselected / out of view), keep bool [B*N], counts int32 [B, 4] = (selected, in view,
+    kept, kept inliers), dist float32 [B*N] or None (want_dist), proj float32 [B, 2, N] = (u, v) as the kernel computed them or None)."""
+    if pts.dim() != 3 or pts.shape[1] != 3:
+        raise ValueError("guided_match: pts must be [B, 3, N], got %s" % (tuple(pts.shape),))
+    B, _, N = pts.shape
+    if pc_feat_rows.dim() != 2 or img_feat_nhwc.dim() != 4:
+        raise ValueError("guided_match: point rows must be 2-D [B*N, C] and pixel features 4-D [B, h, w, C], got %s / %s" % (
+            tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
+    Bi, h, w, C = img_feat_nhwc.shape
+    if C != 64 or pc_feat_rows.shape[1] != 64:
+        raise ValueError("guided_match: feature width must be 64, got %d / %d" % (pc_feat_rows.shape[1], C))
+    if Bi != B or pc_feat_rows.shape[0] != B * N:
+        raise ValueError("guided_match: pts %s, point rows %s and pixel features %s do not agree on B and N" % (
+            tuple(pts.shape), tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
+    if pts.dtype != f32 or pc_feat_rows.dtype != f32 or img_feat_nhwc.dtype != f32 or pose.dtype != f32 or K.dtype != f32:
+        raise ValueError("guided_match: pts, features, pose and K must be float32, got %s / %s / %s / %s / %s" % (
+            pts.dtype, pc_feat_rows.dtype, img_feat_nhwc.dtype, pose.dtype, K.dtype))
+    if tuple(pose.shape) != (B, 4, 4):
+        raise ValueError("guided_match: pose must be [%d, 4, 4], got %s" % (B, tuple(pose.shape)))
+    if tuple(K.shape) != (B, 3, 3):
+        raise ValueError("guided_match: K must be [%d, 3, 3], got %s" % (B, tuple(K.shape)))
+    if B < 1 or B > GRID_Y_MAX or N < 1 or N > GRID_Y_MAX * 256 or h < 1 or w < 1 or h * w > 1 << 24:
+        raise ValueError("guided_match: need 1 <= B <= %d, 1 <= N <= %d and a map of 1 .. 2^24 pixels, got B=%d N=%d map %d x %d" % (
+            GRID_Y_MAX, GRID_Y_MAX * 256, B, N, h, w))
+    if mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N:
+        raise ValueError("guided_match: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (B * N, mask.dtype, tuple(mask.shape)))
+    if gt_xy is not None and (gt_xy.dtype != f32 or tuple(gt_xy.shape) != (B, 2, N)):
+        raise ValueError("guided_match: gt_xy must be float32 [%d, 2, %d], got %s %s" % (B, N, gt_xy.dtype, tuple(gt_xy.shape)))
+    if not _is_int(radius) or not 0 <= radius <= GUIDED_MAX_RADIUS:
+        raise ValueError("guided_match: radius must be an integer in [0, %d], got %r" % (GUIDED_MAX_RADIUS, radius))
+    if not 0.0 <= float(max_dist) < float("inf"):
+        raise ValueError("guided_match: max_dist must be finite and >= 0 (0 = no bound), got %r" % (max_dist,))
+    ts = [t for t in (pts, pc_feat_rows, img_feat_nhwc, mask, pose, K, gt_xy) if t is not None]
+    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
+        raise ValueError("guided_match: every tensor must be a contiguous tensor on the same GPU")
+    if pc_feat_rows.data_ptr() % 16 or img_feat_nhwc.data_ptr() % 16:
+        raise ValueError("guided_match: feature rows must be 16-byte aligned")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    dev = pts.device
+    idx = torch.empty((B * N,), dtype=torch.int32, device=dev)
+    keep = torch.empty((B * N,), dtype=torch.uint8, device=dev)
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    dist = torch.empty((B * N,), dtype=f32, device=dev) if want_dist else None
+    proj = torch.empty((B, 2, N), dtype=f32, device=dev) if want_proj else None
+    nb = _lib.load().cmr_guided_match_workspace_bytes(B, N)
+    ws = _ws(nb, dev)
+    _lib.call("cmr_guided_match_f32", _p(pts), _p(pc_feat_rows), _p(img_feat_nhwc), C, B, N, h, w, _p(mask), mask.element_size(), _p(pose),
+              _p(K), int(radius), float(max_dist), _p(gt_xy), float(thr), _p(idx), _p(keep), _p(counts), _p(dist), _p(proj), _p(ws), nb,
+              _stream())
+    return idx, keep.view(torch.bool), counts, dist, proj
+
+
+def pnp_refine(pts, uv, mask, K, pose, thr=1.0, iters=10):
+    """Gauss-Newton refinement of a given pose on 2-D/3-D correspondences (include/cmr_hip.h cmr_pnp_refine_f32): pts
+    float32 [B, 3, N], uv float32 [B, 2, N], mask [B, N] / [B*N] of bool / uint8 / int64, K float32 [B, 3, 3], pose float32 [B, 4, 4]
+    (finite; maps pts into the camera frame); the rows that are inliers of `pose` within thr pixels are the working set, up to iters steps.
+    -> (pose float32 [B, 4, 4], inliers int32 [B], status int32 [B]: 0 refined, 1 fewer than 4 rows in the working set, 2 refinement
+    not kept; 1 and 2 return the input pose)."""
+    if pts.dim() != 3 or pts.shape[1] != 3:
+        raise ValueError("pnp_refine: pts must be [B, 3, N], got %s" % (tuple(pts.shape),))
+    B, _, N = pts.shape
+    if tuple(uv.shape) != (B, 2, N):
+        raise ValueError("pnp_refine: uv must be [%d, 2, %d], got %s" % (B, N, tuple(uv.shape)))
+    if tuple(K.shape) != (B, 3, 3):
+        raise ValueError("pnp_refine: K must be [%d, 3, 3], got %s" % (B, tuple(K.shape)))
+    if tuple(pose.shape) != (B, 4, 4):
+        raise ValueError("pnp_refine: pose must be [%d, 4, 4], got %s" % (B, tuple(pose.shape)))
+    if pts.dtype != f32 or uv.dtype != f32 or K.dtype != f32 or pose.dtype != f32:
+        raise ValueError("pnp_refine: pts, uv, K and pose must be float32, got %s / %s / %s / %s" % (pts.dtype, uv.dtype, K.dtype, pose.dtype))
+    if mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N:
+        raise ValueError("pnp_refine: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (B * N, mask.dtype, tuple(mask.shape)))
+    if B < 1 or B > GRID_Y_MAX or N < 1 or N > GRID_Y_MAX * 1024:
+        raise ValueError("pnp_refine: need 1 <= B <= %d and 1 <= N <= %d, got B=%d N=%d" % (GRID_Y_MAX, GRID_Y_MAX * 1024, B, N))
+    if not (float(thr) > 0.0 and float(thr) < float("inf")):
+        raise ValueError("pnp_refine: thr must be a finite positive number, got %r" % (thr,))
+    if not _is_int(iters) or not 0 <= iters <= 1000:
+        raise ValueError("pnp_refine: iters must be an integer in [0, 1000], got %r" % (iters,))
+    ts = (pts, uv, mask, K, pose)
+    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
+        raise ValueError("pnp_refine: every tensor must be a contiguous tensor on the same GPU")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    dev = pts.device
+    out = torch.empty((B, 4, 4), dtype=f32, device=dev)
+    inliers = torch.empty((B,), dtype=torch.int32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    nb = _lib.load().cmr_pnp_refine_workspace_bytes(B, N)
+    ws = _ws(nb, dev)
+    _lib.call("cmr_pnp_refine_f32", _p(pts), _p(uv), _p(mask), mask.element_size(), _p(K), _p(pose), B, N, float(thr), int(iters), _p(out),
+              _p(inliers), _p(status), _p(ws), nb, _stream())
+    return out, inliers, status
 
 
 def expert_action(pose_source, pose_target, r_steps, t_steps, six_dof):

@@ -148,6 +148,14 @@ WORK = {
     "cmr_argmax_rows_f32": lambda a: (0, a["outer"] * a["inner"] * (F * a["n"] + 8)),
     "cmr_softmax2_f32": lambda a: (0, a["rows"] * 14),
     "cmr_l2norm64_f32": lambda a: (0, a["rows"] * 512),
+    # DESIGN.md 4n, from the shapes alone (the selected / in-view / working-set counts live on the device): every row taken as selected and
+    # in view.  guided match: per row the point (12 B), its feature row and (2r + 1)^2 gathered pixel rows of 256 B, ~16 B of results;
+    # 3 FLOP per channel and pixel (subtract, multiply, add).  refine: iters + 2 passes over the rows (20 B + mask each); per row and
+    # pass ~60 FLOP of projection and Jacobian + 2 x 2 x 28 for the sums, in float64.
+    "cmr_guided_match_f32": lambda a: (3.0 * 64 * (2 * a["radius"] + 1) ** 2 * a["B"] * a["N"],
+                                       a["B"] * a["N"] * (12 + a["mask_bytes"] + 256 + 256 * (2 * a["radius"] + 1) ** 2 + 16)),
+    "cmr_pnp_refine_f32": lambda a: ((60.0 + 112.0) * (a["iters"] + 1) * a["B"] * a["N"],
+                                     (a["iters"] + 2) * a["B"] * a["N"] * (20 + a["mask_bytes"])),
     # training direction (Train_Agent.py:296-305, Train_Geo.py:166-174): weight gradients as GEMMs over the minibatch's pixels / rows
     "cmr_conv3x3_wgrad_f32": lambda a: (2.0 * 9 * a["Cin"] * a["Cout"] * a["B"] * a["H"] * a["W"],
                                         F * (a["B"] * a["H"] * a["W"] * (a["Cin"] + a["Cout"]) + 9 * a["Cin"] * a["Cout"])),

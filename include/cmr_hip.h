@@ -383,6 +383,47 @@ int cmr_pnp_ransac_f32(const float* pts, const float* uv, const void* mask, int 
                        float thr, uint32_t seed, int refine_iters, float* pose, int32_t* inliers, int32_t* status, int32_t* hyp_inliers,
                        void* ws, int64_t ws_bytes, hipStream_t stream);
 
+/* Pose-guided matching (port extension; ops.guided_match, MultiHeadModel.refine_pose_from_matches, Test_Geo.py --guided,
+ * Test_Agent.py --refine): the nearest pixel feature of every selected point inside a window round its projection under a given pose.
+ * pts f32 [B][3][N] (data['pc']), pc_feat rows [B*N][C], img_feat [B][h*w][C], C must be 64, mask [B*N] with mask_bytes 1 or 8, pose f32
+ * [B][4][4] mapping pts into the camera frame (data['P'], pnp_pose), K f32 [B][3][3] for the h x w map (h*w <= 2^24), 0 <= radius <= 16,
+ * max_dist >= 0 (0 = off).  Per sample and selected row n, all in fp32: X_c = R x + t, p = K X_c, u = p0 / p2, v = p1 / p2, centre
+ * (cx, cy) = (rint u, rint v), half to even.  The row is IN VIEW iff p2 > 0, u and v are finite and [cx - r, cx + r] x [cy - r, cy + r]
+ * meets the map (decided on the floats); the window is clipped to the map.
+ *   idx int32 [B*N]    the pixel p = y * w + x of the clipped window with the least L2 feature distance, lowest p on a tie; -1 for an
+ *                      unselected or out-of-view row;
+ *   dist (optional) f32 [B*N]  that distance, the direct sum of (a - b)^2 in fp32 (order: DESIGN.md 4n), NaN where idx = -1;
+ *   proj (optional) f32 [B][2][N]  (u, v) as computed, NaN for unselected rows and rows with p2 <= 0;
+ *   keep u8 [B*N]      in view and (max_dist <= 0 or dist <= max_dist).  A window without one finite score (NaN features) gives
+ *                      idx = the window's first pixel and dist = +inf, so it is kept only when max_dist is off: feed finite features;
+ *   counts int32 [B][4] = {selected, in view, kept, kept and inlier}; inlier as cmr_feat_match_f32: gt_xy (optional, f32 [B][2][N])
+ *                      finite and within thr of the matched pixel.
+ * Everything is enqueued on the stream (no host round trip); every output element is a plain store by the one thread / 16-lane group
+ * that owns the row and the counts are integer atomics, so two calls agree bit for bit and a sample depends on its own rows only.
+ * Workspace: cmr_guided_match_workspace_bytes(B, N), 16-byte aligned. */
+int64_t cmr_guided_match_workspace_bytes(int B, int N);
+int cmr_guided_match_f32(const float* pts, const float* pc_feat, const float* img_feat, int C, int B, int N, int h, int w, const void* mask,
+                         int mask_bytes, const float* pose, const float* K, int radius, float max_dist, const float* gt_xy, float thr,
+                         int32_t* idx, uint8_t* keep, int32_t* counts, float* dist, float* proj, void* workspace, int64_t workspace_bytes,
+                         hipStream_t stream);
+
+/* Gauss-Newton pose refinement from a given pose (port extension; ops.pnp_refine): cmr_pnp_ransac_f32's refinement step,
+ * startable from any pose, the accumulation split over the correspondences.  pts f32 [B][3][N], uv f32 [B][2][N], mask [B*N] with
+ * mask_bytes 1 or 8, K f32 [B][3][3], pose_in f32 [B][4][4] (finite), thr > 0, 0 <= iters <= 1000.  Per sample: the WORKING SET is fixed
+ * once -- the selected rows that are inliers of K[R|t] of pose_in under cmr_pnp_ransac_f32's fp32 predicate; up to iters Gauss-Newton
+ * steps on it (left increment, J^T J, J^T r and cost in float64 summed in a fixed order, 6x6 Cholesky; a step is kept only if the next
+ * evaluation's cost is lower, else undone and the loop stops); the result is recounted over ALL selected rows and kept if that count is
+ * >= the working set's size.  pose f32 [B][4][4]; inliers int32 [B]; status int32 [B]: 0 = pose is the refined pose (iters = 0: pose_in
+ * and its count), 1 = fewer than 4 rows in the working set (pose = pose_in, inliers = that number), 2 = refinement not kept: non-finite
+ * sums or a failed first factorisation, or the recount dropped (pose = pose_in, inliers = the working set's size).  A factorisation
+ * counts as failed when a pivot is <= 1e-13 of its diagonal entry (cmr_pnp_ransac_f32 asks only for > 0); the same test ends the loop
+ * at a later step too, and then the pose accepted so far goes to the recount (status 0).  3 + 2 (iters + 1) launches whatever the data, no atomics, no host round trip; two calls
+ * agree bit for bit and a sample depends on its own rows only.  Workspace: cmr_pnp_refine_workspace_bytes(B, N), 16-byte aligned. */
+int64_t cmr_pnp_refine_workspace_bytes(int B, int N);
+int cmr_pnp_refine_f32(const float* pts, const float* uv, const void* mask, int mask_bytes, const float* K, const float* pose_in, int B,
+                       int N, float thr, int iters, float* pose, int32_t* inliers, int32_t* status, void* ws, int64_t ws_bytes,
+                       hipStream_t stream);
+
 /* ---- rollout ops of the training loop ---------------------------------------- */
 
 /* environment.py:143-176 (expert): residual pose target * source^-1 -> extrinsic-xyz Euler angles (folded back when the
