@@ -11,7 +11,10 @@ reference's: RTE / RRE per pair and registration recall (RTE < 5 m and RRE < 10 
 the lattice of its step tables, is polished against the geometric features -- a clone of it through env.from_disentangled, rounds of
 (guided match inside the (2R + 1)^2 window -> Gauss-Newton with inlier threshold T; MultiHeadModel.refine_pose_from_matches), back
 through env.to_disentangled.  Per pair one extra line "refined <RTE> <RRE>", and after the closing block the same three lines again with
-the prefix "Refined ".  Without the flag the output is unchanged."""
+the prefix "Refined ".  Without the flag the output is unchanged.
+
+--subpixel (with --refine): every round's correspondences carry sub-pixel positions from a parabola fit on the feature
+distances round the matched pixel (cmr_match_subpixel_f32) instead of the integer pixel.  The lines printed are the same."""
 import argparse
 import json
 import os
@@ -55,7 +58,10 @@ def main():
     ap.add_argument('--refine', type=str, default=None, help="refine the agent's final pose by guided matching, one round per window radius R[,R...]")
     ap.add_argument('--guided-thr', type=str, default=None, help="with --refine: inlier threshold in pixels per round T[,T...] (default: R / 1.5 per round, at least 1)")
     ap.add_argument('--guided-max-dist', type=float, default=None, help="with --refine: keep a guided match only when its feature distance is <= D")
+    ap.add_argument('--subpixel', action='store_true', help="with --refine: sub-pixel match positions (parabola fit on the feature distances) in every round")
     args = ap.parse_args()
+    if args.subpixel and args.refine is None:
+        ap.error("--subpixel belongs to --refine")
     radii = thrs = None
     if args.refine is not None:
         radii, thrs = guided_rounds(ap, args.refine, args.guided_thr, ops.GUIDED_MAX_RADIUS)
@@ -97,7 +103,8 @@ def main():
             rre.append(r_diff)
             if radii is not None:
                 start = env.from_disentangled(pose_source.clone(), data['pc'], data=data)
-                geo_model.refine_pose_from_matches(data, pose=start, radii=radii, thrs=thrs, max_dist=args.guided_max_dist)
+                geo_model.refine_pose_from_matches(data, pose=start, radii=radii, thrs=thrs, max_dist=args.guided_max_dist,
+                                                   subpixel=args.subpixel)
                 ref = env.to_disentangled(data['refined_pose'].clone(), data['pc'], data=data)
                 t_diff, r_diff = get_P_diff(ref[0].cpu().numpy(), pose_target[0].cpu().numpy())
                 print("refined", t_diff, r_diff)

@@ -26,6 +26,11 @@ inlier ratio beside the unfiltered one.  Without these flags the output is uncha
 MultiHeadModel.refine_pose_from_matches).  Per pair one extra line "refined <RTE> <RRE>" after the pair's "RTE RRE" line, and after the
 closing block the same three lines again with the prefix "Refined ".  Without the flag the output is unchanged.
 
+--subpixel (with --pnp): the correspondences handed to PnP, and to every --guided round, carry sub-pixel positions from a
+parabola fit on the feature distances round the matched pixel (cmr_match_subpixel_f32) instead of the integer pixel, and each batch prints
+one extra line "subpixel fitted <fitted> of <matched> IR@0.5 <integer> -> <sub-pixel>": the PnP correspondences fitted on both axes and
+their share within 0.5 px (at 1/4 scale) of the projected point before and after the fit.  Without the flag the output is unchanged.
+
 Pairs come from the synthetic generator (cmr_agent_amd.utils.synthetic) unless --data-root names a dataset in the reference's layout
 (its 'test' split), and the weights are the deterministic hash fill unless --geo-ckpt points at a reference-format state_dict."""
 import argparse
@@ -82,6 +87,7 @@ def main():
     ap.add_argument('--guided', type=str, default=None, help="with --pnp: refine the PnP pose by guided matching, one round per window radius R[,R...]")
     ap.add_argument('--guided-thr', type=str, default=None, help="with --guided: inlier threshold in pixels per round T[,T...] (default: R / 1.5 per round, at least 1)")
     ap.add_argument('--guided-max-dist', type=float, default=None, help="with --guided: keep a guided match only when its feature distance is <= D")
+    ap.add_argument('--subpixel', action='store_true', help="with --pnp: sub-pixel match positions (parabola fit on the feature distances) for PnP and the --guided rounds")
     args = ap.parse_args()
     filtered = args.mutual or args.ratio is not None
     if filtered and not args.pnp:
@@ -90,6 +96,8 @@ def main():
         ap.error("--ratio must lie in (0, 1]")
     if args.excl_radius < 0:
         ap.error("--excl-radius must be >= 0")
+    if args.subpixel and not args.pnp:
+        ap.error("--subpixel refines the matches that go into PnP: give --pnp as well")
     radii = thrs = None
     if args.guided is not None:
         if not args.pnp:
@@ -133,15 +141,20 @@ def main():
             print(np.mean(r1), np.mean(r2))
             if args.pnp:
                 geo_model.pose_from_matches(data, img_overlap=img_overlap, mutual=args.mutual, ratio=args.ratio,
-                                            excl_radius=args.excl_radius)
+                                            excl_radius=args.excl_radius, subpixel=args.subpixel)
                 if filtered:
                     fc = data['pnp_filter_counts'].double().cpu().numpy().sum(0)
                     with np.errstate(invalid="ignore", divide="ignore"):
                         print("kept", int(fc[1]), "of", int(fc[0]), "IR", fc[3] / fc[0], "->", fc[2] / fc[1])
+                if args.subpixel:
+                    sc = data['pnp_subpixel_counts'].double().cpu().numpy().sum(0)
+                    with np.errstate(invalid="ignore", divide="ignore"):
+                        print("subpixel fitted", int(sc[1]), "of", int(sc[0]), "IR@0.5", sc[2] / sc[0], "->", sc[3] / sc[0])
                 pred = env.to_disentangled(data['pnp_pose'].clone(), data['pc'])
                 gt = env.to_disentangled(data['P'].to(dev).float().clone(), data['pc'])
                 if radii is not None:
-                    geo_model.refine_pose_from_matches(data, radii=radii, thrs=thrs, max_dist=args.guided_max_dist, img_overlap=img_overlap)
+                    geo_model.refine_pose_from_matches(data, radii=radii, thrs=thrs, max_dist=args.guided_max_dist, img_overlap=img_overlap,
+                                                       subpixel=args.subpixel)
                     ref = env.to_disentangled(data['refined_pose'].clone(), data['pc'])
                 for b in range(pred.shape[0]):
                     t_diff, r_diff = get_P_diff(pred[b].cpu().numpy(), gt[b].cpu().numpy())

@@ -85,6 +85,7 @@ class OverlapDetectionHead(_Head):
 
 
 MATCH_INLIER_THRES = 3.0       # pixels at 1/4 scale (MultiHeadModel.py:212, 313; Test_Geo.py:75)
+SUBPIXEL_INLIER_THRES = 0.5    # pixels at 1/4 scale: the threshold of the two inlier counts of ops.match_subpixel
 
 
 def point_xy_float_all(K, pc_in_cam_space):
@@ -211,7 +212,7 @@ class MultiHeadModel(Planned):
             data_batch['matching_ir_per_sample'] = _ratio(counts, 1, 0)
 
     def pose_from_matches(self, data_batch, img_overlap=None, n_hyp=1024, thr=1.0, seed=0, refine_iters=10, mutual=False, ratio=None,
-                          excl_radius=2, max_dist=None):
+                          excl_radius=2, max_dist=None, subpixel=False):
         """Port extension (no counterpart in the reference): the camera pose from the geometric model's own matches, PnP
         inside RANSAC (ops.pnp_ransac).  Correspondences: the points of 'pc_overlap_pred', each with its nearest pixel feature
         (match_features), kept only where that pixel lies inside the predicted image overlap (Test_Geo.py's IR2 set); the pixel p gives
@@ -222,7 +223,10 @@ class MultiHeadModel(Planned):
         match_features_filtered and only the kept ones go on -- mutual nearest neighbours, d1 <= ratio * d2 with d2 taken outside the
         (2 excl_radius + 1)^2 window of the best pixel, d1 <= max_dist -- and 'pnp_used' int [B] is the number of correspondences handed
         to PnP, 'pnp_filter_counts' int32 [B, 4] the filter's (selected, kept, kept inliers, selected inliers) before the image-overlap
-        mask."""
+        mask.
+        subpixel (off by default, and then nothing changes): uv comes from ops.match_subpixel on the same idx, under the
+        mask that goes to PnP, instead of the integer pixel; 'pnp_subpixel_counts' int32 [B, 4] = (matched, fitted on both axes, integer
+        pixel within SUBPIXEL_INLIER_THRES = 0.5 px of the projected point, sub-pixel position within it)."""
         with torch.no_grad():
             pc = data_batch['pc']
             dev = pc.device
@@ -248,7 +252,12 @@ class MultiHeadModel(Planned):
                 use = use & keep
                 data_batch['pnp_used'] = use.sum(1)
                 data_batch['pnp_filter_counts'] = fcounts
-            uv = torch.stack([p % w, torch.div(p, w, rounding_mode='floor')], 1).float().contiguous()
+            if subpixel:
+                feat, img = _geo_rows(data_batch)
+                uv, data_batch['pnp_subpixel_counts'] = ops.match_subpixel(feat, img, idx.contiguous(), mask=use.contiguous(),
+                                                                           gt_xy=_gt_xy(data_batch, dev), thr=SUBPIXEL_INLIER_THRES)
+            else:
+                uv = torch.stack([p % w, torch.div(p, w, rounding_mode='floor')], 1).float().contiguous()
             K = data_batch['K'].to(dev).float()
             K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3).contiguous()
             pose, inliers, status = ops.pnp_ransac(pc.float().contiguous(), uv, use.contiguous(), K, n_hyp=n_hyp, thr=thr, seed=seed,
@@ -258,7 +267,7 @@ class MultiHeadModel(Planned):
             data_batch['pnp_status'] = status
 
     def refine_pose_from_matches(self, data_batch, pose=None, radii=(6, 3, 2), thrs=(4.0, 2.0, 1.0), max_dist=None, iters=10, mask=None,
-                                 img_overlap=None):
+                                 img_overlap=None, subpixel=False):
         """Port extension: polish a pose from anywhere -- pose_from_matches' 'pnp_pose' (the default) or the agent's final
         pose through environment.from_disentangled -- against the geometric features.  For each (radius, thr) in turn: ops.guided_match
         under the current pose (every point of `mask`, default 'pc_overlap_pred', is matched inside the (2 radius + 1)^2 window round its
@@ -266,7 +275,10 @@ class MultiHeadModel(Planned):
         inside it), uv = (p % w, p // w), then ops.pnp_refine from the current pose with inlier threshold thr.  pose: float32 [B, 4, 4]
         mapping 'pc' into the camera frame (as 'P').  Sets 'refined_pose' [B, 4, 4], 'refined_inliers' [B] and 'refined_status' [B] (of the
         last round; ops.pnp_refine's codes) and 'guided_counts' int32 [rounds, B, 4] (selected, in view, kept, kept inliers per round).
-        Not called by forward."""
+        subpixel (off by default, and then nothing changes): every round's uv comes from ops.match_subpixel on that round's
+        idx under that round's correspondence mask, and 'guided_subpixel_counts' int32 [rounds, B, 4] holds its counts (matched, fitted on
+        both axes, integer pixel within SUBPIXEL_INLIER_THRES = 0.5 px of the projected point, sub-pixel position within it; the last two 0 without ground
+        truth).  Not called by forward."""
         radii, thrs = tuple(radii), tuple(thrs)
         if len(radii) != len(thrs) or not radii:
             raise ValueError("refine_pose_from_matches: radii and thrs must be non-empty and of equal length, got %r / %r" % (radii, thrs))
@@ -282,7 +294,7 @@ class MultiHeadModel(Planned):
             K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3).contiguous()
             xy = _gt_xy(data_batch, dev) if ('point_xy_float_all' in data_batch or 'pc_in_cam_space' in data_batch) else None
             ov = None if img_overlap is None else img_overlap.to(dev).reshape(B, -1).bool()
-            counts, inliers, status = [], None, None
+            counts, sub_counts, inliers, status = [], [], None, None
             for radius, thr in zip(radii, thrs):
                 idx, keep, cnt, _, _ = ops.guided_match(pc, feat, img, sel, cur, K, radius, max_dist=max_dist or 0.0, gt_xy=xy,
                                                         thr=MATCH_INLIER_THRES)
@@ -291,12 +303,18 @@ class MultiHeadModel(Planned):
                 use = keep.view(B, N)
                 if ov is not None:
                     use = use & torch.gather(ov, 1, p)
-                uv = torch.stack([p % w, torch.div(p, w, rounding_mode='floor')], 1).float().contiguous()
+                if subpixel:
+                    uv, sc = ops.match_subpixel(feat, img, idx, mask=use.contiguous(), gt_xy=xy, thr=SUBPIXEL_INLIER_THRES)
+                    sub_counts.append(sc)
+                else:
+                    uv = torch.stack([p % w, torch.div(p, w, rounding_mode='floor')], 1).float().contiguous()
                 cur, inliers, status = ops.pnp_refine(pc, uv, use.contiguous(), K, cur, thr=thr, iters=iters)
             data_batch['refined_pose'] = cur
             data_batch['refined_inliers'] = inliers
             data_batch['refined_status'] = status
             data_batch['guided_counts'] = torch.stack(counts)
+            if subpixel:
+                data_batch['guided_subpixel_counts'] = torch.stack(sub_counts)
 
     def forward_cl(self, data_batch):
         cl = self.encoder_decoder.forward_cl(data_batch)

@@ -1149,6 +1149,52 @@ def pnp_refine(pts, uv, mask, K, pose, thr=1.0, iters=10):
     return out, inliers, status
 
 
+def match_subpixel(pc_feat_rows, img_feat_nhwc, idx, mask=None, gt_xy=None, thr=0.5):
+    """Sub-pixel positions of given matches by a parabola fit on the squared feature distances of the matched pixel and its two
+    neighbours per axis (include/cmr_hip.h cmr_match_subpixel_f32): pc_feat rows [B*N, 64], img_feat NHWC [B, h, w, 64],
+    idx int32 with B*N elements (the idx of feat_match / feat_match_filter / guided_match), optional mask [B, N] / [B*N] of bool / uint8 /
+    int64 (non-zero = use the row), optional gt_xy float32 [B, 2, N] with threshold thr in pixels.  A row is matched when its mask is
+    non-zero and 0 <= idx < h * w.
+    -> (uv float32 [B, 2, N] = (x + dx, y + dy) with |dx|, |dy| <= 0.5, NaN on unmatched rows, counts int32 [B, 4] = (matched, fitted on
+    both axes, matched whose integer pixel is within thr of gt_xy, matched whose sub-pixel position is))."""
+    if pc_feat_rows.dim() != 2 or img_feat_nhwc.dim() != 4:
+        raise ValueError("match_subpixel: point rows must be 2-D [B*N, C] and pixel features 4-D [B, h, w, C], got %s / %s" % (
+            tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
+    B, h, w, C = img_feat_nhwc.shape
+    if B < 1 or pc_feat_rows.shape[0] % B:
+        raise ValueError("match_subpixel: point rows %s and pixel features %s do not agree on B and N" % (
+            tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
+    N = pc_feat_rows.shape[0] // B
+    if C != 64 or pc_feat_rows.shape[1] != 64:
+        raise ValueError("match_subpixel: feature width must be 64, got %d / %d" % (pc_feat_rows.shape[1], C))
+    if pc_feat_rows.dtype != f32 or img_feat_nhwc.dtype != f32:
+        raise ValueError("match_subpixel: features must be float32, got %s / %s" % (pc_feat_rows.dtype, img_feat_nhwc.dtype))
+    if idx.dtype != torch.int32 or idx.numel() != B * N:
+        raise ValueError("match_subpixel: idx must be int32 with %d elements, got %s %s" % (B * N, idx.dtype, tuple(idx.shape)))
+    if mask is not None and (mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N):
+        raise ValueError("match_subpixel: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (B * N, mask.dtype, tuple(mask.shape)))
+    if gt_xy is not None and (gt_xy.dtype != f32 or tuple(gt_xy.shape) != (B, 2, N)):
+        raise ValueError("match_subpixel: gt_xy must be float32 [%d, 2, %d], got %s %s" % (B, N, gt_xy.dtype, tuple(gt_xy.shape)))
+    if not (float(thr) > 0.0 and float(thr) < float("inf")):
+        raise ValueError("match_subpixel: thr must be a finite positive number, got %r" % (thr,))
+    if B > GRID_Y_MAX or N < 1 or N > GRID_Y_MAX * 256 or h < 1 or w < 1 or h * w > 1 << 24:
+        raise ValueError("match_subpixel: need 1 <= B <= %d, 1 <= N <= %d and a map of 1 .. 2^24 pixels, got B=%d N=%d map %d x %d" % (
+            GRID_Y_MAX, GRID_Y_MAX * 256, B, N, h, w))
+    ts = [t for t in (pc_feat_rows, img_feat_nhwc, idx, mask, gt_xy) if t is not None]
+    if not all(t.is_cuda and t.is_contiguous() and t.device == pc_feat_rows.device for t in ts):
+        raise ValueError("match_subpixel: every tensor must be a contiguous tensor on the same GPU")
+    if pc_feat_rows.data_ptr() % 16 or img_feat_nhwc.data_ptr() % 16:
+        raise ValueError("match_subpixel: feature rows must be 16-byte aligned")
+    if mask is not None and mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    dev = pc_feat_rows.device
+    uv = torch.empty((B, 2, N), dtype=f32, device=dev)
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    _lib.call("cmr_match_subpixel_f32", _p(pc_feat_rows), _p(img_feat_nhwc), C, B, N, h, w, _p(idx), _p(mask),
+              mask.element_size() if mask is not None else 0, _p(gt_xy), float(thr), _p(uv), _p(counts), _stream())
+    return uv, counts
+
+
 def expert_action(pose_source, pose_target, r_steps, t_steps, six_dof):
     """-> (action_r int64 [B, 1|3], action_t int64 [B, 2|3]); the step tables are float64 device tensors."""
     B = pose_source.shape[0]

@@ -156,6 +156,9 @@ WORK = {
                                        a["B"] * a["N"] * (12 + a["mask_bytes"] + 256 + 256 * (2 * a["radius"] + 1) ** 2 + 16)),
     "cmr_pnp_refine_f32": lambda a: ((60.0 + 112.0) * (a["iters"] + 1) * a["B"] * a["N"],
                                      (a["iters"] + 2) * a["B"] * a["N"] * (20 + a["mask_bytes"])),
+    # DESIGN.md 4o, every row taken as matched: the point's feature row and 5 gathered pixel rows of 256 B, idx + mask in, 8 B of uv out;
+    # 3 FLOP per channel and pixel
+    "cmr_match_subpixel_f32": lambda a: (3.0 * 64 * 5 * a["B"] * a["N"], a["B"] * a["N"] * (4 + a["mask_bytes"] + 256 + 256 * 5 + 8)),
     # training direction (Train_Agent.py:296-305, Train_Geo.py:166-174): weight gradients as GEMMs over the minibatch's pixels / rows
     "cmr_conv3x3_wgrad_f32": lambda a: (2.0 * 9 * a["Cin"] * a["Cout"] * a["B"] * a["H"] * a["W"],
                                         F * (a["B"] * a["H"] * a["W"] * (a["Cin"] + a["Cout"]) + 9 * a["Cin"] * a["Cout"])),

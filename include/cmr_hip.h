@@ -424,6 +424,28 @@ int cmr_pnp_refine_f32(const float* pts, const float* uv, const void* mask, int 
                        int N, float thr, int iters, float* pose, int32_t* inliers, int32_t* status, void* ws, int64_t ws_bytes,
                        hipStream_t stream);
 
+/* Sub-pixel match positions by a parabola fit on feature distances (port extension; ops.match_subpixel,
+ * MultiHeadModel.pose_from_matches / refine_pose_from_matches with subpixel=True, Test_Geo.py / Test_Agent.py --subpixel): turns the idx
+ * of cmr_feat_match_f32, cmr_feat_match_filter_f32 or cmr_guided_match_f32 into float pixel coordinates for cmr_pnp_ransac_f32 /
+ * cmr_pnp_refine_f32.  pc_feat rows [B*N][C], img_feat [B][h*w][C], C must be 64 (else CMR_EUNSUPPORTED), h*w <= 2^24, idx int32 [B*N],
+ * mask (optional) [B*N] with mask_bytes 1 or 8, gt_xy (optional) f32 [B][2][N], thr in pixels.
+ * A row is MATCHED iff (mask is null or non-zero) and 0 <= idx < h*w; any other index is treated as unmatched and never dereferenced.
+ * For a matched row p = idx, x = p % w, y = p / w and s(q) = the squared L2 distance of the point feature and pixel q, the direct sum of
+ * (a - b)^2 in fp32 (order: DESIGN.md 4o), not the |q|^2 - 2 p.q expansion.  Along x, with s0 = s(p), sm = s(p - 1), sp = s(p + 1),
+ * num = sm - sp, den = (sm - s0) + (sp - s0): the axis is FITTED iff 1 <= x <= w - 2, num and den are finite and den > 0; then
+ * dx = clamp(0.5 * num / den, -0.5, +0.5), else dx = 0.  Along y the same with p -+ w and 1 <= y <= h - 2.  (The clamp matters for
+ * guided matches: a window minimum on the window's edge need not be a local minimum of the map.)
+ *   uv f32 [B][2][N]     (x + dx, y + dy), pixel centres at the integers as (p % w, p / w); NaN in both planes for an unmatched row;
+ *   counts int32 [B][4] = {matched, fitted on both axes, matched with the INTEGER pixel within thr of gt_xy, matched with the SUB-PIXEL
+ *                        position within thr}; the predicate is cmr_feat_match_f32's: sqrtf(dx^2 + dy^2) <= thr in fp32, a non-finite
+ *                        gt_xy is never an inlier; both inlier counts are 0 when gt_xy is null.  The call zeroes counts itself.
+ * No workspace, no host round trip, no floating-point atomics: one memset and one launch on the stream; every uv element is a plain
+ * store by the 16-lane group that owns the row and the counts are integer atomics (one per workgroup and word), so two calls agree bit
+ * for bit and a sample depends on its own rows only. */
+int cmr_match_subpixel_f32(const float* pc_feat, const float* img_feat, int C, int B, int N, int h, int w, const int32_t* idx,
+                           const void* mask, int mask_bytes, const float* gt_xy, float thr, float* uv, int32_t* counts,
+                           hipStream_t stream);
+
 /* ---- rollout ops of the training loop ---------------------------------------- */
 
 /* environment.py:143-176 (expert): residual pose target * source^-1 -> extrinsic-xyz Euler angles (folded back when the
