@@ -31,6 +31,11 @@ parabola fit on the feature distances round the matched pixel (cmr_match_subpixe
 one extra line "subpixel fitted <fitted> of <matched> IR@0.5 <integer> -> <sub-pixel>": the PnP correspondences fitted on both axes and
 their share within 0.5 px (at 1/4 scale) of the projected point before and after the fit.  Without the flag the output is unchanged.
 
+--min-conf C [--temperature T] (with --pnp, instead of --mutual / --ratio): only the matches whose dual-softmax confidence
+(cmr_match_conf_f32: softmax over the point's row times softmax over the pixel's column of -d^2 / T, default T = 0.1) reaches C go into
+PnP, and each batch prints one extra line "conf kept <kept> of <selected> IR <unfiltered> -> <kept>".  Without the flag the output is
+unchanged.
+
 Pairs come from the synthetic generator (cmr_agent_amd.utils.synthetic) unless --data-root names a dataset in the reference's layout
 (its 'test' split), and the weights are the deterministic hash fill unless --geo-ckpt points at a reference-format state_dict."""
 import argparse
@@ -88,6 +93,8 @@ def main():
     ap.add_argument('--guided-thr', type=str, default=None, help="with --guided: inlier threshold in pixels per round T[,T...] (default: R / 1.5 per round, at least 1)")
     ap.add_argument('--guided-max-dist', type=float, default=None, help="with --guided: keep a guided match only when its feature distance is <= D")
     ap.add_argument('--subpixel', action='store_true', help="with --pnp: sub-pixel match positions (parabola fit on the feature distances) for PnP and the --guided rounds")
+    ap.add_argument('--min-conf', type=float, default=None, help="with --pnp: keep a match when its dual-softmax confidence is >= C (0 < C <= 1)")
+    ap.add_argument('--temperature', type=float, default=None, help="with --min-conf: temperature T of the softmax over -d^2 / T (default 0.1)")
     args = ap.parse_args()
     filtered = args.mutual or args.ratio is not None
     if filtered and not args.pnp:
@@ -98,6 +105,18 @@ def main():
         ap.error("--excl-radius must be >= 0")
     if args.subpixel and not args.pnp:
         ap.error("--subpixel refines the matches that go into PnP: give --pnp as well")
+    if args.min_conf is not None:
+        if not args.pnp:
+            ap.error("--min-conf filters the matches that go into PnP: give --pnp as well")
+        if filtered:
+            ap.error("--min-conf and --mutual / --ratio are alternative filters: give one or the other")
+        if not 0.0 < args.min_conf <= 1.0:
+            ap.error("--min-conf must lie in (0, 1]")
+    elif args.temperature is not None:
+        ap.error("--temperature belongs to --min-conf")
+    if args.temperature is not None and not 0.0 < args.temperature < float("inf"):
+        ap.error("--temperature must be > 0")
+    conf_kw = {} if args.min_conf is None else dict(min_conf=args.min_conf, temperature=0.1 if args.temperature is None else args.temperature)
     radii = thrs = None
     if args.guided is not None:
         if not args.pnp:
@@ -141,7 +160,11 @@ def main():
             print(np.mean(r1), np.mean(r2))
             if args.pnp:
                 geo_model.pose_from_matches(data, img_overlap=img_overlap, mutual=args.mutual, ratio=args.ratio,
-                                            excl_radius=args.excl_radius, subpixel=args.subpixel)
+                                            excl_radius=args.excl_radius, subpixel=args.subpixel, **conf_kw)
+                if conf_kw:
+                    cc = data['pnp_conf_counts'].double().cpu().numpy().sum(0)
+                    with np.errstate(invalid="ignore", divide="ignore"):
+                        print("conf kept", int(cc[1]), "of", int(cc[0]), "IR", cc[3] / cc[0], "->", cc[2] / cc[1])
                 if filtered:
                     fc = data['pnp_filter_counts'].double().cpu().numpy().sum(0)
                     with np.errstate(invalid="ignore", divide="ignore"):

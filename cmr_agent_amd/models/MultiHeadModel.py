@@ -142,6 +142,20 @@ def match_features_filtered(data_batch, mask, mutual=True, ratio=0.0, excl_radiu
     return idx.view(B, N), keep.view(B, N), counts, w
 
 
+def match_features_conf(data_batch, mask, temperature=0.1, min_conf=0.0):
+    """ops.match_conf on the batch's geometric features (as match_features): the nearest pixel of every selected point, its dual-softmax
+    confidence at the given temperature and which of those matches reach min_conf.
+    -> (idx int32 [B, N], conf float32 [B, N], keep bool [B, N], counts int32 [B, 4] = (selected, kept, kept inliers, selected
+    inliers), w)."""
+    pc, img = _geo_rows(data_batch)
+    B, h, w, _ = img.shape
+    N = pc.shape[0] // B
+    dev = pc.device
+    idx, conf, keep, counts, _, _, _ = ops.match_conf(pc, img, mask.to(dev).contiguous(), temperature=temperature, min_conf=min_conf,
+                                                      gt_xy=_gt_xy(data_batch, dev), thr=MATCH_INLIER_THRES)
+    return idx.view(B, N), conf.view(B, N), keep.view(B, N), counts, w
+
+
 def _ratio(counts, num, den):
     c = counts.float()
     return c[:, num] / c[:, den]                                 # 0 / 0 = NaN, as right.sum() / right.shape[0] on an empty selection
@@ -212,7 +226,7 @@ class MultiHeadModel(Planned):
             data_batch['matching_ir_per_sample'] = _ratio(counts, 1, 0)
 
     def pose_from_matches(self, data_batch, img_overlap=None, n_hyp=1024, thr=1.0, seed=0, refine_iters=10, mutual=False, ratio=None,
-                          excl_radius=2, max_dist=None, subpixel=False):
+                          excl_radius=2, max_dist=None, subpixel=False, min_conf=None, temperature=0.1):
         """Port extension (no counterpart in the reference): the camera pose from the geometric model's own matches, PnP
         inside RANSAC (ops.pnp_ransac).  Correspondences: the points of 'pc_overlap_pred', each with its nearest pixel feature
         (match_features), kept only where that pixel lies inside the predicted image overlap (Test_Geo.py's IR2 set); the pixel p gives
@@ -226,7 +240,15 @@ class MultiHeadModel(Planned):
         mask.
         subpixel (off by default, and then nothing changes): uv comes from ops.match_subpixel on the same idx, under the
         mask that goes to PnP, instead of the integer pixel; 'pnp_subpixel_counts' int32 [B, 4] = (matched, fitted on both axes, integer
-        pixel within SUBPIXEL_INLIER_THRES = 0.5 px of the projected point, sub-pixel position within it)."""
+        pixel within SUBPIXEL_INLIER_THRES = 0.5 px of the projected point, sub-pixel position within it).
+        min_conf (None by default, and then nothing changes): the matches come from match_features_conf at `temperature`
+        and only those whose dual-softmax confidence reaches min_conf go on, under the same image-overlap mask; 'pnp_used' int [B] as
+        above, 'pnp_conf_counts' int32 [B, 4] the (selected, kept, kept inliers, selected inliers) before the image-overlap mask and
+        'pnp_conf' float32 [B, N] the confidences (NaN on unselected rows).  It is this filter or mutual / ratio / max_dist, not both
+        (ValueError); it composes with subpixel."""
+        conf_filter = min_conf is not None
+        if conf_filter and (bool(mutual) or bool(ratio) or bool(max_dist)):
+            raise ValueError("pose_from_matches: min_conf and mutual / ratio / max_dist are alternative filters, give one or the other")
         with torch.no_grad():
             pc = data_batch['pc']
             dev = pc.device
@@ -242,6 +264,8 @@ class MultiHeadModel(Planned):
             if filtered:
                 idx, keep, fcounts, w = match_features_filtered(data_batch, mask, mutual=bool(mutual), ratio=ratio or 0.0,
                                                                 excl_radius=excl_radius, max_dist=max_dist or 0.0)
+            elif conf_filter:
+                idx, conf, keep, ccounts, w = match_features_conf(data_batch, mask, temperature=temperature, min_conf=min_conf)
             else:
                 idx, _, _, w = match_features(data_batch, mask)
             B, N = idx.shape
@@ -252,6 +276,11 @@ class MultiHeadModel(Planned):
                 use = use & keep
                 data_batch['pnp_used'] = use.sum(1)
                 data_batch['pnp_filter_counts'] = fcounts
+            if conf_filter:
+                use = use & keep
+                data_batch['pnp_used'] = use.sum(1)
+                data_batch['pnp_conf_counts'] = ccounts
+                data_batch['pnp_conf'] = conf
             if subpixel:
                 feat, img = _geo_rows(data_batch)
                 uv, data_batch['pnp_subpixel_counts'] = ops.match_subpixel(feat, img, idx.contiguous(), mask=use.contiguous(),

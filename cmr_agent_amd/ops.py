@@ -993,6 +993,60 @@ def feat_match_filter(pc_feat_rows, img_feat_nhwc, mask, mutual=True, ratio=0.0,
     return idx, keep.view(torch.bool), counts, d1, d2, rev
 
 
+def match_conf(pc_feat_rows, img_feat_nhwc, mask, temperature=0.1, min_conf=0.0, gt_xy=None, thr=3.0, want_dist=False, want_lse=False):
+    """Nearest pixel feature of every selected point with its dual-softmax confidence (include/cmr_hip.h cmr_match_conf_f32, DESIGN.md
+    4p); tensors as feat_match.  With s(n, p) = -|point n - pixel p|^2 / temperature over the selected points x the sample's pixels,
+    conf = softmax over the row times softmax over the column at the match, in (0, 1]; min_conf in [0, 1] (0 = off): keep a row when
+    conf >= min_conf.
+    -> (idx int32 [B*N] as feat_match, conf float32 [B*N] (NaN on unselected rows), keep bool [B*N], counts int32 [B, 4] = (selected,
+    kept, kept inliers, selected inliers), d1 float32 [B*N] or None (want_dist), row_lse float32 [B*N] / col_lse float32 [B*h*w]: the
+    log-sum-exp of s over a point's pixels / over a pixel's selected points, or None (want_lse))."""
+    if pc_feat_rows.dim() != 2 or img_feat_nhwc.dim() != 4:
+        raise ValueError("match_conf: point rows must be 2-D [B*N, C] and pixel features 4-D [B, h, w, C], got %s / %s" % (
+            tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
+    B, h, w, C = img_feat_nhwc.shape
+    if C != 64 or pc_feat_rows.shape[1] != 64:
+        raise ValueError("match_conf: feature width must be 64, got %d / %d" % (pc_feat_rows.shape[1], C))
+    if pc_feat_rows.dtype != f32 or img_feat_nhwc.dtype != f32:
+        raise ValueError("match_conf: features must be float32, got %s / %s" % (pc_feat_rows.dtype, img_feat_nhwc.dtype))
+    if B < 1 or B > GRID_Y_MAX or pc_feat_rows.shape[0] % B or h < 1 or w < 1 or h * w > 1 << 24:
+        raise ValueError("match_conf: %d point rows do not split into %d samples (1 <= B <= %d) or the map %d x %d is empty / "
+                         "over 2^24 pixels" % (pc_feat_rows.shape[0], B, GRID_Y_MAX, h, w))
+    N = pc_feat_rows.shape[0] // B
+    if N < 1 or N > GRID_Y_MAX * 256:
+        raise ValueError("match_conf: need 1 <= N <= %d rows per sample, got %d" % (GRID_Y_MAX * 256, N))
+    if mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N:
+        raise ValueError("match_conf: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (
+            B * N, mask.dtype, tuple(mask.shape)))
+    if gt_xy is not None and (gt_xy.dtype != f32 or tuple(gt_xy.shape) != (B, 2, N)):
+        raise ValueError("match_conf: gt_xy must be float32 [%d, 2, %d], got %s %s" % (B, N, gt_xy.dtype, tuple(gt_xy.shape)))
+    if not 0.0 < float(temperature) < float("inf"):
+        raise ValueError("match_conf: temperature must be finite and > 0, got %r" % (temperature,))
+    if not 0.0 <= float(min_conf) <= 1.0:
+        raise ValueError("match_conf: min_conf must lie in [0, 1] (0 = no threshold), got %r" % (min_conf,))
+    ts = [t for t in (pc_feat_rows, img_feat_nhwc, mask, gt_xy) if t is not None]
+    if not all(t.is_cuda and t.is_contiguous() and t.device == pc_feat_rows.device for t in ts):
+        raise ValueError("match_conf: every tensor must be a contiguous tensor on the same GPU")
+    if pc_feat_rows.data_ptr() % 16 or img_feat_nhwc.data_ptr() % 16:
+        raise ValueError("match_conf: feature rows must be 16-byte aligned")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    dev = pc_feat_rows.device
+    idx = torch.empty((B * N,), dtype=torch.int32, device=dev)
+    conf = torch.empty((B * N,), dtype=f32, device=dev)
+    keep = torch.empty((B * N,), dtype=torch.uint8, device=dev)
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    d1 = torch.empty((B * N,), dtype=f32, device=dev) if want_dist else None
+    row_lse = torch.empty((B * N,), dtype=f32, device=dev) if want_lse else None
+    col_lse = torch.empty((B * h * w,), dtype=f32, device=dev) if want_lse else None
+    nb = _lib.load().cmr_match_conf_workspace_bytes(B, N, h, w)
+    ws = _ws(nb, dev)
+    _lib.call("cmr_match_conf_f32", _p(pc_feat_rows), _p(img_feat_nhwc), C, B, N, h, w, _p(mask), mask.element_size(), float(temperature),
+              float(min_conf), _p(gt_xy), float(thr), _p(idx), _p(conf), _p(keep), _p(counts), _p(d1), _p(row_lse), _p(col_lse), _p(ws), nb,
+              _stream())
+    return idx, conf, keep.view(torch.bool), counts, d1, row_lse, col_lse
+
+
 def pnp_ransac(pts, uv, mask, K, n_hyp=1024, thr=1.0, seed=0, refine_iters=10, want_hyp_inliers=False):
     """Camera pose from 2-D/3-D correspondences, PnP inside RANSAC (include/cmr_hip.h cmr_pnp_ransac_f32): pts float32 [B, 3, N]
     (data['pc'] layout), uv float32 [B, 2, N] pixel coordinates on the map K refers to, mask [B, N] / [B*N] of bool / uint8 / int64

@@ -159,6 +159,10 @@ WORK = {
     # DESIGN.md 4o, every row taken as matched: the point's feature row and 5 gathered pixel rows of 256 B, idx + mask in, 8 B of uv out;
     # 3 FLOP per channel and pixel
     "cmr_match_subpixel_f32": lambda a: (3.0 * 64 * 5 * a["B"] * a["N"], a["B"] * a["N"] * (4 + a["mask_bytes"] + 256 + 256 * 5 + 8)),
+    # DESIGN.md 4p, every row taken as selected: two sweeps of the points x pixels distance matrix at 2 FLOP per channel and pair (the
+    # exponentials are not counted); each sweep reads its queries once and streams the other side once per 256 queries
+    "cmr_match_conf_f32": lambda a: (2.0 * 2 * 64 * a["B"] * a["N"] * a["h"] * a["w"],
+                                     a["B"] * (256.0 * (a["N"] + a["h"] * a["w"]) + 2.0 * a["N"] * a["h"] * a["w"])),
     # training direction (Train_Agent.py:296-305, Train_Geo.py:166-174): weight gradients as GEMMs over the minibatch's pixels / rows
     "cmr_conv3x3_wgrad_f32": lambda a: (2.0 * 9 * a["Cin"] * a["Cout"] * a["B"] * a["H"] * a["W"],
                                         F * (a["B"] * a["H"] * a["W"] * (a["Cin"] + a["Cout"]) + 9 * a["Cin"] * a["Cout"])),

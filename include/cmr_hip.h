@@ -368,6 +368,32 @@ int cmr_feat_match_filter_f32(const float* pc_feat, const float* img_feat, int C
                               int32_t* idx, uint8_t* keep, int32_t* counts, float* d1, float* d2, int32_t* rev, void* workspace,
                               int64_t workspace_bytes, hipStream_t stream);
 
+/* Dual-softmax match confidence ahead of PnP-RANSAC (port extension; ops.match_conf, MultiHeadModel.match_features_conf,
+ * MultiHeadModel.pose_from_matches(min_conf=), Test_Geo.py --min-conf).  Inputs as cmr_feat_match_filter_f32: pc_feat rows [B*N][C],
+ * img_feat [B][h*w][C], C must be 64 (else CMR_EUNSUPPORTED), mask [B*N] with mask_bytes 1 or 8, gt_xy (optional) f32 [B][2][N],
+ * h*w <= 2^24, temperature T > 0 and finite, 0 <= min_conf <= 1 (0 = no threshold).  Per sample, S = the selected rows, d2(n, p) = the
+ * squared L2 distance of point n and pixel p, s(n, p) = -d2(n, p) / T:
+ *   idx int32 [B*N]    argmin_p d(n, p), ties to the lowest p: cmr_feat_match_f32's idx bit for bit (same arithmetic); -1 outside S;
+ *   d1 (optional) f32 [B*N]  that minimum distance, cmr_feat_match_filter_f32's d1 bit for bit; NaN outside S;
+ *   row_lse (optional) f32 [B*N]  log of the sum over ALL h*w pixels p of exp s(n, p); NaN outside S;
+ *   col_lse (optional) f32 [B*h*w]  log of the sum over n in S of exp s(n, p); -inf when S is empty;
+ *   conf f32 [B*N]     min(1, exp(2 s(n, idx[n]) - row_lse[n] - col_lse[idx[n]])): the match's probability under the softmax over its
+ *                      row times that under the softmax over its column; NaN outside S; in (0, 1], a value under the smallest normal
+ *                      fp32 may come out as 0;
+ *   keep u8 [B*N]      n in S and (min_conf <= 0 or conf[n] >= min_conf);
+ *   counts int32 [B][4] = {|S|, kept, kept and inlier, selected and inlier}; inlier as cmr_feat_match_f32: sqrtf(dx^2 + dy^2) <= thr
+ *                      against gt_xy, a non-finite gt_xy is never an inlier.
+ * Two distance sweeps (points x pixels, pixels x points), each carrying an online log-sum-exp in base 2 whose running maximum is the
+ * running minimum of the distance.  Everything is enqueued on the stream (no host round trip); every output is a plain store of the
+ * workgroup / thread that owns it, the sums are folded in a fixed order that depends only on the sample's own selected count and the map
+ * size, and the counts are integer atomics (at most one per word and workgroup): two calls agree bit for bit and a sample's outputs are
+ * the same bits alone and inside any batch.  Workspace: cmr_match_conf_workspace_bytes(B, N, h, w), 16-byte aligned. */
+int64_t cmr_match_conf_workspace_bytes(int B, int N, int h, int w);
+int cmr_match_conf_f32(const float* pc_feat, const float* img_feat, int C, int B, int N, int h, int w, const void* mask, int mask_bytes,
+                       float temperature, float min_conf, const float* gt_xy, float thr, int32_t* idx, float* conf, uint8_t* keep,
+                       int32_t* counts, float* d1, float* row_lse, float* col_lse, void* workspace, int64_t workspace_bytes,
+                       hipStream_t stream);
+
 /* Camera pose from 2-D/3-D correspondences, PnP inside RANSAC (port extension; MultiHeadModel.pose_from_matches,
  * Test_Geo.py --pnp).  pts f32 [B][3][N] (planar, data['pc']), uv f32 [B][2][N] pixel coordinates on the map K refers to, mask [B*N]
  * with mask_bytes 1 (u8 / bool) or 8 (int64), non-zero = use; K f32 [B][3][3].  Per sample: the selected rows in row order; n_hyp
