@@ -14,7 +14,16 @@ through env.to_disentangled.  Per pair one extra line "refined <RTE> <RRE>", and
 the prefix "Refined ".  Without the flag the output is unchanged.
 
 --subpixel (with --refine): every round's correspondences carry sub-pixel positions from a parabola fit on the feature
-distances round the matched pixel (cmr_match_subpixel_f32) instead of the integer pixel.  The lines printed are the same."""
+distances round the matched pixel (cmr_match_subpixel_f32) instead of the integer pixel.  The lines printed are the same.
+
+--search (port extension): the agent's final pose (through env.from_disentangled) is the start of the derivative-free
+coarse-to-fine lattice search MultiHeadModel.search_pose (729 poses per round under cmr_pose_score_f32).  Per pair one extra line
+"searched <RTE> <RRE>", and after the closing block(s) the same three lines again with the prefix "Searched ".
+
+--verify: the candidate poses of the pair -- the agent's final pose, the refined pose (--refine), the searched pose
+(--search) -- are scored against the geometric features with no ground truth (MultiHeadModel.score_poses, window radius 0) and the pair
+prints "verified <name>=<quality> ... -> <chosen name>", quality = 1 - score / (selected tau^2) in [0, 1]; the chosen pose's RTE / RRE
+are collected and the closing lines printed once more with the prefix "Verified ".  Without these flags the output is unchanged."""
 import argparse
 import json
 import os
@@ -59,6 +68,8 @@ def main():
     ap.add_argument('--guided-thr', type=str, default=None, help="with --refine: inlier threshold in pixels per round T[,T...] (default: R / 1.5 per round, at least 1)")
     ap.add_argument('--guided-max-dist', type=float, default=None, help="with --refine: keep a guided match only when its feature distance is <= D")
     ap.add_argument('--subpixel', action='store_true', help="with --refine: sub-pixel match positions (parabola fit on the feature distances) in every round")
+    ap.add_argument('--search', action='store_true', help="search round the agent's final pose on a coarse-to-fine pose lattice scored against the geometric features")
+    ap.add_argument('--verify', action='store_true', help="score the pair's candidate poses against the geometric features (no ground truth) and report the best")
     args = ap.parse_args()
     if args.subpixel and args.refine is None:
         ap.error("--subpixel belongs to --refine")
@@ -80,6 +91,7 @@ def main():
     geo_model, agent = geo_model.to(dev).eval(), agent.to(dev).eval()
 
     rte, rre, rte_ref, rre_ref = [], [], [], []
+    rte_sea, rre_sea, rte_ver, rre_ver = [], [], [], []
     with torch.no_grad():
         if args.data_root:
             from cmr_agent_amd.dataset import FrameDataset, FrameLoader
@@ -101,6 +113,10 @@ def main():
             print(t_diff, r_diff)
             rte.append(t_diff)
             rre.append(r_diff)
+            cands = [("agent", None, (t_diff, r_diff))]                 # (name, pose mapping 'pc' into the camera frame, (RTE, RRE))
+            if args.search or args.verify:
+                final = env.from_disentangled(pose_source.clone(), data['pc'], data=data)
+                cands[0] = ("agent", final, (t_diff, r_diff))
             if radii is not None:
                 start = env.from_disentangled(pose_source.clone(), data['pc'], data=data)
                 geo_model.refine_pose_from_matches(data, pose=start, radii=radii, thrs=thrs, max_dist=args.guided_max_dist,
@@ -110,9 +126,29 @@ def main():
                 print("refined", t_diff, r_diff)
                 rte_ref.append(t_diff)
                 rre_ref.append(r_diff)
+                cands.append(("refined", data['refined_pose'], (t_diff, r_diff)))
+            if args.search:
+                geo_model.search_pose(data, pose=final)
+                sea = env.to_disentangled(data['searched_pose'].clone(), data['pc'], data=data)
+                t_diff, r_diff = get_P_diff(sea[0].cpu().numpy(), pose_target[0].cpu().numpy())
+                print("searched", t_diff, r_diff)
+                rte_sea.append(t_diff)
+                rre_sea.append(r_diff)
+                cands.append(("searched", data['searched_pose'], (t_diff, r_diff)))
+            if args.verify:
+                geo_model.score_poses(data, torch.stack([c[1].float() for c in cands], 1), radius=0)
+                k = int(data['pose_best'][0])
+                quality = data['pose_quality'][0].cpu().tolist()
+                print("verified", " ".join("%s=%.4f" % (c[0], q) for c, q in zip(cands, quality)), "->", cands[k][0])
+                rte_ver.append(cands[k][2][0])
+                rre_ver.append(cands[k][2][1])
     print_recall(rte, rre)
     if radii is not None:
         print_recall(rte_ref, rre_ref, "Refined ")
+    if args.search:
+        print_recall(rte_sea, rre_sea, "Searched ")
+    if args.verify:
+        print_recall(rte_ver, rre_ver, "Verified ")
 
 
 if __name__ == '__main__':

@@ -36,6 +36,11 @@ their share within 0.5 px (at 1/4 scale) of the projected point before and after
 PnP, and each batch prints one extra line "conf kept <kept> of <selected> IR <unfiltered> -> <kept>".  Without the flag the output is
 unchanged.
 
+--verify (with --pnp): the pair's candidate poses -- the PnP pose and, with --guided, the refined pose -- are scored
+against the geometric features with no ground truth (MultiHeadModel.score_poses, window radius 0); per pair one extra line "verified
+<name>=<quality> ... -> <chosen name>", quality = 1 - score / (selected tau^2) in [0, 1], and after the closing block(s) the same three
+lines again for the chosen poses with the prefix "Verified ".  Without the flag the output is unchanged.
+
 Pairs come from the synthetic generator (cmr_agent_amd.utils.synthetic) unless --data-root names a dataset in the reference's layout
 (its 'test' split), and the weights are the deterministic hash fill unless --geo-ckpt points at a reference-format state_dict."""
 import argparse
@@ -95,7 +100,10 @@ def main():
     ap.add_argument('--subpixel', action='store_true', help="with --pnp: sub-pixel match positions (parabola fit on the feature distances) for PnP and the --guided rounds")
     ap.add_argument('--min-conf', type=float, default=None, help="with --pnp: keep a match when its dual-softmax confidence is >= C (0 < C <= 1)")
     ap.add_argument('--temperature', type=float, default=None, help="with --min-conf: temperature T of the softmax over -d^2 / T (default 0.1)")
+    ap.add_argument('--verify', action='store_true', help="with --pnp: score the pair's candidate poses against the geometric features (no ground truth) and report the best")
     args = ap.parse_args()
+    if args.verify and not args.pnp:
+        ap.error("--verify scores the PnP pose (and the --guided one): give --pnp as well")
     filtered = args.mutual or args.ratio is not None
     if filtered and not args.pnp:
         ap.error("--mutual / --ratio filter the matches that go into PnP: give --pnp as well")
@@ -137,7 +145,7 @@ def main():
 
     bs, nbatch = args.batch_size, (args.pairs + args.batch_size - 1) // args.batch_size
     prec, rec, ir, ir1, ir2 = [], [], [], [], []
-    rte, rre, rte_ref, rre_ref = [], [], [], []
+    rte, rre, rte_ref, rre_ref, rte_ver, rre_ver = [], [], [], [], [], []
     with torch.no_grad():
         if args.data_root:
             from cmr_agent_amd.dataset import FrameDataset, FrameLoader
@@ -179,16 +187,26 @@ def main():
                     geo_model.refine_pose_from_matches(data, radii=radii, thrs=thrs, max_dist=args.guided_max_dist, img_overlap=img_overlap,
                                                        subpixel=args.subpixel)
                     ref = env.to_disentangled(data['refined_pose'].clone(), data['pc'])
+                names = ["pnp"] + (["refined"] if radii is not None else [])
+                if args.verify:
+                    geo_model.score_poses(data, torch.stack([data['pnp_pose']] + ([data['refined_pose']] if radii is not None else []), 1), radius=0)
+                    chosen, quality = data['pose_best'].cpu().tolist(), data['pose_quality'].cpu().tolist()
                 for b in range(pred.shape[0]):
                     t_diff, r_diff = get_P_diff(pred[b].cpu().numpy(), gt[b].cpu().numpy())
                     print(t_diff, r_diff)
                     rte.append(t_diff)
                     rre.append(r_diff)
+                    errs = [(t_diff, r_diff)]
                     if radii is not None:
                         t_diff, r_diff = get_P_diff(ref[b].cpu().numpy(), gt[b].cpu().numpy())
                         print("refined", t_diff, r_diff)
                         rte_ref.append(t_diff)
                         rre_ref.append(r_diff)
+                        errs.append((t_diff, r_diff))
+                    if args.verify:
+                        print("verified", " ".join("%s=%.4f" % (n, q) for n, q in zip(names, quality[b])), "->", names[chosen[b]])
+                        rte_ver.append(errs[chosen[b]][0])
+                        rre_ver.append(errs[chosen[b]][1])
 
     mean = lambda v: float(np.mean(v)) if v else float("nan")
     print(mean(prec), mean(rec), mean(ir), mean(ir1), mean(ir2))
@@ -196,6 +214,8 @@ def main():
         print_recall(rte, rre)
         if radii is not None:
             print_recall(rte_ref, rre_ref, "Refined ")
+        if args.verify:
+            print_recall(rte_ver, rre_ver, "Verified ")
 
 
 if __name__ == '__main__':

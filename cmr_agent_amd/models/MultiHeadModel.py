@@ -9,6 +9,10 @@ buffers the agent loop consumes are kept under data_batch['_cmr'].
 In `train()` mode `forward` runs the train-mode network (batch-statistics BatchNorm, dropout) on the HIP tape as ONE
 autograd node and composes the focal / circle losses (MultiHeadModel.py:49-50,141-178) over it, so that the reference's
 `model(data); data['loss'].backward(); optimizer.step()` trains this module as it stands (cmr_agent_amd/train/bridge.py)."""
+import itertools
+import math
+
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -197,6 +201,43 @@ def _eye4(dev):
     return _EYE4[key]
 
 
+# MultiHeadModel.search_pose: (window radius, rotation step in degrees, translation step, rounds) per level
+SEARCH_LEVELS = ((4, 1.0, 0.1, 3), (2, 0.5, 0.05, 3), (1, 0.25, 0.025, 3), (0, 0.1, 0.01, 6), (0, 0.03, 0.003, 6))
+
+
+def pose_search_offsets():
+    """{-1, 0, 1}^6 ordered by (sum |o_j|, o lexicographic) -> int64 numpy [729, 6]; entry 0 is "stay"."""
+    return np.array(sorted(itertools.product((-1, 0, 1), repeat=6), key=lambda o: (sum(abs(x) for x in o), o)), np.int64)
+
+
+def pose_search_table(rot_step_deg, trans_step):
+    """The 729 left increments of one search_pose level, built in float64 on the host: D_i = [[Exp(w_i), v_i], [0, 1]] with w_i =
+    radians(rot_step_deg) o[:3], v_i = trans_step o[3:] over pose_search_offsets() -> float64 tensor [729, 4, 4]; D_0 is the identity."""
+    o = pose_search_offsets().astype(np.float64)
+    wv = math.radians(float(rot_step_deg)) * o[:, :3]
+    th = np.linalg.norm(wv, axis=1)
+    W = np.zeros((len(o), 3, 3))
+    W[:, 0, 1], W[:, 0, 2], W[:, 1, 2] = -wv[:, 2], wv[:, 1], -wv[:, 0]
+    W[:, 1, 0], W[:, 2, 0], W[:, 2, 1] = wv[:, 2], -wv[:, 1], wv[:, 0]
+    small = th < 1e-8
+    ths = np.where(small, 1.0, th)
+    a = np.where(small, 1.0 - th * th / 6.0, np.sin(ths) / ths)                      # Rodrigues: I + a W + c W^2
+    c = np.where(small, 0.5 - th * th / 24.0, (1.0 - np.cos(ths)) / (ths * ths))
+    D = np.tile(np.eye(4), (len(o), 1, 1))
+    D[:, :3, :3] += a[:, None, None] * W + c[:, None, None] * (W @ W)
+    D[:, :3, 3] = float(trans_step) * o[:, 3:]
+    return torch.from_numpy(D)
+
+
+def _first_min(score):
+    """The index of the lowest entry per row, the lowest index on a tie (torch.argmin does not promise the first minimum on the device);
+    a row of NaN gives 0 -> int64 [B]."""
+    P = score.shape[1]
+    ar = torch.arange(P, device=score.device)
+    k = torch.where(score == score.min(1, keepdim=True).values, ar, torch.full_like(ar, P)).min(1).values
+    return torch.where(k < P, k, torch.zeros_like(k))
+
+
 class MultiHeadModel(Planned):
     def __init__(self, config):
         super().__init__()
@@ -344,6 +385,64 @@ class MultiHeadModel(Planned):
             data_batch['guided_counts'] = torch.stack(counts)
             if subpixel:
                 data_batch['guided_subpixel_counts'] = torch.stack(sub_counts)
+
+    def _score_args(self, data_batch, mask):
+        pc = data_batch['pc'].float().contiguous()
+        dev = pc.device
+        feat, img = _geo_rows(data_batch)
+        B = img.shape[0]
+        sel = (data_batch['pc_overlap_pred'] if mask is None else mask).to(dev).contiguous()
+        K = data_batch['K'].to(dev).float()
+        K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3).contiguous()
+        return pc, feat, img, sel, K
+
+    def score_poses(self, data_batch, poses, radius=0, tau=0.8, mask=None):
+        """Port extension: score candidate poses against the geometric features, with no ground truth (ops.pose_score).
+        poses: float32 [B, P, 4, 4], each mapping 'pc' into the camera frame (as 'P'); mask defaults to 'pc_overlap_pred'.  Per pose every
+        selected point costs min(d, tau)^2, d = its feature distance to the nearest pixel feature inside the (2 radius + 1)^2 window round
+        its projection, and tau^2 when it does not project into the map.  tau = 0.8 suits unit-norm features; it is not tuned on real
+        data.  Sets 'pose_scores' float64 [B, P] (lower is better), 'pose_score_counts' int32 [B, P, 2] (in view, in view and d <= tau),
+        'pose_quality' float64 [B, P] = 1 - score / (selected tau^2) in [0, 1] (tau as rounded to float32; 0 where nothing is selected) and 'pose_best' int64 [B], the
+        lowest score, the lowest index on a tie.  Not called by forward."""
+        with torch.no_grad():
+            pc, feat, img, sel, K = self._score_args(data_batch, mask)
+            poses = poses.to(pc.device).float().contiguous()
+            score, counts, selected = ops.pose_score(pc, feat, img, sel, poses, K, radius=radius, tau=tau)
+            data_batch['pose_scores'] = score
+            data_batch['pose_score_counts'] = counts
+            tau32 = torch.tensor(float(tau), dtype=torch.float32).item()          # the tau the kernel clamps at
+            full = selected.double()[:, None] * (tau32 * tau32)
+            data_batch['pose_quality'] = torch.where(full > 0, (1.0 - score / full.clamp(min=1e-300)).clamp(min=0.0), torch.zeros_like(score))
+            data_batch['pose_best'] = _first_min(score)
+
+    def search_pose(self, data_batch, pose=None, levels=SEARCH_LEVELS, tau=0.8, mask=None):
+        """Port extension: derivative-free coarse-to-fine lattice search of the pose under ops.pose_score -- the
+        counterpart without learned weights of the reference's 9^3-pose IterModel cost volume.  pose: float32 [B, 4, 4], default
+        'pnp_pose'.  levels: a sequence of (radius, rot_step_deg, trans_step, rounds); every round scores the 729 poses D_i cur
+        (pose_search_table: left increments of -1 / 0 / +1 steps on the three rotation and three translation axes, index 0 = stay) in one
+        call and moves to the best, the lowest index on a tie, so a plateau keeps the current pose.  The round count is fixed: no early
+        exit, no host synchronisation.  Sets 'searched_pose' float32 [B, 4, 4] and 'searched_score' float64 [B], the last round's best.
+        Not called by forward."""
+        levels = tuple(tuple(l) for l in levels)
+        if not levels or any(len(l) != 4 or not ops._is_int(l[3]) or l[3] < 1 for l in levels):
+            raise ValueError("search_pose: levels must be a non-empty sequence of (radius, rot_step_deg, trans_step, rounds >= 1), got %r" % (levels,))
+        with torch.no_grad():
+            pc, feat, img, sel, K = self._score_args(data_batch, mask)
+            dev = pc.device
+            B = pc.shape[0]
+            cur = (data_batch['pnp_pose'] if pose is None else pose).to(dev).float().contiguous()
+            rows = torch.arange(B, device=dev)
+            best = None
+            for radius, rot, trans, rounds in levels:
+                D = pose_search_table(rot, trans).to(dev)
+                for _ in range(int(rounds)):
+                    cand = torch.matmul(D[None], cur.double()[:, None]).float().contiguous()      # [B, 729, 4, 4]; D_0 = I: cand[:, 0] is cur
+                    score, _, _ = ops.pose_score(pc, feat, img, sel, cand, K, radius=radius, tau=tau)
+                    k = _first_min(score)
+                    cur = cand[rows, k].contiguous()
+                    best = score[rows, k]
+            data_batch['searched_pose'] = cur
+            data_batch['searched_score'] = best
 
     def forward_cl(self, data_batch):
         cl = self.encoder_decoder.forward_cl(data_batch)

@@ -1162,6 +1162,74 @@ def guided_match(pts, pc_feat_rows, img_feat_nhwc, mask, pose, K, radius, max_di
     return idx, keep.view(torch.bool), counts, dist, proj
 
 
+POSE_SCORE_MAX_POSES = 4096  # csrc/pose_score.hip PS_MAX_POSES
+
+
+def pose_score(pts, pc_feat_rows, img_feat_nhwc, mask, poses, K, radius=0, tau=0.8):
+    """Truncated feature-metric cost of P candidate poses per sample in one sweep, with no ground truth (include/cmr_hip.h
+    cmr_pose_score_f32): pts float32 [B, 3, N] (data['pc']), pc_feat rows [B*N, 64], img_feat NHWC [B, h, w, 64], mask
+    [B, N] / [B*N] of bool / uint8 / int64, poses float32 [B, P, 4, 4] each mapping pts into the camera frame, 1 <= P <=
+    POSE_SCORE_MAX_POSES, K float32 [B, 3, 3] for the h x w map, 0 <= radius <= GUIDED_MAX_RADIUS, tau finite and > 0.  Per pose and
+    selected row: d = min(guided_match's dist under that pose, tau) if the row is in view, else tau; the row costs d^2 in float64.
+    tau = 0.8 is a default for unit-norm features (two unrelated ones lie about sqrt(2) apart); it is not tuned on real data.
+    -> (score float64 [B, P] = the sum over the selected rows, lower is better; counts int32 [B, P, 2] = (in view, in view and dist <=
+    tau); selected int32 [B])."""
+    if pts.dim() != 3 or pts.shape[1] != 3:
+        raise ValueError("pose_score: pts must be [B, 3, N], got %s" % (tuple(pts.shape),))
+    B, _, N = pts.shape
+    if pc_feat_rows.dim() != 2 or img_feat_nhwc.dim() != 4:
+        raise ValueError("pose_score: point rows must be 2-D [B*N, C] and pixel features 4-D [B, h, w, C], got %s / %s" % (
+            tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
+    Bi, h, w, C = img_feat_nhwc.shape
+    if C != 64 or pc_feat_rows.shape[1] != 64:
+        raise ValueError("pose_score: feature width must be 64, got %d / %d" % (pc_feat_rows.shape[1], C))
+    if Bi != B or pc_feat_rows.shape[0] != B * N:
+        raise ValueError("pose_score: pts %s, point rows %s and pixel features %s do not agree on B and N" % (
+            tuple(pts.shape), tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
+    if pts.dtype != f32 or pc_feat_rows.dtype != f32 or img_feat_nhwc.dtype != f32 or poses.dtype != f32 or K.dtype != f32:
+        raise ValueError("pose_score: pts, features, poses and K must be float32, got %s / %s / %s / %s / %s" % (
+            pts.dtype, pc_feat_rows.dtype, img_feat_nhwc.dtype, poses.dtype, K.dtype))
+    if poses.dim() != 4 or poses.shape[0] != B or tuple(poses.shape[2:]) != (4, 4):
+        raise ValueError("pose_score: poses must be [%d, P, 4, 4], got %s" % (B, tuple(poses.shape)))
+    P = poses.shape[1]
+    if P < 1 or P > POSE_SCORE_MAX_POSES:
+        raise ValueError("pose_score: need 1 <= P <= %d poses per sample, got %d" % (POSE_SCORE_MAX_POSES, P))
+    if tuple(K.shape) != (B, 3, 3):
+        raise ValueError("pose_score: K must be [%d, 3, 3], got %s" % (B, tuple(K.shape)))
+    if B < 1 or B > GRID_Y_MAX or N < 1 or N > GRID_Y_MAX * 256 or h < 1 or w < 1 or h * w > 1 << 24:
+        raise ValueError("pose_score: need 1 <= B <= %d, 1 <= N <= %d and a map of 1 .. 2^24 pixels, got B=%d N=%d map %d x %d" % (
+            GRID_Y_MAX, GRID_Y_MAX * 256, B, N, h, w))
+    if mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N:
+        raise ValueError("pose_score: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (B * N, mask.dtype, tuple(mask.shape)))
+    if not _is_int(radius) or not 0 <= radius <= GUIDED_MAX_RADIUS:
+        raise ValueError("pose_score: radius must be an integer in [0, %d], got %r" % (GUIDED_MAX_RADIUS, radius))
+    try:
+        tau_ok = 0.0 < float(tau) < float("inf")
+    except (TypeError, ValueError):
+        tau_ok = False
+    if not tau_ok:
+        raise ValueError("pose_score: tau must be a finite positive number, got %r" % (tau,))
+    nslices = (N + 255) // 256
+    if nslices * ((P + 31) // 32) * B > 0x7fffffff:
+        raise ValueError("pose_score: B=%d N=%d P=%d need more than 2^31 - 1 workgroups, score the poses or the samples in parts" % (B, N, P))
+    ts = (pts, pc_feat_rows, img_feat_nhwc, mask, poses, K)
+    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
+        raise ValueError("pose_score: every tensor must be a contiguous tensor on the same GPU")
+    if pc_feat_rows.data_ptr() % 16 or img_feat_nhwc.data_ptr() % 16:
+        raise ValueError("pose_score: feature rows must be 16-byte aligned")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    dev = pts.device
+    score = torch.empty((B, P), dtype=torch.float64, device=dev)
+    counts = torch.empty((B, P, 2), dtype=torch.int32, device=dev)
+    selected = torch.empty((B,), dtype=torch.int32, device=dev)
+    nb = _lib.load().cmr_pose_score_workspace_bytes(B, N, P)
+    ws = _ws(nb, dev)
+    _lib.call("cmr_pose_score_f32", _p(pts), _p(pc_feat_rows), _p(img_feat_nhwc), C, B, N, h, w, _p(mask), mask.element_size(), _p(poses),
+              P, _p(K), int(radius), float(tau), _p(score), _p(counts), _p(selected), _p(ws), nb, _stream())
+    return score, counts, selected
+
+
 def pnp_refine(pts, uv, mask, K, pose, thr=1.0, iters=10):
     """Gauss-Newton refinement of a given pose on 2-D/3-D correspondences (include/cmr_hip.h cmr_pnp_refine_f32): pts
     float32 [B, 3, N], uv float32 [B, 2, N], mask [B, N] / [B*N] of bool / uint8 / int64, K float32 [B, 3, 3], pose float32 [B, 4, 4]

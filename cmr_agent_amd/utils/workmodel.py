@@ -163,6 +163,12 @@ WORK = {
     # exponentials are not counted); each sweep reads its queries once and streams the other side once per 256 queries
     "cmr_match_conf_f32": lambda a: (2.0 * 2 * 64 * a["B"] * a["N"] * a["h"] * a["w"],
                                      a["B"] * (256.0 * (a["N"] + a["h"] * a["w"]) + 2.0 * a["N"] * a["h"] * a["w"])),
+    # DESIGN.md 4q, every row taken as selected and in view under every pose: per (row, pose) (2r + 1)^2 gathered pixel rows of 256 B at 3
+    # FLOP per channel and pixel (the ~60 FLOP of projection per (row, pose) are not counted); the point and its feature row are read once
+    # per chunk of 32 poses
+    "cmr_pose_score_f32": lambda a: (3.0 * 64 * (2 * a["radius"] + 1) ** 2 * a["B"] * a["N"] * a["P"],
+                                     a["B"] * a["N"] * ((12 + a["mask_bytes"] + 256) * ((a["P"] + 31) // 32)
+                                                        + 256.0 * (2 * a["radius"] + 1) ** 2 * a["P"])),
     # training direction (Train_Agent.py:296-305, Train_Geo.py:166-174): weight gradients as GEMMs over the minibatch's pixels / rows
     "cmr_conv3x3_wgrad_f32": lambda a: (2.0 * 9 * a["Cin"] * a["Cout"] * a["B"] * a["H"] * a["W"],
                                         F * (a["B"] * a["H"] * a["W"] * (a["Cin"] + a["Cout"]) + 9 * a["Cin"] * a["Cout"])),

@@ -472,6 +472,29 @@ int cmr_match_subpixel_f32(const float* pc_feat, const float* img_feat, int C, i
                            const void* mask, int mask_bytes, const float* gt_xy, float thr, float* uv, int32_t* counts,
                            hipStream_t stream);
 
+/* Pose scoring (port extension; ops.pose_score, MultiHeadModel.score_poses / search_pose, Test_Agent.py --verify /
+ * --search, Test_Geo.py --verify): the truncated feature-metric cost of P candidate poses per sample in one sweep, with no ground truth.
+ * pts f32 [B][3][N] (data['pc']), pc_feat rows [B*N][C], img_feat [B][h*w][C], C must be 64, mask [B*N] with mask_bytes 1 or 8, poses f32
+ * [B][P][4][4] each mapping pts into the camera frame, 1 <= P <= 4096, K f32 [B][3][3] for the h x w map (h*w <= 2^24), 0 <= radius <= 16,
+ * tau finite and > 0.  Per sample b, pose p and selected row n the quantities are cmr_guided_match_f32's, all in fp32 with the same
+ * operations in the same order: X_c = R x + t, p = K X_c, u = p0 / p2, v = p1 / p2, centre (cx, cy) = (rint u, rint v), half to even; the
+ * row is IN VIEW iff p2 > 0, u and v are finite and [cx - r, cx + r] x [cy - r, cy + r] meets the map (decided on the floats); dist =
+ * sqrtf of the least direct sum of (a - b)^2 over the window clipped to the map (order: DESIGN.md 4n), +inf for a window without one
+ * finite score.  Row cost: d = min(dist, tau) in fp32 if the row is in view, else d = tau; c = (double)d * (double)d.  So a row that is
+ * out of view, behind the camera or under a NaN pose costs tau^2, the most a row can cost.
+ *   score f64 [B][P]       the sum of c over the selected rows;
+ *   counts int32 [B][P][2] = {in view, close = in view and dist <= tau};
+ *   selected int32 [B]     the selected rows.  A sample without one gives score 0, counts 0, selected 0.
+ * Two launches on the stream whatever P is, no memset, no atomics, no host round trip.  The float64 sum has a fixed order that depends
+ * only on the sample's own rows and mask (256-row slices; inside a slice the selected rows in increasing n dealt to 16 groups, each
+ * summing its rows in order, the groups added in order; then the slices in order): two calls agree bit for bit, a pose scored in a batch
+ * of P equals the same pose scored alone bit for bit, and a sample depends on its own rows only.
+ * Workspace: cmr_pose_score_workspace_bytes(B, N, P), 16-byte aligned. */
+int64_t cmr_pose_score_workspace_bytes(int B, int N, int P);
+int cmr_pose_score_f32(const float* pts, const float* pc_feat, const float* img_feat, int C, int B, int N, int h, int w, const void* mask,
+                       int mask_bytes, const float* poses, int P, const float* K, int radius, float tau, double* score, int32_t* counts,
+                       int32_t* selected, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 /* ---- rollout ops of the training loop ---------------------------------------- */
 
 /* environment.py:143-176 (expert): residual pose target * source^-1 -> extrinsic-xyz Euler angles (folded back when the
