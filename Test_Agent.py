@@ -16,6 +16,11 @@ the prefix "Refined ".  Without the flag the output is unchanged.
 --subpixel (with --refine): every round's correspondences carry sub-pixel positions from a parabola fit on the feature
 distances round the matched pixel (cmr_match_subpixel_f32) instead of the integer pixel.  The lines printed are the same.
 
+--visible (with --refine; optional --visible-radius R, --visible-rel-tol T, --visible-abs-tol A): every --refine round first
+takes a z-buffer of the whole cloud under the round's pose (cmr_visibility_f32) and matches only the predicted-overlap points it leaves
+visible: depth <= nearest depth in the (2R + 1)^2 cells round the point's own * (1 + T) + A, defaults 1 / 0.05 / 0.  Each pair prints
+one extra line "visible <visible> of <in view> of <selected>" for the last round, before its "refined" line.
+
 --search (port extension): the agent's final pose (through env.from_disentangled) is the start of the derivative-free
 coarse-to-fine lattice search MultiHeadModel.search_pose (729 poses per round under cmr_pose_score_f32).  Per pair one extra line
 "searched <RTE> <RRE>", and after the closing block(s) the same three lines again with the prefix "Searched ".
@@ -44,7 +49,7 @@ from cmr_agent_amd.environment import environment as env  # noqa: E402
 from cmr_agent_amd.models import CMRAgent, MultiHeadModel  # noqa: E402
 from cmr_agent_amd.utils import hashfill, synthetic  # noqa: E402
 from cmr_agent_amd.utils.checkpoint import load_checked  # noqa: E402
-from cmr_agent_amd.utils.evalcli import guided_rounds, print_recall  # noqa: E402
+from cmr_agent_amd.utils.evalcli import add_visible_flags, guided_rounds, print_recall, print_visible, visible_option  # noqa: E402
 
 
 def get_P_diff(P_pred, P_gt):
@@ -70,6 +75,7 @@ def main():
     ap.add_argument('--subpixel', action='store_true', help="with --refine: sub-pixel match positions (parabola fit on the feature distances) in every round")
     ap.add_argument('--search', action='store_true', help="search round the agent's final pose on a coarse-to-fine pose lattice scored against the geometric features")
     ap.add_argument('--verify', action='store_true', help="score the pair's candidate poses against the geometric features (no ground truth) and report the best")
+    add_visible_flags(ap, "--refine")
     args = ap.parse_args()
     if args.subpixel and args.refine is None:
         ap.error("--subpixel belongs to --refine")
@@ -78,6 +84,8 @@ def main():
         radii, thrs = guided_rounds(ap, args.refine, args.guided_thr, ops.GUIDED_MAX_RADIUS)
     elif args.guided_thr is not None or args.guided_max_dist is not None:
         ap.error("--guided-thr / --guided-max-dist belong to --refine")
+    visible = visible_option(ap, args, "--refine", radii is not None, ops.GUIDED_MAX_RADIUS)
+    vis_kw = {} if visible is None else dict(visible=visible or True)
     dev = torch.device("cuda")
     Cfg = {"kitti": KittiConfiguration, "nuscenes": NuScenesConfiguration}[args.dataset]
     kw = {}
@@ -120,7 +128,9 @@ def main():
             if radii is not None:
                 start = env.from_disentangled(pose_source.clone(), data['pc'], data=data)
                 geo_model.refine_pose_from_matches(data, pose=start, radii=radii, thrs=thrs, max_dist=args.guided_max_dist,
-                                                   subpixel=args.subpixel)
+                                                   subpixel=args.subpixel, **vis_kw)
+                if vis_kw:
+                    print_visible(data['refine_visible_counts'])
                 ref = env.to_disentangled(data['refined_pose'].clone(), data['pc'], data=data)
                 t_diff, r_diff = get_P_diff(ref[0].cpu().numpy(), pose_target[0].cpu().numpy())
                 print("refined", t_diff, r_diff)

@@ -41,6 +41,11 @@ against the geometric features with no ground truth (MultiHeadModel.score_poses,
 <name>=<quality> ... -> <chosen name>", quality = 1 - score / (selected tau^2) in [0, 1], and after the closing block(s) the same three
 lines again for the chosen poses with the prefix "Verified ".  Without the flag the output is unchanged.
 
+--visible (with --guided; optional --visible-radius R, --visible-rel-tol T, --visible-abs-tol A): every --guided round first
+takes a z-buffer of the whole cloud under the round's pose (cmr_visibility_f32) and matches only the predicted-overlap points it leaves
+visible: depth <= nearest depth in the (2R + 1)^2 cells round the point's own * (1 + T) + A, defaults 1 / 0.05 / 0.  Each batch prints
+one extra line "visible <visible> of <in view> of <selected>" for the last round.  Without the flag the output is unchanged.
+
 Pairs come from the synthetic generator (cmr_agent_amd.utils.synthetic) unless --data-root names a dataset in the reference's layout
 (its 'test' split), and the weights are the deterministic hash fill unless --geo-ckpt points at a reference-format state_dict."""
 import argparse
@@ -63,7 +68,7 @@ from cmr_agent_amd.models import MultiHeadModel  # noqa: E402
 from cmr_agent_amd.models.MultiHeadModel import match_features  # noqa: E402
 from cmr_agent_amd.utils import hashfill, synthetic  # noqa: E402
 from cmr_agent_amd.utils.checkpoint import load_checked  # noqa: E402
-from cmr_agent_amd.utils.evalcli import guided_rounds, print_recall  # noqa: E402
+from cmr_agent_amd.utils.evalcli import add_visible_flags, guided_rounds, print_recall, print_visible, visible_option  # noqa: E402
 
 
 def _ratios(counts):
@@ -101,6 +106,7 @@ def main():
     ap.add_argument('--min-conf', type=float, default=None, help="with --pnp: keep a match when its dual-softmax confidence is >= C (0 < C <= 1)")
     ap.add_argument('--temperature', type=float, default=None, help="with --min-conf: temperature T of the softmax over -d^2 / T (default 0.1)")
     ap.add_argument('--verify', action='store_true', help="with --pnp: score the pair's candidate poses against the geometric features (no ground truth) and report the best")
+    add_visible_flags(ap, "--guided")
     args = ap.parse_args()
     if args.verify and not args.pnp:
         ap.error("--verify scores the PnP pose (and the --guided one): give --pnp as well")
@@ -132,6 +138,8 @@ def main():
         radii, thrs = guided_rounds(ap, args.guided, args.guided_thr, ops.GUIDED_MAX_RADIUS)
     elif args.guided_thr is not None or args.guided_max_dist is not None:
         ap.error("--guided-thr / --guided-max-dist belong to --guided")
+    visible = visible_option(ap, args, "--guided", radii is not None, ops.GUIDED_MAX_RADIUS)
+    vis_kw = {} if visible is None else dict(visible=visible or True)
     dev = torch.device("cuda")
     Cfg = {"kitti": KittiConfiguration, "nuscenes": NuScenesConfiguration}[args.dataset]
     kw = {}
@@ -185,7 +193,9 @@ def main():
                 gt = env.to_disentangled(data['P'].to(dev).float().clone(), data['pc'])
                 if radii is not None:
                     geo_model.refine_pose_from_matches(data, radii=radii, thrs=thrs, max_dist=args.guided_max_dist, img_overlap=img_overlap,
-                                                       subpixel=args.subpixel)
+                                                       subpixel=args.subpixel, **vis_kw)
+                    if vis_kw:
+                        print_visible(data['refine_visible_counts'])
                     ref = env.to_disentangled(data['refined_pose'].clone(), data['pc'])
                 names = ["pnp"] + (["refined"] if radii is not None else [])
                 if args.verify:

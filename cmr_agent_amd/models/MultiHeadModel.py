@@ -238,6 +238,19 @@ def _first_min(score):
     return torch.where(k < P, k, torch.zeros_like(k))
 
 
+def _visible_kw(visible, who):
+    """The `visible` keyword of refine_pose_from_matches / search_pose -> None (off) or ops.visibility's radius / rel_tol / abs_tol."""
+    if visible is None or visible is False:
+        return None
+    kw = dict(radius=1, rel_tol=0.05, abs_tol=0.0)
+    if visible is True:
+        return kw
+    if not isinstance(visible, dict) or set(visible) - set(kw):
+        raise ValueError("%s: visible must be None, True or a dict with keys among radius / rel_tol / abs_tol, got %r" % (who, visible))
+    kw.update(visible)
+    return kw
+
+
 class MultiHeadModel(Planned):
     def __init__(self, config):
         super().__init__()
@@ -337,7 +350,7 @@ class MultiHeadModel(Planned):
             data_batch['pnp_status'] = status
 
     def refine_pose_from_matches(self, data_batch, pose=None, radii=(6, 3, 2), thrs=(4.0, 2.0, 1.0), max_dist=None, iters=10, mask=None,
-                                 img_overlap=None, subpixel=False):
+                                 img_overlap=None, subpixel=False, visible=None):
         """Port extension: polish a pose from anywhere -- pose_from_matches' 'pnp_pose' (the default) or the agent's final
         pose through environment.from_disentangled -- against the geometric features.  For each (radius, thr) in turn: ops.guided_match
         under the current pose (every point of `mask`, default 'pc_overlap_pred', is matched inside the (2 radius + 1)^2 window round its
@@ -348,10 +361,15 @@ class MultiHeadModel(Planned):
         subpixel (off by default, and then nothing changes): every round's uv comes from ops.match_subpixel on that round's
         idx under that round's correspondence mask, and 'guided_subpixel_counts' int32 [rounds, B, 4] holds its counts (matched, fitted on
         both axes, integer pixel within SUBPIXEL_INLIER_THRES = 0.5 px of the projected point, sub-pixel position within it; the last two 0 without ground
-        truth).  Not called by forward."""
+        truth).
+        visible (None by default, and then nothing changes): True, or a dict of ops.visibility's radius / rel_tol / abs_tol
+        (defaults 1 / 0.05 / 0: values for the 1/4-scale map, not tuned on real data).  Every round first runs ops.visibility under that
+        round's current pose, the whole cloud occluding, and matches only the rows of `mask` that are visible; 'refine_visible_counts'
+        int32 [rounds, B, 4] holds its counts (selected, in view, visible, occluder rows in view).  Not called by forward."""
         radii, thrs = tuple(radii), tuple(thrs)
         if len(radii) != len(thrs) or not radii:
             raise ValueError("refine_pose_from_matches: radii and thrs must be non-empty and of equal length, got %r / %r" % (radii, thrs))
+        vis_kw = _visible_kw(visible, "refine_pose_from_matches")
         with torch.no_grad():
             pc = data_batch['pc'].float().contiguous()
             dev = pc.device
@@ -364,9 +382,13 @@ class MultiHeadModel(Planned):
             K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3).contiguous()
             xy = _gt_xy(data_batch, dev) if ('point_xy_float_all' in data_batch or 'pc_in_cam_space' in data_batch) else None
             ov = None if img_overlap is None else img_overlap.to(dev).reshape(B, -1).bool()
-            counts, sub_counts, inliers, status = [], [], None, None
+            counts, sub_counts, vis_counts, inliers, status = [], [], [], None, None
+            rsel = sel
             for radius, thr in zip(radii, thrs):
-                idx, keep, cnt, _, _ = ops.guided_match(pc, feat, img, sel, cur, K, radius, max_dist=max_dist or 0.0, gt_xy=xy,
+                if vis_kw is not None:
+                    rsel, vc, _, _, _ = ops.visibility(pc, cur, K, h, w, sel, **vis_kw)
+                    vis_counts.append(vc)
+                idx, keep, cnt, _, _ = ops.guided_match(pc, feat, img, rsel, cur, K, radius, max_dist=max_dist or 0.0, gt_xy=xy,
                                                         thr=MATCH_INLIER_THRES)
                 counts.append(cnt)
                 p = idx.view(B, N).long().clamp(min=0)
@@ -385,6 +407,8 @@ class MultiHeadModel(Planned):
             data_batch['guided_counts'] = torch.stack(counts)
             if subpixel:
                 data_batch['guided_subpixel_counts'] = torch.stack(sub_counts)
+            if vis_kw is not None:
+                data_batch['refine_visible_counts'] = torch.stack(vis_counts)
 
     def _score_args(self, data_batch, mask):
         pc = data_batch['pc'].float().contiguous()
@@ -403,7 +427,8 @@ class MultiHeadModel(Planned):
         its projection, and tau^2 when it does not project into the map.  tau = 0.8 suits unit-norm features; it is not tuned on real
         data.  Sets 'pose_scores' float64 [B, P] (lower is better), 'pose_score_counts' int32 [B, P, 2] (in view, in view and d <= tau),
         'pose_quality' float64 [B, P] = 1 - score / (selected tau^2) in [0, 1] (tau as rounded to float32; 0 where nothing is selected) and 'pose_best' int64 [B], the
-        lowest score, the lowest index on a tie.  Not called by forward."""
+        lowest score, the lowest index on a tie.  Occlusion composes through `mask`: pass visible_points' 'visible_mask'
+        under the pose of interest and the hidden rows neither score nor pay tau^2.  Not called by forward."""
         with torch.no_grad():
             pc, feat, img, sel, K = self._score_args(data_batch, mask)
             poses = poses.to(pc.device).float().contiguous()
@@ -415,17 +440,20 @@ class MultiHeadModel(Planned):
             data_batch['pose_quality'] = torch.where(full > 0, (1.0 - score / full.clamp(min=1e-300)).clamp(min=0.0), torch.zeros_like(score))
             data_batch['pose_best'] = _first_min(score)
 
-    def search_pose(self, data_batch, pose=None, levels=SEARCH_LEVELS, tau=0.8, mask=None):
+    def search_pose(self, data_batch, pose=None, levels=SEARCH_LEVELS, tau=0.8, mask=None, visible=None):
         """Port extension: derivative-free coarse-to-fine lattice search of the pose under ops.pose_score -- the
         counterpart without learned weights of the reference's 9^3-pose IterModel cost volume.  pose: float32 [B, 4, 4], default
         'pnp_pose'.  levels: a sequence of (radius, rot_step_deg, trans_step, rounds); every round scores the 729 poses D_i cur
         (pose_search_table: left increments of -1 / 0 / +1 steps on the three rotation and three translation axes, index 0 = stay) in one
         call and moves to the best, the lowest index on a tie, so a plateau keeps the current pose.  The round count is fixed: no early
         exit, no host synchronisation.  Sets 'searched_pose' float32 [B, 4, 4] and 'searched_score' float64 [B], the last round's best.
-        Not called by forward."""
+        visible (None by default, and then nothing changes): as in refine_pose_from_matches; ops.visibility runs once at the
+        start of each level under the current pose and the level scores the visible rows of `mask` only; 'search_visible_counts' int32
+        [levels, B, 4].  Not called by forward."""
         levels = tuple(tuple(l) for l in levels)
         if not levels or any(len(l) != 4 or not ops._is_int(l[3]) or l[3] < 1 for l in levels):
             raise ValueError("search_pose: levels must be a non-empty sequence of (radius, rot_step_deg, trans_step, rounds >= 1), got %r" % (levels,))
+        vis_kw = _visible_kw(visible, "search_pose")
         with torch.no_grad():
             pc, feat, img, sel, K = self._score_args(data_batch, mask)
             dev = pc.device
@@ -433,16 +461,63 @@ class MultiHeadModel(Planned):
             cur = (data_batch['pnp_pose'] if pose is None else pose).to(dev).float().contiguous()
             rows = torch.arange(B, device=dev)
             best = None
+            lsel, vis_counts = sel, []
             for radius, rot, trans, rounds in levels:
                 D = pose_search_table(rot, trans).to(dev)
+                if vis_kw is not None:
+                    lsel, vc, _, _, _ = ops.visibility(pc, cur, K, img.shape[1], img.shape[2], sel, **vis_kw)
+                    vis_counts.append(vc)
                 for _ in range(int(rounds)):
                     cand = torch.matmul(D[None], cur.double()[:, None]).float().contiguous()      # [B, 729, 4, 4]; D_0 = I: cand[:, 0] is cur
-                    score, _, _ = ops.pose_score(pc, feat, img, sel, cand, K, radius=radius, tau=tau)
+                    score, _, _ = ops.pose_score(pc, feat, img, lsel, cand, K, radius=radius, tau=tau)
                     k = _first_min(score)
                     cur = cand[rows, k].contiguous()
                     best = score[rows, k]
             data_batch['searched_pose'] = cur
             data_batch['searched_score'] = best
+            if vis_kw is not None:
+                data_batch['search_visible_counts'] = torch.stack(vis_counts)
+
+    def visible_points(self, data_batch, pose=None, radius=1, rel_tol=0.05, abs_tol=0.0, mask=None, occluders='all'):
+        """Port extension: which points of `mask` (default 'pc_overlap_pred') the camera sees under `pose` (float32
+        [B, 4, 4] mapping 'pc' into the camera frame, default 'pnp_pose'), by a z-buffer on the geometric map's h x w with 'K'
+        (ops.visibility).  occluders: 'all' (every point of the cloud blocks the view, also outside the predicted overlap) or 'mask' (only
+        the queried points do).  A point is visible iff it projects into the map and its depth is <= zmin (1 + rel_tol) + abs_tol, zmin =
+        the nearest depth in the (2 radius + 1)^2 cells round its own.  radius = 1 and rel_tol = 0.05 are defaults for the 1/4-scale map;
+        they are not tuned on real data.  Sets 'visible_mask' bool [B, N] and 'visible_counts' int32 [B, 4] (selected, in view, visible,
+        occluder points in view).  Not called by forward."""
+        if occluders not in ('all', 'mask'):
+            raise ValueError("visible_points: occluders must be 'all' or 'mask', got %r" % (occluders,))
+        with torch.no_grad():
+            pc, _, img, sel, K = self._score_args(data_batch, mask)
+            B, h, w, _ = img.shape
+            cur = (data_batch['pnp_pose'] if pose is None else pose).to(pc.device).float().contiguous()
+            vis, counts, _, _, _ = ops.visibility(pc, cur, K, h, w, sel, occ_mask=sel if occluders == 'mask' else None, radius=radius,
+                                                  rel_tol=rel_tol, abs_tol=abs_tol)
+            data_batch['visible_mask'] = vis.view(B, pc.shape[2])
+            data_batch['visible_counts'] = counts
+
+    def render_depth(self, data_batch, pose=None, size=None, K=None):
+        """Port extension: the sparse depth map of the whole cloud under `pose` (default 'pnp_pose'): every point goes to the
+        cell of its rounded projection and a cell keeps the nearest depth (ops.visibility's z-buffer).  By default on the geometric map's
+        h x w with 'K'; size = (H, W) together with K (float32 [B, 3, 3] or [3, 3] for that resolution) renders at another one, e.g. the
+        full image.  Sets 'depth_map' float32 [B, h, w], +inf in the cells no point falls into.  Not called by forward."""
+        if (size is None) != (K is None):
+            raise ValueError("render_depth: size and K go together (both or neither)")
+        with torch.no_grad():
+            pc = data_batch['pc'].float().contiguous()
+            dev = pc.device
+            B, _, N = pc.shape
+            if size is None:
+                h, w = _geo_rows(data_batch)[1].shape[1:3]
+                K = data_batch['K']
+            else:
+                h, w = size
+            K = K.to(dev).float()
+            K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3).contiguous()
+            cur = (data_batch['pnp_pose'] if pose is None else pose).to(dev).float().contiguous()
+            every = torch.ones(B, N, dtype=torch.bool, device=dev)
+            data_batch['depth_map'] = ops.visibility(pc, cur, K, h, w, every, radius=0, want_depth_map=True)[2]
 
     def forward_cl(self, data_batch):
         cl = self.encoder_decoder.forward_cl(data_batch)

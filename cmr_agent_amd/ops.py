@@ -1230,6 +1230,73 @@ def pose_score(pts, pc_feat_rows, img_feat_nhwc, mask, poses, K, radius=0, tau=0
     return score, counts, selected
 
 
+def _tol_ok(v):
+    try:
+        return 0.0 <= float(v) < float("inf") and float(torch.tensor(float(v), dtype=f32)) < float("inf")
+    except (TypeError, ValueError, OverflowError):
+        return False
+
+
+def visibility(pts, pose, K, h, w, mask, occ_mask=None, radius=1, rel_tol=0.05, abs_tol=0.0, want_depth_map=False, want_cell=False,
+               want_depth=False):
+    """Z-buffer visibility of the queried points and the rendered depth of the cloud under `pose` (include/cmr_hip.h cmr_visibility_f32,
+    DESIGN.md 4r): pts float32 [B, 3, N] (data['pc']), pose float32 [B, 4, 4] mapping pts into the camera frame, K float32 [B, 3, 3] for
+    the h x w map (1 <= h w <= 2^24; no features are read, so the 1/4-scale feature map and the full image both work), mask [B, N] /
+    [B*N] of bool / uint8 / int64 = the rows that are queried, occ_mask the same = the rows that occlude (None: every row), 0 <= radius
+    <= GUIDED_MAX_RADIUS, rel_tol and abs_tol finite and >= 0.  Z[b, y, x] = the least depth p2 of the occluder rows whose rounded
+    projection is (x, y), +inf where there is none; a queried row in view (guided_match's predicate at radius 0) is visible iff its own
+    depth z <= zmin * (1 + rel_tol) + abs_tol, zmin = the least Z over the (2 radius + 1)^2 window round its own cell.  radius = 1 and
+    rel_tol = 0.05 are defaults for the 1/4-scale map; they are not tuned on real data.
+    -> (visible bool [B*N], counts int32 [B, 4] = (selected, selected and in view, visible, occluder rows in view), depth_map float32
+    [B, h, w] or None, cell int32 [B*N] = y * w + x of the rows of mask | occ_mask in view, else -1, or None, depth float32 [B*N] = p2 of
+    those rows where p2 > 0, else NaN, or None)."""
+    if pts.dim() != 3 or pts.shape[1] != 3:
+        raise ValueError("visibility: pts must be [B, 3, N], got %s" % (tuple(pts.shape),))
+    B, _, N = pts.shape
+    if pts.dtype != f32 or pose.dtype != f32 or K.dtype != f32:
+        raise ValueError("visibility: pts, pose and K must be float32, got %s / %s / %s" % (pts.dtype, pose.dtype, K.dtype))
+    if tuple(pose.shape) != (B, 4, 4):
+        raise ValueError("visibility: pose must be [%d, 4, 4], got %s" % (B, tuple(pose.shape)))
+    if tuple(K.shape) != (B, 3, 3):
+        raise ValueError("visibility: K must be [%d, 3, 3], got %s" % (B, tuple(K.shape)))
+    if not _is_int(h) or not _is_int(w):
+        raise ValueError("visibility: h and w must be integers, got %r x %r" % (h, w))
+    h, w = int(h), int(w)
+    if B < 1 or B > GRID_Y_MAX or N < 1 or N > GRID_Y_MAX * 256 or h < 1 or w < 1 or h * w > 1 << 24:
+        raise ValueError("visibility: need 1 <= B <= %d, 1 <= N <= %d and a map of 1 .. 2^24 pixels, got B=%d N=%d map %d x %d" % (
+            GRID_Y_MAX, GRID_Y_MAX * 256, B, N, h, w))
+    if mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N:
+        raise ValueError("visibility: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (B * N, mask.dtype, tuple(mask.shape)))
+    if occ_mask is not None and (occ_mask.dtype not in (torch.bool, torch.uint8, torch.int64) or occ_mask.numel() != B * N):
+        raise ValueError("visibility: occ_mask must be bool / uint8 / int64 with %d elements, got %s %s" % (
+            B * N, occ_mask.dtype, tuple(occ_mask.shape)))
+    if not _is_int(radius) or not 0 <= radius <= GUIDED_MAX_RADIUS:
+        raise ValueError("visibility: radius must be an integer in [0, %d], got %r" % (GUIDED_MAX_RADIUS, radius))
+    if not _tol_ok(rel_tol):
+        raise ValueError("visibility: rel_tol must be finite and >= 0, got %r" % (rel_tol,))
+    if not _tol_ok(abs_tol):
+        raise ValueError("visibility: abs_tol must be finite and >= 0, got %r" % (abs_tol,))
+    ts = [t for t in (pts, pose, K, mask, occ_mask) if t is not None]
+    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
+        raise ValueError("visibility: every tensor must be a contiguous tensor on the same GPU")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    if occ_mask is not None and occ_mask.dtype == torch.bool:
+        occ_mask = occ_mask.view(torch.uint8)
+    dev = pts.device
+    visible = torch.empty((B * N,), dtype=torch.uint8, device=dev)
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    depth_map = torch.empty((B, h, w), dtype=f32, device=dev) if want_depth_map else None
+    cell = torch.empty((B * N,), dtype=torch.int32, device=dev) if want_cell else None
+    depth = torch.empty((B * N,), dtype=f32, device=dev) if want_depth else None
+    nb = _lib.load().cmr_visibility_workspace_bytes(B, N, h, w)
+    ws = _ws(nb, dev)
+    _lib.call("cmr_visibility_f32", _p(pts), _p(mask), mask.element_size(), _p(occ_mask), 1 if occ_mask is None else occ_mask.element_size(),
+              _p(pose), _p(K), B, N, h, w, int(radius), float(rel_tol), float(abs_tol), _p(visible), _p(counts), _p(depth_map), _p(cell),
+              _p(depth), _p(ws), nb, _stream())
+    return visible.view(torch.bool), counts, depth_map, cell, depth
+
+
 def pnp_refine(pts, uv, mask, K, pose, thr=1.0, iters=10):
     """Gauss-Newton refinement of a given pose on 2-D/3-D correspondences (include/cmr_hip.h cmr_pnp_refine_f32): pts
     float32 [B, 3, N], uv float32 [B, 2, N], mask [B, N] / [B*N] of bool / uint8 / int64, K float32 [B, 3, 3], pose float32 [B, 4, 4]

@@ -1,4 +1,5 @@
-"""Command-line helpers shared by Test_Geo.py and Test_Agent.py: the round lists of --guided / --refine and the closing recall block."""
+"""Command-line helpers shared by Test_Geo.py and Test_Agent.py: the round lists of --guided / --refine, the --visible flags and the
+closing recall block."""
 import numpy as np
 
 
@@ -12,6 +13,38 @@ def guided_rounds(ap, radii, thrs, max_radius):
     if len(radii) != len(thrs) or not all(0 <= r <= max_radius for r in radii) or not all(0.0 < t < float("inf") for t in thrs):
         ap.error("need one threshold > 0 per window radius, radii in [0, %d]" % max_radius)
     return radii, thrs
+
+
+def add_visible_flags(ap, parent):
+    """--visible and its three optional values; `parent` is the flag whose rounds it acts on (--guided / --refine)."""
+    ap.add_argument('--visible', action='store_true', help="with %s: every round matches only the points a z-buffer of the cloud under the "
+                    "round's pose leaves visible" % parent)
+    ap.add_argument('--visible-radius', type=int, default=None, help="with --visible: the z-buffer is searched in the (2R + 1)^2 cells round the point's own (default 1)")
+    ap.add_argument('--visible-rel-tol', type=float, default=None, help="with --visible: visible when depth <= nearest * (1 + T) + A (default T = 0.05)")
+    ap.add_argument('--visible-abs-tol', type=float, default=None, help="with --visible: the A of the line above (default 0)")
+
+
+def visible_option(ap, args, parent, parent_given, max_radius):
+    """-> None without --visible, else the dict refine_pose_from_matches(visible=) takes; ap.error on a misplaced or malformed value."""
+    given = {"radius": args.visible_radius, "rel_tol": args.visible_rel_tol, "abs_tol": args.visible_abs_tol}
+    given = {k: v for k, v in given.items() if v is not None}
+    if not args.visible:
+        if given:
+            ap.error("--visible-radius / --visible-rel-tol / --visible-abs-tol belong to --visible")
+        return None
+    if not parent_given:
+        ap.error("--visible acts on the rounds of %s: give %s as well" % (parent, parent))
+    if not 0 <= given.get("radius", 1) <= max_radius:
+        ap.error("--visible-radius must lie in [0, %d]" % max_radius)
+    if not all(0.0 <= given.get(k, 0.0) < float("inf") for k in ("rel_tol", "abs_tol")):
+        ap.error("--visible-rel-tol and --visible-abs-tol must be finite and >= 0")
+    return given
+
+
+def print_visible(counts):
+    """One line per batch from refine_pose_from_matches' 'refine_visible_counts' [rounds, B, 4]: the last round's, summed over the batch."""
+    c = counts[-1].sum(0).cpu().tolist()
+    print("visible", int(c[2]), "of", int(c[1]), "of", int(c[0]))
 
 
 def print_recall(rte, rre, prefix=""):

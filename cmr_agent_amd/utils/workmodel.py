@@ -169,6 +169,12 @@ WORK = {
     "cmr_pose_score_f32": lambda a: (3.0 * 64 * (2 * a["radius"] + 1) ** 2 * a["B"] * a["N"] * a["P"],
                                      a["B"] * a["N"] * ((12 + a["mask_bytes"] + 256) * ((a["P"] + 31) // 32)
                                                         + 256.0 * (2 * a["radius"] + 1) ** 2 * a["P"])),
+    # DESIGN.md 4r, every row taken as queried, occluding and in view: the fill of Z (4 B a cell), per row the point and two masks in, cell
+    # and depth out and read back (16 B), a 4-byte atomic on Z, (2r + 1)^2 window cells of 4 B and 1 B of visible; ~40 FLOP of projection
+    # per row, a compare per window cell
+    "cmr_visibility_f32": lambda a: ((40.0 + (2 * a["radius"] + 1) ** 2) * a["B"] * a["N"],
+                                     4.0 * a["B"] * a["h"] * a["w"] + a["B"] * a["N"] * (12 + 2 * a["mask_bytes"] + a["occ_mask_bytes"] + 16 + 4
+                                                                                         + 4 * (2 * a["radius"] + 1) ** 2 + 1)),
     # training direction (Train_Agent.py:296-305, Train_Geo.py:166-174): weight gradients as GEMMs over the minibatch's pixels / rows
     "cmr_conv3x3_wgrad_f32": lambda a: (2.0 * 9 * a["Cin"] * a["Cout"] * a["B"] * a["H"] * a["W"],
                                         F * (a["B"] * a["H"] * a["W"] * (a["Cin"] + a["Cout"]) + 9 * a["Cin"] * a["Cout"])),

@@ -495,6 +495,38 @@ int cmr_pose_score_f32(const float* pts, const float* pc_feat, const float* img_
                        int mask_bytes, const float* poses, int P, const float* K, int radius, float tau, double* score, int32_t* counts,
                        int32_t* selected, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+/* Point visibility and depth rendering under a pose (port extension; ops.visibility, MultiHeadModel.visible_points /
+ * render_depth, refine_pose_from_matches / search_pose with visible=, Test_Geo.py / Test_Agent.py --visible): a one-cell z-buffer of the
+ * cloud on the h x w map and, per queried row, the test of its depth against the nearest depth round its projection.  No features are
+ * read, so h x w may be the 1/4-scale feature map or the full image (h*w <= 2^24).  pts f32 [B][3][N] (data['pc']), pose f32 [B][4][4]
+ * mapping pts into the camera frame, K f32 [B][3][3] for the h x w map; mask [B*N] selects the rows that are QUERIED, occ_mask [B*N] the
+ * rows that OCCLUDE (null: every row of the sample occludes); mask_bytes and occ_mask_bytes are 1 or 8 each (occ_mask_bytes is checked
+ * even when occ_mask is null); 0 <= radius <= 16; rel_tol >= 0, abs_tol >= 0, both finite.  All of this is refused up front with
+ * CMR_EINVAL; nothing depends on the data.
+ * Per sample b and row n, all in fp32 with cmr_guided_match_f32's operations in the same order: X_c = R x + t, p = K X_c, u = p0 / p2,
+ * v = p1 / p2, centre (cx, cy) = (rint u, rint v), half to even; the row is IN VIEW iff p2 > 0, u and v are finite, 0 <= cx <= w - 1 and
+ * 0 <= cy <= h - 1 (decided on the floats: cmr_guided_match_f32's predicate at radius 0); its depth is z = p2.
+ * Z[b][y][x] = the least z over the occluder rows in view whose centre is (x, y), +inf where there is none (an unsigned integer atomic
+ * min on the bits of the positive floats: order independent).  A queried row that is not an occluder does not enter Z.
+ * zmin = the least Z over the (2 radius + 1)^2 window round the row's own centre, clipped to the map; bound = zmin * opr + abs_tol with
+ * opr = (float)(1.0 + (double)rel_tol), the product and the sum each rounded to fp32 (no fma); visible = selected and in view and
+ * z <= bound.  An empty window has zmin = +inf and the row is visible.
+ *   visible u8 [B*N]          0 for unselected rows;
+ *   counts int32 [B][4]     = {selected, selected and in view, visible, occluder rows in view}; the call zeroes it;
+ *   depth_map (optional) f32 [B][h*w] = Z; 4-byte aligned;
+ *   cell (optional) int32 [B*N]  cy * w + cx for every row of mask | occ_mask that is in view, else -1;
+ *   depth (optional) f32 [B*N]   z for the rows of mask | occ_mask with p2 > 0, else NaN.
+ * A NaN pose gives nothing in view, Z all +inf and nothing visible; a sample without a selected row gives visible 0 and counts[0..2] 0.
+ * Three launches on the stream whatever the data (fill of Z and counts, splat, test), no host round trip; every visible / cell / depth
+ * element is a plain store by the thread that owns the row, Z is an integer atomic min, counts are integer atomics, one per workgroup
+ * and word: two calls agree bit for bit and a sample depends on its own rows only.
+ * Workspace: cmr_visibility_workspace_bytes(B, N, h, w), 16-byte aligned (holds Z, cell and depth where the caller passes none). */
+int64_t cmr_visibility_workspace_bytes(int B, int N, int h, int w);
+int cmr_visibility_f32(const float* pts, const void* mask, int mask_bytes, const void* occ_mask, int occ_mask_bytes, const float* pose,
+                       const float* K, int B, int N, int h, int w, int radius, float rel_tol, float abs_tol, uint8_t* visible,
+                       int32_t* counts, float* depth_map, int32_t* cell, float* depth, void* workspace, int64_t workspace_bytes,
+                       hipStream_t stream);
+
 /* ---- rollout ops of the training loop ---------------------------------------- */
 
 /* environment.py:143-176 (expert): residual pose target * source^-1 -> extrinsic-xyz Euler angles (folded back when the
