@@ -28,7 +28,13 @@ coarse-to-fine lattice search MultiHeadModel.search_pose (729 poses per round un
 --verify: the candidate poses of the pair -- the agent's final pose, the refined pose (--refine), the searched pose
 (--search) -- are scored against the geometric features with no ground truth (MultiHeadModel.score_poses, window radius 0) and the pair
 prints "verified <name>=<quality> ... -> <chosen name>", quality = 1 - score / (selected tau^2) in [0, 1]; the chosen pose's RTE / RRE
-are collected and the closing lines printed once more with the prefix "Verified ".  Without these flags the output is unchanged."""
+are collected and the closing lines printed once more with the prefix "Verified ".  Without these flags the output is unchanged.
+
+--paint DIR [--paint-visible]: every pair's cloud is painted with the image under the last pose the run produced -- the
+refined pose with --refine, else the agent's final pose through env.from_disentangled (cmr_paint_points_f32, bilinear) -- and
+DIR/pair_<index>.ply holds the painted points (binary little-endian PLY: x y z float32 in the cloud's own frame, red green blue uchar =
+clamp(rint(255 c), 0, 255)); --paint-visible paints only the points a z-buffer of the cloud under that pose leaves visible.  Each pair
+prints one extra line "painted <painted> of <selected>".  Without the flag the output is unchanged."""
 import argparse
 import json
 import os
@@ -49,7 +55,8 @@ from cmr_agent_amd.environment import environment as env  # noqa: E402
 from cmr_agent_amd.models import CMRAgent, MultiHeadModel  # noqa: E402
 from cmr_agent_amd.utils import hashfill, synthetic  # noqa: E402
 from cmr_agent_amd.utils.checkpoint import load_checked  # noqa: E402
-from cmr_agent_amd.utils.evalcli import add_visible_flags, guided_rounds, print_recall, print_visible, visible_option  # noqa: E402
+from cmr_agent_amd.utils.evalcli import (add_paint_flags, add_visible_flags, guided_rounds, paint_option, paint_pairs, print_recall,  # noqa: E402
+                                         print_visible, visible_option)
 
 
 def get_P_diff(P_pred, P_gt):
@@ -76,7 +83,9 @@ def main():
     ap.add_argument('--search', action='store_true', help="search round the agent's final pose on a coarse-to-fine pose lattice scored against the geometric features")
     ap.add_argument('--verify', action='store_true', help="score the pair's candidate poses against the geometric features (no ground truth) and report the best")
     add_visible_flags(ap, "--refine")
+    add_paint_flags(ap)
     args = ap.parse_args()
+    paint = paint_option(ap, args)
     if args.subpixel and args.refine is None:
         ap.error("--subpixel belongs to --refine")
     radii = thrs = None
@@ -108,7 +117,7 @@ def main():
         else:
             frames = (synthetic.make_batch(1, config.num_pt, config.cropped_img_H, config.cropped_img_W, config.num_node,
                                            hip_fps(dev), hip_nearest(dev), seed=config.seed + i, n_circle=16, device=dev) for i in range(args.pairs))
-        for data in frames:                                          # batch_size = 1 like the reference loader (:125)
+        for index, data in enumerate(frames):                        # batch_size = 1 like the reference loader (:125)
             geo_model(data)
             pose_source, pose_target = env.init(data)
             pose_target = env.to_disentangled(pose_target, data['pc'], data=data)
@@ -152,6 +161,9 @@ def main():
                 print("verified", " ".join("%s=%.4f" % (c[0], q) for c, q in zip(cands, quality)), "->", cands[k][0])
                 rte_ver.append(cands[k][2][0])
                 rre_ver.append(cands[k][2][1])
+            if paint is not None:
+                last = data['refined_pose'] if radii is not None else env.from_disentangled(pose_source.clone(), data['pc'], data=data)
+                paint_pairs(geo_model, data, last, paint, index)
     print_recall(rte, rre)
     if radii is not None:
         print_recall(rte_ref, rre_ref, "Refined ")

@@ -46,6 +46,12 @@ takes a z-buffer of the whole cloud under the round's pose (cmr_visibility_f32) 
 visible: depth <= nearest depth in the (2R + 1)^2 cells round the point's own * (1 + T) + A, defaults 1 / 0.05 / 0.  Each batch prints
 one extra line "visible <visible> of <in view> of <selected>" for the last round.  Without the flag the output is unchanged.
 
+--paint DIR [--paint-visible] (with --pnp): every pair's cloud is painted with the image under the last pose the run produced
+-- the verified choice with --verify, else the refined pose with --guided, else the PnP pose (cmr_paint_points_f32, bilinear) -- and
+DIR/pair_<index>.ply holds the painted points (binary little-endian PLY: x y z float32 in the cloud's own frame, red green blue uchar =
+clamp(rint(255 c), 0, 255)); --paint-visible paints only the points a z-buffer of the cloud under that pose leaves visible.  Each batch
+prints one extra line "painted <painted> of <selected>".  Without the flag the output is unchanged.
+
 Pairs come from the synthetic generator (cmr_agent_amd.utils.synthetic) unless --data-root names a dataset in the reference's layout
 (its 'test' split), and the weights are the deterministic hash fill unless --geo-ckpt points at a reference-format state_dict."""
 import argparse
@@ -68,7 +74,8 @@ from cmr_agent_amd.models import MultiHeadModel  # noqa: E402
 from cmr_agent_amd.models.MultiHeadModel import match_features  # noqa: E402
 from cmr_agent_amd.utils import hashfill, synthetic  # noqa: E402
 from cmr_agent_amd.utils.checkpoint import load_checked  # noqa: E402
-from cmr_agent_amd.utils.evalcli import add_visible_flags, guided_rounds, print_recall, print_visible, visible_option  # noqa: E402
+from cmr_agent_amd.utils.evalcli import (add_paint_flags, add_visible_flags, guided_rounds, paint_option, paint_pairs, print_recall,  # noqa: E402
+                                         print_visible, visible_option)
 
 
 def _ratios(counts):
@@ -107,7 +114,9 @@ def main():
     ap.add_argument('--temperature', type=float, default=None, help="with --min-conf: temperature T of the softmax over -d^2 / T (default 0.1)")
     ap.add_argument('--verify', action='store_true', help="with --pnp: score the pair's candidate poses against the geometric features (no ground truth) and report the best")
     add_visible_flags(ap, "--guided")
+    add_paint_flags(ap, "--pnp")
     args = ap.parse_args()
+    paint = paint_option(ap, args, "--pnp", args.pnp)
     if args.verify and not args.pnp:
         ap.error("--verify scores the PnP pose (and the --guided one): give --pnp as well")
     filtered = args.mutual or args.ratio is not None
@@ -154,6 +163,7 @@ def main():
     bs, nbatch = args.batch_size, (args.pairs + args.batch_size - 1) // args.batch_size
     prec, rec, ir, ir1, ir2 = [], [], [], [], []
     rte, rre, rte_ref, rre_ref, rte_ver, rre_ver = [], [], [], [], [], []
+    done = 0
     with torch.no_grad():
         if args.data_root:
             from cmr_agent_amd.dataset import FrameDataset, FrameLoader
@@ -217,6 +227,13 @@ def main():
                         print("verified", " ".join("%s=%.4f" % (n, q) for n, q in zip(names, quality[b])), "->", names[chosen[b]])
                         rte_ver.append(errs[chosen[b]][0])
                         rre_ver.append(errs[chosen[b]][1])
+                if paint is not None:
+                    last = data['refined_pose'] if radii is not None else data['pnp_pose']
+                    if args.verify:
+                        last = torch.stack([data['pnp_pose']] + ([data['refined_pose']] if radii is not None else []), 1)[
+                            torch.arange(pred.shape[0], device=dev), data['pose_best']]
+                    paint_pairs(geo_model, data, last, paint, done)
+            done += data['pc'].shape[0]
 
     mean = lambda v: float(np.mean(v)) if v else float("nan")
     print(mean(prec), mean(rec), mean(ir), mean(ir1), mean(ir2))

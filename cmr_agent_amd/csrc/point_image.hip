@@ -1,0 +1,317 @@
+// Point painting and z-buffered attribute rendering under a pose (port extension): the two directions between a cloud and
+// an image once a pose is known.  Both project with guided_match.hip:gm_project_kernel's fp32 fmaf chains in the same order (copied, as
+// pose_score.hip and visibility.hip copy them), so "painted", "in view" (guided match at radius 0) and ops.visibility's cell are the same
+// rows and cells bit for bit.
+//
+// cmr_paint_points_f32 -- the image laid over the cloud.  Two launches on the caller's stream:
+//   pi_zero_kernel    counts = 0.
+//   pi_paint_kernel   one thread per row on (ceil(N / 256), B): projection (pose and K are wave-uniform: scalar loads), the in-view test
+//                     on the floats, then the C planes PI_PLANES at a time: the taps of all PI_PLANES planes (4 each when bilinear) are
+//                     loaded before the first is used, the three lerps are rounded operation by operation (pi_lerp, under
+//                     fp contract(off): never an fma, so plain fp32 torch code gives the same bits), and colours are stored coalesced (consecutive
+//                     n within a plane), 0 for the rows that are not painted.  counts by one atomic per workgroup and word.
+// cmr_render_points_f32 -- the cloud laid over the image: a z-buffer that remembers its owner.  Three launches, no memset node:
+//   pi_fill_kernel    key map = all ones (16-byte stores; the workspace is 16-byte aligned) and counts = 0.
+//   pi_splat_kernel   one thread per row: a selected row in view lowers the 64-bit key (bits of z) << 32 | n of its cell with ONE unsigned
+//                     64-bit vector atomic min (positive floats order like their bits, so the nearest row wins and equal depths go to the
+//                     lowest n: the map does not depend on the order of arrival).
+//   pi_resolve_kernel one thread per pixel, templated on the footprint S = splat: the least key over the (2S + 1)^2 cells round the pixel as
+//                     a gather -- compile-time loop bounds, clamped addresses and a select, all loads of a line in flight together; a
+//                     minimum is exact, so this equals (2S + 1)^2 atomics per row -- then coalesced stores of index / depth / attribute
+//                     maps; the gather attr[b, c, owner] (PI_PLANES planes in flight) is the only scattered read.
+// No floating-point atomic anywhere; every output element is a plain store by the thread that owns it.
+#include "cmr_common.h"
+
+namespace {
+
+constexpr int PI_THREADS = 256;
+constexpr int PI_PLANES = 4;       // planes whose taps / gathers are in flight together
+constexpr int PI_MAX_C = 64;
+constexpr int PI_MAX_SPLAT = 4;
+constexpr unsigned long long PI_EMPTY = ~0ull;
+
+__device__ __forceinline__ bool pi_sel(const void* mask, int mask_bytes, int64_t g) {
+  return !mask ? true : (mask_bytes == 1 ? ((const uint8_t*)mask)[g] != 0 : ((const int64_t*)mask)[g] != 0);
+}
+
+// the workgroup's number of set flags per flag, valid in every thread; `part` holds one word per flag and wave
+template <int NF>
+__device__ __forceinline__ void pi_block_counts(const bool (&flag)[NF], int (&part)[NF][PI_THREADS / 64], int (&total)[NF]) {
+#pragma unroll
+  for (int f = 0; f < NF; ++f) {
+    const unsigned long long bal = __ballot(flag[f]);
+    if ((threadIdx.x & 63) == 0) part[f][threadIdx.x >> 6] = __popcll(bal);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int f = 0; f < NF; ++f) total[f] = part[f][0] + part[f][1] + part[f][2] + part[f][3];
+}
+
+struct PiProj {
+  float u, v, z;      // u, v NaN where p2 <= 0; z = p2 (meaningful where view)
+  bool view;
+  int cx, cy;         // the rounded projection, valid where view
+};
+
+// guided_match.hip:gm_project_kernel, the same operations in the same order; the in-view test is its predicate at radius 0
+__device__ __forceinline__ PiProj pi_project(const float* __restrict__ P, const float* __restrict__ K, const float* __restrict__ x, int N,
+                                             int n, int h, int w) {
+  PiProj r;
+  const float X = x[n], Y = x[N + n], Z = x[2 * N + n];
+  const float xc = fmaf(P[0], X, fmaf(P[1], Y, fmaf(P[2], Z, P[3])));
+  const float yc = fmaf(P[4], X, fmaf(P[5], Y, fmaf(P[6], Z, P[7])));
+  const float zc = fmaf(P[8], X, fmaf(P[9], Y, fmaf(P[10], Z, P[11])));
+  const float p0 = fmaf(K[0], xc, fmaf(K[1], yc, K[2] * zc));
+  const float p1 = fmaf(K[3], xc, fmaf(K[4], yc, K[5] * zc));
+  const float p2 = fmaf(K[6], xc, fmaf(K[7], yc, K[8] * zc));
+  r.u = r.v = __builtin_nanf("");
+  r.z = p2;
+  r.view = false;
+  r.cx = r.cy = 0;
+  if (p2 > 0.f) {
+    r.u = p0 / p2;
+    r.v = p1 / p2;
+    if (isfinite(r.u) && isfinite(r.v)) {
+      const float cx = rintf(r.u), cy = rintf(r.v);                      // round half to even; decided on the floats
+      r.view = cx >= 0.f && cx <= (float)(w - 1) && cy >= 0.f && cy <= (float)(h - 1);
+      if (r.view) { r.cx = (int)cx; r.cy = (int)cy; }
+    }
+  }
+  return r;
+}
+
+// a + t (b - a) with three roundings.  HIP's __fmul_rn / __fadd_rn are a plain product and sum that carry the translation unit's
+// default -ffp-contract=fast, and the backend fuses them into one fma; plain operators under the pragma carry no such licence.
+__device__ __forceinline__ float pi_lerp(float a, float b, float t) {
+#pragma clang fp contract(off)
+  const float d = b - a;
+  const float m = t * d;
+  return a + m;
+}
+
+__device__ __forceinline__ int pi_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+__global__ __launch_bounds__(PI_THREADS) void pi_zero_kernel(int32_t* __restrict__ counts, int ncounts) {
+  for (int c = blockIdx.x * PI_THREADS + threadIdx.x; c < ncounts; c += gridDim.x * PI_THREADS) counts[c] = 0;
+}
+
+template <bool BILINEAR>
+__global__ __launch_bounds__(PI_THREADS) void pi_paint_kernel(const float* __restrict__ pts, const void* __restrict__ mask, int mask_bytes,
+                                                              const float* __restrict__ pose, const float* __restrict__ Kin,
+                                                              const float* __restrict__ image, int N, int C, int H, int W,
+                                                              float* __restrict__ colors, uint8_t* __restrict__ painted,
+                                                              int32_t* __restrict__ counts, float* __restrict__ uv) {
+  __shared__ int part[2][PI_THREADS / 64];
+  const int b = blockIdx.y, n = blockIdx.x * PI_THREADS + threadIdx.x;
+  const int64_t g = (int64_t)b * N + n;
+  const bool valid = n < N;
+  const bool sel = valid && pi_sel(mask, mask_bytes, g);
+  PiProj p;
+  p.u = p.v = __builtin_nanf("");
+  p.view = false;
+  p.cx = p.cy = 0;
+  if (sel) p = pi_project(pose + 16 * b, Kin + 9 * b, pts + (int64_t)b * 3 * N, N, n, H, W);
+  const bool paint = sel && p.view;
+  if (valid) {
+    painted[g] = paint ? 1 : 0;
+    if (uv) {
+      uv[(int64_t)b * 2 * N + n] = p.u;
+      uv[(int64_t)b * 2 * N + N + n] = p.v;
+    }
+  }
+  // tap offsets inside a plane, all inside the image: an unpainted row reads nothing
+  int o00 = 0, o01 = 0, o10 = 0, o11 = 0;
+  float fx = 0.f, fy = 0.f;
+  if (paint) {
+    if (BILINEAR) {
+      const float xf = floorf(p.u), yf = floorf(p.v);                    // in [-1, W - 1] / [-1, H - 1]: u >= -0.5 where in view
+      fx = __fsub_rn(p.u, xf);
+      fy = __fsub_rn(p.v, yf);
+      const int x0 = (int)xf, y0 = (int)yf;
+      const int xa = pi_clamp(x0, W - 1), xb = pi_clamp(x0 + 1, W - 1), ya = pi_clamp(y0, H - 1), yb = pi_clamp(y0 + 1, H - 1);
+      o00 = ya * W + xa; o01 = ya * W + xb; o10 = yb * W + xa; o11 = yb * W + xb;
+    } else {
+      o00 = p.cy * W + p.cx;
+    }
+  }
+  const int64_t plane = (int64_t)H * W;
+  const float* img = image + (int64_t)b * C * plane;
+  float* out = colors + (int64_t)b * C * N;
+  for (int c = 0; c < C; c += PI_PLANES) {                               // wave-uniform
+    float val[PI_PLANES];
+#pragma unroll
+    for (int k = 0; k < PI_PLANES; ++k) val[k] = 0.f;
+    if (paint) {
+      float t[PI_PLANES][4];
+#pragma unroll
+      for (int k = 0; k < PI_PLANES; ++k) {
+        const float* ip = img + (int64_t)(c + k < C ? c + k : C - 1) * plane;
+        t[k][0] = ip[o00];
+        if (BILINEAR) { t[k][1] = ip[o01]; t[k][2] = ip[o10]; t[k][3] = ip[o11]; }
+      }
+#pragma unroll
+      for (int k = 0; k < PI_PLANES; ++k)
+        val[k] = BILINEAR ? pi_lerp(pi_lerp(t[k][0], t[k][1], fx), pi_lerp(t[k][2], t[k][3], fx), fy) : t[k][0];
+    }
+    if (valid) {
+#pragma unroll
+      for (int k = 0; k < PI_PLANES; ++k)
+        if (c + k < C) out[(int64_t)(c + k) * N + n] = val[k];
+    }
+  }
+  const bool flag[2] = {sel, paint};
+  int cnt[2];
+  pi_block_counts(flag, part, cnt);
+  if (threadIdx.x < 2 && cnt[threadIdx.x]) atomicAdd(&counts[2 * b + threadIdx.x], cnt[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(PI_THREADS) void pi_fill_kernel(unsigned long long* __restrict__ keys, int64_t cells,
+                                                             int32_t* __restrict__ counts, int ncounts) {
+  const int64_t i = (int64_t)blockIdx.x * PI_THREADS + threadIdx.x, stride = (int64_t)gridDim.x * PI_THREADS;
+  const int64_t nvec = cells >> 1;
+  ulonglong2* kv = reinterpret_cast<ulonglong2*>(keys);                  // the workspace is 16-byte aligned
+  for (int64_t v = i; v < nvec; v += stride) kv[v] = make_ulonglong2(PI_EMPTY, PI_EMPTY);
+  if (i == 0 && (cells & 1)) keys[cells - 1] = PI_EMPTY;
+  for (int64_t c = i; c < ncounts; c += stride) counts[c] = 0;
+}
+
+__global__ __launch_bounds__(PI_THREADS) void pi_splat_kernel(const float* __restrict__ pts, const void* __restrict__ mask, int mask_bytes,
+                                                              const float* __restrict__ pose, const float* __restrict__ Kin, int N, int h,
+                                                              int w, unsigned long long* __restrict__ keys, int32_t* __restrict__ counts) {
+  __shared__ int part[2][PI_THREADS / 64];
+  const int b = blockIdx.y, n = blockIdx.x * PI_THREADS + threadIdx.x;
+  const bool sel = n < N && pi_sel(mask, mask_bytes, (int64_t)b * N + n);
+  bool view = false;
+  if (sel) {
+    const PiProj p = pi_project(pose + 16 * b, Kin + 9 * b, pts + (int64_t)b * 3 * N, N, n, h, w);
+    view = p.view;
+    if (view) {
+      const unsigned long long key = ((unsigned long long)__builtin_bit_cast(unsigned, p.z) << 32) | (unsigned)n;
+      atomicMin(keys + (int64_t)b * h * w + (p.cy * w + p.cx), key);     // cy * w + cx < h * w <= 2^24
+    }
+  }
+  const bool flag[2] = {sel, view};
+  int cnt[2];
+  pi_block_counts(flag, part, cnt);
+  if (threadIdx.x < 2 && cnt[threadIdx.x]) atomicAdd(&counts[3 * b + threadIdx.x], cnt[threadIdx.x]);
+}
+
+template <int S>
+__global__ __launch_bounds__(PI_THREADS) void pi_resolve_kernel(const unsigned long long* __restrict__ keys, const float* __restrict__ attr,
+                                                                int C, int N, int h, int w, float fill, int32_t* __restrict__ index_map,
+                                                                float* __restrict__ depth_map, float* __restrict__ attr_map,
+                                                                int32_t* __restrict__ counts) {
+  __shared__ int part[1][PI_THREADS / 64];
+  const int b = blockIdx.y, cells = h * w;
+  const int i = blockIdx.x * PI_THREADS + threadIdx.x;
+  const bool valid = i < cells;
+  const int pix = valid ? i : cells - 1;
+  const int py = pix / w, px = pix - py * w;
+  const unsigned long long* kb = keys + (int64_t)b * cells;
+  unsigned long long best = PI_EMPTY;
+#pragma unroll
+  for (int dy = -S; dy <= S; ++dy) {
+    const int y = py + dy;
+    const bool iny = y >= 0 && y < h;
+    const unsigned long long* line = kb + (int64_t)pi_clamp(y, h - 1) * w;
+    unsigned long long k[2 * S + 1];
+#pragma unroll
+    for (int dx = -S; dx <= S; ++dx) k[dx + S] = line[pi_clamp(px + dx, w - 1)];
+#pragma unroll
+    for (int dx = -S; dx <= S; ++dx) {
+      const int x = px + dx;
+      const unsigned long long kk = (iny && x >= 0 && x < w) ? k[dx + S] : PI_EMPTY;
+      best = kk < best ? kk : best;
+    }
+  }
+  const bool owned = valid && best != PI_EMPTY;
+  const int owner = owned ? (int)(unsigned)(best & 0xffffffffull) : -1;
+  if (valid) {
+    const int64_t o = (int64_t)b * cells + i;
+    index_map[o] = owner;
+    depth_map[o] = owned ? __builtin_bit_cast(float, (unsigned)(best >> 32)) : __builtin_huge_valf();
+  }
+  if (attr_map) {
+    const float* ab = attr + (int64_t)b * C * N;
+    float* ob = attr_map + (int64_t)b * C * cells;
+    for (int c = 0; c < C; c += PI_PLANES) {                             // wave-uniform
+      float val[PI_PLANES];
+#pragma unroll
+      for (int k = 0; k < PI_PLANES; ++k) val[k] = fill;
+      if (owned) {
+#pragma unroll
+        for (int k = 0; k < PI_PLANES; ++k) val[k] = ab[(int64_t)(c + k < C ? c + k : C - 1) * N + owner];
+      }
+      if (valid) {
+#pragma unroll
+        for (int k = 0; k < PI_PLANES; ++k)
+          if (c + k < C) ob[(int64_t)(c + k) * cells + i] = val[k];
+      }
+    }
+  }
+  const bool flag[1] = {owned};
+  int cnt[1];
+  pi_block_counts(flag, part, cnt);
+  if (threadIdx.x == 0 && cnt[0]) atomicAdd(&counts[3 * b + 2], cnt[0]);
+}
+
+inline int64_t pi_up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+
+inline bool pi_shape_ok(int B, int N, int h, int w) {
+  return B > 0 && B <= 65535 && N > 0 && (int64_t)N <= (int64_t)65535 * 256 && h > 0 && w > 0 && (int64_t)h * w <= (int64_t)1 << 24;
+}
+
+}  // namespace
+
+extern "C" int cmr_paint_points_f32(const float* pts, const void* mask, int mask_bytes, const float* pose, const float* K, const float* image,
+                                    int B, int N, int C, int H, int W, int mode, float* colors, uint8_t* painted, int32_t* counts, float* uv,
+                                    hipStream_t stream) {
+  CMR_REQUIRE(pts && pose && K && image && colors && painted && counts);
+  CMR_REQUIRE(pi_shape_ok(B, N, H, W) && C >= 1 && C <= PI_MAX_C);
+  CMR_REQUIRE((mask_bytes == 1 || mask_bytes == 8) && (mode == 0 || mode == 1));
+  hipLaunchKernelGGL(pi_zero_kernel, dim3(1), dim3(PI_THREADS), 0, stream, counts, 2 * B);
+  const dim3 grid((N + PI_THREADS - 1) / PI_THREADS, B);
+  if (mode == 1)
+    hipLaunchKernelGGL(pi_paint_kernel<true>, grid, dim3(PI_THREADS), 0, stream, pts, mask, mask_bytes, pose, K, image, N, C, H, W, colors,
+                       painted, counts, uv);
+  else
+    hipLaunchKernelGGL(pi_paint_kernel<false>, grid, dim3(PI_THREADS), 0, stream, pts, mask, mask_bytes, pose, K, image, N, C, H, W, colors,
+                       painted, counts, uv);
+  return cmr_launch_status();
+}
+
+extern "C" int64_t cmr_render_points_workspace_bytes(int B, int h, int w) {
+  if (B <= 0 || h <= 0 || w <= 0) return 0;
+  return pi_up16((int64_t)B * h * w * 8);
+}
+
+extern "C" int cmr_render_points_f32(const float* pts, const void* mask, int mask_bytes, const float* pose, const float* K, const float* attr,
+                                     int C, int B, int N, int h, int w, int splat, float fill, int32_t* index_map, float* depth_map,
+                                     float* attr_map, int32_t* counts, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  CMR_REQUIRE(pts && pose && K && index_map && depth_map && counts && workspace);
+  CMR_REQUIRE(pi_shape_ok(B, N, h, w) && (mask_bytes == 1 || mask_bytes == 8) && splat >= 0 && splat <= PI_MAX_SPLAT);
+  CMR_REQUIRE((attr == nullptr) == (attr_map == nullptr) && (attr ? (C >= 1 && C <= PI_MAX_C) : C == 0));
+  CMR_REQUIRE(cmr_aligned16(workspace) && workspace_bytes >= cmr_render_points_workspace_bytes(B, h, w));
+  unsigned long long* keys = (unsigned long long*)workspace;
+  const int64_t cells = (int64_t)B * h * w;
+  const int64_t want = (cells / 2 + PI_THREADS - 1) / PI_THREADS;        // a 16-byte store per thread; the kernel strides when capped
+  const unsigned fill_blocks = (unsigned)(want < 1 ? 1 : (want > 65536 ? 65536 : want));
+  hipLaunchKernelGGL(pi_fill_kernel, dim3(fill_blocks), dim3(PI_THREADS), 0, stream, keys, cells, counts, 3 * B);
+  hipLaunchKernelGGL(pi_splat_kernel, dim3((N + PI_THREADS - 1) / PI_THREADS, B), dim3(PI_THREADS), 0, stream, pts, mask, mask_bytes, pose, K,
+                     N, h, w, keys, counts);
+  const dim3 grid((h * w + PI_THREADS - 1) / PI_THREADS, B);
+#define PI_RESOLVE(S)                                                                                                                  \
+  case S:                                                                                                                              \
+    hipLaunchKernelGGL(pi_resolve_kernel<S>, grid, dim3(PI_THREADS), 0, stream, (const unsigned long long*)keys, attr, C, N, h, w, fill, \
+                       index_map, depth_map, attr_map, counts);                                                                        \
+    break;
+  switch (splat) {
+    PI_RESOLVE(0)
+    PI_RESOLVE(1)
+    PI_RESOLVE(2)
+    PI_RESOLVE(3)
+    PI_RESOLVE(4)
+  }
+#undef PI_RESOLVE
+  return cmr_launch_status();
+}

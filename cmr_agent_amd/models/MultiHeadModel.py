@@ -519,6 +519,74 @@ class MultiHeadModel(Planned):
             every = torch.ones(B, N, dtype=torch.bool, device=dev)
             data_batch['depth_map'] = ops.visibility(pc, cur, K, h, w, every, radius=0, want_depth_map=True)[2]
 
+    def paint_points(self, data_batch, pose=None, image=None, K=None, mask=None, visible=None, mode='bilinear'):
+        """Port extension: lay an image over the cloud under `pose` (float32 [B, 4, 4] mapping 'pc' into the camera frame,
+        default 'pnp_pose'): every point of `mask` (bool / uint8 / int64 [B, N]; default every point) that projects into the image takes
+        the value of the pixel it lands on (ops.paint_points; mode 'bilinear' or 'nearest').  image: float32 planar [B, C, H, W], C <= 64,
+        default 'img'; K: float32 [B, 3, 3] or [3, 3] for that image, default 'K' -- which refers to the geometric map's h x w -- with row
+        0 scaled by W / w and row 1 by H / h, the inverse of the loader's camera_matrix scaling.
+        visible (None by default): True, or a dict of ops.visibility's radius / rel_tol / abs_tol as in refine_pose_from_matches (defaults
+        1 / 0.05 / 0); ops.visibility first runs under `pose` on the geometric map with 'K', the whole cloud occluding, and only the rows
+        of `mask` it leaves visible are painted.  Sets 'point_colors' float32 [B, C, N] (0 where not painted), 'point_painted' bool [B, N]
+        and 'paint_counts' int32 [B, 2] = (selected, painted).  Not called by forward."""
+        vis_kw = _visible_kw(visible, "paint_points")
+        with torch.no_grad():
+            pc = data_batch['pc'].float().contiguous()
+            dev = pc.device
+            B, _, N = pc.shape
+            img = (data_batch['img'] if image is None else image).to(dev).float().contiguous()
+            cur = (data_batch['pnp_pose'] if pose is None else pose).to(dev).float().contiguous()
+            sel = None if mask is None else mask.to(dev).contiguous()
+            if K is None or vis_kw is not None:
+                h, w = _geo_rows(data_batch)[1].shape[1:3]
+                Kg = data_batch['K'].to(dev).float()
+                Kg = (Kg if Kg.dim() == 3 else Kg.unsqueeze(0)).expand(B, 3, 3).contiguous()
+            if K is None:
+                H, W = img.shape[2:]
+                K = Kg * torch.tensor([W / w, H / h, 1.0], dtype=torch.float32, device=dev).view(1, 3, 1)
+            else:
+                K = K.to(dev).float()
+                K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3)
+            if vis_kw is not None:
+                every = torch.ones(B, N, dtype=torch.bool, device=dev)
+                sel = ops.visibility(pc, cur, Kg, h, w, every if sel is None else sel, **vis_kw)[0]
+            colors, painted, counts, _ = ops.paint_points(pc, cur, K.contiguous(), img, mask=sel, mode=mode)
+            data_batch['point_colors'] = colors
+            data_batch['point_painted'] = painted.view(B, N)
+            data_batch['paint_counts'] = counts
+
+    def render_points(self, data_batch, attr=None, pose=None, size=None, K=None, mask=None, splat=0, fill=0.0):
+        """Port extension: lay the cloud over the image under `pose` (default 'pnp_pose'): a z-buffer that remembers which
+        point owns a pixel (ops.render_points).  Every point of `mask` (default every point) goes to the cell of its rounded projection,
+        the nearest one owns it (the lowest row on equal depths), and with splat = s a pixel is owned by the nearest point within s cells
+        in both axes.  attr: float32 [B, C, N], C <= 64, a per-point quantity to render (intensity, a label, 'pc_overlap_pred' as floats,
+        a residual ...), or None.  size and K go together exactly as in render_depth: by default the geometric map's h x w with 'K'.
+        Sets 'index_map' int32 [B, h, w] (-1 where no point owns the pixel), 'render_depth_map' float32 [B, h, w] (+inf there),
+        'render_counts' int32 [B, 3] = (selected, selected and in view, pixels with an owner) and, with attr, 'attr_map' float32
+        [B, C, h, w] (`fill` there).  Not called by forward."""
+        if (size is None) != (K is None):
+            raise ValueError("render_points: size and K go together (both or neither)")
+        with torch.no_grad():
+            pc = data_batch['pc'].float().contiguous()
+            dev = pc.device
+            B = pc.shape[0]
+            if size is None:
+                h, w = _geo_rows(data_batch)[1].shape[1:3]
+                K = data_batch['K']
+            else:
+                h, w = size
+            K = K.to(dev).float()
+            K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3).contiguous()
+            cur = (data_batch['pnp_pose'] if pose is None else pose).to(dev).float().contiguous()
+            index_map, depth_map, attr_map, counts = ops.render_points(
+                pc, cur, K, h, w, attr=None if attr is None else attr.to(dev).float().contiguous(),
+                mask=None if mask is None else mask.to(dev).contiguous(), splat=splat, fill=fill)
+            data_batch['index_map'] = index_map
+            data_batch['render_depth_map'] = depth_map
+            data_batch['render_counts'] = counts
+            if attr is not None:
+                data_batch['attr_map'] = attr_map
+
     def forward_cl(self, data_batch):
         cl = self.encoder_decoder.forward_cl(data_batch)
         # four independent branches (2 heads x {points, pixels}): one flat fork, the pixel convolutions of the

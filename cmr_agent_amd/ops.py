@@ -1297,6 +1297,112 @@ def visibility(pts, pose, K, h, w, mask, occ_mask=None, radius=1, rel_tol=0.05, 
     return visible.view(torch.bool), counts, depth_map, cell, depth
 
 
+POINT_IMAGE_MAX_C = 64      # csrc/point_image.hip PI_MAX_C
+RENDER_MAX_SPLAT = 4        # csrc/point_image.hip PI_MAX_SPLAT
+_PAINT_MODES = {"nearest": 0, "bilinear": 1}
+
+
+def _point_image_args(who, pts, pose, K, h, w, mask):
+    """The checks paint_points and render_points share -> (B, N, h, w); the device check is the caller's, last."""
+    if not torch.is_tensor(pts) or pts.dim() != 3 or pts.shape[1] != 3:
+        raise ValueError("%s: pts must be [B, 3, N], got %s" % (who, tuple(pts.shape) if torch.is_tensor(pts) else type(pts).__name__))
+    B, _, N = pts.shape
+    if not torch.is_tensor(pose) or not torch.is_tensor(K) or pts.dtype != f32 or pose.dtype != f32 or K.dtype != f32:
+        raise ValueError("%s: pts, pose and K must be float32 tensors, got %s / %s / %s" % (
+            who, pts.dtype, getattr(pose, "dtype", type(pose).__name__), getattr(K, "dtype", type(K).__name__)))
+    if tuple(pose.shape) != (B, 4, 4):
+        raise ValueError("%s: pose must be [%d, 4, 4], got %s" % (who, B, tuple(pose.shape)))
+    if tuple(K.shape) != (B, 3, 3):
+        raise ValueError("%s: K must be [%d, 3, 3], got %s" % (who, B, tuple(K.shape)))
+    if not _is_int(h) or not _is_int(w):
+        raise ValueError("%s: h and w must be integers, got %r x %r" % (who, h, w))
+    h, w = int(h), int(w)
+    if B < 1 or B > GRID_Y_MAX or N < 1 or N > GRID_Y_MAX * 256 or h < 1 or w < 1 or h * w > 1 << 24:
+        raise ValueError("%s: need 1 <= B <= %d, 1 <= N <= %d and an image of 1 .. 2^24 pixels, got B=%d N=%d image %d x %d" % (
+            who, GRID_Y_MAX, GRID_Y_MAX * 256, B, N, h, w))
+    if mask is not None and (not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N):
+        raise ValueError("%s: mask must be None or bool / uint8 / int64 with %d elements, got %s %s" % (
+            who, B * N, getattr(mask, "dtype", type(mask).__name__), tuple(mask.shape) if torch.is_tensor(mask) else ""))
+    return B, N, h, w
+
+
+def paint_points(pts, pose, K, image, mask=None, mode='bilinear', want_uv=False):
+    """The image laid over the cloud: every selected point that projects into `image` under `pose` takes the value of the pixel it lands
+    on (include/cmr_hip.h cmr_paint_points_f32).  pts float32 [B, 3, N] (data['pc']), pose float32 [B, 4, 4] mapping pts
+    into the camera frame, K float32 [B, 3, 3] for the H x W image, image float32 planar [B, C, H, W] with 1 <= C <= POINT_IMAGE_MAX_C
+    and 1 <= H W <= 2^24, mask [B, N] / [B*N] of bool / uint8 / int64 (None: every row; pass ops.visibility's flags to paint only what
+    the camera sees).  In view is ops.visibility's predicate (guided_match's at radius 0).  mode 'nearest': the pixel at the rounded
+    projection, the cell ops.visibility reports; 'bilinear': the four pixels round (u, v), pixel centres on the integers, border
+    replicate, each lerp a + t (b - a) rounded operation by operation.
+    -> (colors float32 [B, C, N], 0 on the rows that are not painted; painted bool [B*N]; counts int32 [B, 2] = (selected, painted); uv
+    float32 [B, 2, N] = (u, v) as computed, NaN for unselected rows and behind the camera (guided_match's proj), or None)."""
+    if not torch.is_tensor(image) or image.dim() != 4:
+        raise ValueError("paint_points: image must be planar [B, C, H, W], got %s" % (
+            tuple(image.shape) if torch.is_tensor(image) else type(image).__name__,))
+    Bi, C, H, W = image.shape
+    B, N, H, W = _point_image_args("paint_points", pts, pose, K, H, W, mask)
+    if image.dtype != f32:
+        raise ValueError("paint_points: image must be float32, got %s" % (image.dtype,))
+    if Bi != B or C < 1 or C > POINT_IMAGE_MAX_C:
+        raise ValueError("paint_points: image must be [%d, C, H, W] with 1 <= C <= %d, got %s" % (B, POINT_IMAGE_MAX_C, tuple(image.shape)))
+    if not isinstance(mode, str) or mode not in _PAINT_MODES:
+        raise ValueError("paint_points: mode must be 'nearest' or 'bilinear', got %r" % (mode,))
+    ts = [t for t in (pts, pose, K, image, mask) if t is not None]
+    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
+        raise ValueError("paint_points: every tensor must be a contiguous tensor on the same GPU")
+    if mask is not None and mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    dev = pts.device
+    colors = torch.empty((B, C, N), dtype=f32, device=dev)
+    painted = torch.empty((B * N,), dtype=torch.uint8, device=dev)
+    counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    uv = torch.empty((B, 2, N), dtype=f32, device=dev) if want_uv else None
+    _lib.call("cmr_paint_points_f32", _p(pts), _p(mask), 1 if mask is None else mask.element_size(), _p(pose), _p(K), _p(image), B, N, C, H, W,
+              _PAINT_MODES[mode], _p(colors), _p(painted), _p(counts), _p(uv), _stream())
+    return colors, painted.view(torch.bool), counts, uv
+
+
+def render_points(pts, pose, K, h, w, attr=None, mask=None, splat=0, fill=0.0):
+    """The cloud laid over the image: a z-buffer that remembers its owner (include/cmr_hip.h cmr_render_points_f32).  pts
+    float32 [B, 3, N], pose float32 [B, 4, 4], K float32 [B, 3, 3] for the h x w map (1 <= h w <= 2^24), attr float32 [B, C, N] with
+    1 <= C <= POINT_IMAGE_MAX_C or None, mask [B, N] / [B*N] of bool / uint8 / int64 (None: every row), 0 <= splat <= RENDER_MAX_SPLAT,
+    fill any float (NaN included).  Every selected row in view (ops.visibility's predicate and cell) competes for its cell with the key
+    (bits of depth) << 32 | n; the least key owns the cell -- the nearest row, the lowest n on equal depths -- and a pixel is owned by the
+    least key within `splat` cells of it in both axes.
+    -> (index_map int32 [B, h, w], -1 where no row owns the pixel; depth_map float32 [B, h, w], +inf there; attr_map float32 [B, C, h, w]
+    = attr[b, :, owner], `fill` there, or None without attr; counts int32 [B, 3] = (selected, selected and in view, pixels with an
+    owner))."""
+    B, N, h, w = _point_image_args("render_points", pts, pose, K, h, w, mask)
+    C = 0
+    if attr is not None:
+        if not torch.is_tensor(attr) or attr.dtype != f32 or attr.dim() != 3 or attr.shape[0] != B or attr.shape[2] != N or not (
+                1 <= attr.shape[1] <= POINT_IMAGE_MAX_C):
+            raise ValueError("render_points: attr must be float32 [%d, C, %d] with 1 <= C <= %d, got %s %s" % (
+                B, N, POINT_IMAGE_MAX_C, getattr(attr, "dtype", type(attr).__name__), tuple(attr.shape) if torch.is_tensor(attr) else ""))
+        C = attr.shape[1]
+    if not _is_int(splat) or not 0 <= splat <= RENDER_MAX_SPLAT:
+        raise ValueError("render_points: splat must be an integer in [0, %d], got %r" % (RENDER_MAX_SPLAT, splat))
+    try:
+        fill = float(fill)
+    except (TypeError, ValueError):
+        raise ValueError("render_points: fill must be a number, got %r" % (fill,))
+    ts = [t for t in (pts, pose, K, attr, mask) if t is not None]
+    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
+        raise ValueError("render_points: every tensor must be a contiguous tensor on the same GPU")
+    if mask is not None and mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    dev = pts.device
+    index_map = torch.empty((B, h, w), dtype=torch.int32, device=dev)
+    depth_map = torch.empty((B, h, w), dtype=f32, device=dev)
+    attr_map = torch.empty((B, C, h, w), dtype=f32, device=dev) if attr is not None else None
+    counts = torch.empty((B, 3), dtype=torch.int32, device=dev)
+    nb = _lib.load().cmr_render_points_workspace_bytes(B, h, w)
+    ws = _ws(nb, dev)
+    _lib.call("cmr_render_points_f32", _p(pts), _p(mask), 1 if mask is None else mask.element_size(), _p(pose), _p(K), _p(attr), C, B, N, h, w,
+              int(splat), fill, _p(index_map), _p(depth_map), _p(attr_map), _p(counts), _p(ws), nb, _stream())
+    return index_map, depth_map, attr_map, counts
+
+
 def pnp_refine(pts, uv, mask, K, pose, thr=1.0, iters=10):
     """Gauss-Newton refinement of a given pose on 2-D/3-D correspondences (include/cmr_hip.h cmr_pnp_refine_f32): pts
     float32 [B, 3, N], uv float32 [B, 2, N], mask [B, N] / [B*N] of bool / uint8 / int64, K float32 [B, 3, 3], pose float32 [B, 4, 4]

@@ -1,5 +1,5 @@
-"""Command-line helpers shared by Test_Geo.py and Test_Agent.py: the round lists of --guided / --refine, the --visible flags and the
-closing recall block."""
+"""Command-line helpers shared by Test_Geo.py and Test_Agent.py: the round lists of --guided / --refine, the --visible flags, the --paint flags
+with the per-pair PLY output, and the closing recall block."""
 import numpy as np
 
 
@@ -45,6 +45,47 @@ def print_visible(counts):
     """One line per batch from refine_pose_from_matches' 'refine_visible_counts' [rounds, B, 4]: the last round's, summed over the batch."""
     c = counts[-1].sum(0).cpu().tolist()
     print("visible", int(c[2]), "of", int(c[1]), "of", int(c[0]))
+
+
+def add_paint_flags(ap, parent=None):
+    """--paint DIR and --paint-visible; `parent` is the flag --paint needs beside it (None: free-standing)."""
+    ap.add_argument('--paint', type=str, default=None, metavar="DIR", help="%spaint every pair's cloud with the image under the last pose the run "
+                    "produced and write DIR/pair_<index>.ply (binary PLY: x y z float, red green blue uchar)" % ("with %s: " % parent if parent else ""))
+    ap.add_argument('--paint-visible', action='store_true', help="with --paint: paint only the points a z-buffer of the cloud under that pose leaves visible")
+
+
+def paint_option(ap, args, parent=None, parent_given=True):
+    """-> None without --paint, else (DIR, visible); ap.error on a misplaced flag."""
+    if args.paint is None:
+        if args.paint_visible:
+            ap.error("--paint-visible belongs to --paint")
+        return None
+    if parent is not None and not parent_given:
+        ap.error("--paint paints under the pose %s produces: give %s as well" % (parent, parent))
+    return args.paint, bool(args.paint_visible)
+
+
+def paint_pairs(model, data, pose, option, first_index):
+    """Paint the batch's clouds under `pose` (MultiHeadModel.paint_points, bilinear, every point or the visible ones), write one PLY per
+    pair -- DIR/pair_<first_index + b>.ply with the painted points in the cloud's own frame; the first three planes are red, green, blue, a
+    single plane is grey -- and print the batch's line."""
+    import os
+
+    from .ply import write_ply
+    out_dir, visible = option
+    os.makedirs(out_dir, exist_ok=True)
+    model.paint_points(data, pose=pose, visible=True if visible else None)
+    colors, painted = data['point_colors'].cpu(), data['point_painted'].cpu()
+    if colors.shape[1] == 1:
+        colors = colors.expand(-1, 3, -1)                                # a grey image: the one plane is red, green and blue
+    elif colors.shape[1] < 3:
+        raise ValueError("--paint writes red, green, blue: the image must have 1 plane (grey) or at least 3, got %d" % colors.shape[1])
+    pc = data['pc'].float().cpu()
+    for b in range(pc.shape[0]):
+        m = painted[b]
+        write_ply(os.path.join(out_dir, "pair_%d.ply" % (first_index + b)), pc[b][:, m].t(), colors[b][:3, m].t())
+    c = data['paint_counts'].sum(0).cpu().tolist()
+    print("painted", int(c[1]), "of", int(c[0]))
 
 
 def print_recall(rte, rre, prefix=""):

@@ -175,6 +175,15 @@ WORK = {
     "cmr_visibility_f32": lambda a: ((40.0 + (2 * a["radius"] + 1) ** 2) * a["B"] * a["N"],
                                      4.0 * a["B"] * a["h"] * a["w"] + a["B"] * a["N"] * (12 + 2 * a["mask_bytes"] + a["occ_mask_bytes"] + 16 + 4
                                                                                          + 4 * (2 * a["radius"] + 1) ** 2 + 1)),
+    # DESIGN.md 4s, every row taken as selected and in view.  paint: the point and its mask in, 4 taps of 4 B per plane (1 when nearest),
+    # 4 B per plane and 1 B of painted out; ~40 FLOP of projection per row and 9 per plane for the three lerps.  render: the fill of the
+    # key map (8 B a cell), per row the point, its mask and an 8-byte atomic, per pixel (2s + 1)^2 keys of 8 B, 8 B of index / depth and
+    # per plane a gathered 4 B in and 4 B out
+    "cmr_paint_points_f32": lambda a: ((40.0 + 9.0 * a["C"] * a["mode"]) * a["B"] * a["N"],
+                                       a["B"] * a["N"] * (12 + a["mask_bytes"] + 1 + 4 * a["C"] * (2 + 3 * a["mode"]))),
+    "cmr_render_points_f32": lambda a: (40.0 * a["B"] * a["N"] + (2 * a["splat"] + 1) ** 2 * a["B"] * a["h"] * a["w"],
+                                        a["B"] * a["N"] * (12 + a["mask_bytes"] + 8)
+                                        + a["B"] * a["h"] * a["w"] * (8 + 8 * (2 * a["splat"] + 1) ** 2 + 8 + 8 * a["C"])),
     # training direction (Train_Agent.py:296-305, Train_Geo.py:166-174): weight gradients as GEMMs over the minibatch's pixels / rows
     "cmr_conv3x3_wgrad_f32": lambda a: (2.0 * 9 * a["Cin"] * a["Cout"] * a["B"] * a["H"] * a["W"],
                                         F * (a["B"] * a["H"] * a["W"] * (a["Cin"] + a["Cout"]) + 9 * a["Cin"] * a["Cout"])),

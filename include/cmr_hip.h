@@ -527,6 +527,48 @@ int cmr_visibility_f32(const float* pts, const void* mask, int mask_bytes, const
                        int32_t* counts, float* depth_map, int32_t* cell, float* depth, void* workspace, int64_t workspace_bytes,
                        hipStream_t stream);
 
+/* Point painting and z-buffered attribute rendering under a pose (port extension; ops.paint_points / ops.render_points,
+ * MultiHeadModel.paint_points / render_points, Test_Geo.py / Test_Agent.py --paint): the image laid over the cloud and the cloud laid
+ * over the image.  Common to both: pts f32 [B][3][N] (data['pc']), pose f32 [B][4][4] mapping pts into the camera frame, K f32 [B][3][3]
+ * for the H x W image / h x w map (1 <= H*W <= 2^24), mask [B*N] with mask_bytes 1 or 8 selecting the rows (null: every row; mask_bytes
+ * is checked all the same); 1 <= B <= 65535, 1 <= N <= 65535 * 256.  Per selected row, in fp32 with cmr_guided_match_f32's operations
+ * in the same order: X_c = R x + t, p = K X_c, u = p0 / p2, v = p1 / p2; the row is IN VIEW iff p2 > 0, u and v are finite,
+ * 0 <= rint u <= W - 1 and 0 <= rint v <= H - 1 (half to even, decided on the floats: cmr_visibility_f32's predicate and cell).
+ * Anything outside the contract is refused up front with CMR_EINVAL; nothing depends on the data.
+ *
+ * cmr_paint_points_f32: image f32 planar [B][C][H][W], 1 <= C <= 64, values expected finite; PAINTED = selected and in view.
+ *   mode 0 (nearest): the value is the pixel (rint u, rint v).
+ *   mode 1 (bilinear): pixel centres on the integers; x0 = floorf u, fx = u - x0 (likewise y); the four taps (x0, y0) .. (x0 + 1, y0 + 1)
+ *     with every index clamped to the image (border replicate: a row up to half a pixel outside the outermost centres is in view and reads
+ *     the edge); lerp(a, b, t) = a + t * (b - a) with the difference, the product and the sum each rounded to fp32 (no fma);
+ *     value = lerp(lerp(I00, I01, fx), lerp(I10, I11, fx), fy).
+ *   colors f32 [B][C][N]    0 on the rows that are not painted;
+ *   painted u8 [B*N];
+ *   counts int32 [B][2]   = {selected, painted}; the call zeroes it;
+ *   uv (optional) f32 [B][2][N] = (u, v) as computed; NaN for unselected rows and where p2 <= 0 (cmr_guided_match_f32's proj).
+ * A NaN pose paints nothing.  Two launches on the stream (zero of counts, paint), no workspace, no host round trip; every colors /
+ * painted / uv element is a plain store by the thread that owns the row and counts are integer atomics, one per workgroup and word.
+ *
+ * cmr_render_points_f32: every selected row in view goes to the cell (rint u, rint v) with the 64-bit key (bits of z = p2) << 32 | n; a
+ * cell keeps the least key (one unsigned 64-bit atomic min per row: positive floats order like their bits, so the nearest row wins and
+ * equal depths go to the lowest n, whatever the order of arrival).  0 <= splat <= 4 is a square footprint: a pixel's key is the least key
+ * of the cells within splat of it in both axes, clipped to the map (taken as a window minimum when the maps are written).
+ *   index_map int32 [B][h*w]  the owning row n, -1 where there is none;
+ *   depth_map f32 [B][h*w]    the owner's z, +inf where there is none;
+ *   attr_map (optional, with attr f32 [B][C][N], 1 <= C <= 64; both or neither, C = 0 without) f32 [B][C][h*w] = attr[b][c][owner],
+ *     `fill` (any float, NaN included) where there is none;
+ *   counts int32 [B][3]     = {selected, selected and in view, pixels with an owner}; the call zeroes it.
+ * Three launches on the stream whatever the data (fill of the key map and counts, splat, resolve), no memset, no host round trip, no
+ * floating-point atomic: two calls agree bit for bit and a sample depends on its own rows only.
+ * Workspace: cmr_render_points_workspace_bytes(B, h, w), 16-byte aligned (the key map). */
+int cmr_paint_points_f32(const float* pts, const void* mask, int mask_bytes, const float* pose, const float* K, const float* image, int B,
+                         int N, int C, int H, int W, int mode, float* colors, uint8_t* painted, int32_t* counts, float* uv,
+                         hipStream_t stream);
+int64_t cmr_render_points_workspace_bytes(int B, int h, int w);
+int cmr_render_points_f32(const float* pts, const void* mask, int mask_bytes, const float* pose, const float* K, const float* attr, int C,
+                          int B, int N, int h, int w, int splat, float fill, int32_t* index_map, float* depth_map, float* attr_map,
+                          int32_t* counts, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 /* ---- rollout ops of the training loop ---------------------------------------- */
 
 /* environment.py:143-176 (expert): residual pose target * source^-1 -> extrinsic-xyz Euler angles (folded back when the
