@@ -34,7 +34,14 @@ are collected and the closing lines printed once more with the prefix "Verified 
 refined pose with --refine, else the agent's final pose through env.from_disentangled (cmr_paint_points_f32, bilinear) -- and
 DIR/pair_<index>.ply holds the painted points (binary little-endian PLY: x y z float32 in the cloud's own frame, red green blue uchar =
 clamp(rint(255 c), 0, 255)); --paint-visible paints only the points a z-buffer of the cloud under that pose leaves visible.  Each pair
-prints one extra line "painted <painted> of <selected>".  Without the flag the output is unchanged."""
+prints one extra line "painted <painted> of <selected>".  Without the flag the output is unchanged.
+
+--dense-depth DIR [--dense-radius R] [--dense-sigma-r S] [--dense-visible]: every pair's cloud is rendered at the image's size
+under the same pose --paint uses (cmr_render_points_f32), the sparse depth is filled in by the joint bilateral filter guided by the image
+(cmr_densify_f32; window radius R, default 8; range sigma S, default 0.1) and DIR/pair_<index>_depth.pfm holds the dense map (PFM "Pf",
+little-endian, scale -1.0, rows bottom to top, unfilled pixels 0); --dense-visible renders only the points a z-buffer of the cloud under
+that pose leaves visible.  Each pair prints one extra line "dense <filled> of <pixels> from <samples>".  Without the flag the output is
+unchanged."""
 import argparse
 import json
 import os
@@ -55,8 +62,8 @@ from cmr_agent_amd.environment import environment as env  # noqa: E402
 from cmr_agent_amd.models import CMRAgent, MultiHeadModel  # noqa: E402
 from cmr_agent_amd.utils import hashfill, synthetic  # noqa: E402
 from cmr_agent_amd.utils.checkpoint import load_checked  # noqa: E402
-from cmr_agent_amd.utils.evalcli import (add_paint_flags, add_visible_flags, guided_rounds, paint_option, paint_pairs, print_recall,  # noqa: E402
-                                         print_visible, visible_option)
+from cmr_agent_amd.utils.evalcli import (add_dense_flags, add_paint_flags, add_visible_flags, dense_option, dense_pairs, guided_rounds,  # noqa: E402
+                                         paint_option, paint_pairs, print_recall, print_visible, visible_option)
 
 
 def get_P_diff(P_pred, P_gt):
@@ -84,8 +91,10 @@ def main():
     ap.add_argument('--verify', action='store_true', help="score the pair's candidate poses against the geometric features (no ground truth) and report the best")
     add_visible_flags(ap, "--refine")
     add_paint_flags(ap)
+    add_dense_flags(ap)
     args = ap.parse_args()
     paint = paint_option(ap, args)
+    dense = dense_option(ap, args, ops.DENSIFY_MAX_RADIUS)
     if args.subpixel and args.refine is None:
         ap.error("--subpixel belongs to --refine")
     radii = thrs = None
@@ -161,9 +170,12 @@ def main():
                 print("verified", " ".join("%s=%.4f" % (c[0], q) for c, q in zip(cands, quality)), "->", cands[k][0])
                 rte_ver.append(cands[k][2][0])
                 rre_ver.append(cands[k][2][1])
-            if paint is not None:
+            if paint is not None or dense is not None:
                 last = data['refined_pose'] if radii is not None else env.from_disentangled(pose_source.clone(), data['pc'], data=data)
-                paint_pairs(geo_model, data, last, paint, index)
+                if paint is not None:
+                    paint_pairs(geo_model, data, last, paint, index)
+                if dense is not None:
+                    dense_pairs(geo_model, data, last, dense, index)
     print_recall(rte, rre)
     if radii is not None:
         print_recall(rte_ref, rre_ref, "Refined ")

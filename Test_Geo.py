@@ -52,6 +52,13 @@ DIR/pair_<index>.ply holds the painted points (binary little-endian PLY: x y z f
 clamp(rint(255 c), 0, 255)); --paint-visible paints only the points a z-buffer of the cloud under that pose leaves visible.  Each batch
 prints one extra line "painted <painted> of <selected>".  Without the flag the output is unchanged.
 
+--dense-depth DIR [--dense-radius R] [--dense-sigma-r S] [--dense-visible] (with --pnp): every pair's cloud is rendered at the
+image's size under the same pose --paint uses (cmr_render_points_f32), the sparse depth is filled in by the joint bilateral filter guided
+by the image (cmr_densify_f32; window radius R, default 8; range sigma S, default 0.1) and DIR/pair_<index>_depth.pfm holds the dense map
+(PFM "Pf", little-endian, scale -1.0, rows bottom to top, unfilled pixels 0); --dense-visible renders only the points a z-buffer of the
+cloud under that pose leaves visible.  Each batch prints one extra line "dense <filled> of <pixels> from <samples>".  Without the flag the
+output is unchanged.
+
 Pairs come from the synthetic generator (cmr_agent_amd.utils.synthetic) unless --data-root names a dataset in the reference's layout
 (its 'test' split), and the weights are the deterministic hash fill unless --geo-ckpt points at a reference-format state_dict."""
 import argparse
@@ -74,8 +81,8 @@ from cmr_agent_amd.models import MultiHeadModel  # noqa: E402
 from cmr_agent_amd.models.MultiHeadModel import match_features  # noqa: E402
 from cmr_agent_amd.utils import hashfill, synthetic  # noqa: E402
 from cmr_agent_amd.utils.checkpoint import load_checked  # noqa: E402
-from cmr_agent_amd.utils.evalcli import (add_paint_flags, add_visible_flags, guided_rounds, paint_option, paint_pairs, print_recall,  # noqa: E402
-                                         print_visible, visible_option)
+from cmr_agent_amd.utils.evalcli import (add_dense_flags, add_paint_flags, add_visible_flags, dense_option, dense_pairs, guided_rounds,  # noqa: E402
+                                         paint_option, paint_pairs, print_recall, print_visible, visible_option)
 
 
 def _ratios(counts):
@@ -115,8 +122,10 @@ def main():
     ap.add_argument('--verify', action='store_true', help="with --pnp: score the pair's candidate poses against the geometric features (no ground truth) and report the best")
     add_visible_flags(ap, "--guided")
     add_paint_flags(ap, "--pnp")
+    add_dense_flags(ap, "--pnp")
     args = ap.parse_args()
     paint = paint_option(ap, args, "--pnp", args.pnp)
+    dense = dense_option(ap, args, ops.DENSIFY_MAX_RADIUS, "--pnp", args.pnp)
     if args.verify and not args.pnp:
         ap.error("--verify scores the PnP pose (and the --guided one): give --pnp as well")
     filtered = args.mutual or args.ratio is not None
@@ -227,12 +236,15 @@ def main():
                         print("verified", " ".join("%s=%.4f" % (n, q) for n, q in zip(names, quality[b])), "->", names[chosen[b]])
                         rte_ver.append(errs[chosen[b]][0])
                         rre_ver.append(errs[chosen[b]][1])
-                if paint is not None:
+                if paint is not None or dense is not None:
                     last = data['refined_pose'] if radii is not None else data['pnp_pose']
                     if args.verify:
                         last = torch.stack([data['pnp_pose']] + ([data['refined_pose']] if radii is not None else []), 1)[
                             torch.arange(pred.shape[0], device=dev), data['pose_best']]
-                    paint_pairs(geo_model, data, last, paint, done)
+                    if paint is not None:
+                        paint_pairs(geo_model, data, last, paint, done)
+                    if dense is not None:
+                        dense_pairs(geo_model, data, last, dense, done)
             done += data['pc'].shape[0]
 
     mean = lambda v: float(np.mean(v)) if v else float("nan")

@@ -587,6 +587,57 @@ class MultiHeadModel(Planned):
             if attr is not None:
                 data_batch['attr_map'] = attr_map
 
+    def dense_depth(self, data_batch, pose=None, size=None, K=None, guide=None, attr=None, mask=None, visible=None, splat=0, radius=8,
+                    sigma_s=None, sigma_r=0.1, min_weight=1e-3, keep=True, fill=0.0):
+        """Port extension: a dense depth map aligned to the image under `pose` (default 'pnp_pose'): the cloud is rendered
+        (ops.render_points with `attr`, `mask`, `splat`) and the sparse map is filled in by the joint bilateral filter guided by the image
+        (ops.densify with `radius`, `sigma_s`, `sigma_r`, `min_weight`, `keep`, `fill`).  By default at the full image's H x W: K is 'K'
+        with row 0 scaled by W / w and row 1 by H / h exactly as in paint_points, and guide is 'img' (its first 3 planes when it has more
+        than 4).  size = (H, W) and K (float32 [B, 3, 3] or [3, 3] for that size) go together as in render_depth; the guide (float32
+        [B, Cg, H, W], Cg <= 4; False: no guide, a plain normalised convolution) must then have that size.  attr: float32 [B, C, N], C <= 4,
+        a per-point quantity to densify alongside, or None.  visible as in paint_points: ops.visibility first runs on the geometric map
+        with 'K', the whole cloud occluding, and only the rows of `mask` it leaves visible are rendered.  The densify defaults are not
+        tuned on real data.  Sets 'dense_depth_map' float32 [B, H, W] (+inf where not filled), 'dense_conf_map' float32 [B, H, W],
+        'dense_counts' int32 [B, 3] = (samples, pixels with a sample in their window, filled pixels) and, with attr, 'dense_attr_map'
+        float32 [B, C, H, W] (`fill` where not filled).  Not called by forward."""
+        if (size is None) != (K is None):
+            raise ValueError("dense_depth: size and K go together (both or neither)")
+        vis_kw = _visible_kw(visible, "dense_depth")
+        with torch.no_grad():
+            pc = data_batch['pc'].float().contiguous()
+            dev = pc.device
+            B, _, N = pc.shape
+            cur = (data_batch['pnp_pose'] if pose is None else pose).to(dev).float().contiguous()
+            sel = None if mask is None else mask.to(dev).contiguous()
+            if guide is None:
+                guide = data_batch['img']
+                if guide.shape[1] > 4:
+                    guide = guide[:, :3]
+            g = None if guide is False else guide.to(dev).float().contiguous()
+            if size is None or vis_kw is not None:
+                h, w = _geo_rows(data_batch)[1].shape[1:3]
+                Kg = data_batch['K'].to(dev).float()
+                Kg = (Kg if Kg.dim() == 3 else Kg.unsqueeze(0)).expand(B, 3, 3).contiguous()
+            if size is None:
+                H, W = data_batch['img'].shape[2:] if g is None else g.shape[2:]
+                K = Kg * torch.tensor([W / w, H / h, 1.0], dtype=torch.float32, device=dev).view(1, 3, 1)
+            else:
+                H, W = size
+                K = K.to(dev).float()
+                K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3)
+            if vis_kw is not None:
+                every = torch.ones(B, N, dtype=torch.bool, device=dev)
+                sel = ops.visibility(pc, cur, Kg, h, w, every if sel is None else sel, **vis_kw)[0]
+            _, depth_map, attr_map, _ = ops.render_points(pc, cur, K.contiguous(), H, W, attr=None if attr is None else attr.to(dev).float().contiguous(),
+                                                          mask=sel, splat=splat, fill=fill)
+            dense, dense_attr, conf, _, counts = ops.densify(depth_map, guide=g, attr=attr_map, radius=radius, sigma_s=sigma_s, sigma_r=sigma_r,
+                                                             min_weight=min_weight, keep=keep, fill=fill)
+            data_batch['dense_depth_map'] = dense
+            data_batch['dense_conf_map'] = conf
+            data_batch['dense_counts'] = counts
+            if attr is not None:
+                data_batch['dense_attr_map'] = dense_attr
+
     def forward_cl(self, data_batch):
         cl = self.encoder_decoder.forward_cl(data_batch)
         # four independent branches (2 heads x {points, pixels}): one flat fork, the pixel convolutions of the

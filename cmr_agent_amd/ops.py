@@ -1403,6 +1403,88 @@ def render_points(pts, pose, K, h, w, attr=None, mask=None, splat=0, fill=0.0):
     return index_map, depth_map, attr_map, counts
 
 
+DENSIFY_MAX_RADIUS = 16     # csrc/densify.hip DN_MAX_R
+DENSIFY_MAX_C = 4           # csrc/densify.hip DN_MAX_C: attribute planes, and guide planes
+DENSIFY_TILE_W = 64         # csrc/densify.hip DN_TW x DN_TH: the pixels of one workgroup (tests put their shapes round these)
+DENSIFY_TILE_H = 16
+DENSIFY_MIN_WEIGHT = 1e-24
+
+
+def _pos_f32(v):
+    """a number that is finite and > 0 as a float32"""
+    try:
+        v = float(torch.tensor(float(v), dtype=f32))
+    except (TypeError, ValueError, OverflowError):
+        return False
+    return 0.0 < v < float("inf")
+
+
+def densify(depth, guide=None, attr=None, radius=8, sigma_s=None, sigma_r=0.1, min_weight=1e-3, keep=True, fill=0.0, want_count=False):
+    """Image-guided densification of a sparse depth map and of attribute planes that ride on it: the joint bilateral filter as a
+    normalised convolution (include/cmr_hip.h cmr_densify_f32).  depth float32 [B, h, w] with 1 <= h w <= 2^24: a pixel is
+    a sample iff its depth is finite and > 0 (ops.render_points and ops.visibility write +inf where nothing landed; 0, negatives and NaN
+    are empty too).  guide float32 [B, Cg, h, w] with 1 <= Cg <= DENSIFY_MAX_C or None; it must be finite, which is NOT checked.  attr
+    float32 [B, C, h, w] with 1 <= C <= DENSIFY_MAX_C or None, read at samples only (render_points' fill is never read).  0 <= radius <=
+    DENSIFY_MAX_RADIUS; sigma_s > 0 (None: max(radius, 1) / 2); sigma_r > 0, ignored without a guide; min_weight finite and >=
+    DENSIFY_MIN_WEIGHT; fill any float (NaN included).  sigma_s, sigma_r and min_weight act as their float32 values.  Every pixel p sums
+    over the samples q within `radius` of it in both axes: w = exp(-(|p - q|^2 / (2 sigma_s^2) + sum_c (G_c(p) - G_c(q))^2 /
+    (2 sigma_r^2))), S0 = sum w, and is filled iff S0 >= min_weight; with keep a pixel that is a sample keeps its own depth and
+    attributes bit for bit.  The defaults (radius 8, sigma_r 0.1 for a guide in [0, 1], min_weight 1e-3) are not tuned on real data.
+    -> (dense_depth float32 [B, h, w] = sum w z / S0, +inf where not filled; dense_attr float32 [B, C, h, w] = sum w a / S0, `fill`
+    where not filled, or None without attr; conf float32 [B, h, w] = S0; count int32 [B, h, w] = the samples in the window, or None;
+    counts int32 [B, 3] = (samples in the map, pixels with a sample in their window, filled pixels))."""
+    if not torch.is_tensor(depth) or depth.dim() != 3:
+        raise ValueError("densify: depth must be [B, h, w], got %s" % (tuple(depth.shape) if torch.is_tensor(depth) else type(depth).__name__,))
+    B, h, w = depth.shape
+    if depth.dtype != f32:
+        raise ValueError("densify: depth must be float32, got %s" % (depth.dtype,))
+    if B < 1 or B > GRID_Y_MAX or h < 1 or w < 1 or h * w > 1 << 24:
+        raise ValueError("densify: need 1 <= B <= %d and a map of 1 .. 2^24 pixels, got B=%d map %d x %d" % (GRID_Y_MAX, B, h, w))
+    C = Cg = 0
+    if guide is not None:
+        if not torch.is_tensor(guide) or guide.dtype != f32 or guide.dim() != 4 or guide.shape[0] != B or tuple(guide.shape[2:]) != (h, w) \
+                or not 1 <= guide.shape[1] <= DENSIFY_MAX_C:
+            raise ValueError("densify: guide must be float32 [%d, Cg, %d, %d] with 1 <= Cg <= %d, got %s %s" % (
+                B, h, w, DENSIFY_MAX_C, getattr(guide, "dtype", type(guide).__name__), tuple(guide.shape) if torch.is_tensor(guide) else ""))
+        Cg = guide.shape[1]
+    if attr is not None:
+        if not torch.is_tensor(attr) or attr.dtype != f32 or attr.dim() != 4 or attr.shape[0] != B or tuple(attr.shape[2:]) != (h, w) \
+                or not 1 <= attr.shape[1] <= DENSIFY_MAX_C:
+            raise ValueError("densify: attr must be float32 [%d, C, %d, %d] with 1 <= C <= %d, got %s %s" % (
+                B, h, w, DENSIFY_MAX_C, getattr(attr, "dtype", type(attr).__name__), tuple(attr.shape) if torch.is_tensor(attr) else ""))
+        C = attr.shape[1]
+    if not _is_int(radius) or not 0 <= radius <= DENSIFY_MAX_RADIUS:
+        raise ValueError("densify: radius must be an integer in [0, %d], got %r" % (DENSIFY_MAX_RADIUS, radius))
+    if sigma_s is None:
+        sigma_s = max(int(radius), 1) / 2
+    if not _pos_f32(sigma_s):
+        raise ValueError("densify: sigma_s must be finite and > 0, got %r" % (sigma_s,))
+    if not _pos_f32(sigma_r):
+        raise ValueError("densify: sigma_r must be finite and > 0, got %r" % (sigma_r,))
+    if not _pos_f32(min_weight) or float(min_weight) < DENSIFY_MIN_WEIGHT:
+        raise ValueError("densify: min_weight must be finite and >= %g, got %r" % (DENSIFY_MIN_WEIGHT, min_weight))
+    if _pos_f32(math.log2(math.e) / (2.0 * float(sigma_s) ** 2)) is False or (Cg and _pos_f32(math.log2(math.e) / (2.0 * float(sigma_r) ** 2)) is False):
+        raise ValueError("densify: 1 / (2 sigma^2) must be a float32 > 0, got sigma_s=%r sigma_r=%r" % (sigma_s, sigma_r))
+    if not isinstance(keep, (bool, int)) or keep not in (0, 1):
+        raise ValueError("densify: keep must be True or False, got %r" % (keep,))
+    try:
+        fill = float(fill)
+    except (TypeError, ValueError):
+        raise ValueError("densify: fill must be a number, got %r" % (fill,))
+    ts = [t for t in (depth, guide, attr) if t is not None]
+    if not all(t.is_cuda and t.is_contiguous() and t.device == depth.device for t in ts):
+        raise ValueError("densify: every tensor must be a contiguous tensor on the same GPU")
+    dev = depth.device
+    dense_depth = torch.empty((B, h, w), dtype=f32, device=dev)
+    dense_attr = torch.empty((B, C, h, w), dtype=f32, device=dev) if attr is not None else None
+    conf = torch.empty((B, h, w), dtype=f32, device=dev)
+    count = torch.empty((B, h, w), dtype=torch.int32, device=dev) if want_count else None
+    counts = torch.empty((B, 3), dtype=torch.int32, device=dev)
+    _lib.call("cmr_densify_f32", _p(depth), _p(attr), C, _p(guide), Cg, B, h, w, int(radius), float(sigma_s), float(sigma_r),
+              float(min_weight), int(bool(keep)), fill, _p(dense_depth), _p(dense_attr), _p(conf), _p(count), _p(counts), _stream())
+    return dense_depth, dense_attr, conf, count, counts
+
+
 def pnp_refine(pts, uv, mask, K, pose, thr=1.0, iters=10):
     """Gauss-Newton refinement of a given pose on 2-D/3-D correspondences (include/cmr_hip.h cmr_pnp_refine_f32): pts
     float32 [B, 3, N], uv float32 [B, 2, N], mask [B, N] / [B*N] of bool / uint8 / int64, K float32 [B, 3, 3], pose float32 [B, 4, 4]

@@ -1,5 +1,5 @@
 """Command-line helpers shared by Test_Geo.py and Test_Agent.py: the round lists of --guided / --refine, the --visible flags, the --paint flags
-with the per-pair PLY output, and the closing recall block."""
+with the per-pair PLY output, the --dense-depth flags with the per-pair PFM output, and the closing recall block."""
 import numpy as np
 
 
@@ -86,6 +86,51 @@ def paint_pairs(model, data, pose, option, first_index):
         write_ply(os.path.join(out_dir, "pair_%d.ply" % (first_index + b)), pc[b][:, m].t(), colors[b][:3, m].t())
     c = data['paint_counts'].sum(0).cpu().tolist()
     print("painted", int(c[1]), "of", int(c[0]))
+
+
+def add_dense_flags(ap, parent=None):
+    """--dense-depth DIR, --dense-radius, --dense-sigma-r and --dense-visible; `parent` is the flag --dense-depth needs beside it (None:
+    free-standing)."""
+    ap.add_argument('--dense-depth', type=str, default=None, metavar="DIR", help="%srender every pair's cloud under the last pose the run produced, "
+                    "fill the sparse depth in under the image's guidance and write DIR/pair_<index>_depth.pfm" % ("with %s: " % parent if parent else ""))
+    ap.add_argument('--dense-radius', type=int, default=None, metavar="R", help="with --dense-depth: window radius of the filter in pixels (default 8)")
+    ap.add_argument('--dense-sigma-r', type=float, default=None, metavar="S", help="with --dense-depth: range sigma on the image's values (default 0.1)")
+    ap.add_argument('--dense-visible', action='store_true', help="with --dense-depth: render only the points a z-buffer of the cloud under that pose leaves visible")
+
+
+def dense_option(ap, args, max_radius, parent=None, parent_given=True):
+    """-> None without --dense-depth, else (DIR, radius, sigma_r, visible); ap.error on a misplaced or malformed flag."""
+    if args.dense_depth is None:
+        for name, given in (("--dense-radius", args.dense_radius is not None), ("--dense-sigma-r", args.dense_sigma_r is not None),
+                            ("--dense-visible", args.dense_visible)):
+            if given:
+                ap.error("%s belongs to --dense-depth" % name)
+        return None
+    if parent is not None and not parent_given:
+        ap.error("--dense-depth renders under the pose %s produces: give %s as well" % (parent, parent))
+    radius = 8 if args.dense_radius is None else args.dense_radius
+    sigma_r = 0.1 if args.dense_sigma_r is None else args.dense_sigma_r
+    if not 0 <= radius <= max_radius:
+        ap.error("--dense-radius must be in [0, %d] (--dense-depth), got %d" % (max_radius, radius))
+    if not 0.0 < sigma_r < float("inf"):
+        ap.error("--dense-sigma-r must be finite and > 0 (--dense-depth), got %r" % (sigma_r,))
+    return args.dense_depth, radius, sigma_r, bool(args.dense_visible)
+
+
+def dense_pairs(model, data, pose, option, first_index):
+    """Densify the batch's rendered depth under `pose` (MultiHeadModel.dense_depth at the image's size, guided by the image), write one
+    PFM per pair -- DIR/pair_<first_index + b>_depth.pfm, unfilled pixels as 0 -- and print the batch's line."""
+    import os
+
+    from .pfm import write_pfm
+    out_dir, radius, sigma_r, visible = option
+    os.makedirs(out_dir, exist_ok=True)
+    model.dense_depth(data, pose=pose, radius=radius, sigma_r=sigma_r, visible=True if visible else None)
+    dense = data['dense_depth_map'].cpu()
+    for b in range(dense.shape[0]):
+        write_pfm(os.path.join(out_dir, "pair_%d_depth.pfm" % (first_index + b)), dense[b])
+    c = data['dense_counts'].sum(0).cpu().tolist()
+    print("dense", int(c[2]), "of", dense.shape[0] * dense.shape[1] * dense.shape[2], "from", int(c[0]))
 
 
 def print_recall(rte, rre, prefix=""):

@@ -184,6 +184,10 @@ WORK = {
     "cmr_render_points_f32": lambda a: (40.0 * a["B"] * a["N"] + (2 * a["splat"] + 1) ** 2 * a["B"] * a["h"] * a["w"],
                                         a["B"] * a["N"] * (12 + a["mask_bytes"] + 8)
                                         + a["B"] * a["h"] * a["w"] * (8 + 8 * (2 * a["splat"] + 1) ** 2 + 8 + 8 * a["C"])),
+    # DESIGN.md 4t, the data-independent ceiling: every tap of the (2R + 1)^2 window taken as a sample at (8 + 3 Cg + 2 C) FLOP (the
+    # kernel visits the samples only, 2 - 15 % of that); depth, guide and the samples' attributes in, depth, conf and attributes out
+    "cmr_densify_f32": lambda a: ((8.0 + 3.0 * a["Cg"] + 2.0 * a["C"]) * (2 * a["radius"] + 1) ** 2 * a["B"] * a["h"] * a["w"],
+                                  4.0 * a["B"] * a["h"] * a["w"] * (3 + a["Cg"] + 2 * a["C"])),
     # training direction (Train_Agent.py:296-305, Train_Geo.py:166-174): weight gradients as GEMMs over the minibatch's pixels / rows
     "cmr_conv3x3_wgrad_f32": lambda a: (2.0 * 9 * a["Cin"] * a["Cout"] * a["B"] * a["H"] * a["W"],
                                         F * (a["B"] * a["H"] * a["W"] * (a["Cin"] + a["Cout"]) + 9 * a["Cin"] * a["Cout"])),

@@ -569,6 +569,29 @@ int cmr_render_points_f32(const float* pts, const void* mask, int mask_bytes, co
                           int B, int N, int h, int w, int splat, float fill, int32_t* index_map, float* depth_map, float* attr_map,
                           int32_t* counts, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+/* Image-guided densification of a sparse depth / attribute map (port extension; ops.densify, MultiHeadModel.dense_depth,
+ * Test_Geo.py / Test_Agent.py --dense-depth): the joint bilateral filter as a normalised convolution.  All maps contiguous.
+ *   depth f32 [B][h][w]: a pixel is a SAMPLE iff its depth is finite and > 0 (+inf, as cmr_render_points_f32 and cmr_visibility_f32 write
+ *     it, 0, negatives and NaN are empty); attr f32 [B][C][h][w], 1 <= C <= 4, or null with C = 0, read at samples only; guide f32
+ *     [B][Cg][h][w], 1 <= Cg <= 4, or null with Cg = 0, expected finite (not checked); 0 <= radius <= 16; sigma_s > 0; sigma_r > 0
+ *     (ignored without a guide); min_weight finite and >= 1e-24; keep 0 or 1; fill any float; 1 <= h*w <= 2^24; 1 <= B <= 65535.
+ * For pixel p and every sample q of the map with |qx - px| <= radius and |qy - py| <= radius:
+ *   w(p, q) = exp(-(|p - q|^2 / (2 sigma_s^2) + sum_c (G_c(p) - G_c(q))^2 / (2 sigma_r^2)))   (the second term only with a guide),
+ *   S0 = sum w, S1 = sum w z(q), A_c = sum w a_c(q), n = the number of such samples; the sums run line by line, left to right, in fp32,
+ *   one hardware exponential per sample (weights below 2^-126 count as 0).
+ * The pixel is FILLED iff S0 >= min_weight.  keep = 1: a pixel that is a sample returns its own depth and attributes bit for bit.
+ *   dense_depth f32 [B][h][w]      = S1 / S0 where filled, +inf elsewhere
+ *   dense_attr f32 [B][C][h][w]    = A_c / S0 where filled, `fill` elsewhere; null iff attr is null
+ *   conf f32 [B][h][w]             = S0 as computed, 0 where n = 0
+ *   count int32 [B][h][w] or null  = n
+ *   counts int32 [B][3]            = {samples in the map, pixels with n > 0, filled pixels}; the call zeroes it (integer atomics)
+ * Two launches on the stream whatever the data (zero of counts, the tiled gather), no workspace, no host round trip, no floating-point
+ * atomic: two calls agree bit for bit and a sample's result depends on its own maps only.  Anything outside the contract is refused up
+ * front with CMR_EINVAL. */
+int cmr_densify_f32(const float* depth, const float* attr, int C, const float* guide, int Cg, int B, int h, int w, int radius,
+                    float sigma_s, float sigma_r, float min_weight, int keep, float fill, float* dense_depth, float* dense_attr,
+                    float* conf, int32_t* count, int32_t* counts, hipStream_t stream);
+
 /* ---- rollout ops of the training loop ---------------------------------------- */
 
 /* environment.py:143-176 (expert): residual pose target * source^-1 -> extrinsic-xyz Euler angles (folded back when the
