@@ -102,6 +102,72 @@ __device__ __forceinline__ float cmr_xor16(float v) {
   return __builtin_bit_cast(float, (threadIdx.x & 16) ? r[0] : r[1]);
 }
 
+// The float on the same DPP move, and the sum over the 16 lanes of a DPP row as a butterfly (lane ^ 1, lane ^ 2, row_half_mirror,
+// row_mirror), i.e. the balanced tree ((s0 + s1) + (s2 + s3)) + ...; IEEE addition commutes, so all 16 lanes hold the same bits.  Every
+// lane of the wave must be active.  (guided_match.hip, pose_score.hip and visibility.hip; the matchers keep their own 16-lane cores.)
+template <int CTRL>
+__device__ __forceinline__ float cmr_fdpp(float v) { return __builtin_bit_cast(float, cmr_dpp<CTRL>(__builtin_bit_cast(int, v))); }
+__device__ __forceinline__ float cmr_sum16(float s) {
+  s += cmr_fdpp<0xB1>(s);           // quad_perm:[1,0,3,2]
+  s += cmr_fdpp<0x4E>(s);           // quad_perm:[2,3,0,1]
+  s += cmr_fdpp<0x141>(s);          // row_half_mirror
+  s += cmr_fdpp<0x140>(s);          // row_mirror
+  return s;
+}
+
+// Row selection: the caller's mask holds bytes (torch.bool / uint8) or 64-bit words (torch.int64); a row is selected where it is
+// non-zero.  `mask` is never null here: an entry that accepts "no mask = every row" tests that at its call site (cmr_sel_or_all).
+__device__ __forceinline__ bool cmr_sel(const void* mask, int mask_bytes, int64_t g) {
+  return mask_bytes == 1 ? ((const uint8_t*)mask)[g] != 0 : ((const int64_t*)mask)[g] != 0;
+}
+__device__ __forceinline__ bool cmr_sel_or_all(const void* mask, int mask_bytes, int64_t g) {
+  return !mask ? true : cmr_sel(mask, mask_bytes, g);
+}
+
+// The workgroup's number of set flags per flag, valid in every thread: ballot, popcount, one word per flag and wave in `part` (LDS).
+// Integers: order free.  Every thread of the 1-D workgroup of THREADS calls it (it holds a barrier).
+template <int NF, int THREADS>
+__device__ __forceinline__ void cmr_block_counts(const bool (&flag)[NF], int (&part)[NF][THREADS / 64], int (&total)[NF]) {
+  static_assert(THREADS == 256, "four waves");
+#pragma unroll
+  for (int f = 0; f < NF; ++f) {
+    const unsigned long long bal = __ballot(flag[f]);
+    if ((threadIdx.x & 63) == 0) part[f][threadIdx.x >> 6] = __popcll(bal);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int f = 0; f < NF; ++f) total[f] = part[f][0] + part[f][1] + part[f][2] + part[f][3];
+}
+
+// a * b + c with TWO roundings, and a + t (b - a) with three on top of it, so that plain fp32 torch code gives the same bits.  HIP's
+// __fmul_rn / __fadd_rn are a plain product and sum that carry the translation unit's default -ffp-contract=fast, and the backend fuses
+// them into one fma; plain operators under the pragma carry no such licence (and keep none after inlining).
+__device__ __forceinline__ float cmr_mul_add_rn(float a, float b, float c) {
+#pragma clang fp contract(off)
+  const float m = a * b;
+  return m + c;
+}
+__device__ __forceinline__ float cmr_lerp(float a, float b, float t) {
+#pragma clang fp contract(off)
+  const float d = b - a;
+  return cmr_mul_add_rn(t, d, a);
+}
+
+// ---- host helpers shared by the entries of the pose operations -------------------------------------------------------------------
+// workspace sections start on 16 bytes
+static inline int64_t cmr_up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+
+// a cloud of B x N rows against an h x w map: B is a grid's y extent, N / 256 its x extent, and a cell index must be exact in a float
+static inline bool cmr_cloud_map_ok(int B, int N, int h, int w) {
+  return B > 0 && B <= 65535 && N > 0 && (int64_t)N <= (int64_t)65535 * 256 && h > 0 && w > 0 && (int64_t)h * w <= (int64_t)1 << 24;
+}
+
+// workgroups of a fill kernel that writes `vecs` 16-byte vectors, one per thread; capped at 65536, the kernel strides beyond that
+static inline unsigned cmr_fill_blocks(int64_t vecs, int threads) {
+  const int64_t want = (vecs + threads - 1) / threads;
+  return (unsigned)(want < 1 ? 1 : (want > 65536 ? 65536 : want));
+}
+
 __device__ __forceinline__ int cmr_mfma_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 // Dropout mask, counter based (no state, no stored mask): element `idx` of dropout site `site` in the step whose seed is `seed` is KEPT

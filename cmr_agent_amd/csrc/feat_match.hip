@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void fm_compact_kernel(const void* __restrict_
   const int64_t g = (int64_t)b * N + n;
   bool sel = false;
   if (n < N) {
-    sel = mask_bytes == 1 ? ((const uint8_t*)mask)[g] != 0 : ((const int64_t*)mask)[g] != 0;
+    sel = cmr_sel(mask, mask_bytes, g);
     if (!sel) {
       idx[g] = -1;
       if (dist) dist[g] = __builtin_nanf("");

@@ -41,16 +41,12 @@ __device__ __forceinline__ unsigned fmf_xhalf_u(unsigned u) {
   return (threadIdx.x & 32) ? r[0] : r[1];
 }
 
-__device__ __forceinline__ bool fmf_sel(const void* mask, int mask_bytes, int64_t g) {
-  return mask_bytes == 1 ? ((const uint8_t*)mask)[g] != 0 : ((const int64_t*)mask)[g] != 0;
-}
-
 // ---- order-preserving compaction ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(FMF_CHUNK) void fmf_count_kernel(const void* __restrict__ mask, int mask_bytes, int N, int nchunk,
                                                               int32_t* __restrict__ chunk_cnt) {
   __shared__ int wc[FMF_CHUNK / 64];
   const int b = blockIdx.y, n = blockIdx.x * FMF_CHUNK + threadIdx.x;
-  const bool sel = n < N && fmf_sel(mask, mask_bytes, (int64_t)b * N + n);
+  const bool sel = n < N && cmr_sel(mask, mask_bytes, (int64_t)b * N + n);
   const int c = __popcll(__ballot(sel));
   if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = c;
   __syncthreads();
@@ -73,7 +69,7 @@ __global__ __launch_bounds__(FMF_CHUNK) void fmf_pack_kernel(const void* __restr
   }
   const int base = red[0];
   const int n = c * FMF_CHUNK + threadIdx.x;
-  const bool sel = n < N && fmf_sel(mask, mask_bytes, (int64_t)b * N + n);
+  const bool sel = n < N && cmr_sel(mask, mask_bytes, (int64_t)b * N + n);
   const unsigned long long bal = __ballot(sel);
   if (lane == 0) wc[wave] = __popcll(bal);
   __syncthreads();
@@ -284,7 +280,7 @@ __global__ __launch_bounds__(256) void fmf_best_kernel(const void* __restrict__ 
                                                        int32_t* __restrict__ idx, float* __restrict__ d1w) {
   const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
   const int64_t g = (int64_t)b * N + n;
-  if (n >= N || !fmf_sel(mask, mask_bytes, g)) return;
+  if (n >= N || !cmr_sel(mask, mask_bytes, g)) return;
   int tps;
   const int nact = fmf_splits(counts[4 * b], hw, gridDim.y, zmax, tps);
   float best = pv[g];
@@ -330,7 +326,7 @@ __global__ __launch_bounds__(256) void fmf_final_kernel(const void* __restrict__
   const int nsel = counts[4 * b];                                   // this kernel adds to the other three entries only
   bool kept = false, inl = false;
   if (n < N) {
-    if (fmf_sel(mask, mask_bytes, g)) {
+    if (cmr_sel(mask, mask_bytes, g)) {
       const int p = idx[g];
       const float a = d1w[g];
       kept = true;
@@ -371,20 +367,18 @@ struct FmfWorkspace {
   int64_t list, chunk, pnorm, d1, rev, pv, pi, pstride, total;      // byte offsets, each a multiple of 16; pstride in elements
 };
 
-inline int64_t fmf_up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 inline FmfWorkspace fmf_layout(int B, int N, int h, int w) {
   FmfWorkspace L;
   const int64_t rows = (int64_t)B * N, px = (int64_t)B * h * w, nchunk = (N + FMF_CHUNK - 1) / FMF_CHUNK;
   L.pstride = rows > px ? rows : px;                                // a range's slot serves the forward sweeps and the reverse one in turn
   L.list = 0;
-  L.chunk = L.list + fmf_up16(rows * 4);
-  L.pnorm = L.chunk + fmf_up16((int64_t)B * nchunk * 4);
-  L.d1 = L.pnorm + fmf_up16(rows * 4);
-  L.rev = L.d1 + fmf_up16(rows * 4);
-  L.pv = L.rev + fmf_up16(px * 4);
-  L.pi = L.pv + fmf_up16(FMF_SPLITS * L.pstride * 4);
-  L.total = L.pi + fmf_up16(FMF_SPLITS * L.pstride * 4);
+  L.chunk = L.list + cmr_up16(rows * 4);
+  L.pnorm = L.chunk + cmr_up16((int64_t)B * nchunk * 4);
+  L.d1 = L.pnorm + cmr_up16(rows * 4);
+  L.rev = L.d1 + cmr_up16(rows * 4);
+  L.pv = L.rev + cmr_up16(px * 4);
+  L.pi = L.pv + cmr_up16(FMF_SPLITS * L.pstride * 4);
+  L.total = L.pi + cmr_up16(FMF_SPLITS * L.pstride * 4);
   return L;
 }
 

@@ -17,7 +17,7 @@
 // ((s0 + s1) + (s2 + s3)) + ... ; IEEE addition commutes, so all 16 lanes hold the same bits.  dist = sqrtf of that minimum.
 // The loop bounds are wave-uniform (every group walks the whole (2r + 1)^2 square); a pixel outside the map is read from the clamped
 // address and its score discarded, so there is no divergent branch and no partial EXEC under the DPP moves.
-#include "cmr_common.h"
+#include "cmr_project.h"
 
 namespace {
 
@@ -28,24 +28,6 @@ constexpr int GM_ROWS = GM_THREADS / GM_LANES;   // rows per workgroup
 constexpr int GM_AHEAD = 4;         // window pixels whose loads are in flight together per group
 constexpr int GM_MAX_RADIUS = 16;  // (2r + 1)^2 <= 1089 pixels per point; also keeps centre +- r far from integer overflow
 
-__device__ __forceinline__ bool gm_sel(const void* mask, int mask_bytes, int64_t g) {
-  return mask_bytes == 1 ? ((const uint8_t*)mask)[g] != 0 : ((const int64_t*)mask)[g] != 0;
-}
-
-template <int CTRL>
-__device__ __forceinline__ float gm_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-
-// sum over the 16 lanes of a DPP row; every lane of the wave must be active
-__device__ __forceinline__ float gm_sum16(float s) {
-  s += gm_dpp<0xB1>(s);             // quad_perm:[1,0,3,2]
-  s += gm_dpp<0x4E>(s);             // quad_perm:[2,3,0,1]
-  s += gm_dpp<0x141>(s);            // row_half_mirror
-  s += gm_dpp<0x140>(s);            // row_mirror
-  return s;
-}
-
 __global__ __launch_bounds__(256) void gm_project_kernel(const float* __restrict__ pts, const void* __restrict__ mask, int mask_bytes,
                                                          const float* __restrict__ pose, const float* __restrict__ Kin, int N, int h,
                                                          int w, int radius, int32_t* __restrict__ idx, float* __restrict__ dist,
@@ -54,32 +36,15 @@ __global__ __launch_bounds__(256) void gm_project_kernel(const float* __restrict
                                                          int2* __restrict__ centre) {
   const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
   const int64_t g = (int64_t)b * N + n;
-  const bool sel = n < N && gm_sel(mask, mask_bytes, g);
+  const bool sel = n < N && cmr_sel(mask, mask_bytes, g);
   bool view = false;
   int cxi = 0, cyi = 0;
   if (sel) {
-    const float* P = pose + 16 * b;
-    const float* K = Kin + 9 * b;
-    const float* x = pts + (int64_t)b * 3 * N;
-    const float X = x[n], Y = x[N + n], Z = x[2 * N + n];
-    const float xc = fmaf(P[0], X, fmaf(P[1], Y, fmaf(P[2], Z, P[3])));
-    const float yc = fmaf(P[4], X, fmaf(P[5], Y, fmaf(P[6], Z, P[7])));
-    const float zc = fmaf(P[8], X, fmaf(P[9], Y, fmaf(P[10], Z, P[11])));
-    const float p0 = fmaf(K[0], xc, fmaf(K[1], yc, K[2] * zc));
-    const float p1 = fmaf(K[3], xc, fmaf(K[4], yc, K[5] * zc));
-    const float p2 = fmaf(K[6], xc, fmaf(K[7], yc, K[8] * zc));
-    const float nanv = __builtin_nanf("");
-    float u = nanv, v = nanv;
-    if (p2 > 0.f) {
-      u = p0 / p2;
-      v = p1 / p2;
-      if (isfinite(u) && isfinite(v)) {
-        const float cx = rintf(u), cy = rintf(v), r = (float)radius;     // round half to even; decided on the floats
-        view = cx + r >= 0.f && cx - r <= (float)(w - 1) && cy + r >= 0.f && cy - r <= (float)(h - 1);
-        if (view) { cxi = (int)cx; cyi = (int)cy; }
-      }
-    }
-    if (proj) { proj[(int64_t)b * 2 * N + n] = u; proj[(int64_t)b * 2 * N + N + n] = v; }
+    const CmrProj p = cmr_project(pose + 16 * b, Kin + 9 * b, pts + (int64_t)b * 3 * N, N, n, h, w, radius);
+    view = p.view;
+    cxi = p.cx;
+    cyi = p.cy;
+    if (proj) { proj[(int64_t)b * 2 * N + n] = p.u; proj[(int64_t)b * 2 * N + N + n] = p.v; }
   } else if (n < N && proj) {
     proj[(int64_t)b * 2 * N + n] = __builtin_nanf("");
     proj[(int64_t)b * 2 * N + N + n] = __builtin_nanf("");
@@ -143,7 +108,7 @@ __global__ __launch_bounds__(GM_THREADS) void gm_match_kernel(const float* __res
       s = fmaf(d1, d1, s);
       s = fmaf(d2, d2, s);
       s = fmaf(d3, d3, s);
-      s = gm_sum16(s);
+      s = cmr_sum16(s);
       if (bidx < 0 && in[u]) bidx = p[u];              // all-NaN scores keep the window's first pixel, as torch.argmin
       if (in[u] && s < best) { best = s; bidx = p[u]; }   // strict, p increasing: the lowest p of a tie stays
     }
@@ -169,12 +134,10 @@ __global__ __launch_bounds__(GM_THREADS) void gm_match_kernel(const float* __res
   }
 }
 
-inline int64_t gm_up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 }  // namespace
 
 extern "C" int64_t cmr_guided_match_workspace_bytes(int B, int N) {
-  return B <= 0 || N <= 0 ? 0 : gm_up16((int64_t)B * N * 4) + gm_up16((int64_t)B * N * 8);
+  return B <= 0 || N <= 0 ? 0 : cmr_up16((int64_t)B * N * 4) + cmr_up16((int64_t)B * N * 8);
 }
 
 extern "C" int cmr_guided_match_f32(const float* pts, const float* pc_feat, const float* img_feat, int C, int B, int N, int h, int w,
@@ -182,8 +145,7 @@ extern "C" int cmr_guided_match_f32(const float* pts, const float* pc_feat, cons
                                     const float* gt_xy, float thr, int32_t* idx, uint8_t* keep, int32_t* counts, float* dist, float* proj,
                                     void* workspace, int64_t workspace_bytes, hipStream_t stream) {
   CMR_REQUIRE(pts && pc_feat && img_feat && mask && pose && K && idx && keep && counts && workspace);
-  CMR_REQUIRE(C == GM_C && B > 0 && B <= 65535 && N > 0 && h > 0 && w > 0 && (int64_t)h * w <= (int64_t)1 << 24);
-  CMR_REQUIRE((int64_t)N <= (int64_t)65535 * 256);
+  CMR_REQUIRE(C == GM_C && cmr_cloud_map_ok(B, N, h, w));
   CMR_REQUIRE(mask_bytes == 1 || mask_bytes == 8);
   CMR_REQUIRE(radius >= 0 && radius <= GM_MAX_RADIUS && max_dist >= 0.f && __builtin_isfinite(max_dist));
   CMR_REQUIRE(cmr_aligned16(pc_feat) && cmr_aligned16(img_feat) && cmr_aligned16(workspace));
@@ -191,7 +153,7 @@ extern "C" int cmr_guided_match_f32(const float* pts, const float* pc_feat, cons
   const int64_t groups = ((int64_t)N + GM_ROWS - 1) / GM_ROWS * B;
   CMR_REQUIRE(groups <= 0x7fffffff);
   int32_t* list = (int32_t*)workspace;
-  int2* centre = (int2*)((char*)workspace + gm_up16((int64_t)B * N * 4));
+  int2* centre = (int2*)((char*)workspace + cmr_up16((int64_t)B * N * 4));
   if (hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(int32_t), stream) != hipSuccess) return CMR_ELAUNCH;
   hipLaunchKernelGGL(gm_project_kernel, dim3((N + 255) / 256, B), dim3(256), 0, stream, pts, mask, mask_bytes, pose, K, N, h, w, radius, idx,
                      dist, keep, proj, counts, list, centre);

@@ -44,10 +44,6 @@ __device__ __forceinline__ unsigned mc_xhalf_u(unsigned u) {
   return (threadIdx.x & 32) ? r[0] : r[1];
 }
 
-__device__ __forceinline__ bool mc_sel(const void* mask, int mask_bytes, int64_t g) {
-  return mask_bytes == 1 ? ((const uint8_t*)mask)[g] != 0 : ((const int64_t*)mask)[g] != 0;
-}
-
 // v_exp_f32: base 2, no denormal results (an argument under -126 gives 0, which is what a term that small is worth here)
 __device__ __forceinline__ float mc_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
@@ -60,7 +56,7 @@ __global__ __launch_bounds__(MC_CHUNK) void mc_count_kernel(const void* __restri
                                                             int32_t* __restrict__ chunk_cnt) {
   __shared__ int wc[MC_CHUNK / 64];
   const int b = blockIdx.y, n = blockIdx.x * MC_CHUNK + threadIdx.x;
-  const bool sel = n < N && mc_sel(mask, mask_bytes, (int64_t)b * N + n);
+  const bool sel = n < N && cmr_sel(mask, mask_bytes, (int64_t)b * N + n);
   const int c = __popcll(__ballot(sel));
   if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = c;
   __syncthreads();
@@ -83,7 +79,7 @@ __global__ __launch_bounds__(MC_CHUNK) void mc_pack_kernel(const void* __restric
   }
   const int base = red[0];
   const int n = c * MC_CHUNK + threadIdx.x;
-  const bool sel = n < N && mc_sel(mask, mask_bytes, (int64_t)b * N + n);
+  const bool sel = n < N && cmr_sel(mask, mask_bytes, (int64_t)b * N + n);
   const unsigned long long bal = __ballot(sel);
   if (lane == 0) wc[wave] = __popcll(bal);
   __syncthreads();
@@ -326,7 +322,7 @@ __global__ __launch_bounds__(256) void mc_final_kernel(const void* __restrict__ 
     const float nanv = __builtin_nanf("");
     int p = -1;
     float c = nanv, dist = nanv, lse = nanv;
-    if (mc_sel(mask, mask_bytes, g)) {
+    if (cmr_sel(mask, mask_bytes, g)) {
       int tps;
       const int nact = mc_splits(nsel, hw, tps);
       float best, tot;
@@ -365,22 +361,20 @@ struct McWorkspace {
   int64_t list, chunk, pnorm, qnorm, col, fpv, fpi, fps, rpv, rps, total;     // byte offsets, each a multiple of 16
 };
 
-inline int64_t mc_up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 inline McWorkspace mc_layout(int B, int N, int h, int w) {
   McWorkspace L;
   const int64_t rows = (int64_t)B * N, px = (int64_t)B * h * w, nchunk = (N + MC_CHUNK - 1) / MC_CHUNK;
   L.list = 0;
-  L.chunk = L.list + mc_up16(rows * 4);
-  L.pnorm = L.chunk + mc_up16((int64_t)B * nchunk * 4);
-  L.qnorm = L.pnorm + mc_up16(rows * 4);
-  L.col = L.qnorm + mc_up16(px * 4);
-  L.fpv = L.col + mc_up16(px * 4);
-  L.fpi = L.fpv + mc_up16(MC_SPLITS * rows * 4);
-  L.fps = L.fpi + mc_up16(MC_SPLITS * rows * 4);
-  L.rpv = L.fps + mc_up16(MC_SPLITS * rows * 4);
-  L.rps = L.rpv + mc_up16(MC_SPLITS * px * 4);
-  L.total = L.rps + mc_up16(MC_SPLITS * px * 4);
+  L.chunk = L.list + cmr_up16(rows * 4);
+  L.pnorm = L.chunk + cmr_up16((int64_t)B * nchunk * 4);
+  L.qnorm = L.pnorm + cmr_up16(rows * 4);
+  L.col = L.qnorm + cmr_up16(px * 4);
+  L.fpv = L.col + cmr_up16(px * 4);
+  L.fpi = L.fpv + cmr_up16(MC_SPLITS * rows * 4);
+  L.fps = L.fpi + cmr_up16(MC_SPLITS * rows * 4);
+  L.rpv = L.fps + cmr_up16(MC_SPLITS * rows * 4);
+  L.rps = L.rpv + cmr_up16(MC_SPLITS * px * 4);
+  L.total = L.rps + cmr_up16(MC_SPLITS * px * 4);
   return L;
 }
 

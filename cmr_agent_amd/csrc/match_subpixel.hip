@@ -63,7 +63,7 @@ __global__ __launch_bounds__(MS_THREADS) void ms_subpixel_kernel(const float* __
   const bool valid = n < N;
   const int64_t g = (int64_t)b * N + (valid ? n : N - 1);
   const int32_t pi = idx[g];                                       // issued beside the mask read, not behind it
-  const bool sel = !mask || (mask_bytes == 1 ? ((const uint8_t*)mask)[g] != 0 : ((const int64_t*)mask)[g] != 0);
+  const bool sel = cmr_sel_or_all(mask, mask_bytes, g);
   const bool matched = valid && sel && pi >= 0 && pi < h * w;      // an index outside the map is never dereferenced
   const int p = matched ? pi : 0;
   const int x = p % w, y = p / w;

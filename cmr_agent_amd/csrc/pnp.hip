@@ -12,7 +12,7 @@
 //   pnp_select_kernel       one workgroup per sample: most inliers (ties to the lowest hypothesis index), Gauss-Newton on that
 //                           hypothesis' inlier set in float64, inlier recount, output.
 // The row order of the list is kept (not fm_compact_kernel's atomic order): draws index the list, so its order is part of the result.
-#include "cmr_common.h"
+#include "cmr_pnp.h"
 
 namespace {
 
@@ -40,27 +40,12 @@ __device__ __forceinline__ uint32_t pnp_hash(uint32_t seed, uint32_t b, uint32_t
   return pnp_mix(pnp_mix(pnp_mix(pnp_mix(seed ^ 0x9e3779b9u) ^ b) ^ h) ^ c);
 }
 
-// ---- the inlier test (shared by scoring, selection and recount: the same operations in the same order) --------------------------
-// M = K[R|t] row-major fp32; inlier iff z > 0 and (x - u z)^2 + (y - v z)^2 <= thr^2 z^2 (no division).
-__device__ __forceinline__ bool pnp_inlier(const float* M, float X, float Y, float Z, float u, float v, float thr2) {
-  const float x = fmaf(M[0], X, fmaf(M[1], Y, fmaf(M[2], Z, M[3])));
-  const float y = fmaf(M[4], X, fmaf(M[5], Y, fmaf(M[6], Z, M[7])));
-  const float z = fmaf(M[8], X, fmaf(M[9], Y, fmaf(M[10], Z, M[11])));
-  const float ex = fmaf(-u, z, x), ey = fmaf(-v, z, y);
-  const float e2 = fmaf(ex, ex, ey * ey);
-  return z > 0.f && e2 <= thr2 * (z * z);
-}
-
 // ---- compaction ----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool pnp_sel(const void* mask, int mask_bytes, int64_t g) {
-  return mask_bytes == 1 ? ((const uint8_t*)mask)[g] != 0 : ((const int64_t*)mask)[g] != 0;
-}
-
 __global__ __launch_bounds__(PNP_CHUNK) void pnp_chunk_count_kernel(const void* __restrict__ mask, int mask_bytes, int N, int nchunk,
                                                                     int32_t* __restrict__ chunk_cnt) {
   __shared__ int wc[PNP_CHUNK / 64];
   const int b = blockIdx.y, n = blockIdx.x * PNP_CHUNK + threadIdx.x;
-  const bool sel = n < N && pnp_sel(mask, mask_bytes, (int64_t)b * N + n);
+  const bool sel = n < N && cmr_sel(mask, mask_bytes, (int64_t)b * N + n);
   const int c = __popcll(__ballot(sel));
   if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = c;
   __syncthreads();
@@ -84,7 +69,7 @@ __global__ __launch_bounds__(PNP_CHUNK) void pnp_pack_kernel(const float* __rest
   }
   const int base = red[0];
   const int n = c * PNP_CHUNK + threadIdx.x;
-  const bool sel = n < N && pnp_sel(mask, mask_bytes, (int64_t)b * N + n);
+  const bool sel = n < N && cmr_sel(mask, mask_bytes, (int64_t)b * N + n);
   const unsigned long long bal = __ballot(sel);
   if (lane == 0) wc[wave] = __popcll(bal);
   __syncthreads();
@@ -259,15 +244,6 @@ __device__ __forceinline__ double pnp_orth_err(const double* R) {
   return m;
 }
 
-// K [R | t] -> fp32 row-major 3x4
-__device__ __forceinline__ void pnp_kmat(const double* K, const double* R, V3 t, float* M) {
-  const double tt[3] = {t.x, t.y, t.z};
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) M[4 * i + j] = (float)(K[3 * i] * R[j] + K[3 * i + 1] * R[3 + j] + K[3 * i + 2] * R[6 + j]);
-    M[4 * i + 3] = (float)(K[3 * i] * tt[0] + K[3 * i + 1] * tt[1] + K[3 * i + 2] * tt[2]);
-  }
-}
-
 __device__ __forceinline__ void pnp_load_k(const float* K, int b, double* Kd) {
   for (int i = 0; i < 9; ++i) Kd[i] = (double)K[9 * b + i];
 }
@@ -328,7 +304,8 @@ __global__ __launch_bounds__(64) void pnp_hyp_kernel(const float* __restrict__ c
       if (pick < 0 || e < beste) { beste = e; pick = k; }
     }
     if (pick >= 0) {
-      pnp_kmat(K, Rs[pick], ts[pick], M);
+      const double tp[3] = {ts[pick].x, ts[pick].y, ts[pick].z};
+      cmr_pnp_kmat(K, Rs[pick], tp, M);
       bool fin = true;
       for (int i = 0; i < 12; ++i) fin = fin && isfinite(M[i]);
       if (fin) {
@@ -372,7 +349,7 @@ __global__ __launch_bounds__(PNP_HYP_WG) void pnp_score_kernel(const float* __re
 #pragma unroll 4
   for (int i = 0; i < nloc; ++i) {
     const float4 p = sp[i];
-    n += pnp_inlier(M, p.x, p.y, p.z, p.w, sv[i], thr2) ? 1 : 0;
+    n += cmr_pnp_inlier(M, p.x, p.y, p.z, p.w, sv[i], thr2) ? 1 : 0;
   }
   if (hv && n) atomicAdd(&hyp_cnt[(int64_t)b * n_hyp + h], n);
 }
@@ -392,54 +369,6 @@ __device__ __forceinline__ int pnp_block_count(int v, int* scratch) {      // su
   int s = 0;
   for (int w = 0; w < PNP_SEL_THREADS / 64; ++w) s += scratch[w];
   return s;
-}
-
-// Rodrigues: exp([w]x)
-__device__ void pnp_expso3(const double* w, double* E) {
-  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-  const double th = sqrt(th2);
-  double a, c;
-  if (th < 1e-8) { a = 1.0 - th2 / 6.0; c = 0.5 - th2 / 24.0; }
-  else { a = sin(th) / th; c = (1.0 - cos(th)) / th2; }
-  const double W[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      double ww = 0.0;
-      for (int k = 0; k < 3; ++k) ww += W[3 * i + k] * W[3 * k + j];
-      E[3 * i + j] = (i == j ? 1.0 : 0.0) + a * W[3 * i + j] + c * ww;
-    }
-}
-
-// Cholesky solve of the 6x6 H x = g (H from the 21 upper-triangle entries, row by row); false if H is not positive definite
-__device__ bool pnp_chol6(const double* Hu, const double* g, double* x) {
-  double L[36] = {};
-  double H[36];
-  int k = 0;
-  for (int i = 0; i < 6; ++i)
-    for (int j = i; j < 6; ++j) { H[6 * i + j] = Hu[k]; H[6 * j + i] = Hu[k]; ++k; }
-  for (int j = 0; j < 6; ++j) {
-    double d = H[6 * j + j];
-    for (int p = 0; p < j; ++p) d -= L[6 * j + p] * L[6 * j + p];
-    if (!(d > 0.0)) return false;
-    L[6 * j + j] = sqrt(d);
-    for (int i = j + 1; i < 6; ++i) {
-      double s = H[6 * i + j];
-      for (int p = 0; p < j; ++p) s -= L[6 * i + p] * L[6 * j + p];
-      L[6 * i + j] = s / L[6 * j + j];
-    }
-  }
-  double z[6];
-  for (int i = 0; i < 6; ++i) {
-    double s = g[i];
-    for (int p = 0; p < i; ++p) s -= L[6 * i + p] * z[p];
-    z[i] = s / L[6 * i + i];
-  }
-  for (int i = 5; i >= 0; --i) {
-    double s = z[i];
-    for (int p = i + 1; p < 6; ++p) s -= L[6 * p + i] * x[p];
-    x[i] = s / L[6 * i + i];
-  }
-  return true;
 }
 
 __global__ __launch_bounds__(PNP_SEL_THREADS) void pnp_select_kernel(const float* __restrict__ corr, const int32_t* __restrict__ count,
@@ -497,7 +426,7 @@ __global__ __launch_bounds__(PNP_SEL_THREADS) void pnp_select_kernel(const float
     double a[PNP_NACC] = {};
     for (int i = tid; i < cnt; i += PNP_SEL_THREADS) {
       const float X = cb[i], Y = cb[N + i], Z = cb[2 * N + i], u = cb[3 * N + i], v = cb[4 * N + i];
-      if (!pnp_inlier(Mh, X, Y, Z, u, v, thr2)) continue;
+      if (!cmr_pnp_inlier(Mh, X, Y, Z, u, v, thr2)) continue;
       const V3 xc = v3(R[0] * X + R[1] * Y + R[2] * Z + t[0], R[3] * X + R[4] * Y + R[5] * Z + t[1], R[6] * X + R[7] * Y + R[8] * Z + t[2]);
       const V3 p = mulv(K, xc);
       if (!(p.z > 0.0)) continue;
@@ -535,13 +464,13 @@ __global__ __launch_bounds__(PNP_SEL_THREADS) void pnp_select_kernel(const float
       } else {
         double g[6], dx[6];
         for (int r = 0; r < 6; ++r) g[r] = -tot[21 + r];
-        if (!pnp_chol6(tot, g, dx)) {
+        if (!cmr_pnp_chol6<false>(tot, g, dx)) {
           stop = 1;
         } else {
           for (int i = 0; i < 12; ++i) prev[i] = sh_pose[i];
           cost_prev = cost;
           double E[9];
-          pnp_expso3(dx, E);
+          cmr_pnp_expso3(dx, E);
           double Rn[9], tn[3];
           for (int i = 0; i < 3; ++i) {
             for (int j = 0; j < 3; ++j) Rn[3 * i + j] = E[3 * i] * prev[j] + E[3 * i + 1] * prev[3 + j] + E[3 * i + 2] * prev[6 + j];
@@ -561,11 +490,11 @@ __global__ __launch_bounds__(PNP_SEL_THREADS) void pnp_select_kernel(const float
   float Mr[12];
   double Rf[9];
   for (int i = 0; i < 9; ++i) Rf[i] = sh_pose[i];
-  const V3 tf = v3(sh_pose[9], sh_pose[10], sh_pose[11]);
-  pnp_kmat(K, Rf, tf, Mr);
+  const double tf[3] = {sh_pose[9], sh_pose[10], sh_pose[11]};
+  cmr_pnp_kmat(K, Rf, tf, Mr);
   int n = 0;
   if (refine_iters > 0)
-    for (int i = tid; i < cnt; i += PNP_SEL_THREADS) n += pnp_inlier(Mr, cb[i], cb[N + i], cb[2 * N + i], cb[3 * N + i], cb[4 * N + i], thr2);
+    for (int i = tid; i < cnt; i += PNP_SEL_THREADS) n += cmr_pnp_inlier(Mr, cb[i], cb[N + i], cb[2 * N + i], cb[3 * N + i], cb[4 * N + i], thr2);
   const int rc = refine_iters > 0 ? pnp_block_count(n, scratch) : -1;
   const bool use_ref = refine_iters > 0 && rc >= bc;
   if (tid < 16) {

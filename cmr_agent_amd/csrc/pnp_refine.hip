@@ -7,7 +7,7 @@
 //   prf_init_kernel    per sample: pose_in -> the float64 working pose, K[R|t] of pose_in rounded to fp32 (the working set's predicate);
 //   for it = 0 .. iters:
 //     prf_accum_kernel   grid (slices, B), a slice = PRF_SLICE consecutive rows: the rows of the slice that are selected AND inliers of
-//                        pose_in (pnp.hip's fmaf sequence, copied) add their J^T J (21), J^T r (6) and cost (1) in float64 -- per
+//                        pose_in (cmr_pnp.h: RANSAC's own inlier test) add their J^T J (21), J^T r (6) and cost (1) in float64 -- per
 //                        thread in row order (rows t, t + 256, ...), wave butterfly, the four waves in order -- into the slice's own
 //                        slot, with the integer size of the slice's share of the working set.  Rows need no compaction;
 //     prf_step_kernel    per sample: adds the slots IN SLICE ORDER, then the accept / undo logic of pnp_select_kernel: a cost that did
@@ -16,14 +16,13 @@
 //   prf_final_kernel   per sample: adds the slice counts, keeps the refined pose if the count is >= the working set's size.
 // No floating-point atomics, no atomics at all: every slot, state and output has one writer, and the slice size is a constant, so two
 // calls agree bit for bit and a sample depends on its own rows only.
-#include "cmr_common.h"
+#include "cmr_pnp.h"
 
 namespace {
 
 constexpr int PRF_THREADS = 256;
 constexpr int PRF_SLICE = 1024;      // rows per accumulation workgroup: 4 per thread.  A constant: the summation order must not depend on B
 constexpr int PRF_NACC = 28;         // J^T J (21 upper-triangle entries), J^T r (6), cost
-constexpr double PRF_PIVOT_TOL = 1e-13;
 
 struct PrfState {
   double cur[12];                    // the working pose: R row-major, t
@@ -33,81 +32,9 @@ struct PrfState {
   int32_t stop, status, wcount, pad;
 };
 
-__device__ __forceinline__ bool prf_sel(const void* mask, int mask_bytes, int64_t g) {
-  return mask_bytes == 1 ? ((const uint8_t*)mask)[g] != 0 : ((const int64_t*)mask)[g] != 0;
-}
-
-// pnp.hip:pnp_inlier, the same operations in the same order
-__device__ __forceinline__ bool prf_inlier(const float* M, float X, float Y, float Z, float u, float v, float thr2) {
-  const float x = fmaf(M[0], X, fmaf(M[1], Y, fmaf(M[2], Z, M[3])));
-  const float y = fmaf(M[4], X, fmaf(M[5], Y, fmaf(M[6], Z, M[7])));
-  const float z = fmaf(M[8], X, fmaf(M[9], Y, fmaf(M[10], Z, M[11])));
-  const float ex = fmaf(-u, z, x), ey = fmaf(-v, z, y);
-  const float e2 = fmaf(ex, ex, ey * ey);
-  return z > 0.f && e2 <= thr2 * (z * z);
-}
-
-// pnp.hip:pnp_kmat: K [R | t] -> fp32 row-major 3x4 (pose = R row-major then t)
-__device__ __forceinline__ void prf_kmat(const double* K, const double* pose, float* M) {
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) M[4 * i + j] = (float)(K[3 * i] * pose[j] + K[3 * i + 1] * pose[3 + j] + K[3 * i + 2] * pose[6 + j]);
-    M[4 * i + 3] = (float)(K[3 * i] * pose[9] + K[3 * i + 1] * pose[10] + K[3 * i + 2] * pose[11]);
-  }
-}
-
 __device__ __forceinline__ double prf_wave_sum(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
-}
-
-// Rodrigues: exp([w]x)  (pnp.hip:pnp_expso3)
-__device__ void prf_expso3(const double* w, double* E) {
-  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-  const double th = sqrt(th2);
-  double a, c;
-  if (th < 1e-8) { a = 1.0 - th2 / 6.0; c = 0.5 - th2 / 24.0; }
-  else { a = sin(th) / th; c = (1.0 - cos(th)) / th2; }
-  const double W[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      double ww = 0.0;
-      for (int k = 0; k < 3; ++k) ww += W[3 * i + k] * W[3 * k + j];
-      E[3 * i + j] = (i == j ? 1.0 : 0.0) + a * W[3 * i + j] + c * ww;
-    }
-}
-
-// Cholesky solve of the 6x6 H x = g (H from the 21 upper-triangle entries, row by row; pnp.hip:pnp_chol6); false if H is not positive
-// definite.  Unlike pnp_chol6 a pivot must also exceed PRF_PIVOT_TOL times its diagonal entry: a rank-deficient H (all rows on a
-// line) leaves a pivot of rounding noise, ~1e-16 of the diagonal with either sign, and "status 2" must not hang on that sign.
-__device__ bool prf_chol6(const double* Hu, const double* g, double* x) {
-  double L[36] = {};
-  double H[36];
-  int k = 0;
-  for (int i = 0; i < 6; ++i)
-    for (int j = i; j < 6; ++j) { H[6 * i + j] = Hu[k]; H[6 * j + i] = Hu[k]; ++k; }
-  for (int j = 0; j < 6; ++j) {
-    double d = H[6 * j + j];
-    for (int p = 0; p < j; ++p) d -= L[6 * j + p] * L[6 * j + p];
-    if (!(d > 0.0 && d > PRF_PIVOT_TOL * H[6 * j + j])) return false;
-    L[6 * j + j] = sqrt(d);
-    for (int i = j + 1; i < 6; ++i) {
-      double s = H[6 * i + j];
-      for (int p = 0; p < j; ++p) s -= L[6 * i + p] * L[6 * j + p];
-      L[6 * i + j] = s / L[6 * j + j];
-    }
-  }
-  double z[6];
-  for (int i = 0; i < 6; ++i) {
-    double s = g[i];
-    for (int p = 0; p < i; ++p) s -= L[6 * i + p] * z[p];
-    z[i] = s / L[6 * i + i];
-  }
-  for (int i = 5; i >= 0; --i) {
-    double s = z[i];
-    for (int p = i + 1; p < 6; ++p) s -= L[6 * p + i] * x[p];
-    x[i] = s / L[6 * i + i];
-  }
-  return true;
 }
 
 __global__ __launch_bounds__(64) void prf_init_kernel(const float* __restrict__ pose_in, const float* __restrict__ Kin,
@@ -124,7 +51,7 @@ __global__ __launch_bounds__(64) void prf_init_kernel(const float* __restrict__ 
   }
   for (int i = 0; i < 12; ++i) st.prev[i] = st.cur[i];
   st.cost_prev = 0.0;
-  prf_kmat(K, st.cur, st.Min);
+  cmr_pnp_kmat(K, st.cur, st.cur + 9, st.Min);
   st.stop = 0;
   st.status = 0;
   st.wcount = 0;
@@ -153,9 +80,9 @@ __global__ __launch_bounds__(PRF_THREADS) void prf_accum_kernel(const float* __r
   double a[PRF_NACC] = {};
   int c = 0;
   for (int i = s * PRF_SLICE + tid; i < end; i += PRF_THREADS) {
-    if (!prf_sel(mask, mask_bytes, (int64_t)b * N + i)) continue;
+    if (!cmr_sel(mask, mask_bytes, (int64_t)b * N + i)) continue;
     const float X = pb[i], Y = pb[N + i], Z = pb[2 * N + i], u = qb[i], v = qb[N + i];
-    if (!prf_inlier(Min, X, Y, Z, u, v, thr2)) continue;
+    if (!cmr_pnp_inlier(Min, X, Y, Z, u, v, thr2)) continue;
     ++c;
     const double xc0 = R[0] * X + R[1] * Y + R[2] * Z + t[0], xc1 = R[3] * X + R[4] * Y + R[5] * Z + t[1],
                  xc2 = R[6] * X + R[7] * Y + R[8] * Z + t[2];
@@ -229,11 +156,11 @@ __global__ __launch_bounds__(64) void prf_step_kernel(int it, int iters, int nsl
   if (it == iters) { st.stop = 1; return; }
   double g[6], dx[6];
   for (int r = 0; r < 6; ++r) g[r] = -tot[21 + r];
-  bool ok = prf_chol6(tot, g, dx);
+  bool ok = cmr_pnp_chol6<true>(tot, g, dx);
   double nw[12];
   if (ok) {
     double E[9];
-    prf_expso3(dx, E);
+    cmr_pnp_expso3(dx, E);
     for (int i = 0; i < 3; ++i) {
       for (int j = 0; j < 3; ++j) nw[3 * i + j] = E[3 * i] * st.cur[j] + E[3 * i + 1] * st.cur[3 + j] + E[3 * i + 2] * st.cur[6 + j];
       nw[9 + i] = E[3 * i] * st.cur[9] + E[3 * i + 1] * st.cur[10] + E[3 * i + 2] * st.cur[11] + dx[3 + i];
@@ -260,13 +187,13 @@ __global__ __launch_bounds__(PRF_THREADS) void prf_count_kernel(const float* __r
   double K[9];
   for (int i = 0; i < 9; ++i) K[i] = (double)Kin[9 * b + i];
   float M[12];
-  prf_kmat(K, st.cur, M);
+  cmr_pnp_kmat(K, st.cur, st.cur + 9, M);
   const float* pb = pts + (int64_t)b * 3 * N;
   const float* qb = uv + (int64_t)b * 2 * N;
   const int end = (s + 1) * PRF_SLICE < N ? (s + 1) * PRF_SLICE : N;
   int c = 0;
   for (int i = s * PRF_SLICE + tid; i < end; i += PRF_THREADS)
-    if (prf_sel(mask, mask_bytes, (int64_t)b * N + i)) c += prf_inlier(M, pb[i], pb[N + i], pb[2 * N + i], qb[i], qb[N + i], thr2);
+    if (cmr_sel(mask, mask_bytes, (int64_t)b * N + i)) c += cmr_pnp_inlier(M, pb[i], pb[N + i], pb[2 * N + i], qb[i], qb[N + i], thr2);
   for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
   if (lane == 0) cnt[wave] = c;
   __syncthreads();
@@ -303,15 +230,13 @@ __global__ __launch_bounds__(64) void prf_final_kernel(const float* __restrict__
 
 struct PrfWs { int64_t state, slots, cslots, total; };
 
-inline int64_t prf_up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 inline PrfWs prf_layout(int B, int N) {
   PrfWs L;
   const int64_t nslice = ((int64_t)N + PRF_SLICE - 1) / PRF_SLICE;
   L.state = 0;
-  L.slots = L.state + prf_up16((int64_t)B * sizeof(PrfState));
-  L.cslots = L.slots + prf_up16((int64_t)B * nslice * PRF_NACC * 8);
-  L.total = L.cslots + prf_up16((int64_t)B * nslice * 4);
+  L.slots = L.state + cmr_up16((int64_t)B * sizeof(PrfState));
+  L.cslots = L.slots + cmr_up16((int64_t)B * nslice * PRF_NACC * 8);
+  L.total = L.cslots + cmr_up16((int64_t)B * nslice * 4);
   return L;
 }
 

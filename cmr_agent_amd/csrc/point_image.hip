@@ -1,13 +1,13 @@
 // Point painting and z-buffered attribute rendering under a pose (port extension): the two directions between a cloud and
-// an image once a pose is known.  Both project with guided_match.hip:gm_project_kernel's fp32 fmaf chains in the same order (copied, as
-// pose_score.hip and visibility.hip copy them), so "painted", "in view" (guided match at radius 0) and ops.visibility's cell are the same
-// rows and cells bit for bit.
+// an image once a pose is known.  Both project with cmr_project.h, the one statement of the fp32 fmaf chains and the in-view predicate
+// that guided match, pose score and visibility use too, so "painted", "in view" (guided match at radius 0) and ops.visibility's cell are
+// the same rows and cells bit for bit.
 //
 // cmr_paint_points_f32 -- the image laid over the cloud.  Two launches on the caller's stream:
 //   pi_zero_kernel    counts = 0.
 //   pi_paint_kernel   one thread per row on (ceil(N / 256), B): projection (pose and K are wave-uniform: scalar loads), the in-view test
 //                     on the floats, then the C planes PI_PLANES at a time: the taps of all PI_PLANES planes (4 each when bilinear) are
-//                     loaded before the first is used, the three lerps are rounded operation by operation (pi_lerp, under
+//                     loaded before the first is used, the three lerps are rounded operation by operation (cmr_lerp, under
 //                     fp contract(off): never an fma, so plain fp32 torch code gives the same bits), and colours are stored coalesced (consecutive
 //                     n within a plane), 0 for the rows that are not painted.  counts by one atomic per workgroup and word.
 // cmr_render_points_f32 -- the cloud laid over the image: a z-buffer that remembers its owner.  Three launches, no memset node:
@@ -20,7 +20,7 @@
 //                     minimum is exact, so this equals (2S + 1)^2 atomics per row -- then coalesced stores of index / depth / attribute
 //                     maps; the gather attr[b, c, owner] (PI_PLANES planes in flight) is the only scattered read.
 // No floating-point atomic anywhere; every output element is a plain store by the thread that owns it.
-#include "cmr_common.h"
+#include "cmr_project.h"
 
 namespace {
 
@@ -29,65 +29,6 @@ constexpr int PI_PLANES = 4;       // planes whose taps / gathers are in flight 
 constexpr int PI_MAX_C = 64;
 constexpr int PI_MAX_SPLAT = 4;
 constexpr unsigned long long PI_EMPTY = ~0ull;
-
-__device__ __forceinline__ bool pi_sel(const void* mask, int mask_bytes, int64_t g) {
-  return !mask ? true : (mask_bytes == 1 ? ((const uint8_t*)mask)[g] != 0 : ((const int64_t*)mask)[g] != 0);
-}
-
-// the workgroup's number of set flags per flag, valid in every thread; `part` holds one word per flag and wave
-template <int NF>
-__device__ __forceinline__ void pi_block_counts(const bool (&flag)[NF], int (&part)[NF][PI_THREADS / 64], int (&total)[NF]) {
-#pragma unroll
-  for (int f = 0; f < NF; ++f) {
-    const unsigned long long bal = __ballot(flag[f]);
-    if ((threadIdx.x & 63) == 0) part[f][threadIdx.x >> 6] = __popcll(bal);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int f = 0; f < NF; ++f) total[f] = part[f][0] + part[f][1] + part[f][2] + part[f][3];
-}
-
-struct PiProj {
-  float u, v, z;      // u, v NaN where p2 <= 0; z = p2 (meaningful where view)
-  bool view;
-  int cx, cy;         // the rounded projection, valid where view
-};
-
-// guided_match.hip:gm_project_kernel, the same operations in the same order; the in-view test is its predicate at radius 0
-__device__ __forceinline__ PiProj pi_project(const float* __restrict__ P, const float* __restrict__ K, const float* __restrict__ x, int N,
-                                             int n, int h, int w) {
-  PiProj r;
-  const float X = x[n], Y = x[N + n], Z = x[2 * N + n];
-  const float xc = fmaf(P[0], X, fmaf(P[1], Y, fmaf(P[2], Z, P[3])));
-  const float yc = fmaf(P[4], X, fmaf(P[5], Y, fmaf(P[6], Z, P[7])));
-  const float zc = fmaf(P[8], X, fmaf(P[9], Y, fmaf(P[10], Z, P[11])));
-  const float p0 = fmaf(K[0], xc, fmaf(K[1], yc, K[2] * zc));
-  const float p1 = fmaf(K[3], xc, fmaf(K[4], yc, K[5] * zc));
-  const float p2 = fmaf(K[6], xc, fmaf(K[7], yc, K[8] * zc));
-  r.u = r.v = __builtin_nanf("");
-  r.z = p2;
-  r.view = false;
-  r.cx = r.cy = 0;
-  if (p2 > 0.f) {
-    r.u = p0 / p2;
-    r.v = p1 / p2;
-    if (isfinite(r.u) && isfinite(r.v)) {
-      const float cx = rintf(r.u), cy = rintf(r.v);                      // round half to even; decided on the floats
-      r.view = cx >= 0.f && cx <= (float)(w - 1) && cy >= 0.f && cy <= (float)(h - 1);
-      if (r.view) { r.cx = (int)cx; r.cy = (int)cy; }
-    }
-  }
-  return r;
-}
-
-// a + t (b - a) with three roundings.  HIP's __fmul_rn / __fadd_rn are a plain product and sum that carry the translation unit's
-// default -ffp-contract=fast, and the backend fuses them into one fma; plain operators under the pragma carry no such licence.
-__device__ __forceinline__ float pi_lerp(float a, float b, float t) {
-#pragma clang fp contract(off)
-  const float d = b - a;
-  const float m = t * d;
-  return a + m;
-}
 
 __device__ __forceinline__ int pi_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
@@ -105,12 +46,12 @@ __global__ __launch_bounds__(PI_THREADS) void pi_paint_kernel(const float* __res
   const int b = blockIdx.y, n = blockIdx.x * PI_THREADS + threadIdx.x;
   const int64_t g = (int64_t)b * N + n;
   const bool valid = n < N;
-  const bool sel = valid && pi_sel(mask, mask_bytes, g);
-  PiProj p;
+  const bool sel = valid && cmr_sel_or_all(mask, mask_bytes, g);
+  CmrProj p;
   p.u = p.v = __builtin_nanf("");
   p.view = false;
   p.cx = p.cy = 0;
-  if (sel) p = pi_project(pose + 16 * b, Kin + 9 * b, pts + (int64_t)b * 3 * N, N, n, H, W);
+  if (sel) p = cmr_project(pose + 16 * b, Kin + 9 * b, pts + (int64_t)b * 3 * N, N, n, H, W, 0);
   const bool paint = sel && p.view;
   if (valid) {
     painted[g] = paint ? 1 : 0;
@@ -151,7 +92,7 @@ __global__ __launch_bounds__(PI_THREADS) void pi_paint_kernel(const float* __res
       }
 #pragma unroll
       for (int k = 0; k < PI_PLANES; ++k)
-        val[k] = BILINEAR ? pi_lerp(pi_lerp(t[k][0], t[k][1], fx), pi_lerp(t[k][2], t[k][3], fx), fy) : t[k][0];
+        val[k] = BILINEAR ? cmr_lerp(cmr_lerp(t[k][0], t[k][1], fx), cmr_lerp(t[k][2], t[k][3], fx), fy) : t[k][0];
     }
     if (valid) {
 #pragma unroll
@@ -161,7 +102,7 @@ __global__ __launch_bounds__(PI_THREADS) void pi_paint_kernel(const float* __res
   }
   const bool flag[2] = {sel, paint};
   int cnt[2];
-  pi_block_counts(flag, part, cnt);
+  cmr_block_counts<2, PI_THREADS>(flag, part, cnt);
   if (threadIdx.x < 2 && cnt[threadIdx.x]) atomicAdd(&counts[2 * b + threadIdx.x], cnt[threadIdx.x]);
 }
 
@@ -180,10 +121,10 @@ __global__ __launch_bounds__(PI_THREADS) void pi_splat_kernel(const float* __res
                                                               int w, unsigned long long* __restrict__ keys, int32_t* __restrict__ counts) {
   __shared__ int part[2][PI_THREADS / 64];
   const int b = blockIdx.y, n = blockIdx.x * PI_THREADS + threadIdx.x;
-  const bool sel = n < N && pi_sel(mask, mask_bytes, (int64_t)b * N + n);
+  const bool sel = n < N && cmr_sel_or_all(mask, mask_bytes, (int64_t)b * N + n);
   bool view = false;
   if (sel) {
-    const PiProj p = pi_project(pose + 16 * b, Kin + 9 * b, pts + (int64_t)b * 3 * N, N, n, h, w);
+    const CmrProj p = cmr_project(pose + 16 * b, Kin + 9 * b, pts + (int64_t)b * 3 * N, N, n, h, w, 0);
     view = p.view;
     if (view) {
       const unsigned long long key = ((unsigned long long)__builtin_bit_cast(unsigned, p.z) << 32) | (unsigned)n;
@@ -192,7 +133,7 @@ __global__ __launch_bounds__(PI_THREADS) void pi_splat_kernel(const float* __res
   }
   const bool flag[2] = {sel, view};
   int cnt[2];
-  pi_block_counts(flag, part, cnt);
+  cmr_block_counts<2, PI_THREADS>(flag, part, cnt);
   if (threadIdx.x < 2 && cnt[threadIdx.x]) atomicAdd(&counts[3 * b + threadIdx.x], cnt[threadIdx.x]);
 }
 
@@ -251,14 +192,8 @@ __global__ __launch_bounds__(PI_THREADS) void pi_resolve_kernel(const unsigned l
   }
   const bool flag[1] = {owned};
   int cnt[1];
-  pi_block_counts(flag, part, cnt);
+  cmr_block_counts<1, PI_THREADS>(flag, part, cnt);
   if (threadIdx.x == 0 && cnt[0]) atomicAdd(&counts[3 * b + 2], cnt[0]);
-}
-
-inline int64_t pi_up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
-inline bool pi_shape_ok(int B, int N, int h, int w) {
-  return B > 0 && B <= 65535 && N > 0 && (int64_t)N <= (int64_t)65535 * 256 && h > 0 && w > 0 && (int64_t)h * w <= (int64_t)1 << 24;
 }
 
 }  // namespace
@@ -267,7 +202,7 @@ extern "C" int cmr_paint_points_f32(const float* pts, const void* mask, int mask
                                     int B, int N, int C, int H, int W, int mode, float* colors, uint8_t* painted, int32_t* counts, float* uv,
                                     hipStream_t stream) {
   CMR_REQUIRE(pts && pose && K && image && colors && painted && counts);
-  CMR_REQUIRE(pi_shape_ok(B, N, H, W) && C >= 1 && C <= PI_MAX_C);
+  CMR_REQUIRE(cmr_cloud_map_ok(B, N, H, W) && C >= 1 && C <= PI_MAX_C);
   CMR_REQUIRE((mask_bytes == 1 || mask_bytes == 8) && (mode == 0 || mode == 1));
   hipLaunchKernelGGL(pi_zero_kernel, dim3(1), dim3(PI_THREADS), 0, stream, counts, 2 * B);
   const dim3 grid((N + PI_THREADS - 1) / PI_THREADS, B);
@@ -282,20 +217,19 @@ extern "C" int cmr_paint_points_f32(const float* pts, const void* mask, int mask
 
 extern "C" int64_t cmr_render_points_workspace_bytes(int B, int h, int w) {
   if (B <= 0 || h <= 0 || w <= 0) return 0;
-  return pi_up16((int64_t)B * h * w * 8);
+  return cmr_up16((int64_t)B * h * w * 8);
 }
 
 extern "C" int cmr_render_points_f32(const float* pts, const void* mask, int mask_bytes, const float* pose, const float* K, const float* attr,
                                      int C, int B, int N, int h, int w, int splat, float fill, int32_t* index_map, float* depth_map,
                                      float* attr_map, int32_t* counts, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
   CMR_REQUIRE(pts && pose && K && index_map && depth_map && counts && workspace);
-  CMR_REQUIRE(pi_shape_ok(B, N, h, w) && (mask_bytes == 1 || mask_bytes == 8) && splat >= 0 && splat <= PI_MAX_SPLAT);
+  CMR_REQUIRE(cmr_cloud_map_ok(B, N, h, w) && (mask_bytes == 1 || mask_bytes == 8) && splat >= 0 && splat <= PI_MAX_SPLAT);
   CMR_REQUIRE((attr == nullptr) == (attr_map == nullptr) && (attr ? (C >= 1 && C <= PI_MAX_C) : C == 0));
   CMR_REQUIRE(cmr_aligned16(workspace) && workspace_bytes >= cmr_render_points_workspace_bytes(B, h, w));
   unsigned long long* keys = (unsigned long long*)workspace;
   const int64_t cells = (int64_t)B * h * w;
-  const int64_t want = (cells / 2 + PI_THREADS - 1) / PI_THREADS;        // a 16-byte store per thread; the kernel strides when capped
-  const unsigned fill_blocks = (unsigned)(want < 1 ? 1 : (want > 65536 ? 65536 : want));
+  const unsigned fill_blocks = cmr_fill_blocks(cells / 2, PI_THREADS);   // a 16-byte store per thread
   hipLaunchKernelGGL(pi_fill_kernel, dim3(fill_blocks), dim3(PI_THREADS), 0, stream, keys, cells, counts, 3 * B);
   hipLaunchKernelGGL(pi_splat_kernel, dim3((N + PI_THREADS - 1) / PI_THREADS, B), dim3(PI_THREADS), 0, stream, pts, mask, mask_bytes, pose, K,
                      N, h, w, keys, counts);

@@ -7,7 +7,7 @@
 //                    and PS_CHUNK consecutive poses.  It first packs the slice's SELECTED rows, in increasing n, into a list in LDS
 //                    (ballot + prefix over the four waves), so the work follows the selected rows.  Then a 16-lane group per listed row
 //                    (group g takes list entries g, g + 16, ...): lane j keeps channels 4j .. 4j+3 of the point feature in registers and
-//                    the group walks the chunk's poses PS_AHEAD at a time -- projection (guided_match.hip's fmaf chains, copied; the pose
+//                    the group walks the chunk's poses PS_AHEAD at a time -- projection (cmr_project.h, the form without branches; the pose
 //                    index is wave-uniform, so R, t and K arrive through scalar loads), then the window offsets in increasing p with the
 //                    PS_AHEAD poses' pixel rows loaded together, the direct sum of squared differences and the 16-lane DPP butterfly,
 //                    minimum kept with a strict <.  A row that is not in view reads a clamped address and costs a select, not a branch;
@@ -19,7 +19,7 @@
 // Summation order of one score: inside a slice, per group the listed rows g, g + 16, ... in order, then the groups 0 .. 15 in order; then
 // the slices in order.  The list depends only on the sample's own mask, PS_SLICE is a constant, and a pose's place in its chunk decides
 // only WHICH lane adds, never the order: the sum does not depend on B, on P, on the pose's index or on how the poses are chunked.
-#include "cmr_common.h"
+#include "cmr_project.h"
 
 namespace {
 
@@ -33,24 +33,6 @@ constexpr int PS_AHEAD = 4;         // poses whose pixel loads are in flight tog
 constexpr int PS_MAX_RADIUS = 16;   // guided_match.hip GM_MAX_RADIUS
 constexpr int PS_MAX_POSES = 4096;
 static_assert(PS_SLICE == PS_THREADS && PS_CHUNK % PS_LANES == 0 && PS_LANES % PS_AHEAD == 0, "packing and accumulator layout");
-
-__device__ __forceinline__ bool ps_sel(const void* mask, int mask_bytes, int64_t g) {
-  return mask_bytes == 1 ? ((const uint8_t*)mask)[g] != 0 : ((const int64_t*)mask)[g] != 0;
-}
-
-template <int CTRL>
-__device__ __forceinline__ float ps_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-
-// guided_match.hip:gm_sum16 -- sum over the 16 lanes of a DPP row; every lane of the wave must be active
-__device__ __forceinline__ float ps_sum16(float s) {
-  s += ps_dpp<0xB1>(s);             // quad_perm:[1,0,3,2]
-  s += ps_dpp<0x4E>(s);             // quad_perm:[2,3,0,1]
-  s += ps_dpp<0x141>(s);            // row_half_mirror
-  s += ps_dpp<0x140>(s);            // row_mirror
-  return s;
-}
 
 __global__ __launch_bounds__(PS_THREADS) void ps_score_kernel(const float* __restrict__ pts, const float* __restrict__ pc,
                                                               const float* __restrict__ img, const void* __restrict__ mask, int mask_bytes,
@@ -67,7 +49,7 @@ __global__ __launch_bounds__(PS_THREADS) void ps_score_kernel(const float* __res
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // the slice's selected rows, in increasing n
   const int n0 = s * PS_SLICE + tid;
-  const bool sel = n0 < N && ps_sel(mask, mask_bytes, (int64_t)b * N + n0);
+  const bool sel = n0 < N && cmr_sel(mask, mask_bytes, (int64_t)b * N + n0);
   const unsigned long long bal = __ballot(sel);
   if (lane == 0) wcnt[wave] = __popcll(bal);
   __syncthreads();
@@ -104,22 +86,11 @@ __global__ __launch_bounds__(PS_THREADS) void ps_score_kernel(const float* __res
         float best[PS_AHEAD];
 #pragma unroll
         for (int u = 0; u < PS_AHEAD; ++u) {
-          // guided_match.hip:gm_project_kernel, the same operations in the same order; a pose past the chunk's end repeats the last one
-          const float* Pp = Pb + 16 * (pb + u < np ? pb + u : np - 1);
-          const float xc = fmaf(Pp[0], X, fmaf(Pp[1], Y, fmaf(Pp[2], Z, Pp[3])));
-          const float yc = fmaf(Pp[4], X, fmaf(Pp[5], Y, fmaf(Pp[6], Z, Pp[7])));
-          const float zc = fmaf(Pp[8], X, fmaf(Pp[9], Y, fmaf(Pp[10], Z, Pp[11])));
-          const float q0p = fmaf(K[0], xc, fmaf(K[1], yc, K[2] * zc));
-          const float q1p = fmaf(K[3], xc, fmaf(K[4], yc, K[5] * zc));
-          const float q2p = fmaf(K[6], xc, fmaf(K[7], yc, K[8] * zc));
-          const float uu = q0p / q2p, vv = q1p / q2p;
-          const float cx = rintf(uu), cy = rintf(vv);                    // round half to even; decided on the floats
-          // & not &&: one run of compares and a select, no short-circuit branches
-          const bool vw = (q2p > 0.f) & isfinite(uu) & isfinite(vv) & (cx + r >= 0.f) & (cx - r <= (float)(w - 1)) & (cy + r >= 0.f) &
-                          (cy - r <= (float)(h - 1));
-          view[u] = vw;
-          cxi[u] = (int)(vw ? cx : 0.f);
-          cyi[u] = (int)(vw ? cy : 0.f);
+          // a pose past the chunk's end repeats the last one
+          const CmrProj pr = cmr_project_select(Pb + 16 * (pb + u < np ? pb + u : np - 1), K, X, Y, Z, h, w, r);
+          view[u] = pr.view;
+          cxi[u] = pr.cx;
+          cyi[u] = pr.cy;
           best[u] = __builtin_huge_valf();
         }
         // the window offsets in increasing p (dy outer, dx inner); per offset the PS_AHEAD poses' loads are issued together, then scored
@@ -142,7 +113,7 @@ __global__ __launch_bounds__(PS_THREADS) void ps_score_kernel(const float* __res
             sc = fmaf(d1, d1, sc);
             sc = fmaf(d2, d2, sc);
             sc = fmaf(d3, d3, sc);
-            sc = ps_sum16(sc);
+            sc = cmr_sum16(sc);
             best[u] = fminf(best[u], in[u] ? sc : __builtin_huge_valf());      // a pixel outside the map is scored and dropped; a NaN score never wins
           }
           if (++dx > radius) { dx = -radius; ++dy; }
@@ -203,15 +174,13 @@ __global__ __launch_bounds__(256) void ps_final_kernel(int B, int P, int nslice,
 
 struct PsWs { int64_t part, cpart, nsel, total; };
 
-inline int64_t ps_up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 inline PsWs ps_layout(int B, int N, int P) {
   PsWs L;
   const int64_t nslice = ((int64_t)N + PS_SLICE - 1) / PS_SLICE;
   L.part = 0;
-  L.cpart = L.part + ps_up16((int64_t)B * P * nslice * 8);
-  L.nsel = L.cpart + ps_up16((int64_t)B * P * nslice * 8);
-  L.total = L.nsel + ps_up16((int64_t)B * nslice * 4);
+  L.cpart = L.part + cmr_up16((int64_t)B * P * nslice * 8);
+  L.nsel = L.cpart + cmr_up16((int64_t)B * P * nslice * 8);
+  L.total = L.nsel + cmr_up16((int64_t)B * nslice * 4);
   return L;
 }
 
@@ -226,8 +195,7 @@ extern "C" int cmr_pose_score_f32(const float* pts, const float* pc_feat, const 
                                   double* score, int32_t* counts, int32_t* selected, void* workspace, int64_t workspace_bytes,
                                   hipStream_t stream) {
   CMR_REQUIRE(pts && pc_feat && img_feat && mask && poses && K && score && counts && selected && workspace);
-  CMR_REQUIRE(C == PS_C && B > 0 && B <= 65535 && N > 0 && h > 0 && w > 0 && (int64_t)h * w <= (int64_t)1 << 24);
-  CMR_REQUIRE((int64_t)N <= (int64_t)65535 * 256 && P > 0 && P <= PS_MAX_POSES);
+  CMR_REQUIRE(C == PS_C && cmr_cloud_map_ok(B, N, h, w) && P > 0 && P <= PS_MAX_POSES);
   CMR_REQUIRE(mask_bytes == 1 || mask_bytes == 8);
   CMR_REQUIRE(radius >= 0 && radius <= PS_MAX_RADIUS && tau > 0.f && __builtin_isfinite(tau));
   CMR_REQUIRE(cmr_aligned16(pc_feat) && cmr_aligned16(img_feat) && cmr_aligned16(workspace));

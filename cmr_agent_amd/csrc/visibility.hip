@@ -3,7 +3,7 @@
 //
 // Three launches on the caller's stream, no memset node, whatever the data:
 //   vis_fill_kernel   Z = +inf (16-byte stores on the aligned body, dwords on the head and tail) and counts = 0.
-//   vis_splat_kernel  one thread per row: the rows of mask | occ_mask are projected (guided_match.hip's fmaf chains, copied) and their
+//   vis_splat_kernel  one thread per row: the rows of mask | occ_mask are projected (cmr_project.h, the predicate at radius 0) and their
 //                     cell / depth written -- into the caller's arrays when given, else into the workspace; an occluder row in view
 //                     lowers Z at its centre with an UNSIGNED INTEGER atomic min on the float's bits (positive floats order like their
 //                     bit patterns; a vector atomic, order independent).  counts[3] by one atomic per workgroup.
@@ -17,7 +17,7 @@
 // Why the direct walk and not a separable min-pool of Z through LDS: at the shapes the op is used at (some 10^4 .. 10^5 queried rows,
 // r <= 4) the walk reads rows * (2r + 1)^2 <= a few 10^6 cells that sit in L2, while a pool reads and writes the whole map twice
 // (B h w up to 3.4 10^6 cells at 352 x 1216, B = 8) whatever the rows are and adds a launch.  DESIGN.md 4r has the counts.
-#include "cmr_common.h"
+#include "cmr_project.h"
 
 namespace {
 
@@ -26,28 +26,6 @@ constexpr int VIS_MAX_RADIUS = 16;  // guided_match.hip GM_MAX_RADIUS
 constexpr int VT_LANES = 4;         // lanes per row in the test: one DPP quad
 constexpr int VT_ROWS = VIS_THREADS / VT_LANES;
 constexpr int VT_AHEAD = 4;         // window cells whose loads are in flight together per lane
-
-__device__ __forceinline__ bool vis_sel(const void* mask, int mask_bytes, int64_t g) {
-  return mask_bytes == 1 ? ((const uint8_t*)mask)[g] != 0 : ((const int64_t*)mask)[g] != 0;
-}
-
-template <int CTRL>
-__device__ __forceinline__ float vis_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-
-// the workgroup's number of set flags per flag, valid in every thread; `part` holds one word per flag and wave
-template <int NF>
-__device__ __forceinline__ void vis_block_counts(const bool (&flag)[NF], int (&part)[NF][VIS_THREADS / 64], int (&total)[NF]) {
-#pragma unroll
-  for (int f = 0; f < NF; ++f) {
-    const unsigned long long bal = __ballot(flag[f]);
-    if ((threadIdx.x & 63) == 0) part[f][threadIdx.x >> 6] = __popcll(bal);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int f = 0; f < NF; ++f) total[f] = part[f][0] + part[f][1] + part[f][2] + part[f][3];
-}
 
 __global__ __launch_bounds__(VIS_THREADS) void vis_fill_kernel(float* __restrict__ Z, int64_t total, int32_t* __restrict__ counts,
                                                                int ncounts) {
@@ -71,32 +49,16 @@ __global__ __launch_bounds__(VIS_THREADS) void vis_splat_kernel(const float* __r
   __shared__ int part[1][VIS_THREADS / 64];
   const int b = blockIdx.y, n = blockIdx.x * VIS_THREADS + threadIdx.x;
   const int64_t g = (int64_t)b * N + n;
-  const bool sel = n < N && vis_sel(mask, mask_bytes, g);
-  const bool occ = n < N && (occ_mask ? vis_sel(occ_mask, occ_bytes, g) : true);
+  const bool sel = n < N && cmr_sel(mask, mask_bytes, g);
+  const bool occ = n < N && (occ_mask ? cmr_sel(occ_mask, occ_bytes, g) : true);
   bool view = false;
   int c = -1;
   float z = __builtin_nanf("");
   if (sel || occ) {
-    // guided_match.hip:gm_project_kernel, the same operations in the same order
-    const float* P = pose + 16 * b;
-    const float* K = Kin + 9 * b;
-    const float* x = pts + (int64_t)b * 3 * N;
-    const float X = x[n], Y = x[N + n], Zp = x[2 * N + n];
-    const float xc = fmaf(P[0], X, fmaf(P[1], Y, fmaf(P[2], Zp, P[3])));
-    const float yc = fmaf(P[4], X, fmaf(P[5], Y, fmaf(P[6], Zp, P[7])));
-    const float zc = fmaf(P[8], X, fmaf(P[9], Y, fmaf(P[10], Zp, P[11])));
-    const float p0 = fmaf(K[0], xc, fmaf(K[1], yc, K[2] * zc));
-    const float p1 = fmaf(K[3], xc, fmaf(K[4], yc, K[5] * zc));
-    const float p2 = fmaf(K[6], xc, fmaf(K[7], yc, K[8] * zc));
-    if (p2 > 0.f) {
-      z = p2;
-      const float u = p0 / p2, v = p1 / p2;
-      if (isfinite(u) && isfinite(v)) {
-        const float cx = rintf(u), cy = rintf(v);                        // round half to even; decided on the floats
-        view = cx >= 0.f && cx <= (float)(w - 1) && cy >= 0.f && cy <= (float)(h - 1);
-        if (view) c = (int)cy * w + (int)cx;                             // < h * w <= 2^24
-      }
-    }
+    const CmrProj p = cmr_project<true>(pose + 16 * b, Kin + 9 * b, pts + (int64_t)b * 3 * N, N, n, h, w, 0);
+    z = p.z;
+    view = p.view;
+    c = p.cell;
   }
   if (n < N) {
     cell[g] = c;
@@ -105,7 +67,7 @@ __global__ __launch_bounds__(VIS_THREADS) void vis_splat_kernel(const float* __r
   if (occ && view) atomicMin(Z + (int64_t)b * h * w + c, __builtin_bit_cast(unsigned, z));
   const bool flag[1] = {occ && view};
   int nocc[1];
-  vis_block_counts(flag, part, nocc);
+  cmr_block_counts<1, VIS_THREADS>(flag, part, nocc);
   if (threadIdx.x == 0 && nocc[0]) atomicAdd(&counts[4 * b + 3], nocc[0]);
 }
 
@@ -117,7 +79,7 @@ __global__ __launch_bounds__(VIS_THREADS) void vis_test_kernel(const void* __res
   const int b = blockIdx.y, n = blockIdx.x * VT_ROWS + (threadIdx.x >> 2), j = threadIdx.x & (VT_LANES - 1);
   const int64_t g = (int64_t)b * N + n;
   const bool valid = n < N;
-  const bool sel = valid && vis_sel(mask, mask_bytes, g);
+  const bool sel = valid && cmr_sel(mask, mask_bytes, g);
   const int c = sel ? cell[g] : -1;
   const bool active = c >= 0;                                            // selected and in view
   const float z = active ? depth[g] : 0.f;
@@ -144,25 +106,23 @@ __global__ __launch_bounds__(VIS_THREADS) void vis_test_kernel(const void* __res
       for (int u = 0; u < VT_AHEAD; ++u) zmin = fminf(zmin, in[u] ? f[u] : inf);      // Z holds no NaN: +inf or a positive depth
     }
   }
-  zmin = fminf(zmin, vis_dpp<0xB1>(zmin));                               // quad_perm:[1,0,3,2]; outside every branch
-  zmin = fminf(zmin, vis_dpp<0x4E>(zmin));                               // quad_perm:[2,3,0,1]
-  const float bound = __fadd_rn(__fmul_rn(zmin, opr), abs_tol);          // two roundings, never one fma
+  zmin = fminf(zmin, cmr_fdpp<0xB1>(zmin));                               // quad_perm:[1,0,3,2]; outside every branch
+  zmin = fminf(zmin, cmr_fdpp<0x4E>(zmin));                               // quad_perm:[2,3,0,1]
+  const float bound = cmr_mul_add_rn(zmin, opr, abs_tol);                // two roundings, never one fma
   const bool vis = active && z <= bound;
   const bool first = j == 0;
   if (valid && first) visible[g] = vis ? 1 : 0;
   const bool flag[3] = {sel && first, active && first, vis && first};
   int cnt[3];
-  vis_block_counts(flag, part, cnt);
+  cmr_block_counts<3, VIS_THREADS>(flag, part, cnt);
   if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(&counts[4 * b + threadIdx.x], cnt[threadIdx.x]);
 }
-
-inline int64_t vis_up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
 }  // namespace
 
 extern "C" int64_t cmr_visibility_workspace_bytes(int B, int N, int h, int w) {
   if (B <= 0 || N <= 0 || h <= 0 || w <= 0) return 0;
-  return vis_up16((int64_t)B * h * w * 4) + 2 * vis_up16((int64_t)B * N * 4);
+  return cmr_up16((int64_t)B * h * w * 4) + 2 * cmr_up16((int64_t)B * N * 4);
 }
 
 extern "C" int cmr_visibility_f32(const float* pts, const void* mask, int mask_bytes, const void* occ_mask, int occ_mask_bytes,
@@ -170,8 +130,7 @@ extern "C" int cmr_visibility_f32(const float* pts, const void* mask, int mask_b
                                   uint8_t* visible, int32_t* counts, float* depth_map, int32_t* cell, float* depth, void* workspace,
                                   int64_t workspace_bytes, hipStream_t stream) {
   CMR_REQUIRE(pts && mask && pose && K && visible && counts && workspace);
-  CMR_REQUIRE(B > 0 && B <= 65535 && N > 0 && h > 0 && w > 0 && (int64_t)h * w <= (int64_t)1 << 24);
-  CMR_REQUIRE((int64_t)N <= (int64_t)65535 * 256);
+  CMR_REQUIRE(cmr_cloud_map_ok(B, N, h, w));
   CMR_REQUIRE((mask_bytes == 1 || mask_bytes == 8) && (occ_mask_bytes == 1 || occ_mask_bytes == 8));
   CMR_REQUIRE(radius >= 0 && radius <= VIS_MAX_RADIUS);
   CMR_REQUIRE(rel_tol >= 0.f && abs_tol >= 0.f && __builtin_isfinite(rel_tol) && __builtin_isfinite(abs_tol));
@@ -180,11 +139,10 @@ extern "C" int cmr_visibility_f32(const float* pts, const void* mask, int mask_b
   const int64_t cells = (int64_t)B * h * w;
   char* ws = (char*)workspace;
   float* Z = depth_map ? depth_map : (float*)ws;
-  int32_t* cellp = cell ? cell : (int32_t*)(ws + vis_up16(cells * 4));
-  float* depthp = depth ? depth : (float*)(ws + vis_up16(cells * 4) + vis_up16((int64_t)B * N * 4));
+  int32_t* cellp = cell ? cell : (int32_t*)(ws + cmr_up16(cells * 4));
+  float* depthp = depth ? depth : (float*)(ws + cmr_up16(cells * 4) + cmr_up16((int64_t)B * N * 4));
   const float opr = (float)(1.0 + (double)rel_tol);
-  const int64_t want = (cells / 4 + VIS_THREADS - 1) / VIS_THREADS;      // a float4 per thread; the kernel strides when capped
-  const unsigned fill_blocks = (unsigned)(want < 1 ? 1 : (want > 65536 ? 65536 : want));
+  const unsigned fill_blocks = cmr_fill_blocks(cells / 4, VIS_THREADS);   // a float4 per thread
   hipLaunchKernelGGL(vis_fill_kernel, dim3(fill_blocks), dim3(VIS_THREADS), 0, stream, Z, cells, counts, 4 * B);
   hipLaunchKernelGGL(vis_splat_kernel, dim3((N + VIS_THREADS - 1) / VIS_THREADS, B), dim3(VIS_THREADS), 0, stream, pts, mask, mask_bytes,
                      occ_mask, occ_mask_bytes, pose, K, N, h, w, (unsigned*)Z, cellp, depthp, counts);

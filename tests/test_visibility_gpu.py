@@ -218,6 +218,49 @@ def test_equal_depths_at_zero_tolerance_are_both_visible():
     assert vis.tolist() == [True, True, True]
 
 
+def test_bound_is_rounded_twice():
+    """bound = zmin * opr + abs_tol is a rounded product and then a rounded sum, never one fma.  With both tolerances
+    positive the two differ for about a third of the depths, so rows are planted ON the bound: 96 occluder / query pairs, each alone in
+    its cell of a 12 x 16 map under the identity pose and intrinsics (depth = Z exactly).  Pairs 0 .. 31: the fused bound is lower, the
+    query sits on the two-rounding bound and is visible.  Pairs 32 .. 63: the fused bound is higher, the query sits one float above the
+    two-rounding bound and is not.  Pairs 64 .. 95: the bounds agree; half on the bound, half one float above."""
+    h, w, rel_tol, abs_tol, per = 12, 16, 0.05, 0.1, 32
+    opr, tol = vr.opr32(rel_tol), np.float32(abs_tol)
+    z0 = np.random.default_rng(20261018).uniform(1.0, 50.0, 4096).astype(np.float32)
+    unfused = (z0 * opr).astype(np.float32) + tol                                                     # fp32 product, then fp32 sum
+    fused = (z0.astype(np.float64) * np.float64(opr) + np.float64(tol)).astype(np.float32)            # exact in float64: rounded once
+    assert unfused.dtype == np.float32
+    above = np.nextafter(unfused, np.float32(np.inf))
+    groups = [np.flatnonzero(fused < unfused)[:per], np.flatnonzero(fused > unfused)[:per], np.flatnonzero(fused == unfused)[:per]]
+    assert [len(g) for g in groups] == [per, per, per]
+    pick = np.concatenate(groups)
+    on_bound = np.r_[np.ones(per, bool), np.zeros(per, bool), np.arange(per) < per // 2]              # the planted expectation
+    zo, zq = z0[pick], np.where(on_bound, unfused[pick], above[pick]).astype(np.float32)
+    assert bool(((zq <= unfused[pick]) == on_bound).all())
+    assert bool((zq[:per] > fused[pick[:per]]).all()) and bool((zq[per:2 * per] <= fused[pick[per:2 * per]]).all())
+    assert bool(((zq[2 * per:] <= fused[pick[2 * per:]]) == on_bound[2 * per:]).all())
+    npair = 3 * per
+    N = 2 * npair
+    cells = np.random.default_rng(7).permutation(h * w)[:npair]
+    z = np.stack([zo, zq], 1).reshape(N)                                                              # row 2i occludes, row 2i + 1 is queried
+    cx, cy = np.repeat(cells % w, 2).astype(np.float32), np.repeat(cells // w, 2).astype(np.float32)
+    query = torch.arange(N) % 2 == 1
+    sc = {"pts": np.stack([cx * z, cy * z, z])[None], "pose": np.eye(4, dtype=np.float32)[None], "K": np.eye(3, dtype=np.float32)[None],
+          "h": h, "w": w, "mask": query[None].clone(), "occ_mask": ~query[None]}
+    out = _call(sc, 0, rel_tol=rel_tol, abs_tol=abs_tol)
+    vis, counts, dmap, cell, depth = out
+    assert torch.equal(_bits(depth), _bits(F(z)))                                                     # depth is Z, bit for bit
+    assert cell.tolist() == np.repeat(cells, 2).tolist()                                              # each pair alone in its cell
+    want = torch.zeros(N, dtype=torch.bool)
+    want[1::2] = torch.from_numpy(on_bound)
+    wrong = (vis.cpu() != want)[1::2].view(3, per).sum(1).tolist()
+    print("pairs classified against the two-rounding bound, per group (fused lower, fused higher, equal):", wrong)
+    assert torch.equal(vis.cpu(), want)
+    _, rvis, rcounts = _restated(sc, out, 0, rel_tol, abs_tol)
+    assert torch.equal(vis, rvis)
+    assert torch.equal(counts, rcounts) and counts[0].tolist() == [npair, npair, int(on_bound.sum()), npair]
+
+
 # ---- 6. determinism ------------------------------------------------------------------------------------------------------------------------------
 def test_two_calls_agree_bit_for_bit():
     sc = vr.built("n1025_40x128")
