@@ -30,6 +30,12 @@ coarse-to-fine lattice search MultiHeadModel.search_pose (729 poses per round un
 prints "verified <name>=<quality> ... -> <chosen name>", quality = 1 - score / (selected tau^2) in [0, 1]; the chosen pose's RTE / RRE
 are collected and the closing lines printed once more with the prefix "Verified ".  Without these flags the output is unchanged.
 
+--verify-mi [--mi-bins NB] (with --data-root): the same candidate poses are scored by the mutual information of the LiDAR
+reflectance (the loader keeps it: FrameDataset(..., with_intensity=True)) and the image's grey values under each pose
+(MultiHeadModel.score_poses_mi, NB x NB joint histogram, NB default 32); the pair prints "mi <name>=<MI in nats> ... -> <chosen name>"
+and the closing lines are printed once more for the chosen poses with the prefix "MI-verified ".  Synthetic pairs have a noise image and
+no reflectance: without --data-root the flag is refused.  Without the flag the output is unchanged.
+
 --paint DIR [--paint-visible]: every pair's cloud is painted with the image under the last pose the run produced -- the
 refined pose with --refine, else the agent's final pose through env.from_disentangled (cmr_paint_points_f32, bilinear) -- and
 DIR/pair_<index>.ply holds the painted points (binary little-endian PLY: x y z float32 in the cloud's own frame, red green blue uchar =
@@ -62,8 +68,8 @@ from cmr_agent_amd.environment import environment as env  # noqa: E402
 from cmr_agent_amd.models import CMRAgent, MultiHeadModel  # noqa: E402
 from cmr_agent_amd.utils import hashfill, synthetic  # noqa: E402
 from cmr_agent_amd.utils.checkpoint import load_checked  # noqa: E402
-from cmr_agent_amd.utils.evalcli import (add_dense_flags, add_paint_flags, add_visible_flags, dense_option, dense_pairs, guided_rounds,  # noqa: E402
-                                         paint_option, paint_pairs, print_recall, print_visible, visible_option)
+from cmr_agent_amd.utils.evalcli import (add_dense_flags, add_mi_flags, add_paint_flags, add_visible_flags, dense_option, dense_pairs,  # noqa: E402
+                                         guided_rounds, mi_option, paint_option, paint_pairs, print_mi, print_recall, print_visible, visible_option)
 
 
 def get_P_diff(P_pred, P_gt):
@@ -92,9 +98,11 @@ def main():
     add_visible_flags(ap, "--refine")
     add_paint_flags(ap)
     add_dense_flags(ap)
+    add_mi_flags(ap)
     args = ap.parse_args()
     paint = paint_option(ap, args)
     dense = dense_option(ap, args, ops.DENSIFY_MAX_RADIUS)
+    mi_bins = mi_option(ap, args, ops.POSE_MI_MAX_BINS)
     if args.subpixel and args.refine is None:
         ap.error("--subpixel belongs to --refine")
     radii = thrs = None
@@ -118,11 +126,12 @@ def main():
 
     rte, rre, rte_ref, rre_ref = [], [], [], []
     rte_sea, rre_sea, rte_ver, rre_ver = [], [], [], []
+    rte_mi, rre_mi = [], []
     with torch.no_grad():
         if args.data_root:
             from cmr_agent_amd.dataset import FrameDataset, FrameLoader
             import itertools
-            frames = itertools.islice(iter(FrameLoader(FrameDataset(args.data_root, config, 'test', device=dev), 1, shuffle=False)), args.pairs)
+            frames = itertools.islice(iter(FrameLoader(FrameDataset(args.data_root, config, 'test', device=dev, **({} if mi_bins is None else dict(with_intensity=True))), 1, shuffle=False)), args.pairs)
         else:
             frames = (synthetic.make_batch(1, config.num_pt, config.cropped_img_H, config.cropped_img_W, config.num_node,
                                            hip_fps(dev), hip_nearest(dev), seed=config.seed + i, n_circle=16, device=dev) for i in range(args.pairs))
@@ -140,7 +149,7 @@ def main():
             rte.append(t_diff)
             rre.append(r_diff)
             cands = [("agent", None, (t_diff, r_diff))]                 # (name, pose mapping 'pc' into the camera frame, (RTE, RRE))
-            if args.search or args.verify:
+            if args.search or args.verify or mi_bins is not None:
                 final = env.from_disentangled(pose_source.clone(), data['pc'], data=data)
                 cands[0] = ("agent", final, (t_diff, r_diff))
             if radii is not None:
@@ -170,6 +179,12 @@ def main():
                 print("verified", " ".join("%s=%.4f" % (c[0], q) for c, q in zip(cands, quality)), "->", cands[k][0])
                 rte_ver.append(cands[k][2][0])
                 rre_ver.append(cands[k][2][1])
+            if mi_bins is not None:
+                geo_model.score_poses_mi(data, torch.stack([c[1].float() for c in cands], 1), bins=mi_bins)
+                k = int(data['pose_mi_best'][0])
+                print_mi([c[0] for c in cands], data['pose_mi'][0].cpu().tolist(), k)
+                rte_mi.append(cands[k][2][0])
+                rre_mi.append(cands[k][2][1])
             if paint is not None or dense is not None:
                 last = data['refined_pose'] if radii is not None else env.from_disentangled(pose_source.clone(), data['pc'], data=data)
                 if paint is not None:
@@ -183,6 +198,8 @@ def main():
         print_recall(rte_sea, rre_sea, "Searched ")
     if args.verify:
         print_recall(rte_ver, rre_ver, "Verified ")
+    if mi_bins is not None:
+        print_recall(rte_mi, rre_mi, "MI-verified ")
 
 
 if __name__ == '__main__':

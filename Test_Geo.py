@@ -41,6 +41,13 @@ against the geometric features with no ground truth (MultiHeadModel.score_poses,
 <name>=<quality> ... -> <chosen name>", quality = 1 - score / (selected tau^2) in [0, 1], and after the closing block(s) the same three
 lines again for the chosen poses with the prefix "Verified ".  Without the flag the output is unchanged.
 
+--verify-mi [--mi-bins NB] (with --pnp and --data-root): the same candidate poses are scored by the mutual information of
+the LiDAR reflectance (the loader keeps it: FrameDataset(..., with_intensity=True)) and the image's grey values under each pose
+(MultiHeadModel.score_poses_mi, NB x NB joint histogram, NB default 32) -- a score that reads the sensors, not the learned features;
+per pair one extra line "mi <name>=<MI in nats> ... -> <chosen name>" and after the closing block(s) the same three lines for the chosen
+poses with the prefix "MI-verified ".  Synthetic pairs have a noise image and no reflectance: without --data-root the flag is refused.
+Without the flag the output is unchanged.
+
 --visible (with --guided; optional --visible-radius R, --visible-rel-tol T, --visible-abs-tol A): every --guided round first
 takes a z-buffer of the whole cloud under the round's pose (cmr_visibility_f32) and matches only the predicted-overlap points it leaves
 visible: depth <= nearest depth in the (2R + 1)^2 cells round the point's own * (1 + T) + A, defaults 1 / 0.05 / 0.  Each batch prints
@@ -81,8 +88,8 @@ from cmr_agent_amd.models import MultiHeadModel  # noqa: E402
 from cmr_agent_amd.models.MultiHeadModel import match_features  # noqa: E402
 from cmr_agent_amd.utils import hashfill, synthetic  # noqa: E402
 from cmr_agent_amd.utils.checkpoint import load_checked  # noqa: E402
-from cmr_agent_amd.utils.evalcli import (add_dense_flags, add_paint_flags, add_visible_flags, dense_option, dense_pairs, guided_rounds,  # noqa: E402
-                                         paint_option, paint_pairs, print_recall, print_visible, visible_option)
+from cmr_agent_amd.utils.evalcli import (add_dense_flags, add_mi_flags, add_paint_flags, add_visible_flags, dense_option, dense_pairs,  # noqa: E402
+                                         guided_rounds, mi_option, paint_option, paint_pairs, print_mi, print_recall, print_visible, visible_option)
 
 
 def _ratios(counts):
@@ -123,9 +130,11 @@ def main():
     add_visible_flags(ap, "--guided")
     add_paint_flags(ap, "--pnp")
     add_dense_flags(ap, "--pnp")
+    add_mi_flags(ap, "--pnp")
     args = ap.parse_args()
     paint = paint_option(ap, args, "--pnp", args.pnp)
     dense = dense_option(ap, args, ops.DENSIFY_MAX_RADIUS, "--pnp", args.pnp)
+    mi_bins = mi_option(ap, args, ops.POSE_MI_MAX_BINS, "--pnp", args.pnp)
     if args.verify and not args.pnp:
         ap.error("--verify scores the PnP pose (and the --guided one): give --pnp as well")
     filtered = args.mutual or args.ratio is not None
@@ -172,11 +181,12 @@ def main():
     bs, nbatch = args.batch_size, (args.pairs + args.batch_size - 1) // args.batch_size
     prec, rec, ir, ir1, ir2 = [], [], [], [], []
     rte, rre, rte_ref, rre_ref, rte_ver, rre_ver = [], [], [], [], [], []
+    rte_mi, rre_mi = [], []
     done = 0
     with torch.no_grad():
         if args.data_root:
             from cmr_agent_amd.dataset import FrameDataset, FrameLoader
-            batches = itertools.islice(iter(FrameLoader(FrameDataset(args.data_root, config, 'test', device=dev), bs, shuffle=False)), nbatch)
+            batches = itertools.islice(iter(FrameLoader(FrameDataset(args.data_root, config, 'test', device=dev, **({} if mi_bins is None else dict(with_intensity=True))), bs, shuffle=False)), nbatch)
         else:
             batches = (synthetic.make_batch(bs, config.num_pt, config.cropped_img_H, config.cropped_img_W, config.num_node, hip_fps(dev),
                                             hip_nearest(dev), seed=config.seed + i, n_circle=16, device=dev) for i in range(nbatch))
@@ -220,6 +230,9 @@ def main():
                 if args.verify:
                     geo_model.score_poses(data, torch.stack([data['pnp_pose']] + ([data['refined_pose']] if radii is not None else []), 1), radius=0)
                     chosen, quality = data['pose_best'].cpu().tolist(), data['pose_quality'].cpu().tolist()
+                if mi_bins is not None:
+                    geo_model.score_poses_mi(data, torch.stack([data['pnp_pose']] + ([data['refined_pose']] if radii is not None else []), 1), bins=mi_bins)
+                    mi_chosen, mi_values = data['pose_mi_best'].cpu().tolist(), data['pose_mi'].cpu().tolist()
                 for b in range(pred.shape[0]):
                     t_diff, r_diff = get_P_diff(pred[b].cpu().numpy(), gt[b].cpu().numpy())
                     print(t_diff, r_diff)
@@ -236,6 +249,10 @@ def main():
                         print("verified", " ".join("%s=%.4f" % (n, q) for n, q in zip(names, quality[b])), "->", names[chosen[b]])
                         rte_ver.append(errs[chosen[b]][0])
                         rre_ver.append(errs[chosen[b]][1])
+                    if mi_bins is not None:
+                        print_mi(names, mi_values[b], mi_chosen[b])
+                        rte_mi.append(errs[mi_chosen[b]][0])
+                        rre_mi.append(errs[mi_chosen[b]][1])
                 if paint is not None or dense is not None:
                     last = data['refined_pose'] if radii is not None else data['pnp_pose']
                     if args.verify:
@@ -255,6 +272,8 @@ def main():
             print_recall(rte_ref, rre_ref, "Refined ")
         if args.verify:
             print_recall(rte_ver, rre_ver, "Verified ")
+        if mi_bins is not None:
+            print_recall(rte_mi, rre_mi, "MI-verified ")
 
 
 if __name__ == '__main__':

@@ -20,7 +20,7 @@
 //                     minimum is exact, so this equals (2S + 1)^2 atomics per row -- then coalesced stores of index / depth / attribute
 //                     maps; the gather attr[b, c, owner] (PI_PLANES planes in flight) is the only scattered read.
 // No floating-point atomic anywhere; every output element is a plain store by the thread that owns it.
-#include "cmr_project.h"
+#include "cmr_sample.h"
 
 namespace {
 
@@ -29,8 +29,6 @@ constexpr int PI_PLANES = 4;       // planes whose taps / gathers are in flight 
 constexpr int PI_MAX_C = 64;
 constexpr int PI_MAX_SPLAT = 4;
 constexpr unsigned long long PI_EMPTY = ~0ull;
-
-__device__ __forceinline__ int pi_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 __global__ __launch_bounds__(PI_THREADS) void pi_zero_kernel(int32_t* __restrict__ counts, int ncounts) {
   for (int c = blockIdx.x * PI_THREADS + threadIdx.x; c < ncounts; c += gridDim.x * PI_THREADS) counts[c] = 0;
@@ -61,20 +59,7 @@ __global__ __launch_bounds__(PI_THREADS) void pi_paint_kernel(const float* __res
     }
   }
   // tap offsets inside a plane, all inside the image: an unpainted row reads nothing
-  int o00 = 0, o01 = 0, o10 = 0, o11 = 0;
-  float fx = 0.f, fy = 0.f;
-  if (paint) {
-    if (BILINEAR) {
-      const float xf = floorf(p.u), yf = floorf(p.v);                    // in [-1, W - 1] / [-1, H - 1]: u >= -0.5 where in view
-      fx = __fsub_rn(p.u, xf);
-      fy = __fsub_rn(p.v, yf);
-      const int x0 = (int)xf, y0 = (int)yf;
-      const int xa = pi_clamp(x0, W - 1), xb = pi_clamp(x0 + 1, W - 1), ya = pi_clamp(y0, H - 1), yb = pi_clamp(y0 + 1, H - 1);
-      o00 = ya * W + xa; o01 = ya * W + xb; o10 = yb * W + xa; o11 = yb * W + xb;
-    } else {
-      o00 = p.cy * W + p.cx;
-    }
-  }
+  const CmrTaps tp = cmr_taps<BILINEAR>(p, paint, H, W);
   const int64_t plane = (int64_t)H * W;
   const float* img = image + (int64_t)b * C * plane;
   float* out = colors + (int64_t)b * C * N;
@@ -87,12 +72,12 @@ __global__ __launch_bounds__(PI_THREADS) void pi_paint_kernel(const float* __res
 #pragma unroll
       for (int k = 0; k < PI_PLANES; ++k) {
         const float* ip = img + (int64_t)(c + k < C ? c + k : C - 1) * plane;
-        t[k][0] = ip[o00];
-        if (BILINEAR) { t[k][1] = ip[o01]; t[k][2] = ip[o10]; t[k][3] = ip[o11]; }
+        t[k][0] = ip[tp.o00];
+        if (BILINEAR) { t[k][1] = ip[tp.o01]; t[k][2] = ip[tp.o10]; t[k][3] = ip[tp.o11]; }
       }
 #pragma unroll
       for (int k = 0; k < PI_PLANES; ++k)
-        val[k] = BILINEAR ? cmr_lerp(cmr_lerp(t[k][0], t[k][1], fx), cmr_lerp(t[k][2], t[k][3], fx), fy) : t[k][0];
+        val[k] = cmr_tap_value<BILINEAR>(tp, t[k][0], t[k][1], t[k][2], t[k][3]);
     }
     if (valid) {
 #pragma unroll
@@ -154,10 +139,10 @@ __global__ __launch_bounds__(PI_THREADS) void pi_resolve_kernel(const unsigned l
   for (int dy = -S; dy <= S; ++dy) {
     const int y = py + dy;
     const bool iny = y >= 0 && y < h;
-    const unsigned long long* line = kb + (int64_t)pi_clamp(y, h - 1) * w;
+    const unsigned long long* line = kb + (int64_t)cmr_clampi(y, h - 1) * w;
     unsigned long long k[2 * S + 1];
 #pragma unroll
-    for (int dx = -S; dx <= S; ++dx) k[dx + S] = line[pi_clamp(px + dx, w - 1)];
+    for (int dx = -S; dx <= S; ++dx) k[dx + S] = line[cmr_clampi(px + dx, w - 1)];
 #pragma unroll
     for (int dx = -S; dx <= S; ++dx) {
       const int x = px + dx;

@@ -114,12 +114,14 @@ def read_calib(root):
 class FrameDataset:
     """config: the attribute bag of cmr_agent_amd.config (dataset_root is overridden by `root`); mode 'train' | 'val' | 'test'.
     device: where the samples are produced (default: the current HIP device).  Sequences that are not on disk are skipped (the
-    reference lists 00-08 for training and 09-10 otherwise and fails on a missing folder)."""
+    reference lists 00-08 for training and 09-10 otherwise and fails on a missing folder).  with_intensity (port extension, DESIGN.md
+    4v; off by default, and then the sample dict is the reference's): the sample gains 'pc_intensity' float32 [N], the reflectance (row 3
+    of the cloud on disk) of the down-sampled points, in the order of 'pc'."""
 
     SEQUENCES = {"train": (0, 1, 2, 3, 4, 5, 6, 7, 8), "val": (9, 10), "test": (9, 10)}
     PC_SUBDIR = "voxel0.1-SNr0.6"
 
-    def __init__(self, root, config, mode, device=None, n_circle=512):
+    def __init__(self, root, config, mode, device=None, n_circle=512, with_intensity=False):
         if mode not in self.SEQUENCES:
             raise Exception("Invalid mode...")                                     # KittiDataset.py:162
         self.root, self.config, self.mode = root, config, mode
@@ -127,6 +129,7 @@ class FrameDataset:
         self.num_pt, self.num_node = config.num_pt, config.num_node
         self.img_H, self.img_W = config.cropped_img_H, config.cropped_img_W
         self.n_circle = n_circle
+        self.with_intensity = bool(with_intensity)
         self.amp_t = (config.P_Tx_amplitude, config.P_Ty_amplitude, config.P_Tz_amplitude)
         self.amp_r = (config.P_Rx_amplitude, config.P_Ry_amplitude, config.P_Rz_amplitude)
         self.calib = read_calib(root)
@@ -224,6 +227,10 @@ class FrameDataset:
                                num_node=self.num_node, n_circle=self.n_circle)
         out.pop("in_picture_count", None)
         out["img"] = img
+        if self.with_intensity:
+            if f["raw"].shape[0] < 4:
+                raise ValueError("frame %d: with_intensity needs a [4, n] cloud (x, y, z, reflectance), got %s" % (index, f["raw"].shape))
+            out["pc_intensity"] = torch.from_numpy(np.ascontiguousarray(f["raw"][3, f["choice"]])).to(dev)
         out["angles"] = torch.from_numpy(f["angles"])
         out["translation"] = torch.from_numpy(f["t"])
         self.last_draws = draws

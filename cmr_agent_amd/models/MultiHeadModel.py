@@ -440,6 +440,70 @@ class MultiHeadModel(Planned):
             data_batch['pose_quality'] = torch.where(full > 0, (1.0 - score / full.clamp(min=1e-300)).clamp(min=0.0), torch.zeros_like(score))
             data_batch['pose_best'] = _first_min(score)
 
+    def score_poses_mi(self, data_batch, poses, attr=None, image=None, K=None, mask=None, visible=None, bins=32, mode='nearest',
+                       attr_range=None, grey_range=(0.0, 1.0), min_in_view=0.5):
+        """Port extension: score candidate poses by the mutual information of a per-point attribute and the image's grey
+        values (ops.pose_mi; Pandey et al.) -- a second witness beside score_poses that reads the sensors, not the learned features.
+        poses: float32 [B, P, 4, 4], each mapping 'pc' into the camera frame.  attr: float32 [B, N], default 'pc_intensity' (the loader's
+        with_intensity=True); attr_range: (lo, hi), default the least and the greatest finite selected value of the batch (one device
+        reduction, no host synchronisation: the attribute is mapped onto [0, 1] on the device, (a - lo) / (hi - lo), and binned over the
+        unit range; a constant attribute is binned as it is over [0, 1]).  image: float32 [B, C, H, W] or [B, H, W], default
+        'img'; three or more planes become grey by 0.299 R + 0.587 G + 0.114 B, one plane is used as it is.  K, mask (default every point)
+        and visible are paint_points': K defaults to 'K' rescaled to the image, and visible=True or a dict of ops.visibility's radius /
+        rel_tol / abs_tol keeps the rows of `mask` that a z-buffer of the whole cloud under poses[:, 0] leaves visible, once per call.
+        Sets 'pose_mi' float64 [B, P] (higher is better), 'pose_mi_entropy' float64 [B, P, 3] = (H_a, H_g, H_ag), 'pose_mi_counts' int32
+        [B, P, 2] = (in view, counted), 'pose_nmi' float64 [B, P] = (H_a + H_g) / H_ag, 0 where H_ag = 0, and 'pose_mi_best' int64 [B] =
+        the highest 'pose_mi' among the ELIGIBLE poses, the lowest index on a tie.  A pose is eligible when it counts at least min_in_view
+        x the selected rows: the MI of few rows is spuriously high; if no pose is eligible all of them compete.  Not called by forward."""
+        vis_kw = _visible_kw(visible, "score_poses_mi")
+        if attr is None and 'pc_intensity' not in data_batch:
+            raise ValueError("score_poses_mi: no attribute: pass attr or load the frames with FrameDataset(..., with_intensity=True) ('pc_intensity')")
+        with torch.no_grad():
+            pc = data_batch['pc'].float().contiguous()
+            dev = pc.device
+            B, _, N = pc.shape
+            a = (data_batch['pc_intensity'] if attr is None else attr).to(dev).float().contiguous()
+            img = (data_batch['img'] if image is None else image).to(dev).float()
+            if img.dim() == 4:
+                img = img[:, 0] if img.shape[1] < 3 else 0.299 * img[:, 0] + 0.587 * img[:, 1] + 0.114 * img[:, 2]
+            grey = img.contiguous()
+            poses = poses.to(dev).float().contiguous()
+            sel = None if mask is None else mask.to(dev).contiguous()
+            if K is None or vis_kw is not None:
+                h, w = _geo_rows(data_batch)[1].shape[1:3]
+                Kg = data_batch['K'].to(dev).float()
+                Kg = (Kg if Kg.dim() == 3 else Kg.unsqueeze(0)).expand(B, 3, 3).contiguous()
+            if K is None:
+                H, W = grey.shape[1:]
+                K = Kg * torch.tensor([W / w, H / h, 1.0], dtype=torch.float32, device=dev).view(1, 3, 1)
+            else:
+                K = K.to(dev).float()
+                K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3)
+            if vis_kw is not None:
+                every = torch.ones(B, N, dtype=torch.bool, device=dev)
+                sel = ops.visibility(pc, poses[:, 0].contiguous(), Kg, h, w, every if sel is None else sel, **vis_kw)[0]
+            if attr_range is None:
+                ok = torch.isfinite(a) if sel is None else torch.isfinite(a) & (sel.view(B, N) != 0)
+                inf = torch.full_like(a, float("inf"))
+                ext = torch.stack([torch.where(ok, a, inf), torch.where(ok, -a, inf)]).amin(dim=(1, 2))      # (lo, -hi) in one reduction
+                lo, hi = ext[0], -ext[1]
+                flat = ~(lo < hi)                                            # nothing selected, or one value: a unit range
+                lo, hi = torch.where(flat, torch.zeros_like(lo), lo), torch.where(flat, torch.ones_like(hi), hi)
+                # the range stays on the device: the attribute is mapped onto [0, 1] there and the kernel bins the unit range
+                a = ((a - lo) / (hi - lo)).contiguous()
+                attr_range = (0.0, 1.0)
+            mi, ent, counts, selected, _ = ops.pose_mi(pc, a, grey, sel, poses, K.contiguous(), bins=bins, mode=mode, attr_range=attr_range,
+                                                       grey_range=grey_range)
+            data_batch['pose_mi'] = mi
+            data_batch['pose_mi_entropy'] = ent
+            data_batch['pose_mi_counts'] = counts
+            hag = ent[..., 2]
+            data_batch['pose_nmi'] = torch.where(hag > 0, (ent[..., 0] + ent[..., 1]) / torch.where(hag > 0, hag, torch.ones_like(hag)),
+                                                 torch.zeros_like(hag))
+            ok = counts[..., 1].double() >= float(min_in_view) * selected.double()[:, None]
+            ok = ok | ~ok.any(1, keepdim=True)
+            data_batch['pose_mi_best'] = _first_min(torch.where(ok, -mi, torch.full_like(mi, float("inf"))))
+
     def search_pose(self, data_batch, pose=None, levels=SEARCH_LEVELS, tau=0.8, mask=None, visible=None):
         """Port extension: derivative-free coarse-to-fine lattice search of the pose under ops.pose_score -- the
         counterpart without learned weights of the reference's 9^3-pose IterModel cost volume.  pose: float32 [B, 4, 4], default

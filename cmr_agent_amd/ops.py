@@ -1403,6 +1403,91 @@ def render_points(pts, pose, K, h, w, attr=None, mask=None, splat=0, fill=0.0):
     return index_map, depth_map, attr_map, counts
 
 
+POSE_MI_MAX_BINS = 64       # csrc/pose_mi.hip PMI_MAX_BINS
+POSE_MI_SLICE = 4096        # csrc/pose_mi.hip PMI_SLICE: rows per workgroup
+
+
+def pose_mi_chunk(bins):
+    """Poses per workgroup of cmr_pose_mi_f32 (csrc/pose_mi.hip pmi_chunk): the chunk's histograms take at most 32 KB of LDS."""
+    return min(8, (32 * 1024) // (bins * bins * 4))
+
+
+def _pose_mi_range(name, r, bins):
+    """(lo, hi) as the fp32 values the kernel takes, or a ValueError: both finite, lo < hi and bins / (hi - lo) finite in fp32."""
+    try:
+        lo, hi = (float(torch.tensor(float(v), dtype=f32)) for v in r)
+        ok = abs(lo) < float("inf") and abs(hi) < float("inf") and lo < hi and float(torch.tensor(bins / (hi - lo), dtype=f32)) < float("inf")
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError("pose_mi: %s must be (lo, hi), finite in float32 with lo < hi and bins / (hi - lo) finite, got %r" % (name, r))
+    return lo, hi
+
+
+def pose_mi(pts, attr, grey, mask, poses, K, bins=32, mode='nearest', attr_range=(0.0, 1.0), grey_range=(0.0, 1.0), want_hist=False):
+    """Mutual information of a per-point attribute and the image's grey values under P candidate poses per sample, in one sweep
+    (include/cmr_hip.h cmr_pose_mi_f32): a pose score that reads the sensors alone.  pts float32 [B, 3, N] (data['pc']),
+    attr float32 [B, N] (the LiDAR reflectance, data['pc_intensity']), grey float32 [B, H, W] (one plane, 1 <= H W <= 2^24), mask
+    [B, N] / [B*N] of bool / uint8 / int64 (None: every row), poses float32 [B, P, 4, 4] each mapping pts into the camera frame,
+    1 <= P <= POSE_SCORE_MAX_POSES, K float32 [B, 3, 3] for the H x W image, 2 <= bins <= POSE_MI_MAX_BINS, mode 'nearest' or
+    'bilinear' (ops.paint_points' sampling), attr_range / grey_range = (lo, hi) of the histogram's axes (values outside go to the end
+    bins).  Per pose a selected row is counted iff it is in view (ops.paint_points' predicate) and its attribute and grey value -- the
+    value ops.paint_points gives it at C = 1 -- are finite; bin = min(bins - 1, max(0, floor((x - lo) * scale))), scale = bins /
+    (hi - lo) rounded once to float32.
+    -> (mi float64 [B, P] = H_a + H_g - H_ag in nats, higher is better; entropy float64 [B, P, 3] = (H_a, H_g, H_ag); counts int32
+    [B, P, 2] = (in view, counted); selected int32 [B]; hist int32 [B, P, bins, bins] (attribute bin, grey bin) or None)."""
+    if not torch.is_tensor(pts) or pts.dim() != 3 or pts.shape[1] != 3:
+        raise ValueError("pose_mi: pts must be [B, 3, N], got %s" % (tuple(pts.shape) if torch.is_tensor(pts) else type(pts).__name__,))
+    B, _, N = pts.shape
+    if not all(torch.is_tensor(t) for t in (attr, grey, poses, K)):
+        raise ValueError("pose_mi: attr, grey, poses and K must be tensors")
+    if pts.dtype != f32 or attr.dtype != f32 or grey.dtype != f32 or poses.dtype != f32 or K.dtype != f32:
+        raise ValueError("pose_mi: pts, attr, grey, poses and K must be float32, got %s / %s / %s / %s / %s" % (
+            pts.dtype, attr.dtype, grey.dtype, poses.dtype, K.dtype))
+    if tuple(attr.shape) != (B, N):
+        raise ValueError("pose_mi: attr must be [%d, %d], got %s" % (B, N, tuple(attr.shape)))
+    if grey.dim() != 3 or grey.shape[0] != B:
+        raise ValueError("pose_mi: grey must be one plane per sample [%d, H, W], got %s" % (B, tuple(grey.shape)))
+    H, W = grey.shape[1:]
+    if poses.dim() != 4 or poses.shape[0] != B or tuple(poses.shape[2:]) != (4, 4):
+        raise ValueError("pose_mi: poses must be [%d, P, 4, 4], got %s" % (B, tuple(poses.shape)))
+    P = poses.shape[1]
+    if P < 1 or P > POSE_SCORE_MAX_POSES:
+        raise ValueError("pose_mi: need 1 <= P <= %d poses per sample, got %d" % (POSE_SCORE_MAX_POSES, P))
+    if tuple(K.shape) != (B, 3, 3):
+        raise ValueError("pose_mi: K must be [%d, 3, 3], got %s" % (B, tuple(K.shape)))
+    if B < 1 or B > GRID_Y_MAX or N < 1 or N > GRID_Y_MAX * 256 or H < 1 or W < 1 or H * W > 1 << 24:
+        raise ValueError("pose_mi: need 1 <= B <= %d, 1 <= N <= %d and an image of 1 .. 2^24 pixels, got B=%d N=%d image %d x %d" % (
+            GRID_Y_MAX, GRID_Y_MAX * 256, B, N, H, W))
+    if mask is not None and (not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N):
+        raise ValueError("pose_mi: mask must be None or bool / uint8 / int64 with %d elements, got %s %s" % (
+            B * N, getattr(mask, "dtype", type(mask).__name__), tuple(mask.shape) if torch.is_tensor(mask) else ""))
+    if not _is_int(bins) or not 2 <= bins <= POSE_MI_MAX_BINS:
+        raise ValueError("pose_mi: bins must be an integer in [2, %d], got %r" % (POSE_MI_MAX_BINS, bins))
+    bins = int(bins)
+    if not isinstance(mode, str) or mode not in _PAINT_MODES:
+        raise ValueError("pose_mi: mode must be 'nearest' or 'bilinear', got %r" % (mode,))
+    a_lo, a_hi = _pose_mi_range("attr_range", attr_range, bins)
+    g_lo, g_hi = _pose_mi_range("grey_range", grey_range, bins)
+    chunk = pose_mi_chunk(bins)
+    if ((N + POSE_MI_SLICE - 1) // POSE_MI_SLICE) * ((P + chunk - 1) // chunk) * B > 0x7fffffff:
+        raise ValueError("pose_mi: B=%d N=%d P=%d need more than 2^31 - 1 workgroups, score the poses or the samples in parts" % (B, N, P))
+    ts = [t for t in (pts, attr, grey, mask, poses, K) if t is not None]
+    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
+        raise ValueError("pose_mi: every tensor must be a contiguous tensor on the same GPU")
+    if mask is not None and mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    dev = pts.device
+    hist = torch.empty((B, P, bins, bins), dtype=torch.int32, device=dev)
+    counts = torch.empty((B, P, 2), dtype=torch.int32, device=dev)
+    selected = torch.empty((B,), dtype=torch.int32, device=dev)
+    entropy = torch.empty((B, P, 3), dtype=torch.float64, device=dev)
+    mi = torch.empty((B, P), dtype=torch.float64, device=dev)
+    _lib.call("cmr_pose_mi_f32", _p(pts), _p(attr), _p(mask), 1 if mask is None else mask.element_size(), _p(poses), P, _p(K), _p(grey), B, N,
+              H, W, _PAINT_MODES[mode], bins, a_lo, a_hi, g_lo, g_hi, _p(hist), _p(counts), _p(selected), _p(entropy), _p(mi), _stream())
+    return mi, entropy, counts, selected, hist if want_hist else None
+
+
 DENSIFY_MAX_RADIUS = 16     # csrc/densify.hip DN_MAX_R
 DENSIFY_MAX_C = 4           # csrc/densify.hip DN_MAX_C: attribute planes, and guide planes
 DENSIFY_TILE_W = 64         # csrc/densify.hip DN_TW x DN_TH: the pixels of one workgroup (tests put their shapes round these)

@@ -1,5 +1,5 @@
 """Command-line helpers shared by Test_Geo.py and Test_Agent.py: the round lists of --guided / --refine, the --visible flags, the --paint flags
-with the per-pair PLY output, the --dense-depth flags with the per-pair PFM output, and the closing recall block."""
+with the per-pair PLY output, the --dense-depth flags with the per-pair PFM output, the --verify-mi flags, and the closing recall block."""
 import numpy as np
 
 
@@ -131,6 +131,35 @@ def dense_pairs(model, data, pose, option, first_index):
         write_pfm(os.path.join(out_dir, "pair_%d_depth.pfm" % (first_index + b)), dense[b])
     c = data['dense_counts'].sum(0).cpu().tolist()
     print("dense", int(c[2]), "of", dense.shape[0] * dense.shape[1] * dense.shape[2], "from", int(c[0]))
+
+
+def add_mi_flags(ap, parent=None):
+    """--verify-mi and --mi-bins; `parent` is the flag --verify-mi needs beside it (None: free-standing)."""
+    ap.add_argument('--verify-mi', action='store_true', help="%swith --data-root: score the pair's candidate poses by the mutual information of the "
+                    "LiDAR reflectance and the image's grey values (no ground truth, no learned features) and report the best" % (
+                        "with %s, " % parent if parent else ""))
+    ap.add_argument('--mi-bins', type=int, default=None, metavar="NB", help="with --verify-mi: bins per axis of the joint histogram (default 32)")
+
+
+def mi_option(ap, args, max_bins, parent=None, parent_given=True):
+    """-> None without --verify-mi, else the bin count; ap.error on a misplaced or malformed flag."""
+    if not args.verify_mi:
+        if args.mi_bins is not None:
+            ap.error("--mi-bins belongs to --verify-mi")
+        return None
+    if parent is not None and not parent_given:
+        ap.error("--verify-mi scores the poses %s produces: give %s as well" % (parent, parent))
+    if not args.data_root:
+        ap.error("--verify-mi reads the reflectance of real frames: give --data-root as well (synthetic pairs have a noise image and no reflectance)")
+    bins = 32 if args.mi_bins is None else args.mi_bins
+    if not 2 <= bins <= max_bins:
+        ap.error("--mi-bins must be in [2, %d] (--verify-mi), got %d" % (max_bins, bins))
+    return bins
+
+
+def print_mi(names, values, chosen):
+    """The per-pair line of --verify-mi: mi <name>=<value> ... -> <chosen name>."""
+    print("mi", " ".join("%s=%.4f" % (n, v) for n, v in zip(names, values)), "->", names[chosen])
 
 
 def print_recall(rte, rre, prefix=""):

@@ -184,6 +184,13 @@ WORK = {
     "cmr_render_points_f32": lambda a: (40.0 * a["B"] * a["N"] + (2 * a["splat"] + 1) ** 2 * a["B"] * a["h"] * a["w"],
                                         a["B"] * a["N"] * (12 + a["mask_bytes"] + 8)
                                         + a["B"] * a["h"] * a["w"] * (8 + 8 * (2 * a["splat"] + 1) ** 2 + 8 + 8 * a["C"])),
+    # DESIGN.md 4v, every row taken as selected and counted under every pose: per (row, pose) ~40 FLOP of projection, 9 for the lerps when
+    # bilinear and 2 for the bin, and 1 or 4 gathered grey values of 4 B; the point, its attribute and mask are read once per chunk of
+    # min(8, 8192 / bins^2) poses; hist is filled, added to and read once (4 B a cell each)
+    "cmr_pose_mi_f32": lambda a: ((42.0 + 9.0 * a["mode"]) * a["B"] * a["N"] * a["P"],
+                                  a["B"] * a["N"] * ((16 + a["mask_bytes"]) * -(-a["P"] // min(8, 8192 // a["bins"] ** 2))
+                                                     + 4.0 * (1 + 3 * a["mode"]) * a["P"])
+                                  + 12.0 * a["B"] * a["P"] * a["bins"] ** 2),
     # DESIGN.md 4t, the data-independent ceiling: every tap of the (2R + 1)^2 window taken as a sample at (8 + 3 Cg + 2 C) FLOP (the
     # kernel visits the samples only, 2 - 15 % of that); depth, guide and the samples' attributes in, depth, conf and attributes out
     "cmr_densify_f32": lambda a: ((8.0 + 3.0 * a["Cg"] + 2.0 * a["C"]) * (2 * a["radius"] + 1) ** 2 * a["B"] * a["h"] * a["w"],

@@ -569,6 +569,38 @@ int cmr_render_points_f32(const float* pts, const void* mask, int mask_bytes, co
                           int B, int N, int h, int w, int splat, float fill, int32_t* index_map, float* depth_map, float* attr_map,
                           int32_t* counts, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+/* Pose scoring by mutual information (port extension; ops.pose_mi, MultiHeadModel.score_poses_mi, Test_Geo.py /
+ * Test_Agent.py --verify-mi): per candidate pose the joint histogram of a per-point attribute (the LiDAR reflectance) and the grey value
+ * of the pixel the point lands on, its entropies and the mutual information (Pandey et al., targetless camera-LiDAR calibration) -- a
+ * score that reads the sensors alone, not the geometric model's features.  pts f32 [B][3][N] (data['pc']), attr f32 [B][N], mask [B*N]
+ * with mask_bytes 1 or 8 (null: every row; mask_bytes is checked all the same), poses f32 [B][P][4][4] each mapping pts into the camera
+ * frame, 1 <= P <= 4096, K f32 [B][3][3] for the H x W image, grey f32 [B][H][W] (one plane, 1 <= H*W <= 2^24), mode 0 (nearest) or 1
+ * (bilinear) with cmr_paint_points_f32's meaning, 2 <= bins = nb <= 64, a_lo < a_hi and g_lo < g_hi all finite and such that
+ * nb / (hi - lo) is finite in fp32; hist 16-byte aligned; 1 <= B <= 65535, 1 <= N <= 65535 * 256.  Anything else is refused up front
+ * with CMR_EINVAL; nothing depends on the data.
+ * Per sample b, pose p and selected row n: IN VIEW is cmr_paint_points_f32's predicate under that pose (cmr_visibility_f32's cell), and
+ * the row's grey value g is, bit for bit, what cmr_paint_points_f32 returns for it at C = 1 in the same mode.  The row is COUNTED iff it
+ * is in view and attr[b][n] and g are both finite.  bin(x, lo, scale) = min(nb - 1, max(0, (int)floorf((x - lo) * scale))), the
+ * difference and the product two separately rounded fp32 operations (no fma), scale = nb / (hi - lo) computed in double and rounded
+ * once to fp32; values outside [lo, hi] go to the end bins.
+ *   hist int32 [B][P][nb][nb]  hist[ba][bg] = the counted rows with attribute bin ba and grey bin bg; always produced (it is the
+ *                              workspace);
+ *   counts int32 [B][P][2]   = {in view, counted};
+ *   selected int32 [B]         the selected rows;
+ *   entropy f64 [B][P][3]    = {H_a, H_g, H_ag} in nats, each H = ln n - (sum of c ln c) / n over the non-zero marginal / joint counts,
+ *                              n = the counted rows; the marginals are exact integer sums;
+ *   mi f64 [B][P]            = (H_a + H_g) - H_ag.  n = 0 gives zeros everywhere; a NaN pose counts nothing.
+ * Three launches on the stream whatever the data (fill of hist / counts / selected, histogram, entropies), no host round trip, no
+ * floating-point atomic: every sum that crosses threads is an integer (LDS and global integer atomics), so hist and counts do not
+ * depend on B, P, the chunking of the poses, the slicing of the rows or the order of the atomics -- two calls agree bit for bit, a pose
+ * scored alone equals the same pose in a batch of P, and a sample depends on its own rows only.  Order of the float64 sums of c ln c (it
+ * depends on nb alone): joint -- thread t of 256 adds the cells t, t + 256, ... of the flat index ba * nb + bg in increasing order from
+ * 0.0, then the 256 partial sums fold as a binary tree, v[t] += v[t + s] for s = 128, 64, ..., 1; each marginal -- its nb terms in
+ * increasing bin order from 0.0. */
+int cmr_pose_mi_f32(const float* pts, const float* attr, const void* mask, int mask_bytes, const float* poses, int P, const float* K,
+                    const float* grey, int B, int N, int H, int W, int mode, int bins, float a_lo, float a_hi, float g_lo, float g_hi,
+                    int32_t* hist, int32_t* counts, int32_t* selected, double* entropy, double* mi, hipStream_t stream);
+
 /* Image-guided densification of a sparse depth / attribute map (port extension; ops.densify, MultiHeadModel.dense_depth,
  * Test_Geo.py / Test_Agent.py --dense-depth): the joint bilateral filter as a normalised convolution.  All maps contiguous.
  *   depth f32 [B][h][w]: a pixel is a SAMPLE iff its depth is finite and > 0 (+inf, as cmr_render_points_f32 and cmr_visibility_f32 write
