@@ -322,7 +322,9 @@ __global__ __launch_bounds__(256) void nearest_kernel(const float* __restrict__ 
 }
 
 // three nearest candidates per query (ascending distance) + normalised inverse-distance weights
-// (PointNetFeaturePropagation, pointnet_util.py:287-295): idx int32 GLOBAL rows [B*Nq,3], w [B*Nq,3]
+// (PointNetFeaturePropagation, pointnet_util.py:287-295): idx int32 GLOBAL rows [B*Nq,3], w [B*Nq,3].  With fewer than three candidates
+// (the reference's dists[:, :, :3] is then narrower) a missing neighbour keeps its distance of infinity: weight exactly 0, index = the
+// batch element's first row.
 __global__ __launch_bounds__(256) void three_nn_kernel(const float* __restrict__ q4, const float* __restrict__ c4,
                                                        int32_t* __restrict__ idx, float* __restrict__ wgt, int Nq, int Nc) {
   __shared__ __attribute__((aligned(16))) float tile[1024 * 4];
@@ -940,7 +942,7 @@ extern "C" int cmr_nearest_f32(const float* q4, const float* c4, int32_t* out_gl
 
 extern "C" int cmr_three_nn_f32(const float* q4, const float* c4, int32_t* idx, float* wgt, int B, int Nq, int Nc,
                                 hipStream_t stream) {
-  CMR_REQUIRE(q4 && c4 && idx && wgt && B > 0 && B <= 65535 && Nq > 0 && Nc >= 3);
+  CMR_REQUIRE(q4 && c4 && idx && wgt && B > 0 && B <= 65535 && Nq > 0 && Nc > 0);
   hipLaunchKernelGGL(three_nn_kernel, dim3((Nq + 255) / 256, B), dim3(256), 0, stream, q4, c4, idx, wgt, Nq, Nc);
   return cmr_launch_status();
 }

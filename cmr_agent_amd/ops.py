@@ -706,27 +706,37 @@ def vecattn_front(q, pa4, pb4, ib, d0, d2, g0, g2, rows, iq=None, divq=1, ia=Non
     return a, vp
 
 
-def vecattn_front_train(k, v, q, pa4, pb4, ib, d0, d2, g0, g2, iq=None, divq=1, ia=None, diva=1, ikv=None):
+def _front_outs(outs, n, rows, device):
+    if outs is None:
+        return [torch.empty((rows, 64), dtype=f32, device=device) for _ in range(n)]
+    if len(outs) != n or any(o.dtype != f32 or tuple(o.shape) != (rows, 64) or not o.is_contiguous() or o.device != device for o in outs):
+        raise ValueError("vecattn_front_*_train: outs must be %d contiguous float32 [%d, 64] tensors on %s" % (n, rows, device))
+    return list(outs)
+
+
+def vecattn_front_train(k, v, q, pa4, pb4, ib, d0, d2, g0, g2, iq=None, divq=1, ia=None, diva=1, ikv=None, outs=None):
     """Training forward of the vector-attention front in one launch -> (a, vp, hd, t, g1), all [rows, 64] (see cmr_vecattn_front_train_f32),
-    or False when rows is not a multiple of 32.  ikv: k and v are per-node tables, row ikv[r] of both is the pair's."""
+    or False when rows is not a multiple of 32.  ikv: k and v are per-node tables, row ikv[r] of both is the pair's.  outs: five contiguous
+    [rows, 64] buffers to write instead of fresh ones."""
     _rows(k), _rows(v), _rows(q)
     rows = ib.numel()                                       # one row per (point, node) / (node, neighbour) pair
     if rows % 32 or k.shape[1] != 64 or v.shape[1] != 64 or q.shape[1] != 64 or (ikv is None and (k.shape[0] != rows or v.shape[0] != rows)):
         return False
-    outs = [torch.empty((rows, 64), dtype=f32, device=k.device) for _ in range(5)]
+    outs = _front_outs(outs, 5, rows, k.device)
     _lib.call("cmr_vecattn_front_train_f32", _p(k), _ld(k), _p(v), _ld(v), _p(_i32(ikv)), _p(q), _ld(q), _p(_i32(iq)), int(divq), _p(pa4), _p(_i32(ia)),
               int(diva), _p(pb4), _p(_i32(ib)), _p(d0[0]), _p(d0[1]), _p(d2[0]), _p(d2[1]), _p(g0[0]), _p(g0[1]), _p(g2[0]), _p(g2[1]),
               *[_p(o) for o in outs], rows, _stream())
     return tuple(outs)
 
 
-def vecattn_front_kv_train(feat, fc1, wk, wv, q, pa4, pb4, ib, d0, d2, g0, g2, iq=None, divq=1, ia=None, diva=1):
-    """... with x = fc1(feat), k = Wk x, v = Wv x computed inside -> (a, vp, hd, t, g1, x), or False when rows is not a multiple of 32."""
+def vecattn_front_kv_train(feat, fc1, wk, wv, q, pa4, pb4, ib, d0, d2, g0, g2, iq=None, divq=1, ia=None, diva=1, outs=None):
+    """... with x = fc1(feat), k = Wk x, v = Wv x computed inside -> (a, vp, hd, t, g1, x), or False when rows is not a multiple of 32.
+    outs: six contiguous [rows, 64] buffers to write instead of fresh ones."""
     _rows(feat), _rows(q)
     rows = feat.shape[0]
     if rows % 32 or feat.shape[1] != 64 or q.shape[1] != 64 or tuple(wk.shape) != (64, 64) or tuple(wv.shape) != (64, 64) or not (wk.is_contiguous() and wv.is_contiguous()):
         return False
-    outs = [torch.empty((rows, 64), dtype=f32, device=feat.device) for _ in range(6)]
+    outs = _front_outs(outs, 6, rows, feat.device)
     _lib.call("cmr_vecattn_front_kv_train_f32", _p(feat), _ld(feat), _p(fc1[0]), _p(fc1[1]), _p(wk), _p(wv), _p(q), _ld(q), _p(_i32(iq)), int(divq),
               _p(pa4), _p(_i32(ia)), int(diva), _p(pb4), _p(_i32(ib)), _p(d0[0]), _p(d0[1]), _p(d2[0]), _p(d2[1]), _p(g0[0]), _p(g0[1]),
               _p(g2[0]), _p(g2[1]), *[_p(o) for o in outs], rows, _stream())
@@ -2175,8 +2185,12 @@ def la_bwd(qf, kf, v, kvsum, dmsg, B, L, S, eps, dqf=None, dkf=None, dv=None, ac
     return dqf, dkf, dv
 
 
-def segment_softmax_bwd(attn, vp, dout, nseg, scale, order=None, offsets=None, fixed_len=0):
-    dattn, dvp = torch.empty_like(attn), torch.empty_like(vp)
+def segment_softmax_bwd(attn, vp, dout, nseg, scale, order=None, offsets=None, fixed_len=0, covers_all_rows=False):
+    """Backward of segment_softmax -> (d attn, d vp), both [rows, 64].  The kernel writes the rows the segments list; a row listed in no
+    segment (csr_build drops keys that point outside their batch element's segments) receives zero gradient.  covers_all_rows: the caller
+    vouches that the segments list every row, and the two buffers are not zero-filled first."""
+    alloc = torch.empty_like if covers_all_rows else torch.zeros_like
+    dattn, dvp = alloc(attn), alloc(vp)
     _lib.call("cmr_segment_softmax_bwd_f32", _p(attn), _p(vp), _p(_i32(order)), _p(_i32(offsets)), fixed_len, float(scale), _p(dout), _p(dattn),
               _p(dvp), nseg, _stream(), work_extra={"_rows": attn.shape[0]})
     return dattn, dvp

@@ -688,7 +688,8 @@ class Tape:
         def bwd():
             if y.g is None:
                 return
-            da, dv = ops.segment_softmax_bwd(attn.v, vp.v, y.g, nseg, scale, order=order, offsets=offsets, fixed_len=fixed_len)
+            # (every row of the map belongs to a segment: a point has a node, a neighbourhood its 16 rows -- no zero fill of the two maps)
+            da, dv = ops.segment_softmax_bwd(attn.v, vp.v, y.g, nseg, scale, order=order, offsets=offsets, fixed_len=fixed_len, covers_all_rows=True)
             self.give(attn, da, owned=True)
             self.give(vp, dv, owned=True)
         self.nodes.append(bwd)

@@ -9,6 +9,7 @@ touched the device is never replaced or forked here -- the child is a fresh inte
 
 This module imports neither torch nor the HIP library.
 """
+import json
 import os
 import socket
 import subprocess
@@ -44,6 +45,32 @@ def is_rank_process():
     return "WORLD_SIZE" in os.environ and "RANK" in os.environ
 
 
+def json_parts(line):
+    """-> (the JSON result object in a line of the ranks' output or None, the rest of the line).  The ranks share one pipe, and a rank may
+    write a line and its newline separately: another rank's text then lands on the same line, in front of or behind rank 0's result.  Only
+    a non-empty object that opens the line or closes it counts; braces anywhere else in a rank's chatter stay chatter."""
+    dec = json.JSONDecoder()
+    s = line.strip()
+    if s.startswith("{"):
+        try:
+            obj, end = dec.raw_decode(s)
+            if obj:
+                return s[:end], s[end:]
+        except ValueError:
+            pass
+    if s.endswith("}"):
+        j = s.find("{")
+        while j >= 0:
+            try:
+                obj, end = dec.raw_decode(s, j)
+                if obj and end == len(s):
+                    return s[j:], s[:j]
+            except ValueError:
+                pass
+            j = s.find("{", j + 1)
+    return None, line
+
+
 def spawn_ranks_if_needed(script, argv=None):
     """Call first thing in an entry point.  Returns normally in a rank process (or when --gpus is 1); otherwise runs the
     ranks as a child and exits with its return code."""
@@ -57,11 +84,11 @@ def spawn_ranks_if_needed(script, argv=None):
     cmd = rank_command(os.path.abspath(script), argv, gpus)
     proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, env=env, text=True, bufsize=1)
     for line in proc.stdout:                                 # rank 0's JSON line(s) -> stdout, anything else -> stderr
-        s = line.strip()
-        if s.startswith("{") and s.endswith("}"):
-            sys.stdout.write(line)
+        obj, rest = json_parts(line.rstrip("\n"))
+        if obj is not None:
+            sys.stdout.write(obj + "\n")
             sys.stdout.flush()
-        else:
-            sys.stderr.write(line)
+        if rest.strip() or obj is None:
+            sys.stderr.write(rest + "\n")
             sys.stderr.flush()
     sys.exit(proc.wait())

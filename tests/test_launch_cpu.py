@@ -47,6 +47,17 @@ def test_requested_gpus_and_command():
     assert cmd[-5:] == ["/x/bench.py", "--gpus", "2", "--steps", "5"]
 
 
+def test_json_line_is_found_among_another_ranks_text():
+    """ranks share the pipe: the result object with another rank's text in front of or behind it still reaches stdout, alone; braces
+    elsewhere in a line, an empty object or an object in the middle of a line are chatter"""
+    j = '{"world": 8, "argv": ["--gpus", "8"], "config": {"a": "x}y"}}'
+    assert launch.json_parts(j) == (j, "")
+    assert launch.json_parts(j + "rank 7 chatter") == (j, "rank 7 chatter")
+    assert launch.json_parts("rank 7 chatter" + j) == (j, "rank 7 chatter")
+    for chatter in ("a {brace} and {", "", "warning: {}", "{} was empty", 'logged {"lr": 0.1} here', "rank 3 chatterrank 2 chatter"):
+        assert launch.json_parts(chatter) == (None, chatter)
+
+
 def _run(tmp_path, extra, gpus=2):
     script = tmp_path / "ranks.py"
     script.write_text(RANK_SCRIPT % ROOT)
