@@ -47,7 +47,11 @@ under the same pose --paint uses (cmr_render_points_f32), the sparse depth is fi
 (cmr_densify_f32; window radius R, default 8; range sigma S, default 0.1) and DIR/pair_<index>_depth.pfm holds the dense map (PFM "Pf",
 little-endian, scale -1.0, rows bottom to top, unfilled pixels 0); --dense-visible renders only the points a z-buffer of the cloud under
 that pose leaves visible.  Each pair prints one extra line "dense <filled> of <pixels> from <samples>".  Without the flag the output is
-unchanged."""
+unchanged.
+
+--from-raw (with --data-root): a sequence whose prepared cloud folder is missing is read from its raw scans
+(<seq>/velodyne/*.bin) and voxel-downsampled on the device as it is loaded (FrameDataset(..., from_raw=True));
+`python -m cmr_agent_amd.dataset.prepare --root DIR` writes the folder once instead.  Without the flag nothing changes."""
 import argparse
 import json
 import os
@@ -68,8 +72,9 @@ from cmr_agent_amd.environment import environment as env  # noqa: E402
 from cmr_agent_amd.models import CMRAgent, MultiHeadModel  # noqa: E402
 from cmr_agent_amd.utils import hashfill, synthetic  # noqa: E402
 from cmr_agent_amd.utils.checkpoint import load_checked  # noqa: E402
-from cmr_agent_amd.utils.evalcli import (add_dense_flags, add_mi_flags, add_paint_flags, add_visible_flags, dense_option, dense_pairs,  # noqa: E402
-                                         guided_rounds, mi_option, paint_option, paint_pairs, print_mi, print_recall, print_visible, visible_option)
+from cmr_agent_amd.utils.evalcli import (add_dense_flags, add_mi_flags, add_paint_flags, add_raw_flag, add_visible_flags, dense_option,  # noqa: E402
+                                         dense_pairs, guided_rounds, mi_option, paint_option, paint_pairs, print_mi, print_recall, print_visible,
+                                         raw_option, visible_option)
 
 
 def get_P_diff(P_pred, P_gt):
@@ -99,10 +104,12 @@ def main():
     add_paint_flags(ap)
     add_dense_flags(ap)
     add_mi_flags(ap)
+    add_raw_flag(ap)
     args = ap.parse_args()
     paint = paint_option(ap, args)
     dense = dense_option(ap, args, ops.DENSIFY_MAX_RADIUS)
     mi_bins = mi_option(ap, args, ops.POSE_MI_MAX_BINS)
+    raw_kw = raw_option(ap, args)
     if args.subpixel and args.refine is None:
         ap.error("--subpixel belongs to --refine")
     radii = thrs = None
@@ -131,7 +138,7 @@ def main():
         if args.data_root:
             from cmr_agent_amd.dataset import FrameDataset, FrameLoader
             import itertools
-            frames = itertools.islice(iter(FrameLoader(FrameDataset(args.data_root, config, 'test', device=dev, **({} if mi_bins is None else dict(with_intensity=True))), 1, shuffle=False)), args.pairs)
+            frames = itertools.islice(iter(FrameLoader(FrameDataset(args.data_root, config, 'test', device=dev, **({} if mi_bins is None else dict(with_intensity=True)), **raw_kw), 1, shuffle=False)), args.pairs)
         else:
             frames = (synthetic.make_batch(1, config.num_pt, config.cropped_img_H, config.cropped_img_W, config.num_node,
                                            hip_fps(dev), hip_nearest(dev), seed=config.seed + i, n_circle=16, device=dev) for i in range(args.pairs))

@@ -66,6 +66,10 @@ by the image (cmr_densify_f32; window radius R, default 8; range sigma S, defaul
 cloud under that pose leaves visible.  Each batch prints one extra line "dense <filled> of <pixels> from <samples>".  Without the flag the
 output is unchanged.
 
+--from-raw (with --data-root): a sequence whose prepared cloud folder is missing is read from its raw scans
+(<seq>/velodyne/*.bin) and voxel-downsampled on the device as it is loaded (FrameDataset(..., from_raw=True));
+`python -m cmr_agent_amd.dataset.prepare --root DIR` writes the folder once instead.  Without the flag nothing changes.
+
 Pairs come from the synthetic generator (cmr_agent_amd.utils.synthetic) unless --data-root names a dataset in the reference's layout
 (its 'test' split), and the weights are the deterministic hash fill unless --geo-ckpt points at a reference-format state_dict."""
 import argparse
@@ -88,8 +92,9 @@ from cmr_agent_amd.models import MultiHeadModel  # noqa: E402
 from cmr_agent_amd.models.MultiHeadModel import match_features  # noqa: E402
 from cmr_agent_amd.utils import hashfill, synthetic  # noqa: E402
 from cmr_agent_amd.utils.checkpoint import load_checked  # noqa: E402
-from cmr_agent_amd.utils.evalcli import (add_dense_flags, add_mi_flags, add_paint_flags, add_visible_flags, dense_option, dense_pairs,  # noqa: E402
-                                         guided_rounds, mi_option, paint_option, paint_pairs, print_mi, print_recall, print_visible, visible_option)
+from cmr_agent_amd.utils.evalcli import (add_dense_flags, add_mi_flags, add_paint_flags, add_raw_flag, add_visible_flags, dense_option,  # noqa: E402
+                                         dense_pairs, guided_rounds, mi_option, paint_option, paint_pairs, print_mi, print_recall, print_visible,
+                                         raw_option, visible_option)
 
 
 def _ratios(counts):
@@ -131,10 +136,12 @@ def main():
     add_paint_flags(ap, "--pnp")
     add_dense_flags(ap, "--pnp")
     add_mi_flags(ap, "--pnp")
+    add_raw_flag(ap)
     args = ap.parse_args()
     paint = paint_option(ap, args, "--pnp", args.pnp)
     dense = dense_option(ap, args, ops.DENSIFY_MAX_RADIUS, "--pnp", args.pnp)
     mi_bins = mi_option(ap, args, ops.POSE_MI_MAX_BINS, "--pnp", args.pnp)
+    raw_kw = raw_option(ap, args)
     if args.verify and not args.pnp:
         ap.error("--verify scores the PnP pose (and the --guided one): give --pnp as well")
     filtered = args.mutual or args.ratio is not None
@@ -186,7 +193,7 @@ def main():
     with torch.no_grad():
         if args.data_root:
             from cmr_agent_amd.dataset import FrameDataset, FrameLoader
-            batches = itertools.islice(iter(FrameLoader(FrameDataset(args.data_root, config, 'test', device=dev, **({} if mi_bins is None else dict(with_intensity=True))), bs, shuffle=False)), nbatch)
+            batches = itertools.islice(iter(FrameLoader(FrameDataset(args.data_root, config, 'test', device=dev, **({} if mi_bins is None else dict(with_intensity=True)), **raw_kw), bs, shuffle=False)), nbatch)
         else:
             batches = (synthetic.make_batch(bs, config.num_pt, config.cropped_img_H, config.cropped_img_W, config.num_node, hip_fps(dev),
                                             hip_nearest(dev), seed=config.seed + i, n_circle=16, device=dev) for i in range(nbatch))

@@ -116,12 +116,14 @@ class FrameDataset:
     device: where the samples are produced (default: the current HIP device).  Sequences that are not on disk are skipped (the
     reference lists 00-08 for training and 09-10 otherwise and fails on a missing folder).  with_intensity (port extension, DESIGN.md
     4v; off by default, and then the sample dict is the reference's): the sample gains 'pc_intensity' float32 [N], the reflectance (row 3
-    of the cloud on disk) of the down-sampled points, in the order of 'pc'."""
+    of the cloud on disk) of the down-sampled points, in the order of 'pc'.  from_raw (port extension; off by default, and then
+    nothing changes): a sequence that lacks the prepared cloud folder but has the raw scans (<seq>/velodyne/<i>.bin) is listed too, and its
+    frames are prepared on the fly (dataset.prepare.prepare_cloud without normals: the voxel-grid downsample, on the device)."""
 
     SEQUENCES = {"train": (0, 1, 2, 3, 4, 5, 6, 7, 8), "val": (9, 10), "test": (9, 10)}
     PC_SUBDIR = "voxel0.1-SNr0.6"
 
-    def __init__(self, root, config, mode, device=None, n_circle=512, with_intensity=False):
+    def __init__(self, root, config, mode, device=None, n_circle=512, with_intensity=False, from_raw=False):
         if mode not in self.SEQUENCES:
             raise Exception("Invalid mode...")                                     # KittiDataset.py:162
         self.root, self.config, self.mode = root, config, mode
@@ -130,6 +132,7 @@ class FrameDataset:
         self.img_H, self.img_W = config.cropped_img_H, config.cropped_img_W
         self.n_circle = n_circle
         self.with_intensity = bool(with_intensity)
+        self.from_raw = bool(from_raw)
         self.amp_t = (config.P_Tx_amplitude, config.P_Ty_amplitude, config.P_Tz_amplitude)
         self.amp_r = (config.P_Rx_amplitude, config.P_Ry_amplitude, config.P_Rz_amplitude)
         self.calib = read_calib(root)
@@ -144,6 +147,8 @@ class FrameDataset:
             img2 = os.path.join(self.root, cfg.data_color, "sequences", "%02d" % seq, "image_2")
             img3 = os.path.join(self.root, cfg.data_color, "sequences", "%02d" % seq, "image_3")
             pcs = os.path.join(self.root, cfg.data_velodyne, "sequences", "%02d" % seq, self.PC_SUBDIR)
+            if self.from_raw and not os.path.isdir(pcs) and os.path.isdir(os.path.join(os.path.dirname(pcs), "velodyne")):
+                pcs = os.path.join(os.path.dirname(pcs), "velodyne")                # raw scans: read_frame prepares them
             if not (os.path.isdir(img2) and os.path.isdir(pcs)) or seq not in self.calib:
                 continue
             num = len(os.listdir(img2))
@@ -173,7 +178,11 @@ class FrameDataset:
         -> dict(img uint8 [H, W, 3], raw float32 [>=3, n], P_Tr, K (1/4 scale of the crop), crop, P_random, angles, t, choice, cand, fps_start)."""
         img_folder, pc_folder, seq, i, key = self.frames[index]
         img = np.load(os.path.join(img_folder, "%06d.npy" % i))
-        raw = np.ascontiguousarray(np.load(os.path.join(pc_folder, "%06d.npy" % i)), dtype=np.float32)
+        if os.path.basename(pc_folder) == "velodyne":                                # from_raw: the scan as KITTI ships it
+            from .prepare import prepare_cloud, read_velodyne_bin
+            raw = prepare_cloud(read_velodyne_bin(os.path.join(pc_folder, "%06d.bin" % i)), normals=False, device=self.device).cpu().numpy()
+        else:
+            raw = np.ascontiguousarray(np.load(os.path.join(pc_folder, "%06d.npy" % i)), dtype=np.float32)
         P_Tr = np.dot(self.calib[seq][key], self.calib[seq]["Tr"])                  # :273-274
         choice = self.downsample_choice(raw.shape[1])                              # :284
         rh, rw = int(round(img.shape[0] * 0.5)), int(round(img.shape[1] * 0.5))     # :290-293

@@ -1,0 +1,121 @@
+"""Raw KITTI odometry scans -> the cloud files the loader reads.
+
+    <root>/<data_velodyne>/sequences/<seq>/velodyne/<i>.bin               raw scan, float32 [N, 4]: x, y, z, reflectance
+    <root>/<data_velodyne>/sequences/<seq>/voxel0.1-SNr0.6/<i>.npy        float32 [7, n]: x, y, z, reflectance, nx, ny, nz
+
+The folder name is the recipe: a voxel-grid downsample at 0.1 m (every occupied voxel becomes the mean of its points, the reflectance
+averaged with them), then surface normals from the neighbours within 0.6 m on the downsampled cloud, turned towards the sensor (the origin
+of the velodyne frame).  The reference inherits such files from an Open3D script of its lineage (DeepI2P / CorrI2P) and holds no code that
+makes them; here the two steps are `ops.voxel_downsample` and `ops.point_normals` (HIP, csrc/cloud_prepare.hip), one scan per call.
+
+Differences from Open3D that a reader of the files should know: the normals use EVERY neighbour within the radius (Open3D's hybrid search
+stops at max_nn nearest), and rows come out in ascending voxel key, not in Open3D's hash order.  Nothing in this project reads rows 4-6;
+the loaders read rows 0-3.
+
+    python -m cmr_agent_amd.dataset.prepare --root DIR [--sequences 9,10 --voxel 0.1 --sn-radius 0.6 --no-normals --overwrite]
+"""
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from .. import ops
+
+
+def read_velodyne_bin(path):
+    """KITTI's velodyne/<i>.bin (float32 [N, 4]: x, y, z, reflectance) -> float32 [4, N]."""
+    raw = np.fromfile(path, dtype=np.float32)
+    if raw.size % 4:
+        raise ValueError("%s: %d floats are not rows of x, y, z, reflectance" % (path, raw.size))
+    return np.ascontiguousarray(raw.reshape(-1, 4).T)
+
+
+def subdir(voxel=0.1, sn_radius=0.6):
+    """The folder name of a recipe: 'voxel0.1-SNr0.6' for the defaults (= FrameDataset.PC_SUBDIR)."""
+    return "voxel%s-SNr%s" % (format(float(voxel), "g"), format(float(sn_radius), "g"))
+
+
+def prepare_cloud(raw, voxel=0.1, sn_radius=0.6, normals=True, device=None):
+    """raw: float32 [4, N] (numpy or tensor; x, y, z, reflectance, velodyne frame) -> device float32 [7, n]: the voxel means of x, y, z and
+    reflectance in ascending voxel key and the normals of the downsampled cloud, viewpoint at the sensor origin; [4, n] with normals=False."""
+    raw = torch.as_tensor(raw)
+    if raw.dtype != torch.float32 or raw.dim() != 2 or raw.shape[0] != 4:
+        raise ValueError("raw must be float32 [4, N] (x, y, z, reflectance), got %s %s" % (raw.dtype, tuple(raw.shape)))
+    if device is None:
+        device = raw.device if raw.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    rows = raw.to(device).t().contiguous()
+    down = ops.voxel_downsample(rows[:, 0:3], rows[:, 3:4], voxel=voxel)
+    parts = [down.points, down.attr]
+    if normals:
+        parts.append(ops.point_normals(down.points, radius=sn_radius, viewpoint=(0.0, 0.0, 0.0)).normals)
+    return torch.cat(parts, dim=1).t().contiguous()
+
+
+def prepare_sequence(velodyne_dir, out_dir, voxel=0.1, sn_radius=0.6, normals=True, overwrite=False, device=None):
+    """Every <velodyne_dir>/<i>.bin -> <out_dir>/<i>.npy (%06d, the loader's names).  Existing files are kept unless `overwrite`.
+    -> (frames written, raw points, kept points)."""
+    os.makedirs(out_dir, exist_ok=True)
+    frames = raw_points = kept_points = 0
+    for name in sorted(os.listdir(velodyne_dir)):
+        stem, ext = os.path.splitext(name)
+        if ext != ".bin" or not stem.isdigit():
+            continue
+        out = os.path.join(out_dir, "%06d.npy" % int(stem))
+        if os.path.exists(out) and not overwrite:
+            continue
+        raw = read_velodyne_bin(os.path.join(velodyne_dir, name))
+        cloud = prepare_cloud(raw, voxel, sn_radius, normals, device).cpu().numpy()
+        np.save(out, cloud)
+        frames, raw_points, kept_points = frames + 1, raw_points + raw.shape[1], kept_points + cloud.shape[1]
+    return frames, raw_points, kept_points
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m cmr_agent_amd.dataset.prepare", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--root", required=True, help="dataset root: <root>/<data_velodyne>/sequences/<seq>/velodyne/*.bin is read")
+    ap.add_argument("--data-velodyne", default=None, help="the velodyne folder under --root (default: the KITTI configuration's data_velodyne)")
+    ap.add_argument("--sequences", default=None, help="comma separated sequence numbers (default: every sequence that has a velodyne folder)")
+    ap.add_argument("--voxel", type=float, default=0.1, help="voxel size in metres (default 0.1)")
+    ap.add_argument("--sn-radius", type=float, default=0.6, help="neighbourhood radius of the normals in metres (default 0.6)")
+    ap.add_argument("--no-normals", action="store_true", help="write [4, n] files (x, y, z, reflectance): what the loaders read")
+    ap.add_argument("--overwrite", action="store_true", help="write files that exist again (default: keep them)")
+    args = ap.parse_args(argv)
+    if not (0.0 < args.voxel < float("inf")):
+        ap.error("--voxel must be finite and > 0, got %r" % (args.voxel,))
+    if not (0.0 < args.sn_radius < float("inf")):
+        ap.error("--sn-radius must be finite and > 0, got %r" % (args.sn_radius,))
+    if args.sequences is not None:
+        try:
+            args.sequences = tuple(int(s) for s in args.sequences.split(","))
+        except ValueError:
+            ap.error("--sequences must be integers, comma separated")
+        if not all(0 <= s <= 99 for s in args.sequences):
+            ap.error("--sequences must lie in [0, 99]")
+    if args.data_velodyne is None:
+        from ..config.KittiConfig import KittiConfiguration
+        args.data_velodyne = KittiConfiguration(None).data_velodyne
+    return ap, args
+
+
+def main(argv=None, device=None):
+    ap, args = parse_args(argv)
+    base = os.path.join(args.root, args.data_velodyne, "sequences")
+    if not os.path.isdir(base):
+        ap.error("%s is not a directory" % base)
+    seqs = args.sequences
+    if seqs is None:
+        seqs = tuple(int(s) for s in sorted(os.listdir(base)) if s.isdigit() and os.path.isdir(os.path.join(base, s, "velodyne")))
+    for seq in seqs:
+        src = os.path.join(base, "%02d" % seq, "velodyne")
+        if not os.path.isdir(src):
+            ap.error("sequence %02d has no velodyne folder under %s" % (seq, base))
+    for seq in seqs:
+        src = os.path.join(base, "%02d" % seq, "velodyne")
+        dst = os.path.join(base, "%02d" % seq, subdir(args.voxel, args.sn_radius))
+        frames, raw, kept = prepare_sequence(src, dst, args.voxel, args.sn_radius, not args.no_normals, args.overwrite, device)
+        print("sequence %02d: prepared %d frames, %d -> %d points" % (seq, frames, raw, kept))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,9 +1,11 @@
 """Tensor-level wrappers over the C ABI (include/cmr_hip.h).  PyTorch is used for device
 memory and the current HIP stream only; every computation is a HIP kernel.  Arguments are
 2-D row views ([rows, C], unit inner stride, arbitrary row stride) unless stated otherwise."""
+import collections
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -2507,3 +2509,155 @@ def la_proj_bwd(problems):
         desc += d
     arr = np.asarray(desc, dtype=np.int64)
     _lib.call("cmr_la_proj_bwd_f32", arr.ctypes.data, len(problems), _stream(), work_extra={"_rows": sum(pr["rows"] * len(pr["terms"]) for pr in problems)})
+
+
+# ---- raw scan -> prepared cloud (csrc/cloud_prepare.hip) ----------------------------------------------------------------------
+CLOUD_CELL_LIMIT = 1 << 21          # cells per axis a grid key holds (cz << 42 | cy << 21 | cx)
+CLOUD_MAX_ROWS = (1 << 31) - 1      # the CSR of cmr_segment_reduce_f32 is int32
+
+
+class VoxelCloud(collections.namedtuple("VoxelCloud", "points attr count inverse dropped origin")):
+    """voxel_downsample's result: points [n, 3], attr [n, C] (None without attr), count int32 [n], inverse int64 [N] (None unless asked
+    for), dropped = the number of input rows with a non-finite coordinate, origin = the grid's origin as three python floats (fp32 values)."""
+
+
+class PointNormals(collections.namedtuple("PointNormals", "normals count eigenvalues")):
+    """point_normals' result: normals [n, 3], count int32 [n] (neighbours within the radius, the row itself included), eigenvalues [n, 3]
+    ascending (None unless asked for)."""
+
+
+def _cloud_scalar(value, name):
+    value = float(value)
+    with np.errstate(over="ignore", under="ignore"):
+        v32 = float(np.float32(value))
+    if not (0.0 < value < float("inf")) or not (0.0 < v32 < float("inf")):
+        raise ValueError("%s must be a finite number > 0 (in float32 too), got %r" % (name, value))
+    return value
+
+
+def _cloud_points(points, name="points"):
+    if not isinstance(points, torch.Tensor) or points.dtype != f32 or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("%s must be a float32 [N, 3] tensor, got %s %s" % (name, getattr(points, "dtype", type(points)), tuple(getattr(points, "shape", ()))))
+    if points.shape[0] > CLOUD_MAX_ROWS:
+        raise ValueError("%s holds %d rows; at most 2^31 - 1 (int32 row ids)" % (name, points.shape[0]))
+    if not points.is_cuda:
+        raise ValueError("%s must be a device tensor (there is no CPU path)" % name)
+    return points.contiguous()
+
+
+def _cloud_triple(value, name):
+    try:
+        value = [float(v) for v in value]
+    except TypeError:
+        raise ValueError("%s must be three numbers" % name)
+    with np.errstate(over="ignore"):
+        finite = [math.isfinite(float(np.float32(v))) for v in value]
+    if len(value) != 3 or not all(finite):
+        raise ValueError("%s must be three finite numbers, got %r" % (name, value))
+    return value
+
+
+def _cloud_bounds(points):
+    """-> (float32 minimum [3], float32 maximum [3], kept) of the rows with finite coordinates: one host read."""
+    N, dev = points.shape[0], points.device
+    out = torch.empty((8,), dtype=f32, device=dev)            # six floats and, in the last two words, the int64 count: one read-back
+    nb = _lib.load().cmr_cloud_bounds_workspace_bytes(N)
+    ws = torch.empty((nb,), dtype=torch.uint8, device=dev)
+    _lib.call("cmr_cloud_bounds_f32", _p(points), 3, N, _p(out), _p(out) + 24, _p(ws), nb, _stream())
+    b = out.cpu().numpy()
+    return b[0:3].copy(), b[3:6].copy(), int(b[6:8].view(np.int64)[0])
+
+
+def _cloud_cells(hi, origin, cell, what):
+    """The largest cell index per axis, in the kernel's fp32 arithmetic (the index is monotone in x, so the corners decide); ValueError when a
+    kept row would fall outside [0, 2^21) on an axis."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        top = np.floor((hi.astype(np.float32) - origin) / np.float32(cell))
+    if not np.all(np.isfinite(top)) or top.max() >= CLOUD_CELL_LIMIT:
+        raise ValueError("%s: the cloud spans %s cells of %g on some axis; a grid key holds at most 2^21 = %d per axis"
+                         % (what, "%.0f" % np.nanmax(top + 1) if np.any(np.isfinite(top)) else "too many", cell, CLOUD_CELL_LIMIT))
+
+
+def _sorted_keys(points, origin, cell):
+    N = points.shape[0]
+    keys = torch.empty((N,), dtype=torch.int64, device=points.device)
+    _lib.call("cmr_voxel_keys_f32", _p(points), 3, N, float(origin[0]), float(origin[1]), float(origin[2]), float(cell), _p(keys), _stream())
+    return torch.sort(keys, stable=True)                    # the one torch computation of this path: plumbing, like the allocator
+
+
+def voxel_downsample(points, attr=None, voxel=0.1, origin=None, want_inverse=False):
+    """Voxel-grid downsample of one cloud (cmr_voxel_keys_f32 / cmr_segment_heads_i64 / cmr_segment_reduce_f32; the contract is the
+    header's): one output row per occupied voxel in ascending key order, the fp32 mean of the voxel's rows summed in ascending input index.
+    points float32 [N, 3], attr float32 [N, C] (C >= 0) or None -> VoxelCloud.  Rows with a non-finite coordinate are dropped.  The number
+    of voxels is read back by the host: not capturable in a graph."""
+    voxel = _cloud_scalar(voxel, "voxel")
+    if origin is not None:
+        origin = _cloud_triple(origin, "origin")
+    if attr is not None:
+        if not isinstance(attr, torch.Tensor) or attr.dtype != f32 or attr.dim() != 2:
+            raise ValueError("attr must be a float32 [N, C] tensor or None")
+        if isinstance(points, torch.Tensor) and points.dim() == 2 and attr.shape[0] != points.shape[0]:
+            raise ValueError("attr has %d rows, points %d" % (attr.shape[0], points.shape[0]))
+    points = _cloud_points(points)
+    if attr is not None:
+        if attr.device != points.device:
+            raise ValueError("attr must be on the device of points")
+        attr = attr.contiguous()
+    N, dev = points.shape[0], points.device
+    C = 0 if attr is None else attr.shape[1]
+
+    def result(n, pts, att, cnt, inv, dropped, org):
+        return VoxelCloud(pts, att if attr is not None else None, cnt, inv if want_inverse else None, dropped, tuple(float(v) for v in org))
+
+    lo, hi, kept = _cloud_bounds(points) if N else (None, None, 0)
+    if kept == 0:
+        return result(0, torch.empty((0, 3), dtype=f32, device=dev), torch.empty((0, C), dtype=f32, device=dev),
+                      torch.empty((0,), dtype=torch.int32, device=dev), torch.full((N,), -1, dtype=torch.int64, device=dev), N,
+                      origin if origin is not None else (0.0, 0.0, 0.0))
+    v32 = np.float32(voxel)
+    org = np.asarray(origin, dtype=np.float32) if origin is not None else lo - v32 * np.float32(0.5)
+    if not np.all(np.isfinite(org)):
+        raise ValueError("voxel_downsample: the grid origin %r is not finite in float32" % (org,))
+    if np.any(np.floor((lo - org) / v32) < 0):
+        raise ValueError("voxel_downsample: origin %r lies above the cloud's minimum %r on some axis (cell indices start at 0)" % (org, lo))
+    _cloud_cells(hi, org, voxel, "voxel_downsample")
+    keys, order = _sorted_keys(points, org, voxel)
+    order32 = torch.empty((kept,), dtype=torch.int32, device=dev)
+    offsets = torch.empty((kept + 1,), dtype=torch.int32, device=dev)
+    count = torch.empty((kept,), dtype=torch.int32, device=dev)
+    inverse = torch.empty((N,), dtype=torch.int64, device=dev) if want_inverse else None
+    nseg = torch.empty((1,), dtype=torch.int64, device=dev)
+    nb = _lib.load().cmr_segment_heads_workspace_bytes(N)
+    ws = torch.empty((nb,), dtype=torch.uint8, device=dev)
+    _lib.call("cmr_segment_heads_i64", _p(keys), _p(order), N, kept, _p(order32), _p(offsets), _p(count), _p(inverse), _p(nseg), _p(ws), nb,
+              _stream())
+    n = int(nseg.item())
+    offsets = offsets[:n + 1]
+    out = segment_reduce(points, order32, offsets, n, "mean")
+    att = segment_reduce(attr, order32, offsets, n, "mean") if C else torch.empty((n, C), dtype=f32, device=dev)
+    return result(n, out, att, count[:n], inverse, N - kept, org)
+
+
+def point_normals(points, radius=0.6, viewpoint=(0, 0, 0), min_neighbors=3, want_eigenvalues=False):
+    """Surface normals of one cloud from the neighbours within `radius` (cmr_point_normals_f32; the contract is the header's): the
+    eigenvector of the smallest eigenvalue of the neighbourhood's covariance, turned towards `viewpoint`; the zero vector where a row has
+    fewer than max(3, min_neighbors) neighbours (itself included) or a non-finite coordinate.  points float32 [n, 3] in any order ->
+    PointNormals, in the input's order.  No cap on the number of neighbours (Open3D's hybrid search has max_nn)."""
+    radius = _cloud_scalar(radius, "radius")
+    viewpoint = _cloud_triple(viewpoint, "viewpoint")
+    min_neighbors = int(min_neighbors)
+    points = _cloud_points(points)
+    N, dev = points.shape[0], points.device
+    normals = torch.zeros((N, 3), dtype=f32, device=dev)
+    count = torch.zeros((N,), dtype=torch.int32, device=dev)
+    eig = torch.zeros((N, 3), dtype=f32, device=dev) if want_eigenvalues else None
+    lo, hi, kept = _cloud_bounds(points) if N else (None, None, 0)
+    if kept == 0:
+        return PointNormals(normals, count, eig)
+    _cloud_cells(hi, lo, radius, "point_normals")
+    keys, order = _sorted_keys(points, lo, radius)
+    pts4 = torch.empty((N, 4), dtype=f32, device=dev)
+    _lib.call("cmr_point_normals_f32", _p(points), 3, _p(keys), _p(order), N, kept, float(lo[0]), float(lo[1]), float(lo[2]), radius,
+              viewpoint[0], viewpoint[1], viewpoint[2], min(max(min_neighbors, 3), CLOUD_MAX_ROWS), _p(pts4), _p(normals), _p(count), _p(eig),
+              _stream())
+    return PointNormals(normals, count, eig)

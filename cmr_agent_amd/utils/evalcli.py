@@ -1,5 +1,6 @@
 """Command-line helpers shared by Test_Geo.py and Test_Agent.py: the round lists of --guided / --refine, the --visible flags, the --paint flags
-with the per-pair PLY output, the --dense-depth flags with the per-pair PFM output, the --verify-mi flags, and the closing recall block."""
+with the per-pair PLY output, the --dense-depth flags with the per-pair PFM output, the --verify-mi flags, the --from-raw flag, and the closing
+recall block."""
 import numpy as np
 
 
@@ -155,6 +156,21 @@ def mi_option(ap, args, max_bins, parent=None, parent_given=True):
     if not 2 <= bins <= max_bins:
         ap.error("--mi-bins must be in [2, %d] (--verify-mi), got %d" % (max_bins, bins))
     return bins
+
+
+def add_raw_flag(ap):
+    """--from-raw: the loader prepares raw scans on the fly (FrameDataset(..., from_raw=True))."""
+    ap.add_argument('--from-raw', action='store_true', help="with --data-root: a sequence without the prepared cloud folder is read from its raw "
+                    "scans (<seq>/velodyne/*.bin), voxel-downsampled on the device as it is loaded")
+
+
+def raw_option(ap, args):
+    """-> the keyword arguments --from-raw adds to FrameDataset; ap.error on a misplaced flag."""
+    if not args.from_raw:
+        return {}
+    if not args.data_root:
+        ap.error("--from-raw reads raw scans of real frames: give --data-root as well (synthetic pairs have no files)")
+    return dict(from_raw=True)
 
 
 def print_mi(names, values, chosen):

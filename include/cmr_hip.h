@@ -1204,6 +1204,57 @@ int cmr_la_mlp_bwd_f32(const float* dout, int64_t lddo, const float* o, const fl
  * e_out}; e_out (0: none; may equal d) receives d_i * elu1'(f_i), the dy operand of W_i's weight gradient. */
 int cmr_la_proj_bwd_f32(const int64_t* desc, int nprob, hipStream_t stream);
 
+/* ---- raw scan -> prepared cloud: voxel-grid downsample and surface normals (csrc/cloud_prepare.hip) ------------------
+ * Port extension: the reference reads clouds that an Open3D script of its lineage prepared (voxel_down_sample(0.1), estimate_normals(0.6))
+ * and holds no code that makes them.  One cloud per call.  Every integer below follows from fp32 operations that are stated one by one,
+ * so that a float32 restatement (tests/cloud_prepare_reference.py) reproduces keys, order, counts and the inverse map bit for bit.
+ *
+ * The grid.  A row is KEPT when its three coordinates are finite, else DROPPED.  Per axis the cell index of a kept row is
+ *     c = floorf((x - origin) / cell)      one IEEE fp32 subtraction, one IEEE fp32 division (no reciprocal, no fused operation),
+ * and its key is the int64  cz << 42 | cy << 21 | cx.  The caller guarantees 0 <= c < 2^21 on every axis for every kept row (the host
+ * checks the two corners of cmr_cloud_bounds_f32, c being monotone in x, and raises before a key is used; a kernel handed anything else
+ * clamps c into that range rather than forming a malformed key).  Dropped rows get the key 2^63 - 1, which sorts behind every cell.
+ *
+ * cmr_cloud_bounds_f32: bounds[0..2] / bounds[3..5] = per-axis minimum / maximum over the kept rows of points [N][ld >= 3] (+inf / -inf
+ * when there is none), kept[0] = their number.  Workspace of cmr_cloud_bounds_workspace_bytes(N).  0 < N < 2^31 in all of these (the CSR
+ * of cmr_segment_reduce_f32 is int32). */
+int64_t cmr_cloud_bounds_workspace_bytes(int64_t N);
+int cmr_cloud_bounds_f32(const float* points, int64_t ld, int64_t N, float* bounds, int64_t* kept, void* workspace,
+                         int64_t workspace_bytes, hipStream_t stream);
+/* keys[i] of every row, as above (voxel downsample: cell = the voxel size, origin = minimum - voxel / 2 in fp32 unless the caller names one;
+ * normals: cell = the radius, origin = the minimum). */
+int cmr_voxel_keys_f32(const float* points, int64_t ld, int64_t N, float ox, float oy, float oz, float cell, int64_t* keys,
+                       hipStream_t stream);
+/* Runs of equal keys -> CSR.  keys_sorted / order: the keys in ascending order and the row each came from (a STABLE sort: the rows of a
+ * run are in ascending input index); the first `kept` of the N entries are kept rows (0 < kept <= N).  Run s = 0 .. nseg[0] - 1 in
+ * ascending key order covers sorted positions offsets[s] .. offsets[s + 1] - 1; count[s] is its length; order32 [kept] is `order` as the
+ * int32 row ids cmr_segment_reduce_f32 takes (mode 2 then gives each run's mean, summed in ascending input index and divided by the count);
+ * inverse [N] (or null) = the run of every input row, -1 for dropped rows.  offsets has room for kept + 1 entries, count for kept; entries
+ * past nseg[0] (+ 1) are not written.  The caller reads nseg[0] back: the number of runs is a result, so this step cannot be part of a
+ * captured graph.  Workspace of cmr_segment_heads_workspace_bytes(N). */
+int64_t cmr_segment_heads_workspace_bytes(int64_t N);
+int cmr_segment_heads_i64(const int64_t* keys_sorted, const int64_t* order, int64_t N, int64_t kept, int32_t* order32, int32_t* offsets,
+                          int32_t* count, int64_t* inverse, int64_t* nseg, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+/* Surface normals from fixed-radius neighbourhoods (Open3D estimate_normals with KDTreeSearchParamRadius + orient towards a viewpoint;
+ * WITHOUT the max_nn cap of its hybrid search).  keys_sorted / order / kept: the rows' keys on the grid cell = radius, origin = (ox, oy, oz),
+ * sorted as above.  Row i, kept:
+ *   neighbours  the kept rows j (i included) with fp32  (dx dx + dy dy) + dz dz <= radius radius,  d = p_j - p_i, each product, sum and
+ *               the square of the radius rounded on its own;  count[i] = their number k;
+ *   sums        sum d and sum d d^T in fp32: every lane of a 16-lane group adds the neighbours it meets in sorted order, the 16 partial
+ *               sums are added as a balanced tree -- a fixed order for a fixed input order, so two calls agree bit for bit;
+ *   covariance  m = sum d / k,  C = sum d d^T / k - m m^T,  from those sums in fp64;
+ *   normal      the unit eigenvector of C's smallest eigenvalue (cyclic Jacobi in fp64, eight sweeps), sign such that
+ *               n . (viewpoint - p_i) >= 0;  k < max(3, min_neighbors) gives the zero normal and zero eigenvalues;  a degenerate C gives
+ *               some finite unit vector;
+ *   eigenvalues [N][3] ascending (or null).
+ * A dropped row gets the zero normal and count 0.  Outputs are in the input's row order.  points4: scratch of N float4 (16-byte
+ * aligned), the kept rows gathered into key order.  The search reads, per (z, y) pair of cells round the query, ONE run of the sorted rows
+ * (x is in the key's low bits): 9 runs, found by binary search; a query within rounding of a cell face also reads the cell after next on
+ * that side, so that the neighbour set is exactly the one stated. */
+int cmr_point_normals_f32(const float* points, int64_t ld, const int64_t* keys_sorted, const int64_t* order, int64_t N, int64_t kept,
+                          float ox, float oy, float oz, float radius, float vx, float vy, float vz, int min_neighbors, float* points4,
+                          float* normals, int32_t* count, float* eigenvalues, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
