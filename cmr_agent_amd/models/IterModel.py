@@ -7,7 +7,7 @@ NHWC maps on the 3x3 convolution kernels (Winograd / direct / bf16, ops.conv3x3)
 64-wide tiles.  The first convolution's 130 input channels are [image features | warped point features | occupancy | image overlap];
 only the 64 warped channels differ per pose AND are wide: the image half is convolved once (as CMRAgent does for its observation), the
 two one-channel planes go through a small stencil kernel into the residual operand, and the matrix cores see 64 -> 64 per pose instead
-of 130 -> 64.  Pose sampling, warp + scatter-mean (float atomics), the global pool + 1x1 head and the decision are the kernels of
+of 130 -> 64.  Pose sampling, warp + scatter-mean (binned in LDS per band of map rows; float atomics on maps wider than one band's 384 cells), the global pool + 1x1 head and the decision are the kernels of
 csrc/iter_model.hip.
 
 The reference writes this model for a batch of ONE pair on the 160 x 512 image (`pc_overlap_pred[0]`, the literal 5120 = 40 * 128 dump
@@ -90,10 +90,16 @@ class IterModel(Planned):
         wi, bi, ui = p["img"]
         base = ops.conv3x3(img_feat, wi, bi, 64, 1, 1.0, u=ui)                                # [1, h, w, 64], no activation
         base = ops.iter_finalize(None, None, ov, p["w_ov"], base[0])                          # + overlap plane -> [1, h, w, 64]
-        # warp + scatter-mean binned per band of map rows in LDS; the same launch writes the residual operand (base + occupancy stencil)
-        acc, res, occ, _ = ops.iter_warp_bin(pc[0], feat_rows, f(data_batch["pc_is_in_cam_scores"]).view(-1),
-                                             u8(data_batch["pc_overlap_pred"][0]), u8(data_batch["pc_overlap_pred_standby"][0]),
-                                             rt, f(data_batch["K"]).view(-1), p["w_occ"], base[0], h, w)
+        # warp + scatter-mean binned per band of map rows in LDS; the same launch writes the residual operand (base + occupancy stencil).
+        # A band holds whole rows of at most 384 cells: a wider map takes the atomic scatter and the finalisation pass, which give the same three
+        warp_in = (pc[0], feat_rows, f(data_batch["pc_is_in_cam_scores"]).view(-1), u8(data_batch["pc_overlap_pred"][0]),
+                   u8(data_batch["pc_overlap_pred_standby"][0]), rt, f(data_batch["K"]).view(-1))
+        if w <= ops.ITER_BAND_CELLS:
+            acc, res, occ, _ = ops.iter_warp_bin(*warp_in, p["w_occ"], base[0], h, w)
+        else:
+            acc, cnt, occ, _ = ops.iter_warp_scatter(*warp_in, h, w)
+            res = ops.iter_finalize(acc, cnt, occ, p["w_occ"], base[0])
+            del cnt
         ww, _, uw = p["warped"]
         x = ops.conv3x3(acc, ww, None, 64, 1, SLOPE, res=res, u=uw, out_bf16=True)        # bf16 mode: the chain's maps are stored as bf16
         del res, acc

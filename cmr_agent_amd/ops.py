@@ -2279,6 +2279,9 @@ def iter_warp_scatter(pc_3n, feat_rows, score, mask_u8, standby_u8, rt, K, h, w)
     return acc, cnt, occ, sel
 
 
+ITER_BAND_CELLS = 384      # IB_CELLS of csrc/iter_model.hip: the band kernel holds whole map rows of at most this many cells
+
+
 def iter_warp_bin(pc_3n, feat_rows, score, mask_u8, standby_u8, rt, K, w_occ, base, h, w):
     """-> (warped [P, h, w, 64] scatter mean, res [P, h, w, 64] = base + 3x3 stencil of the occupancy plane, occ [P, h, w], sel [N])."""
     N, P = pc_3n.shape[1], rt.shape[0]
@@ -2286,7 +2289,7 @@ def iter_warp_bin(pc_3n, feat_rows, score, mask_u8, standby_u8, rt, K, w_occ, ba
         raise ValueError("iter_warp_bin: pc [3, N] planar and feat [N, 64] rows, contiguous")
     if score.numel() != N or mask_u8.numel() != N or standby_u8.numel() != N or mask_u8.dtype != torch.uint8 or standby_u8.dtype != torch.uint8:
         raise ValueError("iter_warp_bin: score [N] float32, masks [N] uint8")
-    if tuple(base.shape) != (h, w, 64) or tuple(w_occ.shape) != (9, 64) or w > 384:
+    if tuple(base.shape) != (h, w, 64) or tuple(w_occ.shape) != (9, 64) or w > ITER_BAND_CELLS:
         raise ValueError("iter_warp_bin: base [h, w, 64], w_occ [9, 64], w <= 384")
     dev = pc_3n.device
     warped = torch.empty((P, h, w, 64), dtype=f32, device=dev)

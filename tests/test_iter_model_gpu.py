@@ -200,3 +200,59 @@ def test_band_binned_scatter_equals_the_atomic_scatter(N, n):
         assert torch.equal(occ != 0, occ0 != 0) and float((occ - occ0).abs().max()) <= 1e-5
         assert float((warped - acc).abs().max()) <= 2e-6
         assert float((res - res0).abs().max()) <= 2e-5
+
+
+def test_iter_model_forward_on_a_map_wider_than_the_band_kernel_takes():
+    """Image 32 x 1600: the 1/4-scale map is 8 x 400, wider than the 384 cells a band of cmr_iter_warp_bin_f32 holds, so the forward takes
+    cmr_iter_warp_scatter_f32 + cmr_iter_finalize_f32.  27 poses, 600 points drawn to cover the map (iter_reference.synthetic_cloud), against
+    O.iter_model on CPU and, for the cells and the decisions, against the float64 restatement."""
+    import iter_reference as ir
+    from cmr_agent_amd import ops
+    from cmr_agent_amd.utils import synthetic
+    from oracle import cmr_oracle as O
+    n, N, H, W = 3, 600, 8, 400
+    s = ir.synthetic_cloud(H, W, N, n=n)
+    r = np.random.RandomState(400)
+    img_feat = torch.from_numpy(r.uniform(-1, 1, (1, 64, H, W)).astype(np.float32))
+    batch = synthetic.make_iter_batch("wide_map", N, n, ir.WARP_AMPS[0], ir.WARP_AMPS[1])
+    batch.update(img=torch.zeros(1, 3, 4 * H, 4 * W), K=torch.from_numpy(s["K"].copy()).unsqueeze(0), pc_i=torch.from_numpy(s["pc"].copy()).unsqueeze(0),
+                 pc_geo_feat=torch.from_numpy(s["feat"].T.copy()).unsqueeze(0), img_geo_feat=img_feat / img_feat.norm(dim=1, keepdim=True),
+                 img_overlap_pred=torch.from_numpy((r.uniform(0, 1, (1, H, W)) < 0.7).astype(np.float32)),
+                 pc_is_in_cam_scores=torch.from_numpy(s["score"].copy()).unsqueeze(0), pc_overlap_pred=torch.from_numpy(s["mask"] != 0).unsqueeze(0),
+                 pc_overlap_pred_standby=torch.from_numpy(s["standby"] != 0).unsqueeze(0))
+    model, sd = _model(n)
+    with torch.no_grad():
+        want = O.iter_model(sd, {k: (v.clone() if torch.is_tensor(v) else v) for k, v in batch.items()}, n)
+    data = {k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in batch.items()}
+    with pytest.raises(ValueError):                                              # the band kernel's entry point still refuses this width ...
+        ops.iter_warp_bin(data["pc_i"][0].contiguous(), torch.zeros(N, 64, device=DEV), data["pc_is_in_cam_scores"].view(-1),
+                          torch.ones(N, dtype=torch.uint8, device=DEV), torch.ones(N, dtype=torch.uint8, device=DEV),
+                          torch.zeros(n ** 3, 3, 4, device=DEV), data["K"].view(-1), torch.zeros(9, 64, device=DEV), torch.zeros(H, W, 64, device=DEV), H, W)
+    assert model(data) == 0                                                      # ... and the forward does not go there
+    assert torch.equal(data["delta_R"].cpu(), want["delta_R"]) and torch.equal(data["delta_T"].cpu(), want["delta_T"])
+    # occupancy: on the cells fp32 can decide, from the device's own pose matrices
+    _, _, rt = ops.iter_sample_poses(data["R_amplitude"], data["T_amplitude"], n)
+    ref = ir.warp(s["pc"], s["feat"], s["score"], ir.select_mask(s["mask"], s["standby"]), rt.cpu().numpy(), s["K"], H, W, with_mean=False)
+    pts, cells = ir.shares(ref)
+    assert pts <= ir.MAX_UNDECIDED_POINTS and cells <= ir.MAX_UNDECIDED_CELLS
+    cd = ref["cell_decided"]
+    occ = data["3d_weight"].cpu().double().numpy()[0]
+    assert occ.shape == (n ** 3, H, W) and ref["count"].sum() > 0
+    assert np.array_equal((occ != 0)[cd], (ref["occ"] != 0)[cd]) and (np.abs(occ - ref["occ"])[cd] <= ir.occ_bound(ref)[cd]).all()
+    assert float(((data["3d_weight"].cpu()[0] - want["3d_weight"][0]).abs() * torch.from_numpy(cd)).max()) <= 1e-5
+    err = float((data["cost_colume_logits"].cpu() - want["cost_colume_logits"]).abs().max())
+    print("  wide map: logits max|d| %.2e, %d cells left out" % (err, int((~cd).sum())))
+    assert err <= LOGIT_ATOL
+    # decisions: consistent with the device's own logits wherever fp32 can decide them
+    dec = ir.decide(data["cost_colume_logits"].cpu()[0], n, batch["label_R"], batch["label_T_x"], batch["label_T_z"], data["delta_R"].cpu()[0],
+                    data["delta_T"].cpu()[0])
+    assert (np.abs(data["cost_volume_label"].cpu().double().numpy()[0] - dec["label"]) <= dec["label_bound"]).all()
+    assert int(data["3d_weight_id"]) == dec["idx"][4]
+    if dec["decided"][0]:
+        assert abs(float(data["cost_volume_loss"]) - dec["loss"]) <= dec["loss_bound"]
+    m = data["matrix_i"].cpu().double().numpy()[0]
+    if dec["decided"][1:4].all():
+        assert (np.abs(m - dec["matrix_i"]) <= dec["matrix_bound"]).all()
+    pc_out, pb, acc_out, ab = ir.apply(data["matrix_i"].cpu()[0], batch["pc_i"][0], batch["matrix_accumulated"][0])
+    assert (np.abs(data["pc_i"].cpu().double().numpy()[0] - pc_out) <= pb).all()
+    assert (np.abs(data["matrix_accumulated"].cpu().double().numpy()[0] - acc_out) <= ab).all()
