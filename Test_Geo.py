@@ -66,6 +66,13 @@ by the image (cmr_densify_f32; window radius R, default 8; range sigma S, defaul
 cloud under that pose leaves visible.  Each batch prints one extra line "dense <filled> of <pixels> from <samples>".  Without the flag the
 output is unchanged.
 
+--dense-surfels (with --dense-depth) and --visible-surfels (with --visible) [--surfel-radius R] [--surfel-slope S] [--surfel-max-px M]
+(DESIGN.md 4z): the cloud is drawn as oriented discs from its normals (cmr_render_surfels_f32; r = R + S z metres, defaults 0.1 and 0.004,
+cut to the (2M + 1)^2 pixels round the centre, default 8; the normals are the batch's 'pc_normal' or are computed on the device).  With
+--dense-surfels the map that is densified comes from the discs and each batch prints one more line "surfels <drawn> of <selected> own
+<owned> of <pixels>"; with --visible-surfels every round's z-buffer is the surfel depth map of the whole cloud (cmr_depth_test_f32).
+Without these flags the output is unchanged.
+
 --from-raw (with --data-root): a sequence whose prepared cloud folder is missing is read from its raw scans
 (<seq>/velodyne/*.bin) and voxel-downsampled on the device as it is loaded (FrameDataset(..., from_raw=True));
 `python -m cmr_agent_amd.dataset.prepare --root DIR` writes the folder once instead.  Without the flag nothing changes.
@@ -92,9 +99,9 @@ from cmr_agent_amd.models import MultiHeadModel  # noqa: E402
 from cmr_agent_amd.models.MultiHeadModel import match_features  # noqa: E402
 from cmr_agent_amd.utils import hashfill, synthetic  # noqa: E402
 from cmr_agent_amd.utils.checkpoint import load_checked  # noqa: E402
-from cmr_agent_amd.utils.evalcli import (add_dense_flags, add_mi_flags, add_paint_flags, add_raw_flag, add_visible_flags, dense_option,  # noqa: E402
-                                         dense_pairs, guided_rounds, mi_option, paint_option, paint_pairs, print_mi, print_recall, print_visible,
-                                         raw_option, visible_option)
+from cmr_agent_amd.utils.evalcli import (add_dense_flags, add_mi_flags, add_paint_flags, add_raw_flag, add_surfel_flags,  # noqa: E402
+                                         add_visible_flags, dense_option, dense_pairs, guided_rounds, mi_option, paint_option, paint_pairs,
+                                         print_mi, print_recall, print_visible, raw_option, surfel_option, visible_option)
 
 
 def _ratios(counts):
@@ -137,6 +144,7 @@ def main():
     add_dense_flags(ap, "--pnp")
     add_mi_flags(ap, "--pnp")
     add_raw_flag(ap)
+    add_surfel_flags(ap)
     args = ap.parse_args()
     paint = paint_option(ap, args, "--pnp", args.pnp)
     dense = dense_option(ap, args, ops.DENSIFY_MAX_RADIUS, "--pnp", args.pnp)
@@ -173,6 +181,7 @@ def main():
     elif args.guided_thr is not None or args.guided_max_dist is not None:
         ap.error("--guided-thr / --guided-max-dist belong to --guided")
     visible = visible_option(ap, args, "--guided", radii is not None, ops.GUIDED_MAX_RADIUS)
+    dense, visible = surfel_option(ap, args, dense, visible, ops.SURFEL_MAX_PX)
     vis_kw = {} if visible is None else dict(visible=visible or True)
     dev = torch.device("cuda")
     Cfg = {"kitti": KittiConfiguration, "nuscenes": NuScenesConfiguration}[args.dataset]

@@ -21,6 +21,19 @@ __device__ __forceinline__ void cmr_project_chains(const float* P, const float* 
   cmr_project_chains(P, K, x[n], x[N + n], x[2 * N + n], p0, p1, p2);
 }
 
+// X_c alone, by the same three chains (the same bits as inside cmr_project_chains), and a direction turned by R alone -- the pattern
+// without the translation, the last term a plain product: for a caller that needs the camera-frame point and normal (surfel.hip).
+__device__ __forceinline__ void cmr_camera_chains(const float* P, float X, float Y, float Z, float& xc, float& yc, float& zc) {
+  xc = fmaf(P[0], X, fmaf(P[1], Y, fmaf(P[2], Z, P[3])));
+  yc = fmaf(P[4], X, fmaf(P[5], Y, fmaf(P[6], Z, P[7])));
+  zc = fmaf(P[8], X, fmaf(P[9], Y, fmaf(P[10], Z, P[11])));
+}
+__device__ __forceinline__ void cmr_rotate_chains(const float* P, float X, float Y, float Z, float& xc, float& yc, float& zc) {
+  xc = fmaf(P[0], X, fmaf(P[1], Y, P[2] * Z));
+  yc = fmaf(P[4], X, fmaf(P[5], Y, P[6] * Z));
+  zc = fmaf(P[8], X, fmaf(P[9], Y, P[10] * Z));
+}
+
 struct CmrProj {
   float u, v, z;      // (u, v) = (p0 / p2, p1 / p2); z = p2, the depth
   bool view;

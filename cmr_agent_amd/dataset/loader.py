@@ -118,12 +118,16 @@ class FrameDataset:
     4v; off by default, and then the sample dict is the reference's): the sample gains 'pc_intensity' float32 [N], the reflectance (row 3
     of the cloud on disk) of the down-sampled points, in the order of 'pc'.  from_raw (port extension; off by default, and then
     nothing changes): a sequence that lacks the prepared cloud folder but has the raw scans (<seq>/velodyne/<i>.bin) is listed too, and its
-    frames are prepared on the fly (dataset.prepare.prepare_cloud without normals: the voxel-grid downsample, on the device)."""
+    frames are prepared on the fly (dataset.prepare.prepare_cloud without normals: the voxel-grid downsample, on the device).  with_normals
+    (port extension; off by default, and then the sample dict is unchanged): the sample gains 'pc_normal' float32 [3, N], the
+    surface normals (rows 4 - 6 of the cloud on disk) of the down-sampled points in the frame and the order of 'pc': turned by the rotation of
+    P_random P_Tr, both rigid, the 3 x 3 product formed on the host in float64 and applied in fp32.  A file without those rows is a
+    ValueError naming the frame; with from_raw the scan is prepared with normals."""
 
     SEQUENCES = {"train": (0, 1, 2, 3, 4, 5, 6, 7, 8), "val": (9, 10), "test": (9, 10)}
     PC_SUBDIR = "voxel0.1-SNr0.6"
 
-    def __init__(self, root, config, mode, device=None, n_circle=512, with_intensity=False, from_raw=False):
+    def __init__(self, root, config, mode, device=None, n_circle=512, with_intensity=False, from_raw=False, with_normals=False):
         if mode not in self.SEQUENCES:
             raise Exception("Invalid mode...")                                     # KittiDataset.py:162
         self.root, self.config, self.mode = root, config, mode
@@ -133,6 +137,7 @@ class FrameDataset:
         self.n_circle = n_circle
         self.with_intensity = bool(with_intensity)
         self.from_raw = bool(from_raw)
+        self.with_normals = bool(with_normals)
         self.amp_t = (config.P_Tx_amplitude, config.P_Ty_amplitude, config.P_Tz_amplitude)
         self.amp_r = (config.P_Rx_amplitude, config.P_Ry_amplitude, config.P_Rz_amplitude)
         self.calib = read_calib(root)
@@ -180,7 +185,7 @@ class FrameDataset:
         img = np.load(os.path.join(img_folder, "%06d.npy" % i))
         if os.path.basename(pc_folder) == "velodyne":                                # from_raw: the scan as KITTI ships it
             from .prepare import prepare_cloud, read_velodyne_bin
-            raw = prepare_cloud(read_velodyne_bin(os.path.join(pc_folder, "%06d.bin" % i)), normals=False, device=self.device).cpu().numpy()
+            raw = prepare_cloud(read_velodyne_bin(os.path.join(pc_folder, "%06d.bin" % i)), normals=self.with_normals, device=self.device).cpu().numpy()
         else:
             raw = np.ascontiguousarray(np.load(os.path.join(pc_folder, "%06d.npy" % i)), dtype=np.float32)
         P_Tr = np.dot(self.calib[seq][key], self.calib[seq]["Tr"])                  # :273-274
@@ -240,6 +245,12 @@ class FrameDataset:
             if f["raw"].shape[0] < 4:
                 raise ValueError("frame %d: with_intensity needs a [4, n] cloud (x, y, z, reflectance), got %s" % (index, f["raw"].shape))
             out["pc_intensity"] = torch.from_numpy(np.ascontiguousarray(f["raw"][3, f["choice"]])).to(dev)
+        if self.with_normals:
+            if f["raw"].shape[0] < 7:
+                raise ValueError("frame %d: with_normals needs a [7, n] cloud (x, y, z, reflectance, normal), got %s" % (index, f["raw"].shape))
+            R = np.asarray(f["P_random"], dtype=np.float64)[0:3, 0:3] @ np.asarray(f["P_Tr"], dtype=np.float64)[0:3, 0:3]
+            normal = torch.from_numpy(np.ascontiguousarray(f["raw"][4:7, f["choice"]])).to(dev)
+            out["pc_normal"] = torch.matmul(torch.from_numpy(R.astype(np.float32)).to(dev), normal).contiguous()
         out["angles"] = torch.from_numpy(f["angles"])
         out["translation"] = torch.from_numpy(f["t"])
         self.last_draws = draws

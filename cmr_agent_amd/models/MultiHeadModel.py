@@ -238,17 +238,63 @@ def _first_min(score):
     return torch.where(k < P, k, torch.zeros_like(k))
 
 
+# ops.render_surfels' parameters as the model layer hands them on: one voxel of the prepared clouds, about half of KITTI's ring spacing
+# per metre of range; not tuned on real data
+SURFEL_DEFAULTS = dict(radius=0.1, range_slope=0.004, max_px=8, min_cos=0.1)
+
+
+def _surfel_kw(surfels, who):
+    """The `surfels` keyword -> None (off) or ops.render_surfels' radius / range_slope / max_px / min_cos."""
+    if surfels is None or surfels is False:
+        return None
+    kw = dict(SURFEL_DEFAULTS)
+    if surfels is True:
+        return kw
+    if not isinstance(surfels, dict) or set(surfels) - set(kw):
+        raise ValueError("%s: surfels must be None, True or a dict with keys among radius / range_slope / max_px / min_cos, got %r" % (who, surfels))
+    kw.update(surfels)
+    return kw
+
+
 def _visible_kw(visible, who):
-    """The `visible` keyword of refine_pose_from_matches / search_pose -> None (off) or ops.visibility's radius / rel_tol / abs_tol."""
+    """The `visible` keyword of refine_pose_from_matches / search_pose -> None (off) or ops.visibility's radius / rel_tol / abs_tol.
+    One more key, surfels (True or a dict of ops.render_surfels' parameters), makes the z-buffer the surfel depth map of the
+    whole cloud and the test ops.depth_test (_visible_rows); the window radius then defaults to 0, the map being continuous."""
     if visible is None or visible is False:
         return None
     kw = dict(radius=1, rel_tol=0.05, abs_tol=0.0)
     if visible is True:
         return kw
-    if not isinstance(visible, dict) or set(visible) - set(kw):
-        raise ValueError("%s: visible must be None, True or a dict with keys among radius / rel_tol / abs_tol, got %r" % (who, visible))
+    if not isinstance(visible, dict) or set(visible) - set(kw) - {"surfels"}:
+        raise ValueError("%s: visible must be None, True or a dict with keys among radius / rel_tol / abs_tol / surfels, got %r" % (who, visible))
     kw.update(visible)
+    sf = _surfel_kw(kw.pop("surfels", None), who)
+    if sf is not None:
+        kw["radius"] = visible.get("radius", 0)
+        kw["surfels"] = sf
     return kw
+
+
+def _cloud_normals(data_batch, pc, radius=0.6, again=False):
+    """data['pc_normal'] on pc's device, computed by ops.point_normals when the batch has none or `again` is set: one call per sample,
+    the op takes one cloud (the sign of a normal does not matter to a disc) -> float32 [B, 3, N]."""
+    if again or 'pc_normal' not in data_batch:
+        data_batch['pc_normal'] = torch.stack([ops.point_normals(pc[b].t().contiguous(), radius=radius)[0].t()
+                                               for b in range(pc.shape[0])]).contiguous()
+    return data_batch['pc_normal'].to(pc.device).float().contiguous()
+
+
+def _visible_rows(data_batch, pc, pose, K, h, w, sel, vis_kw):
+    """The rows of `sel` the camera sees under `pose` -> (visible bool [B*N], counts).  Without the surfels key: ops.visibility, the whole
+    cloud occluding, counts [B, 4].  With it: ops.render_surfels of the whole cloud on the same map, then ops.depth_test against its depth
+    map, counts [B, 3] = (selected, in view, visible)."""
+    if "surfels" not in vis_kw:
+        vis, counts, _, _, _ = ops.visibility(pc, pose, K, h, w, sel, **vis_kw)
+        return vis, counts
+    kw = dict(vis_kw)
+    sf = kw.pop("surfels")
+    depth_map = ops.render_surfels(pc, _cloud_normals(data_batch, pc), pose, K, h, w, **sf)[1]
+    return ops.depth_test(pc, pose, K, depth_map, sel, **kw)
 
 
 class MultiHeadModel(Planned):
@@ -365,7 +411,11 @@ class MultiHeadModel(Planned):
         visible (None by default, and then nothing changes): True, or a dict of ops.visibility's radius / rel_tol / abs_tol
         (defaults 1 / 0.05 / 0: values for the 1/4-scale map, not tuned on real data).  Every round first runs ops.visibility under that
         round's current pose, the whole cloud occluding, and matches only the rows of `mask` that are visible; 'refine_visible_counts'
-        int32 [rounds, B, 4] holds its counts (selected, in view, visible, occluder rows in view).  Not called by forward."""
+        int32 [rounds, B, 4] holds its counts (selected, in view, visible, occluder rows in view).  One more key, surfels (DESIGN.md 4z;
+        True or a dict of ops.render_surfels' radius / range_slope / max_px / min_cos), here and wherever a method takes `visible`: the
+        z-buffer is the surfel depth map of the whole cloud on the geometric map (normals from 'pc_normal', computed when absent), the
+        test is ops.depth_test -- its window radius then defaults to 0 -- and the counts are [rounds, B, 3] (selected, in view, visible).
+        Not called by forward."""
         radii, thrs = tuple(radii), tuple(thrs)
         if len(radii) != len(thrs) or not radii:
             raise ValueError("refine_pose_from_matches: radii and thrs must be non-empty and of equal length, got %r / %r" % (radii, thrs))
@@ -386,7 +436,7 @@ class MultiHeadModel(Planned):
             rsel = sel
             for radius, thr in zip(radii, thrs):
                 if vis_kw is not None:
-                    rsel, vc, _, _, _ = ops.visibility(pc, cur, K, h, w, sel, **vis_kw)
+                    rsel, vc = _visible_rows(data_batch, pc, cur, K, h, w, sel, vis_kw)
                     vis_counts.append(vc)
                 idx, keep, cnt, _, _ = ops.guided_match(pc, feat, img, rsel, cur, K, radius, max_dist=max_dist or 0.0, gt_xy=xy,
                                                         thr=MATCH_INLIER_THRES)
@@ -481,7 +531,7 @@ class MultiHeadModel(Planned):
                 K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3)
             if vis_kw is not None:
                 every = torch.ones(B, N, dtype=torch.bool, device=dev)
-                sel = ops.visibility(pc, poses[:, 0].contiguous(), Kg, h, w, every if sel is None else sel, **vis_kw)[0]
+                sel = _visible_rows(data_batch, pc, poses[:, 0].contiguous(), Kg, h, w, every if sel is None else sel, vis_kw)[0]
             if attr_range is None:
                 ok = torch.isfinite(a) if sel is None else torch.isfinite(a) & (sel.view(B, N) != 0)
                 inf = torch.full_like(a, float("inf"))
@@ -529,7 +579,7 @@ class MultiHeadModel(Planned):
             for radius, rot, trans, rounds in levels:
                 D = pose_search_table(rot, trans).to(dev)
                 if vis_kw is not None:
-                    lsel, vc, _, _, _ = ops.visibility(pc, cur, K, img.shape[1], img.shape[2], sel, **vis_kw)
+                    lsel, vc = _visible_rows(data_batch, pc, cur, K, img.shape[1], img.shape[2], sel, vis_kw)
                     vis_counts.append(vc)
                 for _ in range(int(rounds)):
                     cand = torch.matmul(D[None], cur.double()[:, None]).float().contiguous()      # [B, 729, 4, 4]; D_0 = I: cand[:, 0] is cur
@@ -542,22 +592,76 @@ class MultiHeadModel(Planned):
             if vis_kw is not None:
                 data_batch['search_visible_counts'] = torch.stack(vis_counts)
 
-    def visible_points(self, data_batch, pose=None, radius=1, rel_tol=0.05, abs_tol=0.0, mask=None, occluders='all'):
+    def point_normals(self, data_batch, radius=0.6):
+        """Port extension: a surface normal per point of 'pc' from the neighbours within `radius` metres
+        (ops.point_normals, one call per sample; the zero vector where a point has fewer than three neighbours).  Sets 'pc_normal'
+        float32 [B, 3, N] in the cloud's frame.  The sign of a normal does not matter to a disc.  Not called by forward."""
+        with torch.no_grad():
+            _cloud_normals(data_batch, data_batch['pc'].float().contiguous(), radius=radius, again=True)
+
+    def render_surfels(self, data_batch, normals=None, attr=None, pose=None, size=None, K=None, mask=None, radius=SURFEL_DEFAULTS['radius'],
+                       range_slope=SURFEL_DEFAULTS['range_slope'], max_px=SURFEL_DEFAULTS['max_px'], min_cos=SURFEL_DEFAULTS['min_cos'],
+                       fill=0.0):
+        """Port extension: the cloud drawn as oriented discs under `pose` (default 'pnp_pose'): every point of `mask`
+        (default every point) is a disc perpendicular to its normal, r = radius + range_slope z metres wide and cut to the (2 max_px + 1)^2
+        pixels round its centre, every pixel takes the depth of the nearest disc's plane on its own ray (ops.render_surfels).  normals:
+        float32 [B, 3, N] in the cloud's frame, default 'pc_normal', computed by point_normals when the batch has none.  attr: float32
+        [B, C, N], C <= 64, or None.  size and K go together exactly as in render_depth: by default the geometric map's h x w with 'K'.
+        The defaults are one voxel and about half of KITTI's ring spacing; they are not tuned on real data.  Sets 'surfel_index_map' int32
+        [B, h, w] (-1 where no disc covers the pixel), 'surfel_depth_map' float32 [B, h, w] (+inf there), 'surfel_normal_map' float32
+        [B, 3, h, w] (unit, facing the camera; 0 there), 'surfel_counts' int32 [B, 4] = (selected, drawn, pixels with an owner, status) and,
+        with attr, 'surfel_attr_map' float32 [B, C, h, w] (`fill` there).  Not called by forward."""
+        if (size is None) != (K is None):
+            raise ValueError("render_surfels: size and K go together (both or neither)")
+        with torch.no_grad():
+            pc = data_batch['pc'].float().contiguous()
+            dev = pc.device
+            B = pc.shape[0]
+            if size is None:
+                h, w = _geo_rows(data_batch)[1].shape[1:3]
+                K = data_batch['K']
+            else:
+                h, w = size
+            K = K.to(dev).float()
+            K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3).contiguous()
+            cur = (data_batch['pnp_pose'] if pose is None else pose).to(dev).float().contiguous()
+            nrm = _cloud_normals(data_batch, pc) if normals is None else normals.to(dev).float().contiguous()
+            index_map, depth_map, attr_map, counts, normal_map, _ = ops.render_surfels(
+                pc, nrm, cur, K, h, w, radius=radius, range_slope=range_slope, max_px=max_px, min_cos=min_cos,
+                attr=None if attr is None else attr.to(dev).float().contiguous(), mask=None if mask is None else mask.to(dev).contiguous(),
+                fill=fill, want_normal_map=True)
+            data_batch['surfel_index_map'] = index_map
+            data_batch['surfel_depth_map'] = depth_map
+            data_batch['surfel_normal_map'] = normal_map
+            data_batch['surfel_counts'] = counts
+            if attr is not None:
+                data_batch['surfel_attr_map'] = attr_map
+
+    def visible_points(self, data_batch, pose=None, radius=1, rel_tol=0.05, abs_tol=0.0, mask=None, occluders='all', surfels=None):
         """Port extension: which points of `mask` (default 'pc_overlap_pred') the camera sees under `pose` (float32
         [B, 4, 4] mapping 'pc' into the camera frame, default 'pnp_pose'), by a z-buffer on the geometric map's h x w with 'K'
         (ops.visibility).  occluders: 'all' (every point of the cloud blocks the view, also outside the predicted overlap) or 'mask' (only
         the queried points do).  A point is visible iff it projects into the map and its depth is <= zmin (1 + rel_tol) + abs_tol, zmin =
         the nearest depth in the (2 radius + 1)^2 cells round its own.  radius = 1 and rel_tol = 0.05 are defaults for the 1/4-scale map;
         they are not tuned on real data.  Sets 'visible_mask' bool [B, N] and 'visible_counts' int32 [B, 4] (selected, in view, visible,
-        occluder points in view).  Not called by forward."""
-        if occluders not in ('all', 'mask'):
-            raise ValueError("visible_points: occluders must be 'all' or 'mask', got %r" % (occluders,))
+        occluder points in view).  occluders='surfels' (DESIGN.md 4z): the z-buffer is the surfel depth map of the whole cloud
+        (ops.render_surfels with `surfels`: True / None for the defaults, or a dict of radius / range_slope / max_px / min_cos; normals
+        from 'pc_normal', computed when absent), the test is ops.depth_test with `radius`, `rel_tol`, `abs_tol`, and 'visible_counts'
+        is int32 [B, 3] (selected, in view, visible).  Not called by forward."""
+        if occluders not in ('all', 'mask', 'surfels'):
+            raise ValueError("visible_points: occluders must be 'all', 'mask' or 'surfels', got %r" % (occluders,))
+        if surfels is not None and occluders != 'surfels':
+            raise ValueError("visible_points: surfels belongs to occluders='surfels'")
+        sf = _surfel_kw(True if surfels is None else surfels, "visible_points") if occluders == 'surfels' else None
         with torch.no_grad():
             pc, _, img, sel, K = self._score_args(data_batch, mask)
             B, h, w, _ = img.shape
             cur = (data_batch['pnp_pose'] if pose is None else pose).to(pc.device).float().contiguous()
-            vis, counts, _, _, _ = ops.visibility(pc, cur, K, h, w, sel, occ_mask=sel if occluders == 'mask' else None, radius=radius,
-                                                  rel_tol=rel_tol, abs_tol=abs_tol)
+            if sf is not None:
+                vis, counts = _visible_rows(data_batch, pc, cur, K, h, w, sel, dict(radius=radius, rel_tol=rel_tol, abs_tol=abs_tol, surfels=sf))
+            else:
+                vis, counts, _, _, _ = ops.visibility(pc, cur, K, h, w, sel, occ_mask=sel if occluders == 'mask' else None, radius=radius,
+                                                      rel_tol=rel_tol, abs_tol=abs_tol)
             data_batch['visible_mask'] = vis.view(B, pc.shape[2])
             data_batch['visible_counts'] = counts
 
@@ -613,7 +717,7 @@ class MultiHeadModel(Planned):
                 K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3)
             if vis_kw is not None:
                 every = torch.ones(B, N, dtype=torch.bool, device=dev)
-                sel = ops.visibility(pc, cur, Kg, h, w, every if sel is None else sel, **vis_kw)[0]
+                sel = _visible_rows(data_batch, pc, cur, Kg, h, w, every if sel is None else sel, vis_kw)[0]
             colors, painted, counts, _ = ops.paint_points(pc, cur, K.contiguous(), img, mask=sel, mode=mode)
             data_batch['point_colors'] = colors
             data_batch['point_painted'] = painted.view(B, N)
@@ -652,7 +756,7 @@ class MultiHeadModel(Planned):
                 data_batch['attr_map'] = attr_map
 
     def dense_depth(self, data_batch, pose=None, size=None, K=None, guide=None, attr=None, mask=None, visible=None, splat=0, radius=8,
-                    sigma_s=None, sigma_r=0.1, min_weight=1e-3, keep=True, fill=0.0):
+                    sigma_s=None, sigma_r=0.1, min_weight=1e-3, keep=True, fill=0.0, surfels=None):
         """Port extension: a dense depth map aligned to the image under `pose` (default 'pnp_pose'): the cloud is rendered
         (ops.render_points with `attr`, `mask`, `splat`) and the sparse map is filled in by the joint bilateral filter guided by the image
         (ops.densify with `radius`, `sigma_s`, `sigma_r`, `min_weight`, `keep`, `fill`).  By default at the full image's H x W: K is 'K'
@@ -660,13 +764,17 @@ class MultiHeadModel(Planned):
         than 4).  size = (H, W) and K (float32 [B, 3, 3] or [3, 3] for that size) go together as in render_depth; the guide (float32
         [B, Cg, H, W], Cg <= 4; False: no guide, a plain normalised convolution) must then have that size.  attr: float32 [B, C, N], C <= 4,
         a per-point quantity to densify alongside, or None.  visible as in paint_points: ops.visibility first runs on the geometric map
-        with 'K', the whole cloud occluding, and only the rows of `mask` it leaves visible are rendered.  The densify defaults are not
+        with 'K', the whole cloud occluding, and only the rows of `mask` it leaves visible are rendered.  surfels (None by
+        default, and then nothing changes): True, or a dict of ops.render_surfels' radius / range_slope / max_px / min_cos; the map handed to
+        ops.densify then comes from ops.render_surfels (normals from 'pc_normal', computed when absent; `splat` is not used) and
+        'surfel_counts' int32 [B, 4] is set.  The densify and surfel defaults are not
         tuned on real data.  Sets 'dense_depth_map' float32 [B, H, W] (+inf where not filled), 'dense_conf_map' float32 [B, H, W],
         'dense_counts' int32 [B, 3] = (samples, pixels with a sample in their window, filled pixels) and, with attr, 'dense_attr_map'
         float32 [B, C, H, W] (`fill` where not filled).  Not called by forward."""
         if (size is None) != (K is None):
             raise ValueError("dense_depth: size and K go together (both or neither)")
         vis_kw = _visible_kw(visible, "dense_depth")
+        sf_kw = _surfel_kw(surfels, "dense_depth")
         with torch.no_grad():
             pc = data_batch['pc'].float().contiguous()
             dev = pc.device
@@ -691,9 +799,13 @@ class MultiHeadModel(Planned):
                 K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3)
             if vis_kw is not None:
                 every = torch.ones(B, N, dtype=torch.bool, device=dev)
-                sel = ops.visibility(pc, cur, Kg, h, w, every if sel is None else sel, **vis_kw)[0]
-            _, depth_map, attr_map, _ = ops.render_points(pc, cur, K.contiguous(), H, W, attr=None if attr is None else attr.to(dev).float().contiguous(),
-                                                          mask=sel, splat=splat, fill=fill)
+                sel = _visible_rows(data_batch, pc, cur, Kg, h, w, every if sel is None else sel, vis_kw)[0]
+            a = None if attr is None else attr.to(dev).float().contiguous()
+            if sf_kw is not None:
+                _, depth_map, attr_map, data_batch['surfel_counts'], _, _ = ops.render_surfels(
+                    pc, _cloud_normals(data_batch, pc), cur, K.contiguous(), H, W, attr=a, mask=sel, fill=fill, **sf_kw)
+            else:
+                _, depth_map, attr_map, _ = ops.render_points(pc, cur, K.contiguous(), H, W, attr=a, mask=sel, splat=splat, fill=fill)
             dense, dense_attr, conf, _, counts = ops.densify(depth_map, guide=g, attr=attr_map, radius=radius, sigma_s=sigma_s, sigma_r=sigma_r,
                                                              min_weight=min_weight, keep=keep, fill=fill)
             data_batch['dense_depth_map'] = dense

@@ -1415,6 +1415,113 @@ def render_points(pts, pose, K, h, w, attr=None, mask=None, splat=0, fill=0.0):
     return index_map, depth_map, attr_map, counts
 
 
+SURFEL_MAX_PX = 16          # csrc/surfel.hip SF_MAX_PX
+
+
+def _surfel_scalar(who, name, v, hi=None):
+    """A finite float >= 0 (and <= hi) that is also finite as a float32, or a ValueError."""
+    try:
+        ok = not isinstance(v, bool) and 0.0 <= float(v) < float("inf") and float(torch.tensor(float(v), dtype=f32)) < float("inf")
+        ok = ok and (hi is None or float(v) <= hi)
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError("%s: %s must be a finite number in [0, %s], got %r" % (who, name, "inf)" if hi is None else "%g]" % hi, v))
+    return float(v)
+
+
+def render_surfels(pts, normals, pose, K, h, w, radius=0.1, range_slope=0.004, max_px=8, min_cos=0.1, attr=None, mask=None, fill=0.0,
+                   want_normal_map=False, want_surfel=False):
+    """The cloud drawn as oriented discs (surfels): every selected point is a disc in space, centred on it, perpendicular to its normal,
+    r = radius + range_slope z_c metres wide, and every pixel intersects its own ray with that disc (include/cmr_hip.h
+    cmr_render_surfels_f32).  pts and normals float32 [B, 3, N] (normals in the cloud's frame, any length; a zero row is
+    drawn fronto-parallel, a non-finite one is not drawn), pose float32 [B, 4, 4], K float32 [B, 3, 3] for the h x w map (1 <= h w <=
+    2^24) of the form [[fx, s, cx], [0, fy, cy], [0, 0, 1]] (checked on the device: a sample whose K is not draws nothing and has status
+    1), radius and range_slope finite and >= 0, 0 <= max_px <= SURFEL_MAX_PX (a disc is cut to the (2 max_px + 1)^2 pixels round its
+    centre), 0 <= min_cos <= 1 (a pixel whose ray meets the plane at a cosine below it is not covered), attr float32 [B, C, N] with
+    1 <= C <= POINT_IMAGE_MAX_C or None, mask [B, N] / [B*N] of bool / uint8 / int64 (None: every row), fill any float.  The nearest disc
+    owns a pixel, the lowest row on equal depths.  radius = 0.1 is one voxel of the prepared clouds and range_slope = 0.004 about half
+    of KITTI's ring spacing per metre of range; these defaults, max_px and min_cos are not tuned on real data.
+    -> (index_map int32 [B, h, w], -1 where no disc covers the pixel; depth_map float32 [B, h, w], the depth of the owner's plane there,
+    +inf where none; attr_map float32 [B, C, h, w] or None; counts int32 [B, 4] = (selected, drawn, pixels with an owner, status);
+    normal_map float32 [B, 3, h, w] (unit, facing the camera, 0 where no owner) or None; surfel float32 [B, 8, N] = (x_c, y_c, z_c, n_cx,
+    n_cy, n_cz, r, drawn) as computed, NaN in the first seven planes of undrawn rows, or None)."""
+    B, N, h, w = _point_image_args("render_surfels", pts, pose, K, h, w, mask)
+    if not torch.is_tensor(normals) or normals.dtype != f32 or tuple(normals.shape) != (B, 3, N):
+        raise ValueError("render_surfels: normals must be float32 [%d, 3, %d], got %s %s" % (
+            B, N, getattr(normals, "dtype", type(normals).__name__), tuple(normals.shape) if torch.is_tensor(normals) else ""))
+    C = 0
+    if attr is not None:
+        if not torch.is_tensor(attr) or attr.dtype != f32 or attr.dim() != 3 or attr.shape[0] != B or attr.shape[2] != N or not (
+                1 <= attr.shape[1] <= POINT_IMAGE_MAX_C):
+            raise ValueError("render_surfels: attr must be float32 [%d, C, %d] with 1 <= C <= %d, got %s %s" % (
+                B, N, POINT_IMAGE_MAX_C, getattr(attr, "dtype", type(attr).__name__), tuple(attr.shape) if torch.is_tensor(attr) else ""))
+        C = attr.shape[1]
+    radius = _surfel_scalar("render_surfels", "radius", radius)
+    range_slope = _surfel_scalar("render_surfels", "range_slope", range_slope)
+    min_cos = _surfel_scalar("render_surfels", "min_cos", min_cos, 1.0)
+    if not _is_int(max_px) or not 0 <= max_px <= SURFEL_MAX_PX:
+        raise ValueError("render_surfels: max_px must be an integer in [0, %d], got %r" % (SURFEL_MAX_PX, max_px))
+    try:
+        fill = float(fill)
+    except (TypeError, ValueError):
+        raise ValueError("render_surfels: fill must be a number, got %r" % (fill,))
+    ts = [t for t in (pts, normals, pose, K, attr, mask) if t is not None]
+    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
+        raise ValueError("render_surfels: every tensor must be a contiguous tensor on the same GPU")
+    if mask is not None and mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    dev = pts.device
+    index_map = torch.empty((B, h, w), dtype=torch.int32, device=dev)
+    depth_map = torch.empty((B, h, w), dtype=f32, device=dev)
+    attr_map = torch.empty((B, C, h, w), dtype=f32, device=dev) if attr is not None else None
+    normal_map = torch.empty((B, 3, h, w), dtype=f32, device=dev) if want_normal_map else None
+    surfel = torch.empty((B, 8, N), dtype=f32, device=dev) if want_surfel else None
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    nb = _lib.load().cmr_render_surfels_workspace_bytes(B, h, w)
+    ws = _ws(nb, dev)
+    _lib.call("cmr_render_surfels_f32", _p(pts), _p(normals), _p(mask), 1 if mask is None else mask.element_size(), _p(pose), _p(K), _p(attr),
+              C, B, N, h, w, radius, range_slope, int(max_px), min_cos, fill, _p(index_map), _p(depth_map), _p(normal_map), _p(attr_map),
+              _p(counts), _p(surfel), _p(ws), nb, _stream())
+    return index_map, depth_map, attr_map, counts, normal_map, surfel
+
+
+def depth_test(pts, pose, K, depth_map, mask, radius=0, rel_tol=0.05, abs_tol=0.0):
+    """ops.visibility's depth test against a z-buffer the caller brings (include/cmr_hip.h cmr_depth_test_f32): depth_map
+    float32 [B, h, w], +inf where empty -- ops.render_surfels' for a hole-free occluder, or ops.visibility's own, which gives that op's
+    flags back bit for bit.  pts float32 [B, 3, N], pose float32 [B, 4, 4], K float32 [B, 3, 3] for the h x w map, mask [B, N] / [B*N] of
+    bool / uint8 / int64 = the rows that are queried, 0 <= radius <= GUIDED_MAX_RADIUS, rel_tol and abs_tol finite and >= 0.  A queried
+    row in view (the predicate at radius 0) is visible iff its depth z <= zmin * (1 + rel_tol) + abs_tol, zmin = the least depth_map
+    value over the (2 radius + 1)^2 window round its own cell.  A surfel map is continuous, so radius defaults to 0 here; like rel_tol
+    = 0.05 it is not tuned on real data.
+    -> (visible bool [B*N], counts int32 [B, 3] = (selected, selected and in view, visible))."""
+    if not torch.is_tensor(depth_map) or depth_map.dim() != 3 or depth_map.dtype != f32:
+        raise ValueError("depth_test: depth_map must be float32 [B, h, w], got %s %s" % (
+            getattr(depth_map, "dtype", type(depth_map).__name__), tuple(depth_map.shape) if torch.is_tensor(depth_map) else ""))
+    Bd, h, w = depth_map.shape
+    if mask is None:
+        raise ValueError("depth_test: mask must be bool / uint8 / int64 (the rows that are queried), got None")
+    B, N, h, w = _point_image_args("depth_test", pts, pose, K, h, w, mask)
+    if Bd != B:
+        raise ValueError("depth_test: depth_map must be float32 [%d, h, w], got %s" % (B, tuple(depth_map.shape)))
+    if not _is_int(radius) or not 0 <= radius <= GUIDED_MAX_RADIUS:
+        raise ValueError("depth_test: radius must be an integer in [0, %d], got %r" % (GUIDED_MAX_RADIUS, radius))
+    if not _tol_ok(rel_tol):
+        raise ValueError("depth_test: rel_tol must be finite and >= 0, got %r" % (rel_tol,))
+    if not _tol_ok(abs_tol):
+        raise ValueError("depth_test: abs_tol must be finite and >= 0, got %r" % (abs_tol,))
+    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in (pts, pose, K, depth_map, mask)):
+        raise ValueError("depth_test: every tensor must be a contiguous tensor on the same GPU")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    dev = pts.device
+    visible = torch.empty((B * N,), dtype=torch.uint8, device=dev)
+    counts = torch.empty((B, 3), dtype=torch.int32, device=dev)
+    _lib.call("cmr_depth_test_f32", _p(pts), _p(mask), mask.element_size(), _p(pose), _p(K), _p(depth_map), B, N, h, w, int(radius),
+              float(rel_tol), float(abs_tol), _p(visible), _p(counts), _stream())
+    return visible.view(torch.bool), counts
+
+
 POSE_MI_MAX_BINS = 64       # csrc/pose_mi.hip PMI_MAX_BINS
 POSE_MI_SLICE = 4096        # csrc/pose_mi.hip PMI_SLICE: rows per workgroup
 

@@ -1,6 +1,6 @@
 """Command-line helpers shared by Test_Geo.py and Test_Agent.py: the round lists of --guided / --refine, the --visible flags, the --paint flags
-with the per-pair PLY output, the --dense-depth flags with the per-pair PFM output, the --verify-mi flags, the --from-raw flag, and the closing
-recall block."""
+with the per-pair PLY output, the --dense-depth flags with the per-pair PFM output, the surfel flags that extend --dense-depth and --visible,
+the --verify-mi flags, the --from-raw flag, and the closing recall block."""
 import numpy as np
 
 
@@ -120,18 +120,61 @@ def dense_option(ap, args, max_radius, parent=None, parent_given=True):
 
 def dense_pairs(model, data, pose, option, first_index):
     """Densify the batch's rendered depth under `pose` (MultiHeadModel.dense_depth at the image's size, guided by the image), write one
-    PFM per pair -- DIR/pair_<first_index + b>_depth.pfm, unfilled pixels as 0 -- and print the batch's line."""
+    PFM per pair -- DIR/pair_<first_index + b>_depth.pfm, unfilled pixels as 0 -- and print the batch's line.  An option that
+    surfel_option extended by a fifth entry (--dense-surfels) renders the cloud as surfels and prints one more line."""
     import os
 
     from .pfm import write_pfm
-    out_dir, radius, sigma_r, visible = option
+    out_dir, radius, sigma_r, visible = option[:4]
+    kw = dict(surfels=option[4]) if len(option) > 4 else {}
     os.makedirs(out_dir, exist_ok=True)
-    model.dense_depth(data, pose=pose, radius=radius, sigma_r=sigma_r, visible=True if visible else None)
+    model.dense_depth(data, pose=pose, radius=radius, sigma_r=sigma_r, visible=True if visible else None, **kw)
     dense = data['dense_depth_map'].cpu()
     for b in range(dense.shape[0]):
         write_pfm(os.path.join(out_dir, "pair_%d_depth.pfm" % (first_index + b)), dense[b])
     c = data['dense_counts'].sum(0).cpu().tolist()
     print("dense", int(c[2]), "of", dense.shape[0] * dense.shape[1] * dense.shape[2], "from", int(c[0]))
+    if kw:
+        s = data['surfel_counts'].sum(0).cpu().tolist()
+        print("surfels", int(s[1]), "of", int(s[0]), "own", int(s[2]), "of", dense.shape[0] * dense.shape[1] * dense.shape[2])
+
+
+def add_surfel_flags(ap):
+    """--dense-surfels (with --dense-depth), --visible-surfels (with --visible) and the three values both share."""
+    ap.add_argument('--dense-surfels', action='store_true', help="with --dense-depth: render the cloud as oriented discs from its normals "
+                    "instead of one cell per point")
+    ap.add_argument('--visible-surfels', action='store_true', help="with --visible: the z-buffer is the surfel depth map of the whole cloud")
+    ap.add_argument('--surfel-radius', type=float, default=None, metavar="R", help="with --dense-surfels / --visible-surfels: disc radius in "
+                    "metres at range 0 (default 0.1)")
+    ap.add_argument('--surfel-slope', type=float, default=None, metavar="S", help="with --dense-surfels / --visible-surfels: metres of radius "
+                    "per metre of range (default 0.004)")
+    ap.add_argument('--surfel-max-px', type=int, default=None, metavar="M", help="with --dense-surfels / --visible-surfels: a disc is cut to "
+                    "the (2M + 1)^2 pixels round its centre (default 8)")
+
+
+def surfel_option(ap, args, dense, visible, max_px):
+    """dense_option's and visible_option's results with the surfel flags worked in -> (dense, visible): --dense-surfels appends the
+    dict dense_depth(surfels=) takes to the dense option, --visible-surfels puts it under the key 'surfels' of the visible dict.
+    Neither flag: both come back as they are.  ap.error on a misplaced or malformed flag."""
+    given = {"radius": args.surfel_radius, "range_slope": args.surfel_slope, "max_px": args.surfel_max_px}
+    given = {k: v for k, v in given.items() if v is not None}
+    if args.dense_surfels and dense is None:
+        ap.error("--dense-surfels belongs to --dense-depth")
+    if args.visible_surfels and visible is None:
+        ap.error("--visible-surfels belongs to --visible")
+    if not (args.dense_surfels or args.visible_surfels):
+        if given:
+            ap.error("--surfel-radius / --surfel-slope / --surfel-max-px belong to --dense-surfels or --visible-surfels")
+        return dense, visible
+    if not all(0.0 <= given.get(k, 0.0) < float("inf") for k in ("radius", "range_slope")):
+        ap.error("--surfel-radius and --surfel-slope must be finite and >= 0")
+    if not 0 <= given.get("max_px", 0) <= max_px:
+        ap.error("--surfel-max-px must lie in [0, %d]" % max_px)
+    if args.dense_surfels:
+        dense = tuple(dense) + (given or True,)
+    if args.visible_surfels:
+        visible = dict(visible, surfels=given or True)
+    return dense, visible
 
 
 def add_mi_flags(ap, parent=None):

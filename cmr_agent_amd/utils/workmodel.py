@@ -184,6 +184,15 @@ WORK = {
     "cmr_render_points_f32": lambda a: (40.0 * a["B"] * a["N"] + (2 * a["splat"] + 1) ** 2 * a["B"] * a["h"] * a["w"],
                                         a["B"] * a["N"] * (12 + a["mask_bytes"] + 8)
                                         + a["B"] * a["h"] * a["w"] * (8 + 8 * (2 * a["splat"] + 1) ** 2 + 8 + 8 * a["C"])),
+    # DESIGN.md 4z, every row taken as drawn with the whole (2 max_px + 1)^2 window covered (an upper bound: the footprint depends on the
+    # data): the fill of the key map, per row the point, its normal and mask, per window pixel ~30 FLOP of ray test and an 8-byte key read
+    # and atomic, per pixel the key, 8 B of index / depth and per plane a gathered 4 B in and 4 B out.  The depth test: visibility's test
+    # with the projection in front of it
+    "cmr_render_surfels_f32": lambda a: (80.0 * a["B"] * a["N"] + 30.0 * (2 * a["max_px"] + 1) ** 2 * a["B"] * a["N"],
+                                         a["B"] * a["N"] * (24 + a["mask_bytes"] + 16 * (2 * a["max_px"] + 1) ** 2)
+                                         + a["B"] * a["h"] * a["w"] * (8 + 8 + 8 + 8 * a["C"])),
+    "cmr_depth_test_f32": lambda a: ((40.0 + (2 * a["radius"] + 1) ** 2) * a["B"] * a["N"],
+                                     a["B"] * a["N"] * (12 + a["mask_bytes"] + 4 * (2 * a["radius"] + 1) ** 2 + 1)),
     # DESIGN.md 4v, every row taken as selected and counted under every pose: per (row, pose) ~40 FLOP of projection, 9 for the lerps when
     # bilinear and 2 for the bin, and 1 or 4 gathered grey values of 4 B; the point, its attribute and mask are read once per chunk of
     # min(8, 8192 / bins^2) poses; hist is filled, added to and read once (4 B a cell each)

@@ -569,6 +569,82 @@ int cmr_render_points_f32(const float* pts, const void* mask, int mask_bytes, co
                           int B, int N, int h, int w, int splat, float fill, int32_t* index_map, float* depth_map, float* attr_map,
                           int32_t* counts, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+/* Oriented-disc (surfel) rendering of the cloud from its normals, and the depth test against a map the caller brings (port extension,
+ * DESIGN.md 4z; ops.render_surfels / ops.depth_test, MultiHeadModel.render_surfels, dense_depth(surfels=), visible=dict(surfels=...)).
+ * Every selected point is drawn as a disc in space: centred on the point, perpendicular to its normal, r metres wide; every pixel of
+ * its window intersects its own ray with the disc's plane.  pts f32 [B][3][N] (data['pc']); normals f32 [B][3][N] in the cloud's frame,
+ * any length (the zero vector = no normal); mask [B*N] with mask_bytes 1 or 8 (null: every row; mask_bytes is checked all the same);
+ * pose f32 [B][4][4] mapping pts into the camera frame; K f32 [B][3][3] for the h x w map, 1 <= h*w <= 2^24; radius >= 0 and
+ * range_slope >= 0, both finite; 0 <= max_px <= 16; 0 <= min_cos <= 1; attr f32 [B][C][N] with attr_map, 1 <= C <= 64 (both or
+ * neither, C = 0 without); fill any float; 1 <= B <= 65535, 1 <= N <= 65535 * 256.  Anything else is refused up front with CMR_EINVAL;
+ * nothing depends on the data, and K is never read on the host.
+ * Camera model: fx = K[0], s = K[1], cx = K[2], fy = K[4], cy = K[5].  A sample whose K does not have K[3] = 0, K[6] = K[7] = 0,
+ * K[8] = 1 and fx, fy finite and > 0 draws nothing and reports status 1.
+ * Per selected row n, in fp32:
+ *   X_c = (x_c, y_c, z_c) = R x + t and p = K X_c, u = p0 / p2, v = p1 / p2 by cmr_guided_match_f32's fmaf chains (so z_c = p2 under
+ *     the camera model, and the centre's cell agrees bit for bit with the other pose operations);
+ *   n_c = R n by the same pattern without the translation: n_cx = fmaf(R00, nx, fmaf(R01, ny, R02 * nz)), likewise y and z;
+ *   r = range_slope * z_c + radius, the product and the sum each rounded (no fma).
+ * The row is DRAWN iff it is selected, p2 > 0, u and v are finite, the (2 max_px + 1)^2 window round (rint u, rint v) touches the map
+ * (cmr_guided_match_f32's predicate at radius max_px: the centre itself may lie outside), the three floats of its normal are finite, r is
+ * finite and > 0, and z_c > r (no part of the disc reaches the camera plane).
+ * Per pixel (x, y) of a drawn row's window that lies inside the map, pixel centres on the integers, every operation below a plain fp32
+ * operator rounded on its own (no fma), n = n_c:
+ *   dy = (y - cy) / fy;   dx = ((x - cx) - s * dy) / fx;   n2 = (nx * nx + ny * ny) + nz * nz;
+ *   if n2 == 0 (no normal: fronto-parallel):  tau = z_c;  o = (tau * dx - x_c, tau * dy - y_c, 0);
+ *   else:  nd = (nx * dx + ny * dy) + nz;  nX = (nx * x_c + ny * y_c) + nz * z_c;  tau = nX / nd;
+ *          rejected unless nd != 0, tau finite and tau > 0;
+ *          rejected unless nd * nd >= ((min_cos * min_cos) * n2) * ((dx * dx + dy * dy) + 1)   (the grazing cap: the cosine between the
+ *          ray and the normal is at least min_cos; no square root, no unit normal);
+ *          o = (tau * dx - x_c, tau * dy - y_c, tau - z_c);
+ *   COVERED iff (ox * ox + oy * oy) + oz * oz <= r * r (the rim is inclusive).  The pixel's depth under this row is tau.
+ * A pixel keeps the least 64-bit key (bits of tau) << 32 | n over the rows that cover it (one unsigned 64-bit atomic min; positive
+ * floats order like their bits): the nearest surfel wins, equal depths go to the lowest n, the order of arrival is irrelevant.
+ * The window walked is smaller than (2 max_px + 1)^2 where it provably holds every covered pixel.  A covered pixel's ray meets the disc
+ * at Q = X_c + o with |o| <= r, so Q_z >= z_c - r > 0, and Q_y / Q_z - y_c / z_c = (o_y - (y_c / z_c) o_z) / Q_z, at most
+ * r sqrt(1 + (y_c / z_c)^2) / (z_c - r) <= r (1 + |y_c / z_c|) / (z_c - r) in size; likewise in x.  With x = cx + fx Q_x / Q_z + s Q_y / Q_z
+ * the pixel lies within hx = (fx (1 + |x_c / z_c|) + |s| (1 + |y_c / z_c|)) r / (z_c - r) of u and within hy = fy (1 + |y_c / z_c|) r /
+ * (z_c - r) of v (f r / z_c alone is too small off the axis and for a disc that is near).  fp32 rounding moves the rim by a small
+ * fraction of a pixel, so both are widened by 2^-12 of themselves and by one pixel: the walk covers floor(u - hx) .. ceil(u + hx)
+ * by floor(v - hy) .. ceil(v + hy), cut to the (2 max_px + 1)^2 window and to the map.
+ *   index_map int32 [B][h*w]   the owning row, -1 where there is none;
+ *   depth_map f32 [B][h*w]     the owner's tau at that pixel, +inf where there is none;
+ *   normal_map (optional) f32 [B][3][h*w]: the owner's n_c / sqrtf(n2) (correctly rounded square root and divisions), negated when
+ *     nX > 0 so that it faces the camera; (0, 0, -1) for a zero normal; 0 where there is no owner;
+ *   attr_map f32 [B][C][h*w] = attr[b][c][owner], `fill` where there is none;
+ *   counts int32 [B][4]      = {selected, drawn, pixels with an owner, status}; the call writes all four;
+ *   surfel (optional) f32 [B][8][N] = (x_c, y_c, z_c, n_cx, n_cy, n_cz, r, drawn as 0 / 1) as computed, NaN in the first seven planes of
+ *     the rows that are not drawn: a float32 restatement of the per-pixel part started from it gives index_map and depth_map bit for bit.
+ * Accuracy of tau against exact arithmetic on the same inputs, u = 2^-24, for r <= z_c / 2: a term of nd carries at most 7 roundings
+ * (the four of dx, its product, two sums), the terms sum to at most sqrt(3) |n| |d| in size (d = (dx, dy, 1)), and the grazing cap gives
+ * |nd| >= min_cos |n| |d|: at most 7 sqrt(3) u / min_cos < 12.2 u / min_cos relative.  A term of nX carries 3 (its product, two sums) and
+ * the terms sum to at most sqrt(3) |n| |X_c|, with
+ * |X_c| <= tau |d| + r <= 2 tau |d| and |nX| = tau |nd|: at most 6 sqrt(3) u / min_cos < 10.4 u / min_cos.  The division adds u.  In all
+ * |tau - exact| <= 24 u tau / min_cos = 12 2^-23 tau / min_cos to first order; the tests allow c = 16: 16 2^-23 tau / min_cos.  The error
+ * X_c itself carries (three fmas per component: 3 u S_j, S_j = sum_k |R_jk| |x_k| + |t_j|) moves tau by at most |n| |dX| / |nd| <=
+ * 3 sqrt(3) u max_j S_j / min_cos; the tests allow 8 2^-23 max_j S_j / min_cos for it, cmr_visibility_f32's projection term.
+ * Three launches on the stream whatever the data (fill of the key map and counts, splat, resolve), no memset, no host round trip, no
+ * floating-point atomic; every output element is a plain store by the thread that owns it, the key map is an integer atomic min, counts
+ * are integer atomics, one per workgroup and word: two calls agree bit for bit and a sample depends on its own rows only.
+ * Workspace: cmr_render_surfels_workspace_bytes(B, h, w), 16-byte aligned (the key map).
+ *
+ * cmr_depth_test_f32: cmr_visibility_f32's test against a z-buffer the caller brings -- Z f32 [B][h*w], 4-byte aligned, +inf = empty, a
+ * NaN cell is ignored -- e.g. the depth_map above.  pts, mask (not null here: the rows that are queried), mask_bytes, pose, K, radius
+ * 0 .. 16, rel_tol and abs_tol are cmr_visibility_f32's; the projection, the in-view predicate (radius 0), the window minimum zmin over
+ * the (2 radius + 1)^2 cells clipped to the map and bound = zmin * opr + abs_tol, opr = (float)(1.0 + (double)rel_tol), the product and
+ * the sum rounded separately, are its operations: handed cmr_visibility_f32's own depth_map it returns that call's `visible` bit for
+ * bit.  K is used as cmr_visibility_f32 uses it (all nine entries; no camera-model check).
+ *   visible u8 [B*N]          0 for unselected rows;
+ *   counts int32 [B][3]     = {selected, selected and in view, visible}; the call zeroes it.
+ * Two launches on the stream (zero of counts, test), no workspace, no host round trip. */
+int64_t cmr_render_surfels_workspace_bytes(int B, int h, int w);
+int cmr_render_surfels_f32(const float* pts, const float* normals, const void* mask, int mask_bytes, const float* pose, const float* K,
+                           const float* attr, int C, int B, int N, int h, int w, float radius, float range_slope, int max_px, float min_cos,
+                           float fill, int32_t* index_map, float* depth_map, float* normal_map, float* attr_map, int32_t* counts,
+                           float* surfel, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int cmr_depth_test_f32(const float* pts, const void* mask, int mask_bytes, const float* pose, const float* K, const float* Z, int B, int N,
+                       int h, int w, int radius, float rel_tol, float abs_tol, uint8_t* visible, int32_t* counts, hipStream_t stream);
+
 /* Pose scoring by mutual information (port extension; ops.pose_mi, MultiHeadModel.score_poses_mi, Test_Geo.py /
  * Test_Agent.py --verify-mi): per candidate pose the joint histogram of a per-point attribute (the LiDAR reflectance) and the grey value
  * of the pixel the point lands on, its entropies and the mutual information (Pandey et al., targetless camera-LiDAR calibration) -- a
