@@ -630,7 +630,7 @@ __global__ __launch_bounds__(256) void focal_bwd_kernel(const float* __restrict_
   const float m = fmaxf(z0, z1);
   const float e0 = expf(z0 - m), e1 = expf(z1 - m);
   const float p[2] = {e0 / (e0 + e1), e1 / (e0 + e1)};
-  const int lab = (int)label[r];
+  const int lab = label[r] != 0 ? 1 : 0;                            // as the forward reads it (losses.hip focal_partial_kernel)
   float c[2];
 #pragma unroll
   for (int k = 0; k < 2; ++k) {

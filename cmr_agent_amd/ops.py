@@ -892,9 +892,10 @@ def focal_metrics(logits_rows, label_i64, alpha, B):
     return out
 
 
-def circle_loss(pc_feat_rows, img_feat_nhwc, pc_idx, xy_int, xy_float, B, N, dist_thres, pos_margin, neg_margin, log_scale, lam):
+def circle_loss(pc_feat_rows, img_feat_nhwc, pc_idx, xy_int, xy_float, B, N, dist_thres, pos_margin, neg_margin, log_scale, lam, terms=None):
     """Circle loss over the sampled (point, pixel) pairs: pc_feat rows [B*N,64], img_feat [B,h,w,64], pc_idx int64 [B,n],
-    xy_int int64 [B,2,n], xy_float [B,2,n] -> float32 [1]."""
+    xy_int int64 [B,2,n], xy_float [B,2,n] -> float32 [1].  terms: a list that receives the float32 [B, 2n] device view of the
+    softplus terms the loss is the mean of (per sample: the n rows, then the n columns; csrc/losses.hip circle_terms_kernel)."""
     _, h, w, _ = img_feat_nhwc.shape
     n = pc_idx.shape[1]
     ws_bytes = _lib.load().cmr_circle_loss_workspace_bytes(B, n)
@@ -903,6 +904,9 @@ def circle_loss(pc_feat_rows, img_feat_nhwc, pc_idx, xy_int, xy_float, B, N, dis
     _lib.call("cmr_circle_loss_f32", _p(_rows(pc_feat_rows)), _p(img_feat_nhwc), _p(pc_idx), _p(xy_int), _p(xy_float), B, N, h, w, n,
               float(dist_thres), float(pos_margin), float(neg_margin), float(log_scale), float(lam), _p(out), _p(ws), ws_bytes,
               _stream())
+    if terms is not None:
+        first = 2 * B * n * n + B                           # float words of EP, EN [B][n][n] and the [B] partial sums ahead of the terms
+        terms.append(ws[first:first + 2 * B * n].view(B, 2 * n))
     return out
 
 

@@ -321,7 +321,8 @@ int cmr_vecattn_front_kv_train_f32(const float* feat, int64_t ldf, const float* 
 /* ---- loss / metric values of the heads (forward only) ---------------------------------------- */
 
 /* MultiHeadModel.py:68-97 on 2-class logits rows [rows][ld >= 2] with int64 labels: out4 = {focal loss (focal_loss.py:55-110,
- * gamma 2, mean), precision, recall, accuracy}; rows = B * n (accuracy is (correct / B) / n as in the reference). */
+ * gamma 2, mean), precision, recall, accuracy}; rows = B * n (accuracy is (correct / B) / n as in the reference).  A non-zero
+ * label is class 1, here and in cmr_focal_bwd_f32. */
 int64_t cmr_focal_metrics_workspace_bytes(int64_t rows);
 int cmr_focal_metrics_f32(const float* logits, int64_t ld, const int64_t* label, float alpha, int64_t rows, int B, float* out4,
                           void* workspace, int64_t workspace_bytes, hipStream_t stream);
