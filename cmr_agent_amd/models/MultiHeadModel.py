@@ -275,6 +275,52 @@ def _visible_kw(visible, who):
     return kw
 
 
+def _batch_K(K, B, dev):
+    """K as contiguous float32 [B, 3, 3] on dev; a [3, 3] K serves every sample"""
+    K = K.to(dev).float()
+    return (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3).contiguous()
+
+
+def _size_with_K(size, K, who):
+    if (size is None) != (K is None):
+        raise ValueError("%s: size and K go together (both or neither)" % who)
+
+
+def _port_camera(data_batch, size, K, who):
+    """The cloud and the camera of a port extension -> (pc float32 [B, 3, N], h, w, K float32 [B, 3, 3] on pc's device): size = (h, w)
+    with the K for it -- the two go together, refused before the batch is looked at -- or neither: the geometric map's h x w with 'K'."""
+    _size_with_K(size, K, who)
+    pc = data_batch['pc'].float().contiguous()
+    if size is None:
+        size, K = _geo_rows(data_batch)[1].shape[1:3], data_batch['K']
+    h, w = size
+    return pc, h, w, _batch_K(K, pc.shape[0], pc.device)
+
+
+def _image_camera(data_batch, pc, pose, K, image_size, sel, vis_kw):
+    """The camera of a port extension that works on an image of image_size = (H, W), and the rows it uses -> (K float32 [B, 3, 3], sel).
+    K as given; by default 'K' -- which refers to the geometric map's h x w -- with row 0 scaled by W / w and row 1 by H / h, the inverse
+    of the loader's camera_matrix scaling.  With vis_kw, sel (None: every row) is cut to the rows _visible_rows leaves under `pose` on the
+    geometric map."""
+    B, _, N = pc.shape
+    if K is None or vis_kw is not None:
+        _, h, w, Kg = _port_camera(data_batch, None, None, "")
+    if K is None:
+        H, W = image_size
+        K = Kg * torch.tensor([W / w, H / h, 1.0], dtype=torch.float32, device=pc.device).view(1, 3, 1)
+    else:
+        K = _batch_K(K, B, pc.device)
+    if vis_kw is not None:
+        every = torch.ones(B, N, dtype=torch.bool, device=pc.device)
+        sel = _visible_rows(data_batch, pc, pose.contiguous(), Kg, h, w, every if sel is None else sel, vis_kw)[0]
+    return K, sel
+
+
+def _pose_arg(data_batch, pose, dev):
+    """`pose`, by default 'pnp_pose', as contiguous float32 on dev"""
+    return (data_batch['pnp_pose'] if pose is None else pose).to(dev).float().contiguous()
+
+
 def _cloud_normals(data_batch, pc, radius=0.6, again=False):
     """data['pc_normal'] on pc's device, computed by ops.point_normals when the batch has none or `again` is set: one call per sample,
     the op takes one cloud (the sign of a normal does not matter to a disc) -> float32 [B, 3, N]."""
@@ -387,8 +433,7 @@ class MultiHeadModel(Planned):
                                                                            gt_xy=_gt_xy(data_batch, dev), thr=SUBPIXEL_INLIER_THRES)
             else:
                 uv = torch.stack([p % w, torch.div(p, w, rounding_mode='floor')], 1).float().contiguous()
-            K = data_batch['K'].to(dev).float()
-            K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3).contiguous()
+            K = _batch_K(data_batch['K'], B, dev)
             pose, inliers, status = ops.pnp_ransac(pc.float().contiguous(), uv, use.contiguous(), K, n_hyp=n_hyp, thr=thr, seed=seed,
                                                    refine_iters=refine_iters)
             data_batch['pnp_pose'] = pose
@@ -426,10 +471,9 @@ class MultiHeadModel(Planned):
             feat, img = _geo_rows(data_batch)
             B, h, w, _ = img.shape
             N = pc.shape[2]
-            cur = (data_batch['pnp_pose'] if pose is None else pose).to(dev).float().contiguous()
+            cur = _pose_arg(data_batch, pose, dev)
             sel = (data_batch['pc_overlap_pred'] if mask is None else mask).to(dev).contiguous()
-            K = data_batch['K'].to(dev).float()
-            K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3).contiguous()
+            K = _batch_K(data_batch['K'], B, dev)
             xy = _gt_xy(data_batch, dev) if ('point_xy_float_all' in data_batch or 'pc_in_cam_space' in data_batch) else None
             ov = None if img_overlap is None else img_overlap.to(dev).reshape(B, -1).bool()
             counts, sub_counts, vis_counts, inliers, status = [], [], [], None, None
@@ -466,9 +510,7 @@ class MultiHeadModel(Planned):
         feat, img = _geo_rows(data_batch)
         B = img.shape[0]
         sel = (data_batch['pc_overlap_pred'] if mask is None else mask).to(dev).contiguous()
-        K = data_batch['K'].to(dev).float()
-        K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3).contiguous()
-        return pc, feat, img, sel, K
+        return pc, feat, img, sel, _batch_K(data_batch['K'], B, dev)
 
     def score_poses(self, data_batch, poses, radius=0, tau=0.8, mask=None):
         """Port extension: score candidate poses against the geometric features, with no ground truth (ops.pose_score).
@@ -519,19 +561,7 @@ class MultiHeadModel(Planned):
             grey = img.contiguous()
             poses = poses.to(dev).float().contiguous()
             sel = None if mask is None else mask.to(dev).contiguous()
-            if K is None or vis_kw is not None:
-                h, w = _geo_rows(data_batch)[1].shape[1:3]
-                Kg = data_batch['K'].to(dev).float()
-                Kg = (Kg if Kg.dim() == 3 else Kg.unsqueeze(0)).expand(B, 3, 3).contiguous()
-            if K is None:
-                H, W = grey.shape[1:]
-                K = Kg * torch.tensor([W / w, H / h, 1.0], dtype=torch.float32, device=dev).view(1, 3, 1)
-            else:
-                K = K.to(dev).float()
-                K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3)
-            if vis_kw is not None:
-                every = torch.ones(B, N, dtype=torch.bool, device=dev)
-                sel = _visible_rows(data_batch, pc, poses[:, 0].contiguous(), Kg, h, w, every if sel is None else sel, vis_kw)[0]
+            K, sel = _image_camera(data_batch, pc, poses[:, 0], K, grey.shape[1:], sel, vis_kw)
             if attr_range is None:
                 ok = torch.isfinite(a) if sel is None else torch.isfinite(a) & (sel.view(B, N) != 0)
                 inf = torch.full_like(a, float("inf"))
@@ -542,7 +572,7 @@ class MultiHeadModel(Planned):
                 # the range stays on the device: the attribute is mapped onto [0, 1] there and the kernel bins the unit range
                 a = ((a - lo) / (hi - lo)).contiguous()
                 attr_range = (0.0, 1.0)
-            mi, ent, counts, selected, _ = ops.pose_mi(pc, a, grey, sel, poses, K.contiguous(), bins=bins, mode=mode, attr_range=attr_range,
+            mi, ent, counts, selected, _ = ops.pose_mi(pc, a, grey, sel, poses, K, bins=bins, mode=mode, attr_range=attr_range,
                                                        grey_range=grey_range)
             data_batch['pose_mi'] = mi
             data_batch['pose_mi_entropy'] = ent
@@ -572,7 +602,7 @@ class MultiHeadModel(Planned):
             pc, feat, img, sel, K = self._score_args(data_batch, mask)
             dev = pc.device
             B = pc.shape[0]
-            cur = (data_batch['pnp_pose'] if pose is None else pose).to(dev).float().contiguous()
+            cur = _pose_arg(data_batch, pose, dev)
             rows = torch.arange(B, device=dev)
             best = None
             lsel, vis_counts = sel, []
@@ -611,20 +641,10 @@ class MultiHeadModel(Planned):
         [B, h, w] (-1 where no disc covers the pixel), 'surfel_depth_map' float32 [B, h, w] (+inf there), 'surfel_normal_map' float32
         [B, 3, h, w] (unit, facing the camera; 0 there), 'surfel_counts' int32 [B, 4] = (selected, drawn, pixels with an owner, status) and,
         with attr, 'surfel_attr_map' float32 [B, C, h, w] (`fill` there).  Not called by forward."""
-        if (size is None) != (K is None):
-            raise ValueError("render_surfels: size and K go together (both or neither)")
         with torch.no_grad():
-            pc = data_batch['pc'].float().contiguous()
+            pc, h, w, K = _port_camera(data_batch, size, K, "render_surfels")
             dev = pc.device
-            B = pc.shape[0]
-            if size is None:
-                h, w = _geo_rows(data_batch)[1].shape[1:3]
-                K = data_batch['K']
-            else:
-                h, w = size
-            K = K.to(dev).float()
-            K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3).contiguous()
-            cur = (data_batch['pnp_pose'] if pose is None else pose).to(dev).float().contiguous()
+            cur = _pose_arg(data_batch, pose, dev)
             nrm = _cloud_normals(data_batch, pc) if normals is None else normals.to(dev).float().contiguous()
             index_map, depth_map, attr_map, counts, normal_map, _ = ops.render_surfels(
                 pc, nrm, cur, K, h, w, radius=radius, range_slope=range_slope, max_px=max_px, min_cos=min_cos,
@@ -656,7 +676,7 @@ class MultiHeadModel(Planned):
         with torch.no_grad():
             pc, _, img, sel, K = self._score_args(data_batch, mask)
             B, h, w, _ = img.shape
-            cur = (data_batch['pnp_pose'] if pose is None else pose).to(pc.device).float().contiguous()
+            cur = _pose_arg(data_batch, pose, pc.device)
             if sf is not None:
                 vis, counts = _visible_rows(data_batch, pc, cur, K, h, w, sel, dict(radius=radius, rel_tol=rel_tol, abs_tol=abs_tol, surfels=sf))
             else:
@@ -670,20 +690,11 @@ class MultiHeadModel(Planned):
         cell of its rounded projection and a cell keeps the nearest depth (ops.visibility's z-buffer).  By default on the geometric map's
         h x w with 'K'; size = (H, W) together with K (float32 [B, 3, 3] or [3, 3] for that resolution) renders at another one, e.g. the
         full image.  Sets 'depth_map' float32 [B, h, w], +inf in the cells no point falls into.  Not called by forward."""
-        if (size is None) != (K is None):
-            raise ValueError("render_depth: size and K go together (both or neither)")
         with torch.no_grad():
-            pc = data_batch['pc'].float().contiguous()
+            pc, h, w, K = _port_camera(data_batch, size, K, "render_depth")
             dev = pc.device
             B, _, N = pc.shape
-            if size is None:
-                h, w = _geo_rows(data_batch)[1].shape[1:3]
-                K = data_batch['K']
-            else:
-                h, w = size
-            K = K.to(dev).float()
-            K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3).contiguous()
-            cur = (data_batch['pnp_pose'] if pose is None else pose).to(dev).float().contiguous()
+            cur = _pose_arg(data_batch, pose, dev)
             every = torch.ones(B, N, dtype=torch.bool, device=dev)
             data_batch['depth_map'] = ops.visibility(pc, cur, K, h, w, every, radius=0, want_depth_map=True)[2]
 
@@ -703,22 +714,10 @@ class MultiHeadModel(Planned):
             dev = pc.device
             B, _, N = pc.shape
             img = (data_batch['img'] if image is None else image).to(dev).float().contiguous()
-            cur = (data_batch['pnp_pose'] if pose is None else pose).to(dev).float().contiguous()
+            cur = _pose_arg(data_batch, pose, dev)
             sel = None if mask is None else mask.to(dev).contiguous()
-            if K is None or vis_kw is not None:
-                h, w = _geo_rows(data_batch)[1].shape[1:3]
-                Kg = data_batch['K'].to(dev).float()
-                Kg = (Kg if Kg.dim() == 3 else Kg.unsqueeze(0)).expand(B, 3, 3).contiguous()
-            if K is None:
-                H, W = img.shape[2:]
-                K = Kg * torch.tensor([W / w, H / h, 1.0], dtype=torch.float32, device=dev).view(1, 3, 1)
-            else:
-                K = K.to(dev).float()
-                K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3)
-            if vis_kw is not None:
-                every = torch.ones(B, N, dtype=torch.bool, device=dev)
-                sel = _visible_rows(data_batch, pc, cur, Kg, h, w, every if sel is None else sel, vis_kw)[0]
-            colors, painted, counts, _ = ops.paint_points(pc, cur, K.contiguous(), img, mask=sel, mode=mode)
+            K, sel = _image_camera(data_batch, pc, cur, K, img.shape[2:], sel, vis_kw)
+            colors, painted, counts, _ = ops.paint_points(pc, cur, K, img, mask=sel, mode=mode)
             data_batch['point_colors'] = colors
             data_batch['point_painted'] = painted.view(B, N)
             data_batch['paint_counts'] = counts
@@ -732,20 +731,10 @@ class MultiHeadModel(Planned):
         Sets 'index_map' int32 [B, h, w] (-1 where no point owns the pixel), 'render_depth_map' float32 [B, h, w] (+inf there),
         'render_counts' int32 [B, 3] = (selected, selected and in view, pixels with an owner) and, with attr, 'attr_map' float32
         [B, C, h, w] (`fill` there).  Not called by forward."""
-        if (size is None) != (K is None):
-            raise ValueError("render_points: size and K go together (both or neither)")
         with torch.no_grad():
-            pc = data_batch['pc'].float().contiguous()
+            pc, h, w, K = _port_camera(data_batch, size, K, "render_points")
             dev = pc.device
-            B = pc.shape[0]
-            if size is None:
-                h, w = _geo_rows(data_batch)[1].shape[1:3]
-                K = data_batch['K']
-            else:
-                h, w = size
-            K = K.to(dev).float()
-            K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3).contiguous()
-            cur = (data_batch['pnp_pose'] if pose is None else pose).to(dev).float().contiguous()
+            cur = _pose_arg(data_batch, pose, dev)
             index_map, depth_map, attr_map, counts = ops.render_points(
                 pc, cur, K, h, w, attr=None if attr is None else attr.to(dev).float().contiguous(),
                 mask=None if mask is None else mask.to(dev).contiguous(), splat=splat, fill=fill)
@@ -771,41 +760,27 @@ class MultiHeadModel(Planned):
         tuned on real data.  Sets 'dense_depth_map' float32 [B, H, W] (+inf where not filled), 'dense_conf_map' float32 [B, H, W],
         'dense_counts' int32 [B, 3] = (samples, pixels with a sample in their window, filled pixels) and, with attr, 'dense_attr_map'
         float32 [B, C, H, W] (`fill` where not filled).  Not called by forward."""
-        if (size is None) != (K is None):
-            raise ValueError("dense_depth: size and K go together (both or neither)")
+        _size_with_K(size, K, "dense_depth")
         vis_kw = _visible_kw(visible, "dense_depth")
         sf_kw = _surfel_kw(surfels, "dense_depth")
         with torch.no_grad():
             pc = data_batch['pc'].float().contiguous()
             dev = pc.device
-            B, _, N = pc.shape
-            cur = (data_batch['pnp_pose'] if pose is None else pose).to(dev).float().contiguous()
+            cur = _pose_arg(data_batch, pose, dev)
             sel = None if mask is None else mask.to(dev).contiguous()
             if guide is None:
                 guide = data_batch['img']
                 if guide.shape[1] > 4:
                     guide = guide[:, :3]
             g = None if guide is False else guide.to(dev).float().contiguous()
-            if size is None or vis_kw is not None:
-                h, w = _geo_rows(data_batch)[1].shape[1:3]
-                Kg = data_batch['K'].to(dev).float()
-                Kg = (Kg if Kg.dim() == 3 else Kg.unsqueeze(0)).expand(B, 3, 3).contiguous()
-            if size is None:
-                H, W = data_batch['img'].shape[2:] if g is None else g.shape[2:]
-                K = Kg * torch.tensor([W / w, H / h, 1.0], dtype=torch.float32, device=dev).view(1, 3, 1)
-            else:
-                H, W = size
-                K = K.to(dev).float()
-                K = (K if K.dim() == 3 else K.unsqueeze(0)).expand(B, 3, 3)
-            if vis_kw is not None:
-                every = torch.ones(B, N, dtype=torch.bool, device=dev)
-                sel = _visible_rows(data_batch, pc, cur, Kg, h, w, every if sel is None else sel, vis_kw)[0]
+            H, W = size if size is not None else data_batch['img'].shape[2:] if g is None else g.shape[2:]
+            K, sel = _image_camera(data_batch, pc, cur, K, (H, W), sel, vis_kw)
             a = None if attr is None else attr.to(dev).float().contiguous()
             if sf_kw is not None:
                 _, depth_map, attr_map, data_batch['surfel_counts'], _, _ = ops.render_surfels(
-                    pc, _cloud_normals(data_batch, pc), cur, K.contiguous(), H, W, attr=a, mask=sel, fill=fill, **sf_kw)
+                    pc, _cloud_normals(data_batch, pc), cur, K, H, W, attr=a, mask=sel, fill=fill, **sf_kw)
             else:
-                _, depth_map, attr_map, _ = ops.render_points(pc, cur, K.contiguous(), H, W, attr=a, mask=sel, splat=splat, fill=fill)
+                _, depth_map, attr_map, _ = ops.render_points(pc, cur, K, H, W, attr=a, mask=sel, splat=splat, fill=fill)
             dense, dense_attr, conf, _, counts = ops.densify(depth_map, guide=g, attr=attr_map, radius=radius, sigma_s=sigma_s, sigma_r=sigma_r,
                                                              min_weight=min_weight, keep=keep, fill=fill)
             data_batch['dense_depth_map'] = dense

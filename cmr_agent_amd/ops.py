@@ -910,37 +910,152 @@ def circle_loss(pc_feat_rows, img_feat_nhwc, pc_idx, xy_int, xy_float, B, N, dis
     return out
 
 
+# ---- the argument checks of the matching and pose wrappers below, each stated once.  `who` is the wrapper's name; every failure is a
+# ValueError "<who>: ...".  Nothing here looks at a tensor's device or storage but _on_one_gpu, which every wrapper calls last.
+def _is_int(v):
+    """An integer-valued number that is not a bool; inf, NaN and non-numbers are simply not one (no OverflowError / TypeError)."""
+    try:
+        return not isinstance(v, bool) and math.isfinite(v) and int(v) == v
+    except (TypeError, ValueError, OverflowError):
+        return False
+
+
+def _int_arg(who, name, v, lo, hi):
+    if not _is_int(v) or not lo <= v <= hi:
+        raise ValueError("%s: %s must be an integer in [%d, %d], got %r" % (who, name, lo, hi, v))
+    return int(v)
+
+
+def _f32_arg(who, name, v, must, lo=0.0, hi=math.inf, lo_open=False, as_f32=True, bools=True):
+    """float(v) of a number in [lo, hi] -- (lo, hi] with lo_open, and below +inf whatever hi is -- that is still finite, and with lo_open
+    still above lo, as the float32 the kernel takes (as_f32=False: the kernel takes what float32 makes of it).  lo=None: any float, NaN
+    included.  bools=False refuses True and False.  Else the ValueError '<who>: <name> must <must>, got <v>'."""
+    try:
+        x = float(v)
+        y = float(torch.tensor(x, dtype=f32)) if as_f32 else x
+        ok = (bools or not isinstance(v, bool)) and (
+            lo is None or ((lo < x and lo < y if lo_open else lo <= x) and x <= hi and abs(y) < math.inf))
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError("%s: %s must %s, got %r" % (who, name, must, v))
+    return x
+
+
+def _got(t):
+    """(dtype, shape) of a tensor for a message; the type's name and nothing of anything else"""
+    return (t.dtype, tuple(t.shape)) if torch.is_tensor(t) else (type(t).__name__, "")
+
+
+def _shaped(who, name, t, *shape):
+    """t.shape of a tensor of that shape; an entry that is a str ("B", "N", "P") stands for any size"""
+    if not torch.is_tensor(t) or t.dim() != len(shape) or any(not isinstance(s, str) and s != d for s, d in zip(shape, t.shape)):
+        raise ValueError("%s: %s must be [%s], got %s" % (who, name, ", ".join(map(str, shape)), tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    return t.shape
+
+
+def _float32(who, names, *ts, what="float32"):
+    if not all(torch.is_tensor(t) and t.dtype == f32 for t in ts):
+        raise ValueError("%s: %s must be %s, got %s" % (who, names, what, " / ".join(str(_got(t)[0]) for t in ts)))
+
+
+def _poses_arg(who, poses, B):
+    P = _shaped(who, "poses", poses, B, "P", 4, 4)[1]
+    if P < 1 or P > POSE_SCORE_MAX_POSES:
+        raise ValueError("%s: need 1 <= P <= %d poses per sample, got %d" % (who, POSE_SCORE_MAX_POSES, P))
+    return P
+
+
+def _cloud_range(who, B, N, n_cap, h=None, w=None, noun="map"):
+    """1 <= B <= GRID_Y_MAX, 1 <= N <= GRID_Y_MAX * n_cap (the kernel's rows per workgroup) and, given h and w, 1 .. 2^24 pixels"""
+    ok = 1 <= B <= GRID_Y_MAX and 1 <= N <= GRID_Y_MAX * n_cap
+    if h is None and not ok:
+        raise ValueError("%s: need 1 <= B <= %d and 1 <= N <= %d, got B=%d N=%d" % (who, GRID_Y_MAX, GRID_Y_MAX * n_cap, B, N))
+    if h is not None and (not ok or h < 1 or w < 1 or h * w > 1 << 24):
+        raise ValueError("%s: need 1 <= B <= %d, 1 <= N <= %d and %s of 1 .. 2^24 pixels, got B=%d N=%d %s %d x %d" % (
+            who, GRID_Y_MAX, GRID_Y_MAX * n_cap, "an image" if noun == "image" else "a " + noun, B, N, noun, h, w))
+
+
+def _camera_args(who, pts, pose, K, h, w, noun="image", what="float32 tensors"):
+    """The cloud under one pose on an h x w `noun`: pts [B, 3, N], pose [B, 4, 4], K [B, 3, 3], integers h and w -> (B, N, h, w)"""
+    B, _, N = _shaped(who, "pts", pts, "B", 3, "N")
+    _float32(who, "pts, pose and K", pts, pose, K, what=what)
+    _shaped(who, "pose", pose, B, 4, 4)
+    _shaped(who, "K", K, B, 3, 3)
+    if not _is_int(h) or not _is_int(w):
+        raise ValueError("%s: h and w must be integers, got %r x %r" % (who, h, w))
+    h, w = int(h), int(w)
+    _cloud_range(who, B, N, 256, h, w, noun)
+    return B, N, h, w
+
+
+def _feature_pair(who, pc_feat_rows, img_feat_nhwc, pts=None):
+    """Point rows [B*N, 64] and pixel features NHWC [B, h, w, 64] -> (B, h, w, 64); given pts [B, 3, N], they agree with it on B and N"""
+    if not torch.is_tensor(pc_feat_rows) or not torch.is_tensor(img_feat_nhwc) or pc_feat_rows.dim() != 2 or img_feat_nhwc.dim() != 4:
+        raise ValueError("%s: point rows must be 2-D [B*N, C] and pixel features 4-D [B, h, w, C], got %s / %s" % (
+            who, _got(pc_feat_rows)[1], _got(img_feat_nhwc)[1]))
+    B, h, w, C = img_feat_nhwc.shape
+    if C != 64 or pc_feat_rows.shape[1] != 64:
+        raise ValueError("%s: feature width must be 64, got %d / %d" % (who, pc_feat_rows.shape[1], C))
+    if pts is not None and (B != pts.shape[0] or pc_feat_rows.shape[0] != B * pts.shape[2]):
+        raise ValueError("%s: pts %s, point rows %s and pixel features %s do not agree on B and N" % (
+            who, tuple(pts.shape), tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
+    return B, h, w, C
+
+
+def _rows_per_sample(who, pc_feat_rows, B, h, w, px_log2):
+    """N of B*N point rows, within the ranges of the kernels that sweep every pixel of the map for every row"""
+    if B < 1 or B > GRID_Y_MAX or pc_feat_rows.shape[0] % B or h < 1 or w < 1 or h * w > 1 << px_log2:
+        raise ValueError("%s: %d point rows do not split into %d samples (1 <= B <= %d) or the map %d x %d is empty / over 2^%d pixels" % (
+            who, pc_feat_rows.shape[0], B, GRID_Y_MAX, h, w, px_log2))
+    N = pc_feat_rows.shape[0] // B
+    if N < 1 or N > GRID_Y_MAX * 256:
+        raise ValueError("%s: need 1 <= N <= %d rows per sample, got %d" % (who, GRID_Y_MAX * 256, N))
+    return N
+
+
+def _row_mask(who, name, m, n, or_none=False):
+    """A row mask of n elements as the kernels take it: bool viewed as uint8.  or_none: None passes (and the message says so)."""
+    if m is None and or_none:
+        return None
+    if not torch.is_tensor(m) or m.dtype not in (torch.bool, torch.uint8, torch.int64) or m.numel() != n:
+        text = "%s: %s must be None or bool / uint8 / int64 with %d elements, got %s %s" if or_none else \
+               "%s: %s must be bool / uint8 / int64 with %d elements, got %s %s"
+        raise ValueError(text % ((who, name, n) + _got(m)))
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+def _gt_xy_arg(who, gt_xy, B, N):
+    if gt_xy is not None and (not torch.is_tensor(gt_xy) or gt_xy.dtype != f32 or tuple(gt_xy.shape) != (B, 2, N)):
+        raise ValueError("%s: gt_xy must be float32 [%d, 2, %d], got %s %s" % ((who, B, N) + _got(gt_xy)))
+
+
+def _on_one_gpu(who, *ts, aligned=()):
+    """The last check of a wrapper, over the tensors that are not None; `aligned`: the feature rows the kernels load 16 bytes at a time"""
+    ts = [t for t in ts if t is not None]
+    if not all(t.is_cuda and t.is_contiguous() and t.device == ts[0].device for t in ts):
+        raise ValueError("%s: every tensor must be a contiguous tensor on the same GPU" % who)
+    if any(t.data_ptr() % 16 for t in aligned):
+        raise ValueError("%s: feature rows must be 16-byte aligned" % who)
+
+
 def feat_match(pc_feat_rows, img_feat_nhwc, mask, gt_xy=None, thr=3.0, img_overlap=None, want_dist=False):
     """Nearest pixel feature of every selected point (include/cmr_hip.h cmr_feat_match_f32): pc_feat rows [B*N, 64], img_feat NHWC
     [B, h, w, 64] (both contiguous float32), mask [B, N] / [B*N] of bool / uint8 / int64 (non-zero = selected); optional gt_xy float32
     [B, 2, N] with threshold thr, optional img_overlap bool / uint8 [B, h, w] / [B*h*w].
     -> (idx int32 [B*N]: pixel p = y * w + x or -1, dist float32 [B*N] or None, counts int32 [B, 4] = (selected, inliers, selected whose
     pixel is in img_overlap, both))."""
-    if pc_feat_rows.dim() != 2 or img_feat_nhwc.dim() != 4:
-        raise ValueError("feat_match: point rows must be 2-D [B*N, C] and pixel features 4-D [B, h, w, C], got %s / %s" % (
-            tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
-    B, h, w, C = img_feat_nhwc.shape
-    if C != 64 or pc_feat_rows.shape[1] != 64:
-        raise ValueError("feat_match: feature width must be 64, got %d / %d" % (pc_feat_rows.shape[1], C))
-    if pc_feat_rows.dtype != f32 or img_feat_nhwc.dtype != f32:
-        raise ValueError("feat_match: features must be float32, got %s / %s" % (pc_feat_rows.dtype, img_feat_nhwc.dtype))
+    B, h, w, C = _feature_pair("feat_match", pc_feat_rows, img_feat_nhwc)
+    _float32("feat_match", "features", pc_feat_rows, img_feat_nhwc)
     if B < 1 or B > GRID_Y_MAX or pc_feat_rows.shape[0] % B:
         raise ValueError("feat_match: %d point rows do not split into %d samples (1 <= B <= %d)" % (pc_feat_rows.shape[0], B, GRID_Y_MAX))
     N = pc_feat_rows.shape[0] // B
-    if mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N:
-        raise ValueError("feat_match: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (B * N, mask.dtype, tuple(mask.shape)))
-    if gt_xy is not None and (gt_xy.dtype != f32 or tuple(gt_xy.shape) != (B, 2, N)):
-        raise ValueError("feat_match: gt_xy must be float32 [%d, 2, %d], got %s %s" % (B, N, gt_xy.dtype, tuple(gt_xy.shape)))
-    if img_overlap is not None and (img_overlap.dtype not in (torch.bool, torch.uint8) or img_overlap.numel() != B * h * w):
+    mask = _row_mask("feat_match", "mask", mask, B * N)
+    _gt_xy_arg("feat_match", gt_xy, B, N)
+    if img_overlap is not None and (img_overlap.dtype not in (torch.bool, torch.uint8) or img_overlap.numel() != B * h * w):    # no int64 here
         raise ValueError("feat_match: img_overlap must be bool / uint8 with %d elements, got %s %s" % (
             B * h * w, img_overlap.dtype, tuple(img_overlap.shape)))
-    ts = [t for t in (pc_feat_rows, img_feat_nhwc, mask, gt_xy, img_overlap) if t is not None]
-    if not all(t.is_cuda and t.is_contiguous() and t.device == pc_feat_rows.device for t in ts):
-        raise ValueError("feat_match: every tensor must be a contiguous tensor on the same GPU")
-    if pc_feat_rows.data_ptr() % 16 or img_feat_nhwc.data_ptr() % 16:
-        raise ValueError("feat_match: feature rows must be 16-byte aligned")
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
+    _on_one_gpu("feat_match", pc_feat_rows, img_feat_nhwc, mask, gt_xy, img_overlap, aligned=(pc_feat_rows, img_feat_nhwc))
     if img_overlap is not None and img_overlap.dtype == torch.bool:
         img_overlap = img_overlap.view(torch.uint8)
     dev = pc_feat_rows.device
@@ -962,38 +1077,17 @@ def feat_match_filter(pc_feat_rows, img_feat_nhwc, mask, mutual=True, ratio=0.0,
     the best pixel; max_dist >= 0 (0 = off): keep when d1 <= max_dist.
     -> (idx int32 [B*N] as feat_match, keep bool [B*N], counts int32 [B, 4] = (selected, kept, kept inliers, selected inliers),
     d1 / d2 float32 [B*N] or None (want_dist), rev int32 [B*h*w]: the nearest selected row of every pixel, or None (want_rev))."""
-    if pc_feat_rows.dim() != 2 or img_feat_nhwc.dim() != 4:
-        raise ValueError("feat_match_filter: point rows must be 2-D [B*N, C] and pixel features 4-D [B, h, w, C], got %s / %s" % (
-            tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
-    B, h, w, C = img_feat_nhwc.shape
-    if C != 64 or pc_feat_rows.shape[1] != 64:
-        raise ValueError("feat_match_filter: feature width must be 64, got %d / %d" % (pc_feat_rows.shape[1], C))
-    if pc_feat_rows.dtype != f32 or img_feat_nhwc.dtype != f32:
-        raise ValueError("feat_match_filter: features must be float32, got %s / %s" % (pc_feat_rows.dtype, img_feat_nhwc.dtype))
-    if B < 1 or B > GRID_Y_MAX or pc_feat_rows.shape[0] % B or h < 1 or w < 1 or h * w > 1 << 30:
-        raise ValueError("feat_match_filter: %d point rows do not split into %d samples (1 <= B <= %d) or the map %d x %d is empty / "
-                         "over 2^30 pixels" % (pc_feat_rows.shape[0], B, GRID_Y_MAX, h, w))
-    N = pc_feat_rows.shape[0] // B
-    if N < 1 or N > GRID_Y_MAX * 256:
-        raise ValueError("feat_match_filter: need 1 <= N <= %d rows per sample, got %d" % (GRID_Y_MAX * 256, N))
-    if mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N:
-        raise ValueError("feat_match_filter: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (
-            B * N, mask.dtype, tuple(mask.shape)))
-    if gt_xy is not None and (gt_xy.dtype != f32 or tuple(gt_xy.shape) != (B, 2, N)):
-        raise ValueError("feat_match_filter: gt_xy must be float32 [%d, 2, %d], got %s %s" % (B, N, gt_xy.dtype, tuple(gt_xy.shape)))
-    if isinstance(excl_radius, bool) or int(excl_radius) != excl_radius or not 0 <= excl_radius < 1 << 31:
+    who = "feat_match_filter"
+    B, h, w, C = _feature_pair(who, pc_feat_rows, img_feat_nhwc)
+    _float32(who, "features", pc_feat_rows, img_feat_nhwc)
+    N = _rows_per_sample(who, pc_feat_rows, B, h, w, 30)
+    mask = _row_mask(who, "mask", mask, B * N)
+    _gt_xy_arg(who, gt_xy, B, N)
+    if not _is_int(excl_radius) or not 0 <= excl_radius < 1 << 31:
         raise ValueError("feat_match_filter: excl_radius must be a non-negative integer, got %r" % (excl_radius,))
-    if not 0.0 <= float(ratio) <= 1.0:
-        raise ValueError("feat_match_filter: ratio must lie in [0, 1] (0 = no ratio test), got %r" % (ratio,))
-    if not 0.0 <= float(max_dist) < float("inf"):
-        raise ValueError("feat_match_filter: max_dist must be finite and >= 0 (0 = no bound), got %r" % (max_dist,))
-    ts = [t for t in (pc_feat_rows, img_feat_nhwc, mask, gt_xy) if t is not None]
-    if not all(t.is_cuda and t.is_contiguous() and t.device == pc_feat_rows.device for t in ts):
-        raise ValueError("feat_match_filter: every tensor must be a contiguous tensor on the same GPU")
-    if pc_feat_rows.data_ptr() % 16 or img_feat_nhwc.data_ptr() % 16:
-        raise ValueError("feat_match_filter: feature rows must be 16-byte aligned")
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
+    _f32_arg(who, "ratio", ratio, "lie in [0, 1] (0 = no ratio test)", hi=1.0)
+    _f32_arg(who, "max_dist", max_dist, "be finite and >= 0 (0 = no bound)", as_f32=False)      # the kernel takes +inf for no bound as well
+    _on_one_gpu(who, pc_feat_rows, img_feat_nhwc, mask, gt_xy, aligned=(pc_feat_rows, img_feat_nhwc))
     dev = pc_feat_rows.device
     idx = torch.empty((B * N,), dtype=torch.int32, device=dev)
     keep = torch.empty((B * N,), dtype=torch.uint8, device=dev)
@@ -1017,36 +1111,15 @@ def match_conf(pc_feat_rows, img_feat_nhwc, mask, temperature=0.1, min_conf=0.0,
     -> (idx int32 [B*N] as feat_match, conf float32 [B*N] (NaN on unselected rows), keep bool [B*N], counts int32 [B, 4] = (selected,
     kept, kept inliers, selected inliers), d1 float32 [B*N] or None (want_dist), row_lse float32 [B*N] / col_lse float32 [B*h*w]: the
     log-sum-exp of s over a point's pixels / over a pixel's selected points, or None (want_lse))."""
-    if pc_feat_rows.dim() != 2 or img_feat_nhwc.dim() != 4:
-        raise ValueError("match_conf: point rows must be 2-D [B*N, C] and pixel features 4-D [B, h, w, C], got %s / %s" % (
-            tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
-    B, h, w, C = img_feat_nhwc.shape
-    if C != 64 or pc_feat_rows.shape[1] != 64:
-        raise ValueError("match_conf: feature width must be 64, got %d / %d" % (pc_feat_rows.shape[1], C))
-    if pc_feat_rows.dtype != f32 or img_feat_nhwc.dtype != f32:
-        raise ValueError("match_conf: features must be float32, got %s / %s" % (pc_feat_rows.dtype, img_feat_nhwc.dtype))
-    if B < 1 or B > GRID_Y_MAX or pc_feat_rows.shape[0] % B or h < 1 or w < 1 or h * w > 1 << 24:
-        raise ValueError("match_conf: %d point rows do not split into %d samples (1 <= B <= %d) or the map %d x %d is empty / "
-                         "over 2^24 pixels" % (pc_feat_rows.shape[0], B, GRID_Y_MAX, h, w))
-    N = pc_feat_rows.shape[0] // B
-    if N < 1 or N > GRID_Y_MAX * 256:
-        raise ValueError("match_conf: need 1 <= N <= %d rows per sample, got %d" % (GRID_Y_MAX * 256, N))
-    if mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N:
-        raise ValueError("match_conf: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (
-            B * N, mask.dtype, tuple(mask.shape)))
-    if gt_xy is not None and (gt_xy.dtype != f32 or tuple(gt_xy.shape) != (B, 2, N)):
-        raise ValueError("match_conf: gt_xy must be float32 [%d, 2, %d], got %s %s" % (B, N, gt_xy.dtype, tuple(gt_xy.shape)))
-    if not 0.0 < float(temperature) < float("inf"):
-        raise ValueError("match_conf: temperature must be finite and > 0, got %r" % (temperature,))
-    if not 0.0 <= float(min_conf) <= 1.0:
-        raise ValueError("match_conf: min_conf must lie in [0, 1] (0 = no threshold), got %r" % (min_conf,))
-    ts = [t for t in (pc_feat_rows, img_feat_nhwc, mask, gt_xy) if t is not None]
-    if not all(t.is_cuda and t.is_contiguous() and t.device == pc_feat_rows.device for t in ts):
-        raise ValueError("match_conf: every tensor must be a contiguous tensor on the same GPU")
-    if pc_feat_rows.data_ptr() % 16 or img_feat_nhwc.data_ptr() % 16:
-        raise ValueError("match_conf: feature rows must be 16-byte aligned")
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
+    who = "match_conf"
+    B, h, w, C = _feature_pair(who, pc_feat_rows, img_feat_nhwc)
+    _float32(who, "features", pc_feat_rows, img_feat_nhwc)
+    N = _rows_per_sample(who, pc_feat_rows, B, h, w, 24)
+    mask = _row_mask(who, "mask", mask, B * N)
+    _gt_xy_arg(who, gt_xy, B, N)
+    _f32_arg(who, "temperature", temperature, "be finite and > 0", lo_open=True)
+    _f32_arg(who, "min_conf", min_conf, "lie in [0, 1] (0 = no threshold)", hi=1.0)
+    _on_one_gpu(who, pc_feat_rows, img_feat_nhwc, mask, gt_xy, aligned=(pc_feat_rows, img_feat_nhwc))
     dev = pc_feat_rows.device
     idx = torch.empty((B * N,), dtype=torch.int32, device=dev)
     conf = torch.empty((B * N,), dtype=f32, device=dev)
@@ -1069,32 +1142,22 @@ def pnp_ransac(pts, uv, mask, K, n_hyp=1024, thr=1.0, seed=0, refine_iters=10, w
     (non-zero = use), K float32 [B, 3, 3]; n_hyp hypotheses, inlier threshold thr pixels, hash seed, up to refine_iters Gauss-Newton steps.
     -> (pose float32 [B, 4, 4] mapping pts into the camera frame, inliers int32 [B], status int32 [B] (0 ok, 1 fewer than 4
     correspondences, 2 no valid hypothesis)[, hyp_inliers int32 [B, n_hyp], -1 = invalid hypothesis])."""
-    if pts.dim() != 3 or pts.shape[1] != 3:
-        raise ValueError("pnp_ransac: pts must be [B, 3, N], got %s" % (tuple(pts.shape),))
-    B, _, N = pts.shape
-    if tuple(uv.shape) != (B, 2, N):
-        raise ValueError("pnp_ransac: uv must be [%d, 2, %d], got %s" % (B, N, tuple(uv.shape)))
-    if tuple(K.shape) != (B, 3, 3):
-        raise ValueError("pnp_ransac: K must be [%d, 3, 3], got %s" % (B, tuple(K.shape)))
-    if pts.dtype != f32 or uv.dtype != f32 or K.dtype != f32:
-        raise ValueError("pnp_ransac: pts, uv and K must be float32, got %s / %s / %s" % (pts.dtype, uv.dtype, K.dtype))
-    if mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N:
-        raise ValueError("pnp_ransac: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (B * N, mask.dtype, tuple(mask.shape)))
-    if B < 1 or B > GRID_Y_MAX or N < 1 or N > GRID_Y_MAX * 512:
-        raise ValueError("pnp_ransac: need 1 <= B <= %d and 1 <= N <= %d, got B=%d N=%d" % (GRID_Y_MAX, GRID_Y_MAX * 512, B, N))
+    who = "pnp_ransac"
+    B, _, N = _shaped(who, "pts", pts, "B", 3, "N")
+    _shaped(who, "uv", uv, B, 2, N)
+    _shaped(who, "K", K, B, 3, 3)
+    _float32(who, "pts, uv and K", pts, uv, K)
+    mask = _row_mask(who, "mask", mask, B * N)
+    _cloud_range(who, B, N, 512)
+    # n_hyp, refine_iters and seed take True for 1, which _is_int refuses: their own test
     if int(n_hyp) != n_hyp or not 1 <= n_hyp <= 1 << 20:
         raise ValueError("pnp_ransac: n_hyp must be an integer in [1, 2^20], got %r" % (n_hyp,))
-    if not (float(thr) > 0.0 and float(thr) < float("inf")):
-        raise ValueError("pnp_ransac: thr must be a finite positive number, got %r" % (thr,))
+    _f32_arg(who, "thr", thr, "be a finite positive number", lo_open=True)
     if int(refine_iters) != refine_iters or refine_iters < 0:
         raise ValueError("pnp_ransac: refine_iters must be a non-negative integer, got %r" % (refine_iters,))
     if int(seed) != seed or not 0 <= seed < 1 << 32:
         raise ValueError("pnp_ransac: seed must be an unsigned 32-bit integer, got %r" % (seed,))
-    ts = (pts, uv, mask, K)
-    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
-        raise ValueError("pnp_ransac: every tensor must be a contiguous tensor on the same GPU")
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
+    _on_one_gpu(who, pts, uv, mask, K)
     dev = pts.device
     n_hyp, refine_iters, seed = int(n_hyp), int(refine_iters), int(seed)
     pose = torch.empty((B, 4, 4), dtype=f32, device=dev)
@@ -1111,14 +1174,6 @@ def pnp_ransac(pts, uv, mask, K, n_hyp=1024, thr=1.0, seed=0, refine_iters=10, w
 GUIDED_MAX_RADIUS = 16      # csrc/guided_match.hip GM_MAX_RADIUS
 
 
-def _is_int(v):
-    """An integer-valued number that is not a bool; inf, NaN and non-numbers are simply not one (no OverflowError / TypeError)."""
-    try:
-        return not isinstance(v, bool) and math.isfinite(v) and int(v) == v
-    except (TypeError, ValueError, OverflowError):
-        return False
-
-
 def guided_match(pts, pc_feat_rows, img_feat_nhwc, mask, pose, K, radius, max_dist=0.0, gt_xy=None, thr=3.0, want_dist=False,
                  want_proj=False):
     """Nearest pixel feature of every selected point inside the (2 radius + 1)^2 window round its projection under `pose`
@@ -1127,43 +1182,18 @@ def guided_match(pts, pc_feat_rows, img_feat_nhwc, mask, pose, K, radius, max_di
     [B, 3, 3] for the h x w map, 0 <= radius <= GUIDED_MAX_RADIUS, max_dist >= 0 (0 = off), optional gt_xy float32 [B, 2, N] with thr.
     -> (idx int32 [B*N]: pixel p = y * w + x or -1 (unselected / out of view), keep bool [B*N], counts int32 [B, 4] = (selected, in view,
     kept, kept inliers), dist float32 [B*N] or None (want_dist), proj float32 [B, 2, N] = (u, v) as the kernel computed them or None)."""
-    if pts.dim() != 3 or pts.shape[1] != 3:
-        raise ValueError("guided_match: pts must be [B, 3, N], got %s" % (tuple(pts.shape),))
-    B, _, N = pts.shape
-    if pc_feat_rows.dim() != 2 or img_feat_nhwc.dim() != 4:
-        raise ValueError("guided_match: point rows must be 2-D [B*N, C] and pixel features 4-D [B, h, w, C], got %s / %s" % (
-            tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
-    Bi, h, w, C = img_feat_nhwc.shape
-    if C != 64 or pc_feat_rows.shape[1] != 64:
-        raise ValueError("guided_match: feature width must be 64, got %d / %d" % (pc_feat_rows.shape[1], C))
-    if Bi != B or pc_feat_rows.shape[0] != B * N:
-        raise ValueError("guided_match: pts %s, point rows %s and pixel features %s do not agree on B and N" % (
-            tuple(pts.shape), tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
-    if pts.dtype != f32 or pc_feat_rows.dtype != f32 or img_feat_nhwc.dtype != f32 or pose.dtype != f32 or K.dtype != f32:
-        raise ValueError("guided_match: pts, features, pose and K must be float32, got %s / %s / %s / %s / %s" % (
-            pts.dtype, pc_feat_rows.dtype, img_feat_nhwc.dtype, pose.dtype, K.dtype))
-    if tuple(pose.shape) != (B, 4, 4):
-        raise ValueError("guided_match: pose must be [%d, 4, 4], got %s" % (B, tuple(pose.shape)))
-    if tuple(K.shape) != (B, 3, 3):
-        raise ValueError("guided_match: K must be [%d, 3, 3], got %s" % (B, tuple(K.shape)))
-    if B < 1 or B > GRID_Y_MAX or N < 1 or N > GRID_Y_MAX * 256 or h < 1 or w < 1 or h * w > 1 << 24:
-        raise ValueError("guided_match: need 1 <= B <= %d, 1 <= N <= %d and a map of 1 .. 2^24 pixels, got B=%d N=%d map %d x %d" % (
-            GRID_Y_MAX, GRID_Y_MAX * 256, B, N, h, w))
-    if mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N:
-        raise ValueError("guided_match: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (B * N, mask.dtype, tuple(mask.shape)))
-    if gt_xy is not None and (gt_xy.dtype != f32 or tuple(gt_xy.shape) != (B, 2, N)):
-        raise ValueError("guided_match: gt_xy must be float32 [%d, 2, %d], got %s %s" % (B, N, gt_xy.dtype, tuple(gt_xy.shape)))
-    if not _is_int(radius) or not 0 <= radius <= GUIDED_MAX_RADIUS:
-        raise ValueError("guided_match: radius must be an integer in [0, %d], got %r" % (GUIDED_MAX_RADIUS, radius))
-    if not 0.0 <= float(max_dist) < float("inf"):
-        raise ValueError("guided_match: max_dist must be finite and >= 0 (0 = no bound), got %r" % (max_dist,))
-    ts = [t for t in (pts, pc_feat_rows, img_feat_nhwc, mask, pose, K, gt_xy) if t is not None]
-    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
-        raise ValueError("guided_match: every tensor must be a contiguous tensor on the same GPU")
-    if pc_feat_rows.data_ptr() % 16 or img_feat_nhwc.data_ptr() % 16:
-        raise ValueError("guided_match: feature rows must be 16-byte aligned")
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
+    who = "guided_match"
+    B, _, N = _shaped(who, "pts", pts, "B", 3, "N")
+    _, h, w, C = _feature_pair(who, pc_feat_rows, img_feat_nhwc, pts)
+    _float32(who, "pts, features, pose and K", pts, pc_feat_rows, img_feat_nhwc, pose, K)
+    _shaped(who, "pose", pose, B, 4, 4)
+    _shaped(who, "K", K, B, 3, 3)
+    _cloud_range(who, B, N, 256, h, w)
+    mask = _row_mask(who, "mask", mask, B * N)
+    _gt_xy_arg(who, gt_xy, B, N)
+    _int_arg(who, "radius", radius, 0, GUIDED_MAX_RADIUS)
+    _f32_arg(who, "max_dist", max_dist, "be finite and >= 0 (0 = no bound)")
+    _on_one_gpu(who, pts, pc_feat_rows, img_feat_nhwc, mask, pose, K, gt_xy, aligned=(pc_feat_rows, img_feat_nhwc))
     dev = pts.device
     idx = torch.empty((B * N,), dtype=torch.int32, device=dev)
     keep = torch.empty((B * N,), dtype=torch.uint8, device=dev)
@@ -1190,51 +1220,20 @@ def pose_score(pts, pc_feat_rows, img_feat_nhwc, mask, poses, K, radius=0, tau=0
     tau = 0.8 is a default for unit-norm features (two unrelated ones lie about sqrt(2) apart); it is not tuned on real data.
     -> (score float64 [B, P] = the sum over the selected rows, lower is better; counts int32 [B, P, 2] = (in view, in view and dist <=
     tau); selected int32 [B])."""
-    if pts.dim() != 3 or pts.shape[1] != 3:
-        raise ValueError("pose_score: pts must be [B, 3, N], got %s" % (tuple(pts.shape),))
-    B, _, N = pts.shape
-    if pc_feat_rows.dim() != 2 or img_feat_nhwc.dim() != 4:
-        raise ValueError("pose_score: point rows must be 2-D [B*N, C] and pixel features 4-D [B, h, w, C], got %s / %s" % (
-            tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
-    Bi, h, w, C = img_feat_nhwc.shape
-    if C != 64 or pc_feat_rows.shape[1] != 64:
-        raise ValueError("pose_score: feature width must be 64, got %d / %d" % (pc_feat_rows.shape[1], C))
-    if Bi != B or pc_feat_rows.shape[0] != B * N:
-        raise ValueError("pose_score: pts %s, point rows %s and pixel features %s do not agree on B and N" % (
-            tuple(pts.shape), tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
-    if pts.dtype != f32 or pc_feat_rows.dtype != f32 or img_feat_nhwc.dtype != f32 or poses.dtype != f32 or K.dtype != f32:
-        raise ValueError("pose_score: pts, features, poses and K must be float32, got %s / %s / %s / %s / %s" % (
-            pts.dtype, pc_feat_rows.dtype, img_feat_nhwc.dtype, poses.dtype, K.dtype))
-    if poses.dim() != 4 or poses.shape[0] != B or tuple(poses.shape[2:]) != (4, 4):
-        raise ValueError("pose_score: poses must be [%d, P, 4, 4], got %s" % (B, tuple(poses.shape)))
-    P = poses.shape[1]
-    if P < 1 or P > POSE_SCORE_MAX_POSES:
-        raise ValueError("pose_score: need 1 <= P <= %d poses per sample, got %d" % (POSE_SCORE_MAX_POSES, P))
-    if tuple(K.shape) != (B, 3, 3):
-        raise ValueError("pose_score: K must be [%d, 3, 3], got %s" % (B, tuple(K.shape)))
-    if B < 1 or B > GRID_Y_MAX or N < 1 or N > GRID_Y_MAX * 256 or h < 1 or w < 1 or h * w > 1 << 24:
-        raise ValueError("pose_score: need 1 <= B <= %d, 1 <= N <= %d and a map of 1 .. 2^24 pixels, got B=%d N=%d map %d x %d" % (
-            GRID_Y_MAX, GRID_Y_MAX * 256, B, N, h, w))
-    if mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N:
-        raise ValueError("pose_score: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (B * N, mask.dtype, tuple(mask.shape)))
-    if not _is_int(radius) or not 0 <= radius <= GUIDED_MAX_RADIUS:
-        raise ValueError("pose_score: radius must be an integer in [0, %d], got %r" % (GUIDED_MAX_RADIUS, radius))
-    try:
-        tau_ok = 0.0 < float(tau) < float("inf")
-    except (TypeError, ValueError):
-        tau_ok = False
-    if not tau_ok:
-        raise ValueError("pose_score: tau must be a finite positive number, got %r" % (tau,))
+    who = "pose_score"
+    B, _, N = _shaped(who, "pts", pts, "B", 3, "N")
+    _, h, w, C = _feature_pair(who, pc_feat_rows, img_feat_nhwc, pts)
+    _float32(who, "pts, features, poses and K", pts, pc_feat_rows, img_feat_nhwc, poses, K)
+    P = _poses_arg(who, poses, B)
+    _shaped(who, "K", K, B, 3, 3)
+    _cloud_range(who, B, N, 256, h, w)
+    mask = _row_mask(who, "mask", mask, B * N)
+    _int_arg(who, "radius", radius, 0, GUIDED_MAX_RADIUS)
+    _f32_arg(who, "tau", tau, "be a finite positive number", lo_open=True)
     nslices = (N + 255) // 256
     if nslices * ((P + 31) // 32) * B > 0x7fffffff:
         raise ValueError("pose_score: B=%d N=%d P=%d need more than 2^31 - 1 workgroups, score the poses or the samples in parts" % (B, N, P))
-    ts = (pts, pc_feat_rows, img_feat_nhwc, mask, poses, K)
-    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
-        raise ValueError("pose_score: every tensor must be a contiguous tensor on the same GPU")
-    if pc_feat_rows.data_ptr() % 16 or img_feat_nhwc.data_ptr() % 16:
-        raise ValueError("pose_score: feature rows must be 16-byte aligned")
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
+    _on_one_gpu(who, pts, pc_feat_rows, img_feat_nhwc, mask, poses, K, aligned=(pc_feat_rows, img_feat_nhwc))
     dev = pts.device
     score = torch.empty((B, P), dtype=torch.float64, device=dev)
     counts = torch.empty((B, P, 2), dtype=torch.int32, device=dev)
@@ -1244,13 +1243,6 @@ def pose_score(pts, pc_feat_rows, img_feat_nhwc, mask, poses, K, radius=0, tau=0
     _lib.call("cmr_pose_score_f32", _p(pts), _p(pc_feat_rows), _p(img_feat_nhwc), C, B, N, h, w, _p(mask), mask.element_size(), _p(poses),
               P, _p(K), int(radius), float(tau), _p(score), _p(counts), _p(selected), _p(ws), nb, _stream())
     return score, counts, selected
-
-
-def _tol_ok(v):
-    try:
-        return 0.0 <= float(v) < float("inf") and float(torch.tensor(float(v), dtype=f32)) < float("inf")
-    except (TypeError, ValueError, OverflowError):
-        return False
 
 
 def visibility(pts, pose, K, h, w, mask, occ_mask=None, radius=1, rel_tol=0.05, abs_tol=0.0, want_depth_map=False, want_cell=False,
@@ -1266,39 +1258,14 @@ def visibility(pts, pose, K, h, w, mask, occ_mask=None, radius=1, rel_tol=0.05, 
     -> (visible bool [B*N], counts int32 [B, 4] = (selected, selected and in view, visible, occluder rows in view), depth_map float32
     [B, h, w] or None, cell int32 [B*N] = y * w + x of the rows of mask | occ_mask in view, else -1, or None, depth float32 [B*N] = p2 of
     those rows where p2 > 0, else NaN, or None)."""
-    if pts.dim() != 3 or pts.shape[1] != 3:
-        raise ValueError("visibility: pts must be [B, 3, N], got %s" % (tuple(pts.shape),))
-    B, _, N = pts.shape
-    if pts.dtype != f32 or pose.dtype != f32 or K.dtype != f32:
-        raise ValueError("visibility: pts, pose and K must be float32, got %s / %s / %s" % (pts.dtype, pose.dtype, K.dtype))
-    if tuple(pose.shape) != (B, 4, 4):
-        raise ValueError("visibility: pose must be [%d, 4, 4], got %s" % (B, tuple(pose.shape)))
-    if tuple(K.shape) != (B, 3, 3):
-        raise ValueError("visibility: K must be [%d, 3, 3], got %s" % (B, tuple(K.shape)))
-    if not _is_int(h) or not _is_int(w):
-        raise ValueError("visibility: h and w must be integers, got %r x %r" % (h, w))
-    h, w = int(h), int(w)
-    if B < 1 or B > GRID_Y_MAX or N < 1 or N > GRID_Y_MAX * 256 or h < 1 or w < 1 or h * w > 1 << 24:
-        raise ValueError("visibility: need 1 <= B <= %d, 1 <= N <= %d and a map of 1 .. 2^24 pixels, got B=%d N=%d map %d x %d" % (
-            GRID_Y_MAX, GRID_Y_MAX * 256, B, N, h, w))
-    if mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N:
-        raise ValueError("visibility: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (B * N, mask.dtype, tuple(mask.shape)))
-    if occ_mask is not None and (occ_mask.dtype not in (torch.bool, torch.uint8, torch.int64) or occ_mask.numel() != B * N):
-        raise ValueError("visibility: occ_mask must be bool / uint8 / int64 with %d elements, got %s %s" % (
-            B * N, occ_mask.dtype, tuple(occ_mask.shape)))
-    if not _is_int(radius) or not 0 <= radius <= GUIDED_MAX_RADIUS:
-        raise ValueError("visibility: radius must be an integer in [0, %d], got %r" % (GUIDED_MAX_RADIUS, radius))
-    if not _tol_ok(rel_tol):
-        raise ValueError("visibility: rel_tol must be finite and >= 0, got %r" % (rel_tol,))
-    if not _tol_ok(abs_tol):
-        raise ValueError("visibility: abs_tol must be finite and >= 0, got %r" % (abs_tol,))
-    ts = [t for t in (pts, pose, K, mask, occ_mask) if t is not None]
-    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
-        raise ValueError("visibility: every tensor must be a contiguous tensor on the same GPU")
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
-    if occ_mask is not None and occ_mask.dtype == torch.bool:
-        occ_mask = occ_mask.view(torch.uint8)
+    who = "visibility"
+    B, N, h, w = _camera_args(who, pts, pose, K, h, w, "map", "float32")
+    mask = _row_mask(who, "mask", mask, B * N)
+    occ_mask = None if occ_mask is None else _row_mask(who, "occ_mask", occ_mask, B * N)
+    _int_arg(who, "radius", radius, 0, GUIDED_MAX_RADIUS)
+    _f32_arg(who, "rel_tol", rel_tol, "be finite and >= 0")
+    _f32_arg(who, "abs_tol", abs_tol, "be finite and >= 0")
+    _on_one_gpu(who, pts, pose, K, mask, occ_mask)
     dev = pts.device
     visible = torch.empty((B * N,), dtype=torch.uint8, device=dev)
     counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
@@ -1318,28 +1285,14 @@ RENDER_MAX_SPLAT = 4        # csrc/point_image.hip PI_MAX_SPLAT
 _PAINT_MODES = {"nearest": 0, "bilinear": 1}
 
 
-def _point_image_args(who, pts, pose, K, h, w, mask):
-    """The checks paint_points and render_points share -> (B, N, h, w); the device check is the caller's, last."""
-    if not torch.is_tensor(pts) or pts.dim() != 3 or pts.shape[1] != 3:
-        raise ValueError("%s: pts must be [B, 3, N], got %s" % (who, tuple(pts.shape) if torch.is_tensor(pts) else type(pts).__name__))
-    B, _, N = pts.shape
-    if not torch.is_tensor(pose) or not torch.is_tensor(K) or pts.dtype != f32 or pose.dtype != f32 or K.dtype != f32:
-        raise ValueError("%s: pts, pose and K must be float32 tensors, got %s / %s / %s" % (
-            who, pts.dtype, getattr(pose, "dtype", type(pose).__name__), getattr(K, "dtype", type(K).__name__)))
-    if tuple(pose.shape) != (B, 4, 4):
-        raise ValueError("%s: pose must be [%d, 4, 4], got %s" % (who, B, tuple(pose.shape)))
-    if tuple(K.shape) != (B, 3, 3):
-        raise ValueError("%s: K must be [%d, 3, 3], got %s" % (who, B, tuple(K.shape)))
-    if not _is_int(h) or not _is_int(w):
-        raise ValueError("%s: h and w must be integers, got %r x %r" % (who, h, w))
-    h, w = int(h), int(w)
-    if B < 1 or B > GRID_Y_MAX or N < 1 or N > GRID_Y_MAX * 256 or h < 1 or w < 1 or h * w > 1 << 24:
-        raise ValueError("%s: need 1 <= B <= %d, 1 <= N <= %d and an image of 1 .. 2^24 pixels, got B=%d N=%d image %d x %d" % (
-            who, GRID_Y_MAX, GRID_Y_MAX * 256, B, N, h, w))
-    if mask is not None and (not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N):
-        raise ValueError("%s: mask must be None or bool / uint8 / int64 with %d elements, got %s %s" % (
-            who, B * N, getattr(mask, "dtype", type(mask).__name__), tuple(mask.shape) if torch.is_tensor(mask) else ""))
-    return B, N, h, w
+def _point_attr(who, attr, B, N):
+    """render_points' and render_surfels' attr float32 [B, C, N] or None -> C (0 without)"""
+    if attr is None:
+        return 0
+    if not torch.is_tensor(attr) or attr.dtype != f32 or attr.dim() != 3 or attr.shape[0] != B or attr.shape[2] != N or not (
+            1 <= attr.shape[1] <= POINT_IMAGE_MAX_C):
+        raise ValueError("%s: attr must be float32 [%d, C, %d] with 1 <= C <= %d, got %s %s" % ((who, B, N, POINT_IMAGE_MAX_C) + _got(attr)))
+    return attr.shape[1]
 
 
 def paint_points(pts, pose, K, image, mask=None, mode='bilinear', want_uv=False):
@@ -1356,18 +1309,15 @@ def paint_points(pts, pose, K, image, mask=None, mode='bilinear', want_uv=False)
         raise ValueError("paint_points: image must be planar [B, C, H, W], got %s" % (
             tuple(image.shape) if torch.is_tensor(image) else type(image).__name__,))
     Bi, C, H, W = image.shape
-    B, N, H, W = _point_image_args("paint_points", pts, pose, K, H, W, mask)
+    B, N, H, W = _camera_args("paint_points", pts, pose, K, H, W)
+    mask = _row_mask("paint_points", "mask", mask, B * N, or_none=True)
     if image.dtype != f32:
         raise ValueError("paint_points: image must be float32, got %s" % (image.dtype,))
     if Bi != B or C < 1 or C > POINT_IMAGE_MAX_C:
         raise ValueError("paint_points: image must be [%d, C, H, W] with 1 <= C <= %d, got %s" % (B, POINT_IMAGE_MAX_C, tuple(image.shape)))
     if not isinstance(mode, str) or mode not in _PAINT_MODES:
         raise ValueError("paint_points: mode must be 'nearest' or 'bilinear', got %r" % (mode,))
-    ts = [t for t in (pts, pose, K, image, mask) if t is not None]
-    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
-        raise ValueError("paint_points: every tensor must be a contiguous tensor on the same GPU")
-    if mask is not None and mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
+    _on_one_gpu("paint_points", pts, pose, K, image, mask)
     dev = pts.device
     colors = torch.empty((B, C, N), dtype=f32, device=dev)
     painted = torch.empty((B * N,), dtype=torch.uint8, device=dev)
@@ -1388,25 +1338,13 @@ def render_points(pts, pose, K, h, w, attr=None, mask=None, splat=0, fill=0.0):
     -> (index_map int32 [B, h, w], -1 where no row owns the pixel; depth_map float32 [B, h, w], +inf there; attr_map float32 [B, C, h, w]
     = attr[b, :, owner], `fill` there, or None without attr; counts int32 [B, 3] = (selected, selected and in view, pixels with an
     owner))."""
-    B, N, h, w = _point_image_args("render_points", pts, pose, K, h, w, mask)
-    C = 0
-    if attr is not None:
-        if not torch.is_tensor(attr) or attr.dtype != f32 or attr.dim() != 3 or attr.shape[0] != B or attr.shape[2] != N or not (
-                1 <= attr.shape[1] <= POINT_IMAGE_MAX_C):
-            raise ValueError("render_points: attr must be float32 [%d, C, %d] with 1 <= C <= %d, got %s %s" % (
-                B, N, POINT_IMAGE_MAX_C, getattr(attr, "dtype", type(attr).__name__), tuple(attr.shape) if torch.is_tensor(attr) else ""))
-        C = attr.shape[1]
-    if not _is_int(splat) or not 0 <= splat <= RENDER_MAX_SPLAT:
-        raise ValueError("render_points: splat must be an integer in [0, %d], got %r" % (RENDER_MAX_SPLAT, splat))
-    try:
-        fill = float(fill)
-    except (TypeError, ValueError):
-        raise ValueError("render_points: fill must be a number, got %r" % (fill,))
-    ts = [t for t in (pts, pose, K, attr, mask) if t is not None]
-    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
-        raise ValueError("render_points: every tensor must be a contiguous tensor on the same GPU")
-    if mask is not None and mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
+    who = "render_points"
+    B, N, h, w = _camera_args(who, pts, pose, K, h, w)
+    mask = _row_mask(who, "mask", mask, B * N, or_none=True)
+    C = _point_attr(who, attr, B, N)
+    _int_arg(who, "splat", splat, 0, RENDER_MAX_SPLAT)
+    fill = _f32_arg(who, "fill", fill, "be a number", lo=None)
+    _on_one_gpu(who, pts, pose, K, attr, mask)
     dev = pts.device
     index_map = torch.empty((B, h, w), dtype=torch.int32, device=dev)
     depth_map = torch.empty((B, h, w), dtype=f32, device=dev)
@@ -1420,18 +1358,6 @@ def render_points(pts, pose, K, h, w, attr=None, mask=None, splat=0, fill=0.0):
 
 
 SURFEL_MAX_PX = 16          # csrc/surfel.hip SF_MAX_PX
-
-
-def _surfel_scalar(who, name, v, hi=None):
-    """A finite float >= 0 (and <= hi) that is also finite as a float32, or a ValueError."""
-    try:
-        ok = not isinstance(v, bool) and 0.0 <= float(v) < float("inf") and float(torch.tensor(float(v), dtype=f32)) < float("inf")
-        ok = ok and (hi is None or float(v) <= hi)
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError("%s: %s must be a finite number in [0, %s], got %r" % (who, name, "inf)" if hi is None else "%g]" % hi, v))
-    return float(v)
 
 
 def render_surfels(pts, normals, pose, K, h, w, radius=0.1, range_slope=0.004, max_px=8, min_cos=0.1, attr=None, mask=None, fill=0.0,
@@ -1450,31 +1376,19 @@ def render_surfels(pts, normals, pose, K, h, w, radius=0.1, range_slope=0.004, m
     +inf where none; attr_map float32 [B, C, h, w] or None; counts int32 [B, 4] = (selected, drawn, pixels with an owner, status);
     normal_map float32 [B, 3, h, w] (unit, facing the camera, 0 where no owner) or None; surfel float32 [B, 8, N] = (x_c, y_c, z_c, n_cx,
     n_cy, n_cz, r, drawn) as computed, NaN in the first seven planes of undrawn rows, or None)."""
-    B, N, h, w = _point_image_args("render_surfels", pts, pose, K, h, w, mask)
+    who = "render_surfels"
+    B, N, h, w = _camera_args(who, pts, pose, K, h, w)
+    mask = _row_mask(who, "mask", mask, B * N, or_none=True)
     if not torch.is_tensor(normals) or normals.dtype != f32 or tuple(normals.shape) != (B, 3, N):
-        raise ValueError("render_surfels: normals must be float32 [%d, 3, %d], got %s %s" % (
-            B, N, getattr(normals, "dtype", type(normals).__name__), tuple(normals.shape) if torch.is_tensor(normals) else ""))
-    C = 0
-    if attr is not None:
-        if not torch.is_tensor(attr) or attr.dtype != f32 or attr.dim() != 3 or attr.shape[0] != B or attr.shape[2] != N or not (
-                1 <= attr.shape[1] <= POINT_IMAGE_MAX_C):
-            raise ValueError("render_surfels: attr must be float32 [%d, C, %d] with 1 <= C <= %d, got %s %s" % (
-                B, N, POINT_IMAGE_MAX_C, getattr(attr, "dtype", type(attr).__name__), tuple(attr.shape) if torch.is_tensor(attr) else ""))
-        C = attr.shape[1]
-    radius = _surfel_scalar("render_surfels", "radius", radius)
-    range_slope = _surfel_scalar("render_surfels", "range_slope", range_slope)
-    min_cos = _surfel_scalar("render_surfels", "min_cos", min_cos, 1.0)
-    if not _is_int(max_px) or not 0 <= max_px <= SURFEL_MAX_PX:
-        raise ValueError("render_surfels: max_px must be an integer in [0, %d], got %r" % (SURFEL_MAX_PX, max_px))
-    try:
-        fill = float(fill)
-    except (TypeError, ValueError):
-        raise ValueError("render_surfels: fill must be a number, got %r" % (fill,))
-    ts = [t for t in (pts, normals, pose, K, attr, mask) if t is not None]
-    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
-        raise ValueError("render_surfels: every tensor must be a contiguous tensor on the same GPU")
-    if mask is not None and mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
+        raise ValueError("render_surfels: normals must be float32 [%d, 3, %d], got %s %s" % ((B, N) + _got(normals)))
+    C = _point_attr(who, attr, B, N)
+    # the second closing bracket is the wording these three have had, and callers may match on it
+    radius = _f32_arg(who, "radius", radius, "be a finite number in [0, inf)]", bools=False)
+    range_slope = _f32_arg(who, "range_slope", range_slope, "be a finite number in [0, inf)]", bools=False)
+    min_cos = _f32_arg(who, "min_cos", min_cos, "be a finite number in [0, 1]]", hi=1.0, bools=False)
+    _int_arg(who, "max_px", max_px, 0, SURFEL_MAX_PX)
+    fill = _f32_arg(who, "fill", fill, "be a number", lo=None)
+    _on_one_gpu(who, pts, normals, pose, K, attr, mask)
     dev = pts.device
     index_map = torch.empty((B, h, w), dtype=torch.int32, device=dev)
     depth_map = torch.empty((B, h, w), dtype=f32, device=dev)
@@ -1500,24 +1414,18 @@ def depth_test(pts, pose, K, depth_map, mask, radius=0, rel_tol=0.05, abs_tol=0.
     = 0.05 it is not tuned on real data.
     -> (visible bool [B*N], counts int32 [B, 3] = (selected, selected and in view, visible))."""
     if not torch.is_tensor(depth_map) or depth_map.dim() != 3 or depth_map.dtype != f32:
-        raise ValueError("depth_test: depth_map must be float32 [B, h, w], got %s %s" % (
-            getattr(depth_map, "dtype", type(depth_map).__name__), tuple(depth_map.shape) if torch.is_tensor(depth_map) else ""))
+        raise ValueError("depth_test: depth_map must be float32 [B, h, w], got %s %s" % _got(depth_map))
     Bd, h, w = depth_map.shape
     if mask is None:
         raise ValueError("depth_test: mask must be bool / uint8 / int64 (the rows that are queried), got None")
-    B, N, h, w = _point_image_args("depth_test", pts, pose, K, h, w, mask)
+    B, N, h, w = _camera_args("depth_test", pts, pose, K, h, w)
+    mask = _row_mask("depth_test", "mask", mask, B * N, or_none=True)
     if Bd != B:
         raise ValueError("depth_test: depth_map must be float32 [%d, h, w], got %s" % (B, tuple(depth_map.shape)))
-    if not _is_int(radius) or not 0 <= radius <= GUIDED_MAX_RADIUS:
-        raise ValueError("depth_test: radius must be an integer in [0, %d], got %r" % (GUIDED_MAX_RADIUS, radius))
-    if not _tol_ok(rel_tol):
-        raise ValueError("depth_test: rel_tol must be finite and >= 0, got %r" % (rel_tol,))
-    if not _tol_ok(abs_tol):
-        raise ValueError("depth_test: abs_tol must be finite and >= 0, got %r" % (abs_tol,))
-    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in (pts, pose, K, depth_map, mask)):
-        raise ValueError("depth_test: every tensor must be a contiguous tensor on the same GPU")
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
+    _int_arg("depth_test", "radius", radius, 0, GUIDED_MAX_RADIUS)
+    _f32_arg("depth_test", "rel_tol", rel_tol, "be finite and >= 0")
+    _f32_arg("depth_test", "abs_tol", abs_tol, "be finite and >= 0")
+    _on_one_gpu("depth_test", pts, pose, K, depth_map, mask)
     dev = pts.device
     visible = torch.empty((B * N,), dtype=torch.uint8, device=dev)
     counts = torch.empty((B, 3), dtype=torch.int32, device=dev)
@@ -1559,35 +1467,20 @@ def pose_mi(pts, attr, grey, mask, poses, K, bins=32, mode='nearest', attr_range
     (hi - lo) rounded once to float32.
     -> (mi float64 [B, P] = H_a + H_g - H_ag in nats, higher is better; entropy float64 [B, P, 3] = (H_a, H_g, H_ag); counts int32
     [B, P, 2] = (in view, counted); selected int32 [B]; hist int32 [B, P, bins, bins] (attribute bin, grey bin) or None)."""
-    if not torch.is_tensor(pts) or pts.dim() != 3 or pts.shape[1] != 3:
-        raise ValueError("pose_mi: pts must be [B, 3, N], got %s" % (tuple(pts.shape) if torch.is_tensor(pts) else type(pts).__name__,))
-    B, _, N = pts.shape
+    who = "pose_mi"
+    B, _, N = _shaped(who, "pts", pts, "B", 3, "N")
     if not all(torch.is_tensor(t) for t in (attr, grey, poses, K)):
         raise ValueError("pose_mi: attr, grey, poses and K must be tensors")
-    if pts.dtype != f32 or attr.dtype != f32 or grey.dtype != f32 or poses.dtype != f32 or K.dtype != f32:
-        raise ValueError("pose_mi: pts, attr, grey, poses and K must be float32, got %s / %s / %s / %s / %s" % (
-            pts.dtype, attr.dtype, grey.dtype, poses.dtype, K.dtype))
-    if tuple(attr.shape) != (B, N):
-        raise ValueError("pose_mi: attr must be [%d, %d], got %s" % (B, N, tuple(attr.shape)))
+    _float32(who, "pts, attr, grey, poses and K", pts, attr, grey, poses, K)
+    _shaped(who, "attr", attr, B, N)
     if grey.dim() != 3 or grey.shape[0] != B:
         raise ValueError("pose_mi: grey must be one plane per sample [%d, H, W], got %s" % (B, tuple(grey.shape)))
     H, W = grey.shape[1:]
-    if poses.dim() != 4 or poses.shape[0] != B or tuple(poses.shape[2:]) != (4, 4):
-        raise ValueError("pose_mi: poses must be [%d, P, 4, 4], got %s" % (B, tuple(poses.shape)))
-    P = poses.shape[1]
-    if P < 1 or P > POSE_SCORE_MAX_POSES:
-        raise ValueError("pose_mi: need 1 <= P <= %d poses per sample, got %d" % (POSE_SCORE_MAX_POSES, P))
-    if tuple(K.shape) != (B, 3, 3):
-        raise ValueError("pose_mi: K must be [%d, 3, 3], got %s" % (B, tuple(K.shape)))
-    if B < 1 or B > GRID_Y_MAX or N < 1 or N > GRID_Y_MAX * 256 or H < 1 or W < 1 or H * W > 1 << 24:
-        raise ValueError("pose_mi: need 1 <= B <= %d, 1 <= N <= %d and an image of 1 .. 2^24 pixels, got B=%d N=%d image %d x %d" % (
-            GRID_Y_MAX, GRID_Y_MAX * 256, B, N, H, W))
-    if mask is not None and (not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N):
-        raise ValueError("pose_mi: mask must be None or bool / uint8 / int64 with %d elements, got %s %s" % (
-            B * N, getattr(mask, "dtype", type(mask).__name__), tuple(mask.shape) if torch.is_tensor(mask) else ""))
-    if not _is_int(bins) or not 2 <= bins <= POSE_MI_MAX_BINS:
-        raise ValueError("pose_mi: bins must be an integer in [2, %d], got %r" % (POSE_MI_MAX_BINS, bins))
-    bins = int(bins)
+    P = _poses_arg(who, poses, B)
+    _shaped(who, "K", K, B, 3, 3)
+    _cloud_range(who, B, N, 256, H, W, "image")
+    mask = _row_mask(who, "mask", mask, B * N, or_none=True)
+    bins = _int_arg(who, "bins", bins, 2, POSE_MI_MAX_BINS)
     if not isinstance(mode, str) or mode not in _PAINT_MODES:
         raise ValueError("pose_mi: mode must be 'nearest' or 'bilinear', got %r" % (mode,))
     a_lo, a_hi = _pose_mi_range("attr_range", attr_range, bins)
@@ -1595,11 +1488,7 @@ def pose_mi(pts, attr, grey, mask, poses, K, bins=32, mode='nearest', attr_range
     chunk = pose_mi_chunk(bins)
     if ((N + POSE_MI_SLICE - 1) // POSE_MI_SLICE) * ((P + chunk - 1) // chunk) * B > 0x7fffffff:
         raise ValueError("pose_mi: B=%d N=%d P=%d need more than 2^31 - 1 workgroups, score the poses or the samples in parts" % (B, N, P))
-    ts = [t for t in (pts, attr, grey, mask, poses, K) if t is not None]
-    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
-        raise ValueError("pose_mi: every tensor must be a contiguous tensor on the same GPU")
-    if mask is not None and mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
+    _on_one_gpu(who, pts, attr, grey, mask, poses, K)
     dev = pts.device
     hist = torch.empty((B, P, bins, bins), dtype=torch.int32, device=dev)
     counts = torch.empty((B, P, 2), dtype=torch.int32, device=dev)
@@ -1616,15 +1505,6 @@ DENSIFY_MAX_C = 4           # csrc/densify.hip DN_MAX_C: attribute planes, and g
 DENSIFY_TILE_W = 64         # csrc/densify.hip DN_TW x DN_TH: the pixels of one workgroup (tests put their shapes round these)
 DENSIFY_TILE_H = 16
 DENSIFY_MIN_WEIGHT = 1e-24
-
-
-def _pos_f32(v):
-    """a number that is finite and > 0 as a float32"""
-    try:
-        v = float(torch.tensor(float(v), dtype=f32))
-    except (TypeError, ValueError, OverflowError):
-        return False
-    return 0.0 < v < float("inf")
 
 
 def densify(depth, guide=None, attr=None, radius=8, sigma_s=None, sigma_r=0.1, min_weight=1e-3, keep=True, fill=0.0, want_count=False):
@@ -1652,36 +1532,26 @@ def densify(depth, guide=None, attr=None, radius=8, sigma_s=None, sigma_r=0.1, m
     if guide is not None:
         if not torch.is_tensor(guide) or guide.dtype != f32 or guide.dim() != 4 or guide.shape[0] != B or tuple(guide.shape[2:]) != (h, w) \
                 or not 1 <= guide.shape[1] <= DENSIFY_MAX_C:
-            raise ValueError("densify: guide must be float32 [%d, Cg, %d, %d] with 1 <= Cg <= %d, got %s %s" % (
-                B, h, w, DENSIFY_MAX_C, getattr(guide, "dtype", type(guide).__name__), tuple(guide.shape) if torch.is_tensor(guide) else ""))
+            raise ValueError("densify: guide must be float32 [%d, Cg, %d, %d] with 1 <= Cg <= %d, got %s %s" % ((B, h, w, DENSIFY_MAX_C) + _got(guide)))
         Cg = guide.shape[1]
     if attr is not None:
         if not torch.is_tensor(attr) or attr.dtype != f32 or attr.dim() != 4 or attr.shape[0] != B or tuple(attr.shape[2:]) != (h, w) \
                 or not 1 <= attr.shape[1] <= DENSIFY_MAX_C:
-            raise ValueError("densify: attr must be float32 [%d, C, %d, %d] with 1 <= C <= %d, got %s %s" % (
-                B, h, w, DENSIFY_MAX_C, getattr(attr, "dtype", type(attr).__name__), tuple(attr.shape) if torch.is_tensor(attr) else ""))
+            raise ValueError("densify: attr must be float32 [%d, C, %d, %d] with 1 <= C <= %d, got %s %s" % ((B, h, w, DENSIFY_MAX_C) + _got(attr)))
         C = attr.shape[1]
-    if not _is_int(radius) or not 0 <= radius <= DENSIFY_MAX_RADIUS:
-        raise ValueError("densify: radius must be an integer in [0, %d], got %r" % (DENSIFY_MAX_RADIUS, radius))
+    _int_arg("densify", "radius", radius, 0, DENSIFY_MAX_RADIUS)
     if sigma_s is None:
         sigma_s = max(int(radius), 1) / 2
-    if not _pos_f32(sigma_s):
-        raise ValueError("densify: sigma_s must be finite and > 0, got %r" % (sigma_s,))
-    if not _pos_f32(sigma_r):
-        raise ValueError("densify: sigma_r must be finite and > 0, got %r" % (sigma_r,))
-    if not _pos_f32(min_weight) or float(min_weight) < DENSIFY_MIN_WEIGHT:
-        raise ValueError("densify: min_weight must be finite and >= %g, got %r" % (DENSIFY_MIN_WEIGHT, min_weight))
-    if _pos_f32(math.log2(math.e) / (2.0 * float(sigma_s) ** 2)) is False or (Cg and _pos_f32(math.log2(math.e) / (2.0 * float(sigma_r) ** 2)) is False):
+    _f32_arg("densify", "sigma_s", sigma_s, "be finite and > 0", lo_open=True)
+    _f32_arg("densify", "sigma_r", sigma_r, "be finite and > 0", lo_open=True)
+    _f32_arg("densify", "min_weight", min_weight, "be finite and >= %g" % DENSIFY_MIN_WEIGHT, lo=DENSIFY_MIN_WEIGHT)
+    coefs = [math.log2(math.e) / (2.0 * float(s) ** 2) for s in ((sigma_s, sigma_r) if Cg else (sigma_s,))]      # the kernel's exponents' factors
+    if not all(0.0 < float(torch.tensor(c, dtype=f32)) < math.inf for c in coefs):
         raise ValueError("densify: 1 / (2 sigma^2) must be a float32 > 0, got sigma_s=%r sigma_r=%r" % (sigma_s, sigma_r))
     if not isinstance(keep, (bool, int)) or keep not in (0, 1):
         raise ValueError("densify: keep must be True or False, got %r" % (keep,))
-    try:
-        fill = float(fill)
-    except (TypeError, ValueError):
-        raise ValueError("densify: fill must be a number, got %r" % (fill,))
-    ts = [t for t in (depth, guide, attr) if t is not None]
-    if not all(t.is_cuda and t.is_contiguous() and t.device == depth.device for t in ts):
-        raise ValueError("densify: every tensor must be a contiguous tensor on the same GPU")
+    fill = _f32_arg("densify", "fill", fill, "be a number", lo=None)
+    _on_one_gpu("densify", depth, guide, attr)
     dev = depth.device
     dense_depth = torch.empty((B, h, w), dtype=f32, device=dev)
     dense_attr = torch.empty((B, C, h, w), dtype=f32, device=dev) if attr is not None else None
@@ -1699,30 +1569,17 @@ def pnp_refine(pts, uv, mask, K, pose, thr=1.0, iters=10):
     (finite; maps pts into the camera frame); the rows that are inliers of `pose` within thr pixels are the working set, up to iters steps.
     -> (pose float32 [B, 4, 4], inliers int32 [B], status int32 [B]: 0 refined, 1 fewer than 4 rows in the working set, 2 refinement
     not kept; 1 and 2 return the input pose)."""
-    if pts.dim() != 3 or pts.shape[1] != 3:
-        raise ValueError("pnp_refine: pts must be [B, 3, N], got %s" % (tuple(pts.shape),))
-    B, _, N = pts.shape
-    if tuple(uv.shape) != (B, 2, N):
-        raise ValueError("pnp_refine: uv must be [%d, 2, %d], got %s" % (B, N, tuple(uv.shape)))
-    if tuple(K.shape) != (B, 3, 3):
-        raise ValueError("pnp_refine: K must be [%d, 3, 3], got %s" % (B, tuple(K.shape)))
-    if tuple(pose.shape) != (B, 4, 4):
-        raise ValueError("pnp_refine: pose must be [%d, 4, 4], got %s" % (B, tuple(pose.shape)))
-    if pts.dtype != f32 or uv.dtype != f32 or K.dtype != f32 or pose.dtype != f32:
-        raise ValueError("pnp_refine: pts, uv, K and pose must be float32, got %s / %s / %s / %s" % (pts.dtype, uv.dtype, K.dtype, pose.dtype))
-    if mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N:
-        raise ValueError("pnp_refine: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (B * N, mask.dtype, tuple(mask.shape)))
-    if B < 1 or B > GRID_Y_MAX or N < 1 or N > GRID_Y_MAX * 1024:
-        raise ValueError("pnp_refine: need 1 <= B <= %d and 1 <= N <= %d, got B=%d N=%d" % (GRID_Y_MAX, GRID_Y_MAX * 1024, B, N))
-    if not (float(thr) > 0.0 and float(thr) < float("inf")):
-        raise ValueError("pnp_refine: thr must be a finite positive number, got %r" % (thr,))
-    if not _is_int(iters) or not 0 <= iters <= 1000:
-        raise ValueError("pnp_refine: iters must be an integer in [0, 1000], got %r" % (iters,))
-    ts = (pts, uv, mask, K, pose)
-    if not all(t.is_cuda and t.is_contiguous() and t.device == pts.device for t in ts):
-        raise ValueError("pnp_refine: every tensor must be a contiguous tensor on the same GPU")
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
+    who = "pnp_refine"
+    B, _, N = _shaped(who, "pts", pts, "B", 3, "N")
+    _shaped(who, "uv", uv, B, 2, N)
+    _shaped(who, "K", K, B, 3, 3)
+    _shaped(who, "pose", pose, B, 4, 4)
+    _float32(who, "pts, uv, K and pose", pts, uv, K, pose)
+    mask = _row_mask(who, "mask", mask, B * N)
+    _cloud_range(who, B, N, 1024)
+    _f32_arg(who, "thr", thr, "be a finite positive number", lo_open=True)
+    _int_arg(who, "iters", iters, 0, 1000)
+    _on_one_gpu(who, pts, uv, mask, K, pose)
     dev = pts.device
     out = torch.empty((B, 4, 4), dtype=f32, device=dev)
     inliers = torch.empty((B,), dtype=torch.int32, device=dev)
@@ -1742,36 +1599,20 @@ def match_subpixel(pc_feat_rows, img_feat_nhwc, idx, mask=None, gt_xy=None, thr=
     non-zero and 0 <= idx < h * w.
     -> (uv float32 [B, 2, N] = (x + dx, y + dy) with |dx|, |dy| <= 0.5, NaN on unmatched rows, counts int32 [B, 4] = (matched, fitted on
     both axes, matched whose integer pixel is within thr of gt_xy, matched whose sub-pixel position is))."""
-    if pc_feat_rows.dim() != 2 or img_feat_nhwc.dim() != 4:
-        raise ValueError("match_subpixel: point rows must be 2-D [B*N, C] and pixel features 4-D [B, h, w, C], got %s / %s" % (
-            tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
-    B, h, w, C = img_feat_nhwc.shape
+    who = "match_subpixel"
+    B, h, w, C = _feature_pair(who, pc_feat_rows, img_feat_nhwc)
     if B < 1 or pc_feat_rows.shape[0] % B:
         raise ValueError("match_subpixel: point rows %s and pixel features %s do not agree on B and N" % (
             tuple(pc_feat_rows.shape), tuple(img_feat_nhwc.shape)))
     N = pc_feat_rows.shape[0] // B
-    if C != 64 or pc_feat_rows.shape[1] != 64:
-        raise ValueError("match_subpixel: feature width must be 64, got %d / %d" % (pc_feat_rows.shape[1], C))
-    if pc_feat_rows.dtype != f32 or img_feat_nhwc.dtype != f32:
-        raise ValueError("match_subpixel: features must be float32, got %s / %s" % (pc_feat_rows.dtype, img_feat_nhwc.dtype))
+    _float32(who, "features", pc_feat_rows, img_feat_nhwc)
     if idx.dtype != torch.int32 or idx.numel() != B * N:
         raise ValueError("match_subpixel: idx must be int32 with %d elements, got %s %s" % (B * N, idx.dtype, tuple(idx.shape)))
-    if mask is not None and (mask.dtype not in (torch.bool, torch.uint8, torch.int64) or mask.numel() != B * N):
-        raise ValueError("match_subpixel: mask must be bool / uint8 / int64 with %d elements, got %s %s" % (B * N, mask.dtype, tuple(mask.shape)))
-    if gt_xy is not None and (gt_xy.dtype != f32 or tuple(gt_xy.shape) != (B, 2, N)):
-        raise ValueError("match_subpixel: gt_xy must be float32 [%d, 2, %d], got %s %s" % (B, N, gt_xy.dtype, tuple(gt_xy.shape)))
-    if not (float(thr) > 0.0 and float(thr) < float("inf")):
-        raise ValueError("match_subpixel: thr must be a finite positive number, got %r" % (thr,))
-    if B > GRID_Y_MAX or N < 1 or N > GRID_Y_MAX * 256 or h < 1 or w < 1 or h * w > 1 << 24:
-        raise ValueError("match_subpixel: need 1 <= B <= %d, 1 <= N <= %d and a map of 1 .. 2^24 pixels, got B=%d N=%d map %d x %d" % (
-            GRID_Y_MAX, GRID_Y_MAX * 256, B, N, h, w))
-    ts = [t for t in (pc_feat_rows, img_feat_nhwc, idx, mask, gt_xy) if t is not None]
-    if not all(t.is_cuda and t.is_contiguous() and t.device == pc_feat_rows.device for t in ts):
-        raise ValueError("match_subpixel: every tensor must be a contiguous tensor on the same GPU")
-    if pc_feat_rows.data_ptr() % 16 or img_feat_nhwc.data_ptr() % 16:
-        raise ValueError("match_subpixel: feature rows must be 16-byte aligned")
-    if mask is not None and mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
+    mask = None if mask is None else _row_mask(who, "mask", mask, B * N)
+    _gt_xy_arg(who, gt_xy, B, N)
+    _f32_arg(who, "thr", thr, "be a finite positive number", lo_open=True, as_f32=False)    # the kernel compares with whatever float32 makes of it
+    _cloud_range(who, B, N, 256, h, w)
+    _on_one_gpu(who, pc_feat_rows, img_feat_nhwc, idx, mask, gt_xy, aligned=(pc_feat_rows, img_feat_nhwc))
     dev = pc_feat_rows.device
     uv = torch.empty((B, 2, N), dtype=f32, device=dev)
     counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
