@@ -388,14 +388,11 @@ __device__ __forceinline__ void ws_barrier_lds() { asm volatile("s_waitcnt lgkmc
 
 // dbg: compile-time ablation mask used while tuning (see launch_wino_ws); the library instantiates 0 only, where every
 // `dbg & ...` test folds away.
-// MW = MFMA waves per SIMD.  1: waves 0-3 multiply (4 positions x 2 cout tiles = 128 accumulator registers each), waves 4-7 help:
-// 8 waves x 256 registers.  2: waves 0-7 multiply -- wave m owns position row m & 3 and cout tile m >> 2 (64 accumulator registers,
-// the same products in the same order: bit-identical results) -- and waves 8-11 help: 12 waves x 168 registers.  Two MFMA waves share
-// a SIMD's matrix pipe, so one wave's wait for its U fragments is the other's issue slot; the price is that both waves of a SIMD read
-// and transform the same patch rows (LDS reads and VALU x 2) and that 168 registers make the helpers spill.  MEASURED (round 5,
-// tools/wino_mw_ab.py, profiles/r05_wino_mw_ab.txt): bit-identical and 10 - 25 % slower at every shape of the step (352x1216 64->64:
-// 1 112 -> 1 432 us; 88x304 128->128: 257 -> 293 us) -- the single MFMA wave was not starved (it issues 80 % of the launch's cycles at
-// the ~1.93 GHz the chip sustains under this load), so MW = 1 stays the library's choice; MW = 2 is kept for the A/B.
+// One MFMA wave per SIMD: waves 0-3 multiply (4 positions x 2 cout tiles = 128 accumulator registers each), waves 4-7 help: 8 waves x
+// 256 registers.  Two MFMA waves per SIMD (8 multiplying waves of one cout tile each, 12 waves x 168 registers) were MEASURED (round 5,
+// recorded in docs/MEASUREMENT_ROUNDS_1_5.md and profiles/README_r05.md): bit-identical and 10 - 25 % slower at every shape of the step
+// (352x1216 64->64: 1 112 -> 1 432 us; 88x304 128->128: 257 -> 293 us) -- the single MFMA wave was not starved (it issues 80 % of the
+// launch's cycles at the ~1.93 GHz the chip sustains under this load); that variant was removed.
 #ifndef CMR_WS_STATS
 #define CMR_WS_STATS 1        // BatchNorm sums in the helpers' epilogue (0 / CMR_WS_BNBWD 0: compiled out, for same-box A/B builds)
 #endif
@@ -406,11 +403,11 @@ __device__ __forceinline__ void ws_barrier_lds() { asm volatile("s_waitcnt lgkmc
                               // 76; compiled out (cmr_conv3x3_wino_bnbwd_nhwc_f32 answers -3), -DCMR_WS_BNBWD=1 brings it back
 #endif
 constexpr bool WS_STATS = CMR_WS_STATS != 0, WS_BNBWD = CMR_WS_STATS != 0 && CMR_WS_BNBWD != 0;
-template <int dbg, int MW>
-__global__ __launch_bounds__(256 * (MW + 1), 1) void conv3x3_wino_ws_kernel(const WinoArgs a, const int tiles_x, const int tiles_y, const int ntiles) {
+template <int dbg>
+__global__ __launch_bounds__(512, 1) void conv3x3_wino_ws_kernel(const WinoArgs a, const int tiles_x, const int tiles_y, const int ntiles) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int NT = 2 / MW;                         // cout tiles per MFMA wave
-  constexpr int NMW = 4 * MW;                        // MFMA waves
+  constexpr int NT = 2;                              // cout tiles per MFMA wave
+  constexpr int NMW = 4;                             // MFMA waves
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nco = a.Cout / 64;
@@ -850,23 +847,15 @@ __global__ __launch_bounds__(256 * (MW + 1), 1) void conv3x3_wino_ws_kernel(cons
 #ifndef CMR_WS_DBG
 #define CMR_WS_DBG 0
 #endif
-#ifndef CMR_WINO_MW
-#define CMR_WINO_MW 1
-#endif
-#ifdef CMR_AB_SWITCHES
-static int g_wino_mw = CMR_WINO_MW;                  // cmr_set_wino_mfma_waves: A/B measurements, libcmr_hip_ab.so only
-#else
-static constexpr int g_wino_mw = CMR_WINO_MW;
-#endif
 // workgroups of a wave-specialised launch (= partial-sum slots of a statistics launch / 4)
 inline unsigned wino_ws_grid(int64_t ntiles, int cu_budget, int slices);
-template <int DBG, int MW>
+template <int DBG>
 int launch_wino_ws_t(const WinoArgs& a, int tiles_x, int tiles_y, int64_t ntiles, int cu_budget, int slices, hipStream_t stream) {
   constexpr int smem = WS_SMEM_FLOATS * (int)sizeof(float);
   static CmrSmemCache granted{};
-  if (cmr_grant_smem(reinterpret_cast<const void*>(conv3x3_wino_ws_kernel<DBG, MW>), smem, granted) != CMR_OK) return CMR_ELAUNCH;
+  if (cmr_grant_smem(reinterpret_cast<const void*>(conv3x3_wino_ws_kernel<DBG>), smem, granted) != CMR_OK) return CMR_ELAUNCH;
   const unsigned grid = wino_ws_grid(ntiles, cu_budget, slices);
-  hipLaunchKernelGGL((conv3x3_wino_ws_kernel<DBG, MW>), dim3(grid), dim3(256 * (MW + 1)), smem, stream, a, tiles_x, tiles_y, (int)ntiles);
+  hipLaunchKernelGGL(conv3x3_wino_ws_kernel<DBG>, dim3(grid), dim3(512), smem, stream, a, tiles_x, tiles_y, (int)ntiles);
   return cmr_launch_status();
 }
 inline unsigned wino_ws_grid(int64_t ntiles, int cu_budget, int slices) {
@@ -892,8 +881,7 @@ int launch_wino_ws(const WinoArgs& a, int tiles_x, int tiles_y, int64_t ntiles, 
   // DBG bits (compile-time ablations used while tuning: 1 no stores, 2 no epilogue, 4 no T hand-over, 8 no U loads, 16 no LDS
   // prefetch, 32 no MFMAs, 128 every tile stored over the same few tiles (stores without HBM write traffic), 64 s_memtime stamps of busy / barrier-wait cycles per wave into the buffer passed as `post`) are not
   // instantiated in the shipped library: tools/ab_build.sh cmr_agent_amd/csrc/conv_wino.hip <tag> -DCMR_WS_DBG=<mask>
-  if (g_wino_mw == 2) return launch_wino_ws_t<CMR_WS_DBG, 2>(a, tiles_x, tiles_y, ntiles, cu_budget, slices, stream);
-  return launch_wino_ws_t<CMR_WS_DBG, 1>(a, tiles_x, tiles_y, ntiles, cu_budget, slices, stream);
+  return launch_wino_ws_t<CMR_WS_DBG>(a, tiles_x, tiles_y, ntiles, cu_budget, slices, stream);
 }
 
 template <int NT>
@@ -914,11 +902,6 @@ int launch_wino(const WinoArgs& a, int tiles_x, int tiles_y, int64_t ntiles, hip
 // Both are ARGUMENTS of the call: the library keeps no launch policy of its own (round 3 had process-global setters here).
 #ifdef CMR_AB_SWITCHES
 static int CMR_WINO_WS = 1;      // wave-specialised persistent kernel for large maps (cmr_set_wino_variant: A/B measurements, libcmr_hip_ab.so only)
-extern "C" int cmr_set_wino_mfma_waves(int per_simd) {
-  const int old = g_wino_mw;
-  g_wino_mw = per_simd == 2 ? 2 : 1;
-  return old;
-}
 extern "C" int cmr_set_wino_variant(int wave_specialised) {
   const int old = CMR_WINO_WS;
   CMR_WINO_WS = wave_specialised & 1;

@@ -25,11 +25,6 @@ int cmr_set_linear_wreg(int on, int64_t min_rows);
  * the default; 0 = 4-wave workgroups for every map): A/B measurements and tests only.  Returns the previous setting. */
 int cmr_set_wino_variant(int wave_specialised);
 
-/* MFMA waves per SIMD of the wave-specialised Winograd kernel: 1 = 8-wave workgroups (4 multiply, 4 help: the default), 2 = 12-wave
- * workgroups (8 multiply -- position row x cout tile -- 4 help; round-5 experiment, 10 - 25 % SLOWER: profiles/r05_wino_mw_ab.txt).  Same
- * products in the same order: bit-identical results.  A/B measurements and tests only.  Returns the previous setting. */
-int cmr_set_wino_mfma_waves(int per_simd);
-
 /* Process-wide switch of the bf16 convolution's kernel choice for 128-cout layers without residual / table operand (stride 1,
  * Cin = 64 | 128): matrix_class = 1 (default) routes maps of at least min_tiles 8x32-pixel tiles (x Cout / 128; min_tiles <= 0 keeps the
  * current threshold) to the register-tiled kernel that streams the weight fragments from L2 (conv3x3_bf16_mm_kernel), 0 keeps the
@@ -46,18 +41,11 @@ int cmr_set_mha_variant(int mfma);
  * to fp32 rounding); returns the previous setting. */
 int cmr_set_wgrad_variant(int lds_staged);
 
-/* A/B switch of the bf16 3x3 weight gradient on Cin 128 / Cout % 64 == 0 maps of >= 32 768 pixels: 1 (default, the product library's only
- * choice) = second generation (rows staged through registers as they lie in memory, operands through ds_read_b64_tr_b16, 64 couts per
- * 8-wave workgroup), 2 = third generation (rows by LDS-DMA into a raw ring, one input row per iteration; on the same strips bit-identical
- * to 1; round-5 experiment, measured slower: profiles/r05_wgrad_dma_ablate.txt), 16 + mask = its timing-only ablations, 0 = the
- * first-generation kernel everywhere (rows transposed by the lanes on the way into LDS; same products, other summation order).
- * Returns the previous setting. */
-int cmr_set_wgrad_bf16_variant(int generation);
-
-/* bf16 weight gradient: strips per workgroup the row count of a strip is sized for -- per_workgroup > 0: third generation (default 4),
- * < 0: second generation (- per_workgroup; default 8; 4 measured 4 % faster alone and no different in the update: profiles/r05_wgrad_dma_ablate.txt),
- * 0 keeps both.  Other strips = other partial sums: results agree to fp32 rounding.  Returns the third generation's previous setting. */
-int cmr_set_wgrad_bf16_strips(int per_workgroup);
+/* A/B switch of the bf16 3x3 weight gradient on Cin 128 / Cout % 64 == 0 maps of >= 32 768 pixels: nonzero (default 1, the product
+ * library's only choice) = second generation (rows staged through registers as they lie in memory, operands through ds_read_b64_tr_b16,
+ * 64 couts per 8-wave workgroup), 0 = the first-generation kernel everywhere (rows transposed by the lanes on the way into LDS; same
+ * products, other summation order).  Returns the previous setting. */
+int cmr_set_wgrad_bf16_variant(int transposed_reads);
 
 /* A/B switch: 1 (default) = row maps of >= 65 536 rows with n, k multiples of 32 up to 128 take the LDS-staged kernel (whole-row
  * float4 staging, the full gradient per workgroup), 2 = from 8192 rows on (tests), 0 = the direct kernel everywhere.  Same sums in

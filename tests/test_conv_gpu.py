@@ -158,24 +158,6 @@ def test_forward_is_exact(ops, ir, impulse):
         exact(ops.conv3x3_wino(o.x, o.u, o.bias, cout, o.c.slope, o.res, o.post, o.c.pool), ref, "ops.conv3x3_wino under the policy")
 
 
-@pytest.mark.parametrize("i", [i for i, r in FWD if r.kernel == "wino_ws"])
-def test_wave_specialised_winograd_with_two_mfma_waves(ops, i):
-    """the A/B library's two-matrix-waves-per-SIMD variant of the wave-specialised kernel, on the same cases"""
-    o, ref = _prepared(i, False)
-    oi, refi = _prepared(i, True)
-    with _lib().ab() as lib:
-        old = lib.cmr_set_wino_mfma_waves(2)
-        try:
-            for oo, rr in ((o, ref), (oi, refi)):
-                for budget, slices in ((0, 1), (8, 1), (24, 3)):
-                    rc, y = call_wino(oo, budget, slices)
-                    assert rc == 0
-                    exact(y, rr, "wino_ws, 2 MFMA waves, cu_budget %d slices %d" % (budget, slices))
-        finally:
-            lib.cmr_set_wino_mfma_waves(old)
-    assert old == 1
-
-
 def test_stride2_fragment_kernel_refuses_a_table(ops):
     i = next(i for i, r in FWD if r.entry == "s2" and r.shape == (2, 7, 9, 64, 64))
     o, _ = _prepared(i, False)
