@@ -89,10 +89,25 @@ __global__ __launch_bounds__(256) void observation_finalize_kernel(const float* 
 //   obs_scatter_kernel  (wave per 4 points) proj[cell][c] += feat[p][c] / cnt[cell]      (scatter_mean as a sum of pre-divided terms)
 // The clears of a step never meet the increments of the same step (different launches), so no buffer parity has to survive between
 // hipGraph replays; cells hit by nobody stay zero from the initial fill.
+// Tile reach of an occupied cell (cmr_observation_proj_reach_f32): map[b][ty][tx] = 1 for every 8 x 16 tile of the h x w grid (ceil at the
+// borders) whose area dilated by r pixels holds (yi, xi) -- at most 2 x 2 tiles for r < 8.  Every writer stores the same byte, so the
+// races between points are benign.
+__device__ __forceinline__ void obs_mark_reach(uint8_t* __restrict__ map, int r, int b, int yi, int xi, int h, int w) {
+  const int tiles_y = (h + 7) >> 3, tiles_x = (w + 15) >> 4;
+  const int ya = (yi - r > 0 ? yi - r : 0) >> 3, yb = (yi + r) >> 3 < tiles_y ? (yi + r) >> 3 : tiles_y - 1;
+  const int xa = (xi - r > 0 ? xi - r : 0) >> 4, xb = (xi + r) >> 4 < tiles_x ? (xi + r) >> 4 : tiles_x - 1;
+  uint8_t* m = map + (int64_t)b * tiles_y * tiles_x;
+  m[ya * tiles_x + xa] = 1;
+  m[ya * tiles_x + xb] = 1;
+  m[yb * tiles_x + xa] = 1;
+  m[yb * tiles_x + xb] = 1;
+}
+
 __global__ __launch_bounds__(256) void obs_project_kernel(const float* __restrict__ pc4, const uint8_t* __restrict__ overlap,
                                                           const float* __restrict__ pose, const float* __restrict__ Kmat,
                                                           const float* __restrict__ mean4, float* __restrict__ proj, float* __restrict__ cnt,
-                                                          int32_t* __restrict__ cell, float* __restrict__ state3d, int B, int N, int h, int w) {
+                                                          int32_t* __restrict__ cell, float* __restrict__ state3d, int B, int N, int h, int w,
+                                                          uint8_t* __restrict__ reach1, uint8_t* __restrict__ reach2) {
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= (int64_t)B * N) return;
   const int32_t prev = cell[p];
@@ -125,6 +140,10 @@ __global__ __launch_bounds__(256) void obs_project_kernel(const float* __restric
   if (ov && inside) {
     const int xi = (int)rintf(u), yi = (int)rintf(v);            // torch.round = half to even
     c = (int32_t)((int64_t)b * h * w + (int64_t)yi * w + xi);
+    if (reach1) {                                                // (uniform) the convolutions' 8 x 16 tiles this cell can reach
+      obs_mark_reach(reach1, 1, b, yi, xi, h, w);
+      obs_mark_reach(reach2, 2, b, yi, xi, h, w);
+    }
   }
   cell[p] = c;
 }
@@ -268,19 +287,28 @@ extern "C" int cmr_project_scatter_f32(const float* pc4, const float* feat, cons
   return cmr_launch_status();
 }
 
-extern "C" int cmr_observation_proj_f32(const float* pc4, const float* feat, const uint8_t* overlap, const float* pose, const float* Kmat,
-                                        const float* mean4, float* proj, float* cnt, int32_t* cell, float* state3d, int B, int N, int h,
-                                        int w, hipStream_t stream) {
+// reach1 / reach2 (both or neither): byte maps [B][ceil(h / 8)][ceil(w / 16)] that receive a 1 for every tile within 1 / 2 pixels of a cell
+// hit now (see obs_mark_reach); never cleared here -- their consumer (cmr_wino_tile_lists) does that.
+extern "C" int cmr_observation_proj_reach_f32(const float* pc4, const float* feat, const uint8_t* overlap, const float* pose, const float* Kmat,
+                                              const float* mean4, float* proj, float* cnt, int32_t* cell, float* state3d, int B, int N, int h,
+                                              int w, uint8_t* reach1, uint8_t* reach2, hipStream_t stream) {
   CMR_REQUIRE(pc4 && feat && overlap && pose && Kmat && mean4 && proj && cnt && cell && state3d && B > 0 && N > 0 && h > 0 && w > 0);
   CMR_REQUIRE((int64_t)B * h * w < 0x7fffffff && cmr_aligned16(proj) && cmr_aligned16(state3d) && cmr_aligned16(pc4));
+  CMR_REQUIRE((reach1 == nullptr) == (reach2 == nullptr));
   const int64_t total = (int64_t)B * N;
   const unsigned per_point = (unsigned)((total + 255) / 256);
   hipLaunchKernelGGL(obs_project_kernel, dim3(per_point), dim3(256), 0, stream, pc4, overlap, pose, Kmat, mean4, proj, cnt, cell, state3d, B, N,
-                     h, w);
+                     h, w, reach1, reach2);
   hipLaunchKernelGGL(obs_count_kernel, dim3(per_point), dim3(256), 0, stream, (const int32_t*)cell, cnt, total);
   hipLaunchKernelGGL(obs_scatter_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, stream, feat, (const int32_t*)cell,
                      (const float*)cnt, proj, total);
   return cmr_launch_status();
+}
+
+extern "C" int cmr_observation_proj_f32(const float* pc4, const float* feat, const uint8_t* overlap, const float* pose, const float* Kmat,
+                                        const float* mean4, float* proj, float* cnt, int32_t* cell, float* state3d, int B, int N, int h,
+                                        int w, hipStream_t stream) {
+  return cmr_observation_proj_reach_f32(pc4, feat, overlap, pose, Kmat, mean4, proj, cnt, cell, state3d, B, N, h, w, nullptr, nullptr, stream);
 }
 
 extern "C" int cmr_observation_finalize_f32(const float* img_feat, float* acc, float* cnt, float* state2d,

@@ -403,8 +403,13 @@ __device__ __forceinline__ void ws_barrier_lds() { asm volatile("s_waitcnt lgkmc
                               // 76; compiled out (cmr_conv3x3_wino_bnbwd_nhwc_f32 answers -3), -DCMR_WS_BNBWD=1 brings it back
 #endif
 constexpr bool WS_STATS = CMR_WS_STATS != 0, WS_BNBWD = CMR_WS_STATS != 0 && CMR_WS_BNBWD != 0;
-template <int dbg>
-__global__ __launch_bounds__(512, 1) void conv3x3_wino_ws_kernel(const WinoArgs a, const int tiles_x, const int tiles_y, const int ntiles) {
+// LIST instantiation (cmr_conv3x3_wino_list_nhwc_f32): only the tiles order[0 .. *nlive) are multiplied -- the workgroups walk the COMPACTED
+// index range in the same XCD-banded order and look the tile up in order[] -- and the tiles order[*nlive .. ntiles) are copied from y0, a
+// map of y's geometry (null: the ordinary epilogue on a zero product).  The dense instantiation never reads a WsList and compiles to the
+// program it was without it.
+struct WsList { const int* order; const int* nlive; const float* y0; };
+template <int dbg, bool LIST>
+__global__ __launch_bounds__(512, 1) void conv3x3_wino_ws_kernel(const WinoArgs a, const int tiles_x, const int tiles_y, const int ntiles, const WsList l) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int NT = 2;                              // cout tiles per MFMA wave
   constexpr int NMW = 4;                             // MFMA waves
@@ -412,13 +417,22 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino_ws_kernel(const WinoArgs 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nco = a.Cout / 64;
   const int nchunk = a.Cin / WT_KC;
-  const int nk = (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;     // tiles of this workgroup (>= 1)
+  int nt = ntiles;                                   // tiles to multiply
+  if constexpr (LIST) {
+    nt = __builtin_amdgcn_readfirstlane(*l.nlive);
+    nt = nt < 0 ? 0 : (nt < ntiles ? nt : ntiles);
+  }
+  const int nk = (nt - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;     // tiles of this workgroup (dense: >= 1)
 
   struct Tile { int b, co0, oy0, ox0; };
-  auto decode = [&](int id) {                                      // same XCD-banded order as above, over ntiles virtual workgroups
-    id = id < ntiles ? id : ntiles - 1;
-    const int per = ntiles >> 3, rem = ntiles & 7, xcd = id & 7;
+  auto decode = [&](int id) {                                      // same XCD-banded order as above, over nt virtual workgroups
+    id = id < nt ? id : nt - 1;
+    const int per = nt >> 3, rem = nt & 7, xcd = id & 7;
     int t = xcd * per + (xcd < rem ? xcd : rem) + (id >> 3);
+    if constexpr (LIST) {
+      t = l.order[t];
+      t = (unsigned)t < (unsigned)ntiles ? t : ntiles - 1;       // a list that is no permutation must not send a store out of the map
+    }
     Tile r;
     r.co0 = (t % nco) * 64; t /= nco;
     r.ox0 = (t % tiles_x) * WT_TW; t /= tiles_x;
@@ -427,7 +441,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino_ws_kernel(const WinoArgs 
     return r;
   };
 
-  if (wave < NMW) {
+  if (LIST && nk == 0) {
+    // (uniform) more workgroups than live tiles: nothing to multiply, and no barrier is executed by anybody
+  } else if (wave < NMW) {
     // =========================================== MFMA waves ===========================================
     const int h = lane >> 5, l31 = lane & 31;
     const int wr = wave & 3, nsel = (wave >> 2) * NT;  // position row, first cout tile of this wave
@@ -842,6 +858,39 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino_ws_kernel(const WinoArgs 
       }
     }
   }
+  if constexpr (LIST) {
+    // The skipped tiles, dealt round-robin to the workgroups; all eight waves copy (no LDS, no barrier: a wave starts as soon as its own
+    // part of the tile loop is over).  Output block of a tile: 8 x 16 pixels, pooled 4 x 8, times the tile's 64 couts = 16 float4 per pixel.
+    const int pw = a.pool == 2 ? WT_TW / 2 : WT_TW, pn = a.pool == 2 ? WT_TH * WT_TW / 4 : WT_TH * WT_TW;
+    const int Hy = a.pool == 2 ? a.H >> 1 : a.H, Wy = a.pool == 2 ? a.W >> 1 : a.W;
+    const int c4 = tid & 15;
+    for (int s = nt + (int)blockIdx.x; s < ntiles; s += (int)gridDim.x) {
+      int t = l.order[s];
+      t = (unsigned)t < (unsigned)ntiles ? t : ntiles - 1;
+      const int co0 = (t % nco) * 64; t /= nco;
+      const int bx0 = (t % tiles_x) * pw; t /= tiles_x;
+      const int by0 = (t % tiles_y) * (pn / pw);
+      const int b = t / tiles_y;
+      for (int p = tid >> 4; p < pn; p += 32) {
+        const int py = by0 + p / pw, px = bx0 + p % pw;
+        if (py >= Hy || px >= Wy) continue;
+        const int64_t o = (((int64_t)b * Hy + py) * Wy + px) * a.Cout + co0 + 4 * c4;
+        f32x4 v;
+        if (l.y0) {
+          v = *reinterpret_cast<const f32x4*>(l.y0 + o);
+        } else {
+          // (uniform; pool 1 only) no map to copy from: the epilogue above on a product of exactly +0, operation for operation
+          const f32x4 bsv = *reinterpret_cast<const f32x4*>(a.bias ? a.bias + co0 + 4 * c4 : wt_zero16);
+          const f32x4 rs = *reinterpret_cast<const f32x4*>(a.res ? a.res + o : wt_zero16);
+          v = f32x4{0.f, 0.f, 0.f, 0.f} + bsv;
+          v += rs;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], v[e] * a.slope);
+        }
+        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(a.y + o));
+      }
+    }
+  }
 }
 
 #ifndef CMR_WS_DBG
@@ -849,13 +898,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino_ws_kernel(const WinoArgs 
 #endif
 // workgroups of a wave-specialised launch (= partial-sum slots of a statistics launch / 4)
 inline unsigned wino_ws_grid(int64_t ntiles, int cu_budget, int slices);
-template <int DBG>
-int launch_wino_ws_t(const WinoArgs& a, int tiles_x, int tiles_y, int64_t ntiles, int cu_budget, int slices, hipStream_t stream) {
+template <int DBG, bool LIST = false>
+int launch_wino_ws_t(const WinoArgs& a, int tiles_x, int tiles_y, int64_t ntiles, int cu_budget, int slices, hipStream_t stream, const WsList l = WsList{}) {
   constexpr int smem = WS_SMEM_FLOATS * (int)sizeof(float);
   static CmrSmemCache granted{};
-  if (cmr_grant_smem(reinterpret_cast<const void*>(conv3x3_wino_ws_kernel<DBG>), smem, granted) != CMR_OK) return CMR_ELAUNCH;
-  const unsigned grid = wino_ws_grid(ntiles, cu_budget, slices);
-  hipLaunchKernelGGL(conv3x3_wino_ws_kernel<DBG>, dim3(grid), dim3(512), smem, stream, a, tiles_x, tiles_y, (int)ntiles);
+  if (cmr_grant_smem(reinterpret_cast<const void*>(conv3x3_wino_ws_kernel<DBG, LIST>), smem, granted) != CMR_OK) return CMR_ELAUNCH;
+  const unsigned grid = wino_ws_grid(ntiles, cu_budget, slices);   // (list: sized for every tile live -- the count is only known on the device)
+  hipLaunchKernelGGL((conv3x3_wino_ws_kernel<DBG, LIST>), dim3(grid), dim3(512), smem, stream, a, tiles_x, tiles_y, (int)ntiles, l);
   return cmr_launch_status();
 }
 inline unsigned wino_ws_grid(int64_t ntiles, int cu_budget, int slices) {
@@ -969,4 +1018,79 @@ extern "C" int cmr_conv3x3_wino_nhwc_f32(const float* x, int B, int H, int W, in
   if (CMR_WINO_WS && Cin >= 64 && ntiles64 >= 200 && slope >= 0.f && slope <= 1.f) return launch_wino_ws(a, tiles_x, tiles_y, ntiles64, cu_budget, slices, stream);
   if (ntiles64 >= 512) return launch_wino<2>(a, tiles_x, tiles_y, ntiles64, stream);
   return launch_wino<1>(a, tiles_x, tiles_y, 2 * ntiles64, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Convolutions on a sparsely occupied input: tile lists.  Where the 3x3 support of an output pixel holds only zeros the
+// F(2x2,3x3) product is exactly +0 (the rows and columns of B^T outside the support contribute exact zeros, and every sum
+// of zeros that starts from +0 stays +0; finite weights assumed: 0 x Inf would be NaN), so a tile whose 1-pixel surrounding
+// is empty equals the same tile of a run on an all-zero input -- which a caller whose other operands stay the same from
+// call to call (CMRAgent._embed_2d: the image half of the observation during one registration) computes once.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// Workgroup m (0 / 1) turns the byte map reach_m [ntile] (cmr_observation_proj_reach_f32) into the list of convolution m:
+// order_m = the live tiles in ascending order, then the others in ascending order, each expanded to its nco_m virtual tiles
+// (id = tile * nco + cout group, the order the convolution kernel decodes); *nlive_m = live virtual tiles.  The map is cleared.
+__global__ __launch_bounds__(1024) void wino_tile_lists_kernel(uint8_t* __restrict__ reach1, uint8_t* __restrict__ reach2, int ntile, int nco1,
+                                                               int nco2, int* __restrict__ order1, int* __restrict__ nlive1,
+                                                               int* __restrict__ order2, int* __restrict__ nlive2) {
+  __shared__ int cnt[1024];
+  uint8_t* reach = blockIdx.x ? reach2 : reach1;
+  int* order = blockIdx.x ? order2 : order1;
+  const int nco = blockIdx.x ? nco2 : nco1;
+  const int tid = threadIdx.x;
+  const int per = (ntile + 1023) / 1024;                       // consecutive tiles per thread
+  const int lo = tid * per < ntile ? tid * per : ntile, hi = lo + per < ntile ? lo + per : ntile;
+  int n = 0;
+  for (int i = lo; i < hi; ++i) n += reach[i] != 0;
+  cnt[tid] = n;
+  __syncthreads();
+  for (int d = 1; d < 1024; d <<= 1) {                         // inclusive scan
+    const int v = tid >= d ? cnt[tid - d] : 0;
+    __syncthreads();
+    cnt[tid] += v;
+    __syncthreads();
+  }
+  const int total = cnt[1023];
+  int live = cnt[tid] - n, dead = total + (lo - live);         // next slot of a live / of a skipped tile of this thread
+  for (int i = lo; i < hi; ++i) {
+    const int slot = reach[i] != 0 ? live++ : dead++;
+    reach[i] = 0;
+    for (int c = 0; c < nco; ++c) order[slot * nco + c] = i * nco + c;
+  }
+  if (tid == 0) *(blockIdx.x ? nlive2 : nlive1) = total * nco;
+}
+
+}  // namespace
+
+extern "C" int cmr_wino_tile_lists(uint8_t* reach1, uint8_t* reach2, int B, int H, int W, int Cout1, int Cout2, int* order1, int* nlive1,
+                                   int* order2, int* nlive2, hipStream_t stream) {
+  CMR_REQUIRE(reach1 && reach2 && order1 && nlive1 && order2 && nlive2 && B > 0 && H > 0 && W > 0);
+  CMR_REQUIRE(Cout1 >= 64 && Cout1 % 64 == 0 && Cout2 >= 64 && Cout2 % 64 == 0);
+  const int64_t ntile = (int64_t)((W + WT_TW - 1) / WT_TW) * ((H + WT_TH - 1) / WT_TH) * B;
+  CMR_REQUIRE(ntile * (Cout1 / 64) < 0x3fffffff && ntile * (Cout2 / 64) < 0x3fffffff);
+  hipLaunchKernelGGL(wino_tile_lists_kernel, dim3(2), dim3(1024), 0, stream, reach1, reach2, (int)ntile, Cout1 / 64, Cout2 / 64, order1, nlive1,
+                     order2, nlive2);
+  return cmr_launch_status();
+}
+
+// cmr_conv3x3_wino_nhwc_f32 (no table operand) on the tiles order[0 .. *nlive) only; the tiles order[*nlive .. ntiles) of y are copied
+// from y0 [B][H / pool][W / pool][Cout], or, with y0 null (pool 1), receive the epilogue of a zero product: act(bias + res).  order is a
+// permutation of the ntiles = B ceil(H / 8) ceil(W / 16) Cout / 64 virtual tiles as cmr_wino_tile_lists writes it; order and nlive are
+// read on the device.  Bit-identical to the dense call wherever the live tiles cover every tile whose input halo (the tile dilated by one
+// pixel) is not all zero and y0 is the dense result on an all-zero x.  Served where the dense call runs the wave-specialised kernel.
+extern "C" int cmr_conv3x3_wino_list_nhwc_f32(const float* x, int B, int H, int W, int Cin, const float* u, const float* bias, const float* res,
+                                              float* y, int Cout, float slope, int pool, const int* order, const int* nlive, const float* y0,
+                                              int cu_budget, int slices, hipStream_t stream) {
+  CMR_REQUIRE(x && u && y && order && nlive && B > 0 && H > 0 && W > 0 && Cin % 32 == 0 && Cin >= 32 && Cout % 64 == 0 && Cout >= 64);
+  CMR_REQUIRE(cmr_aligned16(x) && cmr_aligned16(u) && cmr_aligned16(y) && (!bias || cmr_aligned16(bias)) && (!res || cmr_aligned16(res)) &&
+              (!y0 || cmr_aligned16(y0)));
+  CMR_REQUIRE((pool == 1 || (pool == 2 && !res && y0)) && y0 != y);
+  const int tiles_x = (W + WT_TW - 1) / WT_TW, tiles_y = (H + WT_TH - 1) / WT_TH;
+  const int64_t ntiles64 = (int64_t)tiles_x * tiles_y * B * (Cout / 64);
+  CMR_REQUIRE(2 * ntiles64 < 0x7fffffff);
+  if (!(CMR_WINO_WS && Cin >= 64 && ntiles64 >= 200 && slope >= 0.f && slope <= 1.f)) return CMR_EUNSUPPORTED;
+  const WinoArgs a{x, B, H, W, Cin, u, bias, res, nullptr, y, Cout, slope, pool};
+  return launch_wino_ws_t<0, true>(a, tiles_x, tiles_y, ntiles64, cu_budget, slices, stream, WsList{order, nlive, y0});
 }

@@ -10,6 +10,7 @@ reference's crash (environment.py:74-82)."""
 import torch
 
 from .. import ops
+from ..models.CMRAgent import CMRAgent
 from ..models.ImageResNet import to_nhwc
 from ..models.PointNN import rows_from_bcl
 
@@ -47,6 +48,7 @@ class _ObsContext:
         # state of the direct projected-half path (materialize_state_2d=False): the map itself, its counts and every point's cell of the
         # previous observation; created on first use
         self.proj = self.proj_cnt = self.proj_cell = None
+        self.reach, self.obs_serial = None, 0     # tile marks of the direct path's observations (zeroed once, cleared by their consumer)
         self.agent_cache = {}     # CMRAgent keeps the image half of its first conv here (constant over the steps of THIS registration)
         self.dirty = False        # True between a scatter and its finalize: an interrupted call must not leak accumulators
 
@@ -121,8 +123,15 @@ def observation_from_a_pose(data, RT, materialize_state_2d=True):
             ctx.proj = torch.zeros((B, h, w, 64), dtype=torch.float32, device=dev)
             ctx.proj_cnt = torch.zeros((B * h * w,), dtype=torch.float32, device=dev)
             ctx.proj_cell = torch.full((B * N,), -1, dtype=torch.int32, device=dev)
+        sparse = CMRAgent.sparse_obs()
+        if sparse and ctx.reach is None:
+            ctx.reach = torch.zeros((2, B, (h + 7) // 8, (w + 15) // 16), dtype=torch.uint8, device=dev)
         ops.observation_proj(ctx.pc4, ctx.feat, ctx.overlap, RT.contiguous(), ctx.K, ctx.mean4, B, N, h, w, ctx.proj, ctx.proj_cnt,
-                             ctx.proj_cell, state3d)
+                             ctx.proj_cell, state3d, reach=ctx.reach if sparse else None)
+        # which convolution tiles the points of THIS observation can reach (CMRAgent.SPARSE_OBS): the agent turns the marks into tile
+        # lists once per observation (the serial tells a second forward on the same observation that its lists are still the right ones)
+        ctx.obs_serial += 1
+        ctx.agent_cache["reach"] = (ctx.reach, ctx.proj, ctx.obs_serial) if sparse else None
         obs2d = torch.empty((B, 128, h, w), dtype=torch.float32, device="meta")
         obs2d._cmr_split = (ctx.img, ctx.proj, ctx.agent_cache)
         return obs2d, state3d.view(B, N, 8)[:, :, :5].permute(0, 2, 1)

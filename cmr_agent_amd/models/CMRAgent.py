@@ -117,6 +117,30 @@ class CMRAgent(Planned):
     FUSED_TAIL = True
     TAIL_T = True           # ... on the transposed-weight kernel (cmr_agent_heads_t_f32); False: the row-per-wave kernel
 
+    # Stage 0 of the 2-D branch multiplies only the 8x16 tiles that a projected point can reach (1 pixel for conv 0, 2 for conv 1, marked
+    # by the observation kernel); every other tile is, bit for bit, that of the same two convolutions on an empty projection, computed once
+    # per registration next to the image half of conv 0 ("Sparse observation").  fp32 evaluation only: the bf16 chain and
+    # the training engine run the dense calls.  False: every call is the dense one.
+    SPARSE_OBS = True
+
+    @classmethod
+    def sparse_obs(cls):
+        return cls.SPARSE_OBS and ops.WINOGRAD and not ops.CONV_BF16
+
+    def _tile_lists(self, cache, proj, c, u0, u1):
+        """-> ((order, nlive) of conv 0, of conv 1) of stage 0 for the observation `proj` belongs to, or None where stage 0 runs dense."""
+        mark = cache.get("reach")
+        if mark is None or not self.sparse_obs() or self.training or mark[1] is not proj or u0 is None or u1 is None:
+            return None
+        B, h, w, cin = proj.shape
+        if h % 2 or w % 2 or not (ops.wino_list_served(B, h, w, cin, c) and ops.wino_list_served(B, h, w, c, c)):
+            return None
+        if cache.get("lists_of") != mark[2]:                  # once per observation: the list kernel clears the marks
+            cache["lists"] = (c, ops.wino_tile_lists(mark[0], B, h, w, c, c))
+            cache["lists_of"] = mark[2]
+        width, lists = cache["lists"]
+        return lists if width == c else None
+
     def _embed_2d(self, state2d, B, split):
         p = self.plan()
         c = 2 * self.config.embed_dim
@@ -134,6 +158,18 @@ class CMRAgent(Planned):
                     cache["val"] = ops.conv3x3(img_src, wi, bi, c, 1, 1.0, u=ui)
                     cache["tag"] = tag
                 wp, _, up = p["conv0_proj"]
+                lists = self._tile_lists(cache, proj, c, up, ub)
+                if lists is not None:
+                    # stage 0 on the tiles the projected points can reach; the others are those of the image-only maps
+                    if cache.get("tag0") != tag:
+                        none = torch.zeros((1,), dtype=torch.int32, device=proj.device)         # no live tile: every tile from the y0 path
+                        cache["x1_0"] = ops.conv3x3_wino_list(proj, up, None, c, SLOPE, lists[0][0], none, None, res=cache["val"])
+                        cache["x2_0"] = ops.conv3x3(cache["x1_0"], wb, bb, c, 1, SLOPE, pool=2, u=ub)
+                        cache["tag0"] = tag
+                    (o1, n1), (o2, n2) = lists
+                    x = ops.conv3x3_wino_list(proj, up, None, c, SLOPE, o1, n1, cache["x1_0"], res=cache["val"])
+                    x = ops.conv3x3_wino_list(x, ub, bb, c, SLOPE, o2, n2, cache["x2_0"], pool=2)
+                    continue
                 x = ops.conv3x3(proj, wp, None, c, 1, SLOPE, res=cache["val"], u=up, out_bf16=True)
             else:
                 x = ops.conv3x3(x, wa, ba, c, 1, SLOPE, u=ua, out_bf16=True)

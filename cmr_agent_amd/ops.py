@@ -242,6 +242,43 @@ def conv3x3_wino(x, u, bias, cout, slope=1.0, res=None, post=None, pool=1):
     return y
 
 
+def wino_list_served(B, H, W, cin, cout):
+    """Shapes cmr_conv3x3_wino_list_nhwc_f32 serves: those the dense call runs on the persistent Winograd kernel."""
+    return WINOGRAD and cin >= 64 and cin % 32 == 0 and cout % 64 == 0 and ((W + 15) // 16) * ((H + 7) // 8) * B * (cout // 64) >= max(200, WINO_MIN_TILES)
+
+
+def conv3x3_wino_list(x, u, bias, cout, slope, order, nlive, y0, res=None, pool=1):
+    """conv3x3_wino on the virtual tiles order[:nlive] (device tensors, see wino_tile_lists); the other tiles are copied from y0, the result
+    on an all-zero x -- or, with y0 None (pool 1), computed as act(bias + res), which IS that result."""
+    B, H, W, cin = x.shape
+    hp, wp = (H // 2, W // 2) if pool == 2 else (H, W)
+    ntiles = ((W + 15) // 16) * ((H + 7) // 8) * B * (cout // 64)
+    if not x.is_contiguous() or x.dtype != f32 or tuple(u.shape) != (16, cout, cin):
+        raise ValueError("conv3x3_wino_list: bad operand layout")
+    if order.dtype != torch.int32 or nlive.dtype != torch.int32 or order.numel() != ntiles or nlive.numel() != 1 or not order.is_contiguous():
+        raise ValueError("conv3x3_wino_list: order must be int32 [%d] and nlive int32 [1]" % ntiles)
+    if (y0 is not None and (tuple(y0.shape) != (B, hp, wp, cout) or not y0.is_contiguous() or y0.dtype != f32)) or (
+            res is not None and (tuple(res.shape) != (B, H, W, cout) or not res.is_contiguous() or res.dtype != f32)):
+        raise ValueError("conv3x3_wino_list: y0 / res of the wrong shape")
+    y = torch.empty((B, hp, wp, cout), dtype=f32, device=x.device)
+    _lib.call("cmr_conv3x3_wino_list_nhwc_f32", _p(x), B, H, W, cin, _p(u), _p(bias), _p(res), _p(y), cout, float(slope), pool, _p(order),
+              _p(nlive), _p(y0), _cu_budget(), _slices(), _stream())
+    return y
+
+
+def wino_tile_lists(reach, B, H, W, cout1, cout2):
+    """reach uint8 [2, B, ceil(H/8), ceil(W/16)] (observation_proj marks it; cleared here) -> ((order1, nlive1), (order2, nlive2)) for two
+    chained list convolutions of cout1 / cout2 channels: live virtual tiles first, ascending, then the others."""
+    nt = B * ((H + 7) // 8) * ((W + 15) // 16)
+    if reach.dtype != torch.uint8 or reach.numel() != 2 * nt or not reach.is_contiguous():
+        raise ValueError("wino_tile_lists: reach must be uint8 [2, %d]" % nt)
+    n1, n2 = nt * (cout1 // 64), nt * (cout2 // 64)
+    buf = torch.empty((n1 + n2 + 8,), dtype=torch.int32, device=reach.device)
+    o1, o2, l1, l2 = buf[:n1], buf[n1:n1 + n2], buf[n1 + n2:n1 + n2 + 1], buf[n1 + n2 + 4:n1 + n2 + 5]
+    _lib.call("cmr_wino_tile_lists", _p(reach), reach.data_ptr() + nt, B, H, W, cout1, cout2, _p(o1), _p(l1), _p(o2), _p(l2), _stream())
+    return (o1, l1), (o2, l2)
+
+
 def conv3x3_wino_stats(x, u, bias, cout):
     """conv3x3 (stride 1, + bias, nothing else) through the wave-specialised Winograd kernel WITH the BatchNorm sums of its output from the
     kernel's own epilogue -> (y [B,H,W,Cout], part [parts, 2, Cout]) for bn_stats_from_sums (pivot = bias), or None where not served."""
@@ -849,10 +886,19 @@ def observation_finalize(img_feat, acc, cnt, state2d, proj, B, h, w, write_img, 
               int(write_img), int(clear), _stream())
 
 
-def observation_proj(pc4, feat, overlap_u8, pose, K, mean4, B, N, h, w, proj, cnt, cell, state3d):
-    """The projected half of the observation maintained in place (see cmr_observation_proj_f32): proj / cnt / cell are the caller's state."""
+def observation_proj(pc4, feat, overlap_u8, pose, K, mean4, B, N, h, w, proj, cnt, cell, state3d, reach=None):
+    """The projected half of the observation maintained in place (see cmr_observation_proj_f32): proj / cnt / cell are the caller's state.
+    reach (uint8 [2, B, ceil(h/8), ceil(w/16)], zero before the first call): the tiles within 1 / 2 pixels of a cell hit now are marked in
+    reach[0] / reach[1], for wino_tile_lists."""
     if cell.dtype != torch.int32 or cell.numel() != B * N or proj.numel() != B * h * w * 64 or cnt.numel() != B * h * w:
         raise ValueError("observation_proj: state buffers of the wrong shape / dtype")
+    if reach is not None:
+        nt = B * ((h + 7) // 8) * ((w + 15) // 16)
+        if reach.dtype != torch.uint8 or reach.numel() != 2 * nt or not reach.is_contiguous():
+            raise ValueError("observation_proj: reach must be uint8 [2, %d]" % nt)
+        _lib.call("cmr_observation_proj_reach_f32", _p(pc4), _p(feat), _p(overlap_u8), _p(pose), _p(K), _p(mean4), _p(proj), _p(cnt), _p(cell),
+                  _p(state3d), B, N, h, w, _p(reach), reach.data_ptr() + nt, _stream())
+        return
     _lib.call("cmr_observation_proj_f32", _p(pc4), _p(feat), _p(overlap_u8), _p(pose), _p(K), _p(mean4), _p(proj), _p(cnt), _p(cell), _p(state3d),
               B, N, h, w, _stream())
 

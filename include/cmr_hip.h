@@ -97,6 +97,22 @@ int cmr_conv3x3_nhwc_f32(const float* x, int B, int H, int W, int Cin, const flo
 int cmr_conv3x3_wino_nhwc_f32(const float* x, int B, int H, int W, int Cin, const float* u, const float* bias,
                               const float* res, const float* post, float* y, int Cout, float slope, int pool,
                               int cu_budget, int slices, hipStream_t stream);
+/* The same convolution (no table operand) where the input is sparsely occupied and the other operands stay the same from call to call
+ * (CMRAgent._embed_2d: the projected half of the observation on top of the image half of one registration).  Only the virtual tiles
+ * order[0 .. *nlive) (8x16 output pixels x 64 couts; id = ((b tiles_y + ty) tiles_x + tx) Cout / 64 + cout group) are multiplied; the tiles
+ * order[*nlive .. ntiles) of y are copied from y0 [B][H / pool][W / pool][Cout], or, with y0 null (pool 1 only), receive the epilogue of a
+ * zero product, act(bias + res).  order (a permutation of all tiles) and nlive are read on the DEVICE.  F(2x2,3x3) output pixels are a
+ * function of their own 3x3 input support alone, bit for bit, so with every tile live whose 1-pixel surrounding holds a non-zero input and
+ * y0 = the dense result on an all-zero input the result equals the dense call's (finite weights assumed: 0 x Inf is not 0).  Served where
+ * the dense call runs the persistent kernel (Cin >= 64, >= 200 tiles, 0 <= slope <= 1), CMR_EUNSUPPORTED (-3) otherwise. */
+int cmr_conv3x3_wino_list_nhwc_f32(const float* x, int B, int H, int W, int Cin, const float* u, const float* bias, const float* res,
+                                   float* y, int Cout, float slope, int pool, const int* order, const int* nlive, const float* y0,
+                                   int cu_budget, int slices, hipStream_t stream);
+/* The lists of two chained convolutions (H x W maps, Cout1 then Cout2 channels) from the byte maps cmr_observation_proj_reach_f32 marks:
+ * order_m = the tiles with reach_m set in ascending order, then the others in ascending order, each expanded to its Cout_m / 64 virtual
+ * tiles; *nlive_m = live virtual tiles.  Both maps are cleared for the next observation.  One launch. */
+int cmr_wino_tile_lists(uint8_t* reach1, uint8_t* reach2, int B, int H, int W, int Cout1, int Cout2, int* order1, int* nlive1,
+                        int* order2, int* nlive2, hipStream_t stream);
 /* Training forward of a 3x3 convolution that feeds a batch-statistics BatchNorm (models/ImageResNet.py:5-40 under Train_Geo.py:166-174):
  * y = conv(x) + bias as the call above with slope 1, no residual / table / pool, AND the sums the BatchNorm needs, accumulated by the helper
  * waves of the wave-specialised kernel while they finish the output tiles (they wait 25 - 50 % of a launch): part [parts][2][64] = per helper
@@ -824,6 +840,12 @@ int cmr_observation_finalize_f32(const float* img_feat, float* acc, float* cnt, 
 int cmr_observation_proj_f32(const float* pc4, const float* feat, const uint8_t* overlap, const float* pose, const float* Kmat,
                              const float* mean4, float* proj, float* cnt, int32_t* cell, float* state3d, int B, int N, int h, int w,
                              hipStream_t stream);
+/* ... and, in the same launches, the reach of the cells hit now on the 8x16 tile grid of the stride-1 convolutions that read proj: byte maps
+ * reach1 / reach2 [B][ceil(h / 8)][ceil(w / 16)] (both or neither) receive a 1 for every tile whose area dilated by 1 / 2 pixels holds such a
+ * cell.  Zero before the first call; cmr_wino_tile_lists consumes and clears them. */
+int cmr_observation_proj_reach_f32(const float* pc4, const float* feat, const uint8_t* overlap, const float* pose, const float* Kmat,
+                                   const float* mean4, float* proj, float* cnt, int32_t* cell, float* state3d, int B, int N, int h, int w,
+                                   uint8_t* reach1, uint8_t* reach2, hipStream_t stream);
 /* environment.py:179-260 (step + euler_angles_to_matrix 'XYZ'), :14-21 (to_disentangled). */
 int cmr_pose_step_f32(float* pose, const int64_t* act_r, const int64_t* act_t, const double* r_steps,
                       const double* t_steps, int B, int six_dof, hipStream_t stream);
