@@ -106,7 +106,7 @@ constexpr int MHA_KCH = 512;
 template <bool LIBM_EXP>
 __device__ __forceinline__ float mha_exp(float x) {
   if constexpr (LIBM_EXP) return expf(x);
-  else return __builtin_amdgcn_exp2f(x * 1.4426950408889634f);
+  else return cmr_exp2_fast(x);
 }
 template <bool LIBM_EXP>
 __global__ __launch_bounds__(256) void mha_mfma_kernel(const float* __restrict__ q, int64_t ldq, const float* __restrict__ k, int64_t ldk,

@@ -52,26 +52,19 @@ __device__ __forceinline__ f32x4 blb_fma4(f32x4 a, f32x4 b, f32x4 c) {
 }
 
 // ---- helpers of the bf16-product variants further down ----
-typedef __bf16 bl_bf16x8 __attribute__((ext_vector_type(8)));
 typedef short bl_s4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ unsigned bl_pack2(float lo, float hi) {            // (bf16(lo) | bf16(hi) << 16), round to nearest even
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){lo, hi}, b2));
-}
 __device__ __forceinline__ int bl_off(int row, int chunk) { return 256 * row + 16 * (chunk ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
 __device__ __forceinline__ uint2 bl_tr(const unsigned char* base, int byte_off) {
   const bl_s4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bl_s4*)(base + byte_off));
   return __builtin_bit_cast(uint2, v);
 }
-__device__ __forceinline__ bl_bf16x8 bl_tr8(const unsigned char* base, int off0, int off1) {
+__device__ __forceinline__ cmr_bf16x8 bl_tr8(const unsigned char* base, int off0, int off1) {
   const uint2 a0 = bl_tr(base, off0), a1 = bl_tr(base, off1);
-  return __builtin_bit_cast(bl_bf16x8, uint4{a0.x, a0.y, a1.x, a1.y});
+  return __builtin_bit_cast(cmr_bf16x8, uint4{a0.x, a0.y, a1.x, a1.y});
 }
 // sum over the 32 lanes that share lane >> 5 (the 32 rows of a block in the transposed product's layout): DPP row sum, then the partner row
 __device__ __forceinline__ float bl_sum32(float v) {
-  v = m16_sum16(v);
-  v += cmr_xor16(v);
+  v = m16_sum32(v);
   asm volatile("" : "+v"(v));
   return v;
 }
@@ -554,12 +547,6 @@ __global__ __launch_bounds__(256) void bn_linear_fwd_kernel(const BlfArgs a) {
   }
 }
 
-__device__ __forceinline__ double blf_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // one wave per channel: merge the workgroups' (pivot, sum, sum of squares) over their row counts in double (parallel variance), then what
 // cmr_bn_stats_f32's final step does: stat = (mean, rstd, scale, shift), running statistics.  Workgroup w = (segment, i) of seg_groups per
 // segment held the blocks i, i + seg_groups, ... of its segment's seg_blocks.
@@ -580,11 +567,11 @@ __global__ __launch_bounds__(64) void bn_stats_merge_kernel(const float* __restr
     s_np += n * p;
     s_npp += n * p * p;
   }
-  s_s = blf_wave_sum(s_s);
-  s_ss = blf_wave_sum(s_ss);
-  s_ps = blf_wave_sum(s_ps);
-  s_np = blf_wave_sum(s_np);
-  s_npp = blf_wave_sum(s_npp);
+  s_s = cmr_wave_sum_d(s_s);
+  s_ss = cmr_wave_sum_d(s_ss);
+  s_ps = cmr_wave_sum_d(s_ps);
+  s_np = cmr_wave_sum_d(s_np);
+  s_npp = cmr_wave_sum_d(s_npp);
   if (lane != 0) return;
   const double n = (double)rows;
   const double mean = (s_np + s_s) / n;
@@ -620,7 +607,7 @@ template <int KS, bool PRO>
 __global__ __launch_bounds__(256, 2) void bn_linear_fwd_bf16_kernel(const BlfArgs a, int n_total) {
   constexpr int K = 16 * KS;
   extern __shared__ __attribute__((aligned(16))) unsigned char blg_smem[];
-  bl_bf16x8* Wf = reinterpret_cast<bl_bf16x8*>(blg_smem);                  // [2][KS][64 lanes]
+  cmr_bf16x8* Wf = reinterpret_cast<cmr_bf16x8*>(blg_smem);                 // [2][KS][64 lanes]
   float* paff = reinterpret_cast<float*>(blg_smem + 2 * KS * 1024);        // PRO: [2][K] scale | shift
   float* bslot = paff + 2 * K;                                             // [4 waves][64]  bias
   float* pslot = bslot + 256;                                              // [4 waves][64]  pivot
@@ -633,7 +620,7 @@ __global__ __launch_bounds__(256, 2) void bn_linear_fwd_bf16_kernel(const BlfArg
     const int t = f / KS, ks = f % KS;
     const float* wr = a.w + (int64_t)(cb + 32 * t + l31) * a.ldw + 16 * ks + 8 * h;
     const f32x4 lo = *reinterpret_cast<const f32x4*>(wr), hi = *reinterpret_cast<const f32x4*>(wr + 4);
-    Wf[f * 64 + lane] = __builtin_bit_cast(bl_bf16x8, uint4{bl_pack2(lo[0], lo[1]), bl_pack2(lo[2], lo[3]), bl_pack2(hi[0], hi[1]), bl_pack2(hi[2], hi[3])});
+    Wf[f * 64 + lane] = __builtin_bit_cast(cmr_bf16x8, uint4{cmr_bf16_pack2(lo[0], lo[1]), cmr_bf16_pack2(lo[2], lo[3]), cmr_bf16_pack2(hi[0], hi[1]), cmr_bf16_pack2(hi[2], hi[3])});
   }
   if (PRO) {
     for (int i = tid; i < 2 * K; i += 256) paff[i] = a.pro[2 * K + i];
@@ -670,7 +657,7 @@ __global__ __launch_bounds__(256, 2) void bn_linear_fwd_bf16_kernel(const BlfArg
     int opq = 0;
     asm volatile("" : "+v"(opq));
     const float* paff_ = paff + opq;
-    const bl_bf16x8* Wf_ = Wf + opq;
+    const cmr_bf16x8* Wf_ = Wf + opq;
     if (a.bias) {
       const int64_t seg = a.bias_stride ? tile / a.seg_blocks : 0;          // (wave-uniform)
       if (seg != cur_seg) {
@@ -704,7 +691,7 @@ __global__ __launch_bounds__(256, 2) void bn_linear_fwd_bf16_kernel(const BlfArg
           hi[e] = hi[e] > 0.f ? hi[e] : hi[e] * a.pro_slope;
         }
       }
-      const bl_bf16x8 xb = __builtin_bit_cast(bl_bf16x8, uint4{bl_pack2(lo[0], lo[1]), bl_pack2(lo[2], lo[3]), bl_pack2(hi[0], hi[1]), bl_pack2(hi[2], hi[3])});
+      const cmr_bf16x8 xb = __builtin_bit_cast(cmr_bf16x8, uint4{cmr_bf16_pack2(lo[0], lo[1]), cmr_bf16_pack2(lo[2], lo[3]), cmr_bf16_pack2(hi[0], hi[1]), cmr_bf16_pack2(hi[2], hi[3])});
 #pragma unroll
       for (int t = 0; t < 2; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf_[(t * KS + ks) * 64 + lane], xb, acc[t], 0, 0, 0);
       if (ks & 1) __builtin_amdgcn_sched_barrier(0);              // (keeps the steps in order: hoisting every operand read costs ~100 registers)
@@ -783,11 +770,11 @@ __global__ __launch_bounds__(256) void bn_stats_merge_cnt_kernel(const float* __
     s_np += n * p;
     s_npp += n * p * p;
   }
-  s_s = blf_wave_sum(s_s);
-  s_ss = blf_wave_sum(s_ss);
-  s_ps = blf_wave_sum(s_ps);
-  s_np = blf_wave_sum(s_np);
-  s_npp = blf_wave_sum(s_npp);
+  s_s = cmr_wave_sum_d(s_s);
+  s_ss = cmr_wave_sum_d(s_ss);
+  s_ps = cmr_wave_sum_d(s_ps);
+  s_np = cmr_wave_sum_d(s_np);
+  s_npp = cmr_wave_sum_d(s_npp);
   if (lane == 0) {
     sm[wave][0] = s_s; sm[wave][1] = s_ss; sm[wave][2] = s_ps; sm[wave][3] = s_np; sm[wave][4] = s_npp;
   }
@@ -970,7 +957,7 @@ __global__ __launch_bounds__(256, (XL || NT == 4 || KT == 4) ? 2 : 3) void bn_li
   }
   if (BN || XL) __syncthreads();
   // data gradient: W^T as the A operand -- lane (channel 32 wave + l31, half h), step ks: W[16 ks + 8 h .. + 7][channel]
-  bl_bf16x8 wa[NS];
+  cmr_bf16x8 wa[NS];
   if (dg) {
     const float* wp = a.w + 32 * wave + l31;
 #pragma unroll
@@ -978,7 +965,7 @@ __global__ __launch_bounds__(256, (XL || NT == 4 || KT == 4) ? 2 : 3) void bn_li
       float v[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = wp[(int64_t)(16 * ks + 8 * h + e) * a.ldw];
-      wa[ks] = __builtin_bit_cast(bl_bf16x8, uint4{bl_pack2(v[0], v[1]), bl_pack2(v[2], v[3]), bl_pack2(v[4], v[5]), bl_pack2(v[6], v[7])});
+      wa[ks] = __builtin_bit_cast(cmr_bf16x8, uint4{cmr_bf16_pack2(v[0], v[1]), cmr_bf16_pack2(v[2], v[3]), cmr_bf16_pack2(v[4], v[5]), cmr_bf16_pack2(v[6], v[7])});
     }
   }
   // transposed-read offsets of this lane (they do not change from block to block): 16-lane group g16 covers channels 16 (g16 & 1) .. + 15 of
@@ -1002,7 +989,7 @@ __global__ __launch_bounds__(256, (XL || NT == 4 || KT == 4) ? 2 : 3) void bn_li
   const int rdb = 256 * l31 + 16 * (h ^ (swr & 1)), rdx = swr >> 1;
   // N = 128: the W^T fragments live in LDS (fragment order, one ds_read_b128 per matrix instruction) -- 32 registers the kernel does not have
   constexpr bool WLDS = NS == 8;
-  bl_bf16x8* wfr = reinterpret_cast<bl_bf16x8*>(blh_smem + NIMG * BLH_IMG + (6 * N + (XL ? 4 * K : 0)) * sizeof(float)) + wave * NS * 64;
+  cmr_bf16x8* wfr = reinterpret_cast<cmr_bf16x8*>(blh_smem + NIMG * BLH_IMG + (6 * N + (XL ? 4 * K : 0)) * sizeof(float)) + wave * NS * 64;
   if (WLDS && dg) {
 #pragma unroll
     for (int ks = 0; ks < NS; ++ks) wfr[ks * 64 + lane] = wa[ks];
@@ -1062,12 +1049,12 @@ __global__ __launch_bounds__(256, (XL || NT == 4 || KT == 4) ? 2 : 3) void bn_li
         d = scale * (d - *reinterpret_cast<const f32x4*>(caff + 4 * N + 4 * dc) - xh * *reinterpret_cast<const f32x4*>(caff + 5 * N + 4 * dc));
       }
       if (want_b) bs += d;
-      const unsigned w0 = bl_pack2(d[0], d[1]), w1 = bl_pack2(d[2], d[3]);
+      const unsigned w0 = cmr_bf16_pack2(d[0], d[1]), w1 = cmr_bf16_pack2(d[2], d[3]);
       *reinterpret_cast<uint2*>(di + bl_off(r, dc >> 1) + 8 * (dc & 1)) = uint2{w0, w1};
       if (HL) {                                              // residues dh - bf16(dh), rounded to bf16 again
         const float l0 = d[0] - __builtin_bit_cast(float, w0 << 16), l1 = d[1] - __builtin_bit_cast(float, w0 & 0xffff0000u);
         const float l2 = d[2] - __builtin_bit_cast(float, w1 << 16), l3 = d[3] - __builtin_bit_cast(float, w1 & 0xffff0000u);
-        *reinterpret_cast<uint2*>(DLI + buf * BLH_IMG + bl_off(r, (dc >> 1) + 2 * LO_KS) + 8 * (dc & 1)) = uint2{bl_pack2(l0, l1), bl_pack2(l2, l3)};
+        *reinterpret_cast<uint2*>(DLI + buf * BLH_IMG + bl_off(r, (dc >> 1) + 2 * LO_KS) + 8 * (dc & 1)) = uint2{cmr_bf16_pack2(l0, l1), cmr_bf16_pack2(l2, l3)};
       }
     }
 #pragma unroll
@@ -1079,7 +1066,7 @@ __global__ __launch_bounds__(256, (XL || NT == 4 || KT == 4) ? 2 : 3) void bn_li
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * a.xslope;
       }
-      *reinterpret_cast<uint2*>(xi + bl_off(r, xc >> 1) + 8 * (xc & 1)) = uint2{bl_pack2(v[0], v[1]), bl_pack2(v[2], v[3])};
+      *reinterpret_cast<uint2*>(xi + bl_off(r, xc >> 1) + 8 * (xc & 1)) = uint2{cmr_bf16_pack2(v[0], v[1]), cmr_bf16_pack2(v[2], v[3])};
     }
   };
   auto multiply = [&](int64_t blk, int buf, const f32x4 (&rv)[4], const f32x4 (&xv)[4]) {
@@ -1088,12 +1075,12 @@ __global__ __launch_bounds__(256, (XL || NT == 4 || KT == 4) ? 2 : 3) void bn_li
     const unsigned char* dli = DLI + buf * BLH_IMG;
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const bl_bf16x8 av = bl_tr8(di, trb[s][0] + tqd, trb[s][1] + tqd);
-      bl_bf16x8 al;
+      const cmr_bf16x8 av = bl_tr8(di, trb[s][0] + tqd, trb[s][1] + tqd);
+      cmr_bf16x8 al;
       if (HL) al = bl_tr8(dli, trb[s][0] + tql, trb[s][1] + tql);
 #pragma unroll
       for (int t = 0; t < TPW; ++t) {
-        const bl_bf16x8 bv = bl_tr8(xi, trb[s][0] + tqx[t], trb[s][1] + tqx[t]);
+        const cmr_bf16x8 bv = bl_tr8(xi, trb[s][0] + tqx[t], trb[s][1] + tqx[t]);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[t], 0, 0, 0);
         if (HL) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bv, acc[t], 0, 0, 0);
       }
@@ -1104,9 +1091,9 @@ __global__ __launch_bounds__(256, (XL || NT == 4 || KT == 4) ? 2 : 3) void bn_li
     for (int e = 0; e < 16; ++e) dacc[e] = 0.f;
 #pragma unroll
     for (int ks = 0; ks < NS; ++ks) {
-      const bl_bf16x8 wv = WLDS ? wfr[ks * 64 + lane] : wa[ks];
-      dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv, *reinterpret_cast<const bl_bf16x8*>(di + rdb + 32 * (ks ^ rdx)), dacc, 0, 0, 0);
-      if (HL) dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv, *reinterpret_cast<const bl_bf16x8*>(dli + rdb + 32 * ((ks + LO_KS) ^ rdx)), dacc, 0, 0, 0);
+      const cmr_bf16x8 wv = WLDS ? wfr[ks * 64 + lane] : wa[ks];
+      dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv, *reinterpret_cast<const cmr_bf16x8*>(di + rdb + 32 * (ks ^ rdx)), dacc, 0, 0, 0);
+      if (HL) dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv, *reinterpret_cast<const cmr_bf16x8*>(dli + rdb + 32 * ((ks + LO_KS) ^ rdx)), dacc, 0, 0, 0);
     }
     float* dxp = a.dx + (blk * R + l31) * a.lddx + 32 * wave + 4 * h;
 #pragma unroll

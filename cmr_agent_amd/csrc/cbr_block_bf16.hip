@@ -16,8 +16,6 @@
 
 namespace {
 
-typedef __bf16 cb_bf16x8 __attribute__((ext_vector_type(8)));
-
 __device__ __attribute__((aligned(16))) float cbb_zero[256] = {0.f};   // NOT const (see cbr_block.hip)
 
 struct CbbArgs {
@@ -34,16 +32,6 @@ struct CbbArgs {
 
 constexpr int CBB_MAXB = 16;
 
-__device__ __forceinline__ cb_bf16x8 cbb_pack(const f32x4& a, const f32x4& b) {
-  cb_bf16x8 r;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    r[i] = (__bf16)a[i];
-    r[4 + i] = (__bf16)b[i];
-  }
-  return r;
-}
-
 // KX, CH may be 8 (the agent's first block: 5 + 3 padding channels): one k step whose upper half is zero.
 template <int KX, int CH, int CO, bool CONV_SC>
 __global__ __launch_bounds__(512) void cbr_block_bf16_kernel(const CbbArgs a) {
@@ -52,9 +40,9 @@ __global__ __launch_bounds__(512) void cbr_block_bf16_kernel(const CbbArgs a) {
   constexpr int CHP = 32 * T1;
   constexpr int S2 = 2 * T1;                    // k steps over the (padded) hidden width
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  cb_bf16x8* W1f = reinterpret_cast<cb_bf16x8*>(smem_raw);                  // [T1][S1][64]
-  cb_bf16x8* W2f = W1f + T1 * S1 * 64;                                       // [T2][S2][64]
-  cb_bf16x8* Wsf = W2f + T2 * S2 * 64;                                       // [T2][S1][64]   (only if CONV_SC)
+  cmr_bf16x8* W1f = reinterpret_cast<cmr_bf16x8*>(smem_raw);                 // [T1][S1][64]
+  cmr_bf16x8* W2f = W1f + T1 * S1 * 64;                                       // [T2][S2][64]
+  cmr_bf16x8* Wsf = W2f + T2 * S2 * 64;                                       // [T2][S1][64]   (only if CONV_SC)
   float* B1s = reinterpret_cast<float*>(Wsf + (CONV_SC ? T2 * S1 * 64 : 0)); // [nb][CHP]
   float* B2s = B1s + CBB_MAXB * CHP;                                          // [nb][CO]
   const int tid = threadIdx.x, lane = tid & 63;
@@ -66,7 +54,7 @@ __global__ __launch_bounds__(512) void cbr_block_bf16_kernel(const CbbArgs a) {
   for (int e = tid; e < T1 * S1 * 64; e += 512) {
     const int ln = e & 63, s = (e >> 6) % S1, t = (e >> 6) / S1;
     const int n = 32 * t + (ln & 31), k0 = 16 * s + 8 * (ln >> 5);
-    cb_bf16x8 v;
+    cmr_bf16x8 v;
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = (__bf16)((n < CH && k0 + j < KX) ? a.w1[(int64_t)n * KX + k0 + j] : 0.f);
     W1f[e] = v;
@@ -75,7 +63,7 @@ __global__ __launch_bounds__(512) void cbr_block_bf16_kernel(const CbbArgs a) {
     const int ln = e & 63, s = (e >> 6) % S2, n = (e >> 6) / S2;
     const int t = s >> 1, s2 = s & 1, hh = ln >> 5;
     const int co = 32 * n + (ln & 31);
-    cb_bf16x8 v;
+    cmr_bf16x8 v;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int c = 32 * t + (j & 3) + 8 * (2 * s2 + (j >> 2)) + 4 * hh;     // hidden channel held by accumulator register 8 s2 + j
@@ -87,7 +75,7 @@ __global__ __launch_bounds__(512) void cbr_block_bf16_kernel(const CbbArgs a) {
     for (int e = tid; e < T2 * S1 * 64; e += 512) {
       const int ln = e & 63, s = (e >> 6) % S1, n = (e >> 6) / S1;
       const int co = 32 * n + (ln & 31), k0 = 16 * s + 8 * (ln >> 5);
-      cb_bf16x8 v;
+      cmr_bf16x8 v;
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = (__bf16)(k0 + j < KX ? a.wsc[(int64_t)co * KX + k0 + j] : 0.f);
       Wsf[e] = v;
@@ -147,9 +135,9 @@ __global__ __launch_bounds__(512) void cbr_block_bf16_kernel(const CbbArgs a) {
           sc[n][q] = *reinterpret_cast<const f32x4*>(c < KX ? (c < a.k1 ? rc.p1 : rc.p2) + c : cbb_zero);
         }
     }
-    cb_bf16x8 xb[S1];
+    cmr_bf16x8 xb[S1];
 #pragma unroll
-    for (int s = 0; s < S1; ++s) xb[s] = cbb_pack(xlo[s], xhi[s]);
+    for (int s = 0; s < S1; ++s) xb[s] = cmr_bf16x8_each(xlo[s], xhi[s]);
     // ---- GEMM 1
     f32x16 hid[T1];
 #pragma unroll
@@ -184,7 +172,7 @@ __global__ __launch_bounds__(512) void cbr_block_bf16_kernel(const CbbArgs a) {
     for (int t = 0; t < T1; ++t)
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
-        cb_bf16x8 hb;
+        cmr_bf16x8 hb;
 #pragma unroll
         for (int j = 0; j < 8; ++j) hb[j] = (__bf16)hid[t][8 * s2 + j];
 #pragma unroll

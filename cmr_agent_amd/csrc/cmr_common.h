@@ -37,12 +37,30 @@ static inline bool cmr_aligned16(const void* p) { return (reinterpret_cast<uintp
 // activation codes shared by the GEMM / conv epilogues
 enum { CMR_ACT_NONE = 0, CMR_ACT_RELU = 1, CMR_ACT_LRELU = 2, CMR_ACT_GELU = 3, CMR_ACT_ELU1 = 4 };
 
+// erf-GELU, v Phi(v) with Phi = 0.5 (1 + erf(v / sqrt 2)), and its derivative Phi(v) + v phi(v).  The ONE statement of both: the backward
+// kernels recompute the forward's GELU from the saved pre-activation.  cmr_gelu_both gives the two from one erf (g has the bits of cmr_gelu:
+// 0.5 v (1 + erf) is evaluated as written).
+__device__ __forceinline__ float cmr_gelu(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
+__device__ __forceinline__ float cmr_gelu_grad(float v) {
+  return 0.5f * (1.f + erff(v * 0.70710678118654752440f)) + v * 0.39894228040143267794f * expf(-0.5f * v * v);
+}
+__device__ __forceinline__ void cmr_gelu_both(float v, float& g, float& dg) {
+  const float e = 1.f + erff(v * 0.70710678118654752440f);
+  g = 0.5f * v * e;
+  dg = 0.5f * e + v * 0.39894228040143267794f * expf(-0.5f * v * v);
+}
+
+// exp(x) as v_exp_f32(x log2 e), and F.elu(v) + 1 on it -- libm's expf costs five more instructions per value for a range reduction that
+// buys nothing at |v| of a projected feature (linear-attention state kernel 67 -> 62 us fp32, 39 -> 34 us bf16 at 8 x 26 752 rows)
+__device__ __forceinline__ float cmr_exp2_fast(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
+__device__ __forceinline__ float cmr_elu1_fast(float v) { return v > 0.f ? v + 1.f : cmr_exp2_fast(v); }
+
 __device__ __forceinline__ float cmr_act(float v, int act, float p) {
   switch (act) {
     case CMR_ACT_RELU: return v > 0.f ? v : 0.f;
     case CMR_ACT_LRELU: return v > 0.f ? v : v * p;
-    case CMR_ACT_GELU: return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
-    case CMR_ACT_ELU1: return v > 0.f ? v + 1.f : expf(v);  // elu(v) + 1
+    case CMR_ACT_GELU: return cmr_gelu(v);
+    case CMR_ACT_ELU1: return v > 0.f ? v + 1.f : expf(v);  // elu(v) + 1; libm's expf on purpose, not cmr_elu1_fast: full range and accuracy
     default: return v;
   }
 }
@@ -66,6 +84,97 @@ __device__ __forceinline__ float cmr_xhalf(float v) {
   const unsigned u = __builtin_bit_cast(unsigned, v);
   const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);      // r[0] = [lo | lo], r[1] = [hi | hi]
   return __builtin_bit_cast(float, (threadIdx.x & 32) ? r[0] : r[1]);
+}
+
+// LayerNorm over the 64 channels of a row of which this lane holds 32 and lane ^ 32 the other 32, in place; fp32 and bf16 twins share it.
+// Two bodies by necessity, one per register layout, because their sums are ORDERED differently and every user's bits depend on the order:
+//  * two MFMA accumulator tiles (register 4 qd + e of tile t = channel 32 t + 8 qd + 4 h + e): summed sequentially;
+//  * eight float4 pieces, chan(i) = first channel of piece i: each piece summed pairwise, (v0 + v1) + (v2 + v3), then sequentially.
+__device__ __forceinline__ void cmr_layernorm64(f32x16 (&v)[2], const float* __restrict__ gs, const float* __restrict__ bs, int h, float eps) {
+  float s = 0.f;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s += v[t][r];
+  s += cmr_xhalf(s);
+  const float mean = s * (1.f / 64.f);
+  float q = 0.f;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float d = v[t][r] - mean;
+      v[t][r] = d;
+      q += d * d;
+    }
+  q += cmr_xhalf(q);
+  const float rstd = 1.f / sqrtf(q * (1.f / 64.f) + eps);
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) {
+      const f32x4 g = *reinterpret_cast<const f32x4*>(gs + 32 * t + 8 * qd + 4 * h);
+      const f32x4 b = *reinterpret_cast<const f32x4*>(bs + 32 * t + 8 * qd + 4 * h);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[t][4 * qd + e] = v[t][4 * qd + e] * rstd * g[e] + b[e];
+    }
+}
+template <typename CH>
+__device__ __forceinline__ void cmr_layernorm64(f32x4 (&v)[8], const float* __restrict__ g, const float* __restrict__ b, float eps, CH chan) {
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+  s += cmr_xhalf(s);
+  const float mean = s * (1.f / 64.f);
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float d = v[i][e] - mean;
+      v[i][e] = d;
+      q += d * d;
+    }
+  q += cmr_xhalf(q);
+  const float rstd = 1.f / sqrtf(q * (1.f / 64.f) + eps);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + chan(i));
+    const f32x4 bv = *reinterpret_cast<const f32x4*>(b + chan(i));
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[i][e] = v[i][e] * rstd * gv[e] + bv[e];
+  }
+}
+
+// sum over a wave of doubles, the same value in every lane afterwards (fixed butterfly order: deterministic)
+__device__ __forceinline__ double cmr_wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// fp32 -> bf16, round to nearest even (v_cvt_pk_bf16_f32): the ONE rounding of the bf16 kernels.  cmr_bf16_pack2 = bf16(lo) | bf16(hi) << 16.
+// The two eight-wide packs give the same bits -- four v_cvt_pk_bf16_f32 each -- but NOT the same program: with `each` written as `pairs`,
+// vit_fused_bf16.hip came out at 4752 instead of 4750 instruction lines with another register allocation and load order from the first tile
+// on, and nobody has timed that.  Every kernel stays on the form it was written with; folding the two is a change to measure.
+typedef __bf16 cmr_bf16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ unsigned cmr_bf16_pack2(float lo, float hi) {
+  typedef float f2 __attribute__((ext_vector_type(2)));
+  typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){lo, hi}, b2));
+}
+__device__ __forceinline__ cmr_bf16x8 cmr_bf16x8_pairs(const f32x4& lo, const f32x4& hi) {       // four two-wide vector conversions
+  return __builtin_bit_cast(cmr_bf16x8, uint4{cmr_bf16_pack2(lo[0], lo[1]), cmr_bf16_pack2(lo[2], lo[3]),
+                                              cmr_bf16_pack2(hi[0], hi[1]), cmr_bf16_pack2(hi[2], hi[3])});
+}
+__device__ __forceinline__ cmr_bf16x8 cmr_bf16x8_each(const f32x4& lo, const f32x4& hi) {        // eight element casts
+  cmr_bf16x8 r;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    r[i] = (__bf16)lo[i];
+    r[4 + i] = (__bf16)hi[i];
+  }
+  return r;
 }
 
 // Maximum over the 32 lanes that share lane >> 5 (the 32 rows of a tile in the MFMA result layout), on the DPP data path: quad
@@ -182,10 +291,22 @@ __device__ __forceinline__ uint64_t cmr_mix64(uint64_t x) {
   x ^= x >> 33;
   return x;
 }
+__device__ __forceinline__ uint64_t cmr_drop_key(uint64_t seed, uint64_t site) { return cmr_mix64(seed + site * 0x9E3779B97F4A7C15ull); }
 __device__ __forceinline__ bool cmr_keep(uint64_t seed, uint64_t site, uint64_t idx, uint32_t thr) {
-  const uint64_t key = cmr_mix64(seed + site * 0x9E3779B97F4A7C15ull);
-  return (uint32_t)cmr_mix64(key ^ idx) >= thr;
+  return (uint32_t)cmr_mix64(cmr_drop_key(seed, site) ^ idx) >= thr;
 }
+// one dropout site with the wave-uniform half of cmr_keep hoisted: mul(idx) = the 1 / (1 - p) scale where element idx is kept, else 0
+struct CmrDrop {
+  uint64_t key;
+  uint32_t thr;
+  float scale;
+  __device__ __forceinline__ void init(const int64_t* seed, uint64_t site, uint32_t thr_, float scale_) {
+    key = cmr_drop_key((uint64_t)seed[0], site);
+    thr = thr_;
+    scale = scale_;
+  }
+  __device__ __forceinline__ float mul(uint64_t idx) const { return (uint32_t)cmr_mix64(key ^ idx) >= thr ? scale : 0.f; }
+};
 static inline uint32_t cmr_drop_threshold(float p) {
   const double t = (double)p * 4294967296.0;
   return t <= 0.0 ? 0u : (t >= 4294967295.0 ? 4294967295u : (uint32_t)t);

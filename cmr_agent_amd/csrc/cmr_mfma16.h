@@ -1,6 +1,7 @@
-// Building blocks of the row-tile kernels on v_mfma_f32_16x16x4_f32 (train-mode transformer block, csrc/vit_train.hip).
+// Building blocks of the row-tile kernels on v_mfma_f32_16x16x4_f32: the transformer block's 16-row MLP kernel (csrc/vit_fused.hip) and its
+// train-mode kernels (csrc/vit_train.hip); the row sums also serve the 32-row tiles of csrc/la_train.hip and csrc/bn_linear.hip.
 //
-// Operand layout (as in csrc/vit_fused.hip): weights are the A operand, lane = 16 g + m supplies W[m][4 ks + g]; activations are the B
+// Operand layout: weights are the A operand, lane = 16 g + m supplies W[m][4 ks + g]; activations are the B
 // operand, lane = 16 g + n supplies x[row n][4 ks + g]; D: lane 16 g + n holds channels 4 g + r (r = 0..3) of row n.  A lane therefore owns
 // ONE row and, of every 16-channel tile T, the channels 16 T + 4 g + r -- again the B operand of k-tile T of the next GEMM when its weights
 // are stored in that order ([n_out/16][k/16][64 lanes][4], lane = 16 g + m holding W[16 To + m][16 T + 4 g + r]: frag16 layout,
@@ -67,28 +68,8 @@ __device__ __forceinline__ float m16_sum16(float v) {
   return v;
 }
 
-__device__ __forceinline__ float m16_gelu(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
-// gelu(v) and its derivative from ONE erf: Phi = 0.5 (1 + erf(v / sqrt 2)); gelu = v Phi (the same bits as m16_gelu: 0.5 v (1 + erf) is
-// evaluated as written); gelu' = Phi + v phi(v)
-__device__ __forceinline__ void m16_gelu_both(float v, float& g, float& dg) {
-  const float e = 1.f + erff(v * 0.70710678118654752440f);
-  g = 0.5f * v * e;
-  dg = 0.5f * e + v * 0.39894228040143267794f * expf(-0.5f * v * v);
+// sum over the 32 rows of a 32-row tile (the 32 lanes that share lane >> 5): the DPP row sum, then the partner row
+__device__ __forceinline__ float m16_sum32(float v) {
+  v = m16_sum16(v);
+  return v + cmr_xor16(v);
 }
-// d/dv gelu(v) = Phi(v) + v phi(v)
-__device__ __forceinline__ float m16_gelu_grad(float v) {
-  return 0.5f * (1.f + erff(v * 0.70710678118654752440f)) + v * 0.39894228040143267794f * expf(-0.5f * v * v);
-}
-
-// counter-based dropout of one site (csrc/cmr_common.h:cmr_keep with the wave-uniform half hoisted): keep(idx) and the 1 / (1 - p) scale
-struct M16Drop {
-  uint64_t key;
-  uint32_t thr;
-  float scale;
-  __device__ __forceinline__ void init(const int64_t* seed, uint64_t site, uint32_t thr_, float scale_) {
-    key = cmr_mix64((uint64_t)seed[0] + site * 0x9E3779B97F4A7C15ull);
-    thr = thr_;
-    scale = scale_;
-  }
-  __device__ __forceinline__ float mul(uint64_t idx) const { return (uint32_t)cmr_mix64(key ^ idx) >= thr ? scale : 0.f; }
-};

@@ -20,7 +20,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 struct B16Args {
@@ -47,12 +46,7 @@ __device__ __attribute__((aligned(16))) float b16_zero16[4] = {0.f, 0.f, 0.f, 0.
 
 // four floats -> four bf16 (round to nearest even, v_cvt_pk_bf16_f32) as 8 bytes
 __device__ __forceinline__ uint2 b16_pack4(const f32x4& v) {
-  typedef float f32x2_t __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-  uint2 w;
-  w.x = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){v[0], v[1]}, bf16x2_t));
-  w.y = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){v[2], v[3]}, bf16x2_t));
-  return w;
+  return uint2{cmr_bf16_pack2(v[0], v[1]), cmr_bf16_pack2(v[2], v[3])};
 }
 
 // TW = 32: wave w owns rows 2w, 2w+1 as two 32-pixel blocks (lane = column).
@@ -213,13 +207,13 @@ __global__ __launch_bounds__(256) void conv3x3_bf16_kernel(const B16Args a) {
       const int ky = tap / 3, kx = tap % 3;
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        bf16x8 av[NT], bv[NB];
+        cmr_bf16x8 av[NT], bv[NB];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
-          av[nt] = *reinterpret_cast<const bf16x8*>(Ws + ((tap * KS + ks) * NT + nt) * 1024 + lane * 16);
+          av[nt] = *reinterpret_cast<const cmr_bf16x8*>(Ws + ((tap * KS + ks) * NT + nt) * 1024 + lane * 16);
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
-          bv[nb] = *reinterpret_cast<const bf16x8*>(Xs + ((prow[nb] * S + ky) * HC + pcol[nb] * S + kx) * PS + ks * 32 + h * 16);
+          bv[nb] = *reinterpret_cast<const cmr_bf16x8*>(Xs + ((prow[nb] * S + ky) * HC + pcol[nb] * S + kx) * PS + ks * 32 + h * 16);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -493,11 +487,11 @@ __global__ __launch_bounds__(512) void conv3x3_bf16_tt_kernel(const B16Args a) {
       const int ky = tap / 3, kx = tap % 3;
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        bf16x8 av[NTW];
+        cmr_bf16x8 av[NTW];
 #pragma unroll
         for (int nt = 0; nt < NTW; ++nt)
-          av[nt] = *reinterpret_cast<const bf16x8*>(Ws + ((tap * KS + kc * 4 + ks) * NT + nt0 + nt) * 1024 + lane * 16);
-        const bf16x8 bv = *reinterpret_cast<const bf16x8*>(Xs + ((prow * S + ky) * HC + pcol * S + kx) * PS + ks * 32 + h * 16);
+          av[nt] = *reinterpret_cast<const cmr_bf16x8*>(Ws + ((tap * KS + kc * 4 + ks) * NT + nt0 + nt) * 1024 + lane * 16);
+        const cmr_bf16x8 bv = *reinterpret_cast<const cmr_bf16x8*>(Xs + ((prow * S + ky) * HC + pcol * S + kx) * PS + ks * 32 + h * 16);
 #pragma unroll
         for (int nt = 0; nt < NTW; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[nt], bv, acc[nt], 0, 0, 0);
       }
@@ -805,12 +799,12 @@ __global__ __launch_bounds__(512) void conv3x3_bf16_mm_kernel(const B16Args a) {
     wp[nt] = static_cast<const unsigned char*>(a.wfrag) + ((size_t)(T / WNT) * 9 * KSG * WNT + (T % WNT)) * 1024;
   }
   unsigned lane16 = lane * 16;
-  bf16x8 ring[D][2];
-  auto load_a = [&](int j, bf16x8 (&dst)[2]) __attribute__((always_inline)) {     // stream position j of the tile: (chunk, tap, ks)
+  cmr_bf16x8 ring[D][2];
+  auto load_a = [&](int j, cmr_bf16x8 (&dst)[2]) __attribute__((always_inline)) {     // stream position j of the tile: (chunk, tap, ks)
     const int r = j % 36;
     const unsigned off = (unsigned)(((r / 4) * KSG + (j / 36) * 4 + (r % 4)) * WNT * 1024);
 #pragma unroll
-    for (int nt = 0; nt < 2; ++nt) dst[nt] = *reinterpret_cast<const bf16x8*>(wp[nt] + (size_t)(lane16 + off));
+    for (int nt = 0; nt < 2; ++nt) dst[nt] = *reinterpret_cast<const cmr_bf16x8*>(wp[nt] + (size_t)(lane16 + off));
   };
 #pragma unroll
   for (int d = 0; d < D; ++d) load_a(d, ring[d]);
@@ -821,11 +815,11 @@ __global__ __launch_bounds__(512) void conv3x3_bf16_mm_kernel(const B16Args a) {
     constexpr int ch = decltype(CH)::value;
     asm volatile("" : "+v"(lane16));                    // see load_a
     const unsigned char* xs = smem + buf * XBYTES + lanebase;
-    bf16x8 bv[2][4];
-    auto read_b = [&](int jj, bf16x8 (&dst)[4]) __attribute__((always_inline)) {
+    cmr_bf16x8 bv[2][4];
+    auto read_b = [&](int jj, cmr_bf16x8 (&dst)[4]) __attribute__((always_inline)) {
       const int tap = jj / 4, ks = jj % 4, ky = tap / 3, kx = tap % 3;
 #pragma unroll
-      for (int nb = 0; nb < 4; ++nb) dst[nb] = *reinterpret_cast<const bf16x8*>(xs + ((nb + ky) * HC + kx) * PS + ks * 32);
+      for (int nb = 0; nb < 4; ++nb) dst[nb] = *reinterpret_cast<const cmr_bf16x8*>(xs + ((nb + ky) * HC + kx) * PS + ks * 32);
     };
     read_b(0, bv[0]);
 #pragma unroll

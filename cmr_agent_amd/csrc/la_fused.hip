@@ -19,43 +19,6 @@ namespace {
 constexpr int LA_D = 64, LA_HID = 128, LA_STATE = 576;    // 8 heads x (8x8 KV + 8 Ksum)
 constexpr int LA_LD64 = LA_D + 4, LA_LD128 = LA_HID + 4;  // padded LDS weight rows (conflict-free b128 reads)
 
-// F.elu(v) + 1; the negative branch as v_exp_f32(v log2 e) -- libm's expf costs five more instructions per value for a range reduction
-// that buys nothing at |v| of a projected feature (state kernel 67 -> 62 us fp32, 39 -> 34 us bf16 at 8 x 26 752 rows)
-__device__ __forceinline__ float la_elu1(float v) { return v > 0.f ? v + 1.f : __builtin_amdgcn_exp2f(v * 1.4426950408889634f); }
-__device__ __forceinline__ float la_xhalf(float v) { return cmr_xhalf(v); }            // partner lane (other 4 dims of the head)
-
-// LayerNorm over the 64 channels of this lane's row (32 here, 32 in the partner lane), in place
-__device__ __forceinline__ void la_layernorm(f32x16 (&v)[2], const float* __restrict__ gs, const float* __restrict__ bs,
-                                             int h, float eps) {
-  float s = 0.f;
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s += v[t][r];
-  s += la_xhalf(s);
-  const float mean = s * (1.f / 64.f);
-  float q = 0.f;
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float d = v[t][r] - mean;
-      v[t][r] = d;
-      q += d * d;
-    }
-  q += la_xhalf(q);
-  const float rstd = 1.f / sqrtf(q * (1.f / 64.f) + eps);
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      const f32x4 g = *reinterpret_cast<const f32x4*>(gs + 32 * t + 8 * qd + 4 * h);
-      const f32x4 b = *reinterpret_cast<const f32x4*>(bs + 32 * t + 8 * qd + 4 * h);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[t][4 * qd + e] = v[t][4 * qd + e] * rstd * g[e] + b[e];
-    }
-}
-
 struct LaQueryArgs {
   const float* x; int64_t ldx;
   const float* kv;                     // [B][576]
@@ -71,10 +34,6 @@ struct LaQueryArgs {
   const int64_t* seed; uint64_t site_att, site_hid, site_out;
   uint32_t thr; float ks;
 };
-
-__device__ __forceinline__ float la_drop_mul(uint64_t key, uint64_t idx, uint32_t thr, float ks) {
-  return (uint32_t)cmr_mix64(key ^ idx) >= thr ? ks : 0.f;
-}
 
 template <bool TRAIN>
 __global__ __launch_bounds__(512) void la_query_layer_kernel(const LaQueryArgs a) {
@@ -124,14 +83,17 @@ __global__ __launch_bounds__(512) void la_query_layer_kernel(const LaQueryArgs a
     *reinterpret_cast<f32x4*>(&Kv[e * 4]) = *reinterpret_cast<const f32x4*>(a.kv + e * 4);
   __syncthreads();
 
+  // the seed is optional here: the keys are formed under the test and the three CmrDrop built behind it (CmrDrop::init under the test
+  // compiles to another program)
   uint64_t key_att = 0, key_hid = 0, key_out = 0;
   const bool drop = TRAIN && a.seed != nullptr;
   if (drop) {
     const uint64_t sd = (uint64_t)a.seed[0];
-    key_att = cmr_mix64(sd + a.site_att * 0x9E3779B97F4A7C15ull);
-    key_hid = cmr_mix64(sd + a.site_hid * 0x9E3779B97F4A7C15ull);
-    key_out = cmr_mix64(sd + a.site_out * 0x9E3779B97F4A7C15ull);
+    key_att = cmr_drop_key(sd, a.site_att);
+    key_hid = cmr_drop_key(sd, a.site_hid);
+    key_out = cmr_drop_key(sd, a.site_out);
   }
+  const CmrDrop d_att{key_att, a.thr, a.ks}, d_hid{key_hid, a.thr, a.ks}, d_out{key_out, a.thr, a.ks};
   const uint32_t ntiles = (a.rows + 31) / 32;
   for (uint32_t tile = blockIdx.x * 8 + wave; tile < ntiles; tile += gridDim.x * 8) {
     const uint32_t row = tile * 32 + l31;
@@ -154,10 +116,10 @@ __global__ __launch_bounds__(512) void la_query_layer_kernel(const LaQueryArgs a
         const int hd = 4 * t + qd;
         float qo[4], qp[4];                      // this lane's 4 dims of the head (4h..4h+3), the partner's 4
 #pragma unroll
-        for (int e = 0; e < 4; ++e) qo[e] = la_elu1(msg[t][4 * qd + e]);
+        for (int e = 0; e < 4; ++e) qo[e] = cmr_elu1_fast(msg[t][4 * qd + e]);
         if (TRAIN) *reinterpret_cast<f32x4*>(a.sv_qf + (int64_t)row * LA_D + 8 * hd + 4 * h) = f32x4{qo[0], qo[1], qo[2], qo[3]};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) qp[e] = la_xhalf(qo[e]);
+        for (int e = 0; e < 4; ++e) qp[e] = cmr_xhalf(qo[e]);
         // dims in natural order d = 0..7: lane half 0 owns 0..3, half 1 owns 4..7
         float qd8[8];
 #pragma unroll
@@ -192,14 +154,14 @@ __global__ __launch_bounds__(512) void la_query_layer_kernel(const LaQueryArgs a
         *reinterpret_cast<f32x4*>(a.sv_mm + (int64_t)row * LA_D + 8 * kg + 4 * h) = f32x4{mrg[t][4 * qd], mrg[t][4 * qd + 1], mrg[t][4 * qd + 2], mrg[t][4 * qd + 3]};
       }
     }
-    la_layernorm(mrg, Ln, Ln + LA_D, h, a.ln_eps);
+    cmr_layernorm64(mrg, Ln, Ln + LA_D, h, a.ln_eps);
     if (TRAIN) {
 #pragma unroll
       for (int kg = 0; kg < 8; ++kg) {
         const int t = kg / 4, qd = kg % 4;
         if (drop) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) mrg[t][4 * qd + e] *= la_drop_mul(key_att, (uint64_t)row * LA_D + 8 * kg + 4 * h + e, a.thr, a.ks);
+          for (int e = 0; e < 4; ++e) mrg[t][4 * qd + e] *= d_att.mul((uint64_t)row * LA_D + 8 * kg + 4 * h + e);
         }
         *reinterpret_cast<f32x4*>(a.sv_d1 + (int64_t)row * LA_D + 8 * kg + 4 * h) = f32x4{mrg[t][4 * qd], mrg[t][4 * qd + 1], mrg[t][4 * qd + 2], mrg[t][4 * qd + 3]};
         __builtin_amdgcn_sched_barrier(0);     // one k-group at a time: interleaved, the 64-bit mask arithmetic of all of them spills
@@ -221,7 +183,7 @@ __global__ __launch_bounds__(512) void la_query_layer_kernel(const LaQueryArgs a
         const int t = kg / 4, qd = kg % 4;
         if (drop) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) hid[t][4 * qd + e] *= la_drop_mul(key_hid, (uint64_t)row * LA_HID + 8 * kg + 4 * h + e, a.thr, a.ks);
+          for (int e = 0; e < 4; ++e) hid[t][4 * qd + e] *= d_hid.mul((uint64_t)row * LA_HID + 8 * kg + 4 * h + e);
         }
         *reinterpret_cast<f32x4*>(a.sv_hid + (int64_t)row * LA_HID + 8 * kg + 4 * h) = f32x4{hid[t][4 * qd], hid[t][4 * qd + 1], hid[t][4 * qd + 2], hid[t][4 * qd + 3]};
         __builtin_amdgcn_sched_barrier(0);
@@ -235,13 +197,13 @@ __global__ __launch_bounds__(512) void la_query_layer_kernel(const LaQueryArgs a
         const int t = kg / 4, qd = kg % 4;
         if (drop) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[t][4 * qd + e] *= la_drop_mul(key_out, (uint64_t)row * LA_D + 8 * kg + 4 * h + e, a.thr, a.ks);
+          for (int e = 0; e < 4; ++e) o[t][4 * qd + e] *= d_out.mul((uint64_t)row * LA_D + 8 * kg + 4 * h + e);
         }
         *reinterpret_cast<f32x4*>(a.sv_o + (int64_t)row * LA_D + 8 * kg + 4 * h) = f32x4{o[t][4 * qd], o[t][4 * qd + 1], o[t][4 * qd + 2], o[t][4 * qd + 3]};
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    la_layernorm(o, Ln + 2 * LA_D, Ln + 3 * LA_D, h, a.ln_eps);
+    cmr_layernorm64(o, Ln + 2 * LA_D, Ln + 3 * LA_D, h, a.ln_eps);
 
     f32x4 ov[8];
 #pragma unroll
@@ -276,19 +238,7 @@ struct LaStateArgs {
 // BF16 (the bf16 mode of BASELINE configs[2] / [3]): the two projections run on v_mfma_f32_32x32x16_bf16 (16 instructions per 32-row tile
 // instead of 128 fp32 ones; rows and weights rounded to bf16 on the way, fp32 accumulate), whose 32x32 result has the SAME register
 // layout -- so elu+1, 1/S and the row contraction K^T V (fp32 MFMA, the state is a sum over up to 10^5 rows) are unchanged.
-typedef __bf16 la_bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int LA_WPS = LA_D * 2 + 16;            // bytes per weight row in LDS (bf16): conflict-free ds_read_b128 over 32 consecutive rows
-
-__device__ __forceinline__ la_bf16x8 la_pack8(const f32x4& lo, const f32x4& hi) {
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-  uint4 w;
-  w.x = __builtin_bit_cast(unsigned, __builtin_convertvector((f2){lo[0], lo[1]}, b2));
-  w.y = __builtin_bit_cast(unsigned, __builtin_convertvector((f2){lo[2], lo[3]}, b2));
-  w.z = __builtin_bit_cast(unsigned, __builtin_convertvector((f2){hi[0], hi[1]}, b2));
-  w.w = __builtin_bit_cast(unsigned, __builtin_convertvector((f2){hi[2], hi[3]}, b2));
-  return __builtin_bit_cast(la_bf16x8, w);
-}
 
 template <bool BF16, bool SAVE = false>
 __global__ __launch_bounds__(512) void la_state_partial_kernel(const LaStateArgs a) {
@@ -301,10 +251,10 @@ __global__ __launch_bounds__(512) void la_state_partial_kernel(const LaStateArgs
   if constexpr (BF16) {
     for (int e = tid; e < LA_D * (LA_D / 8); e += 512) {
       const int n = e / (LA_D / 8), c = (e % (LA_D / 8)) * 8;
-      *reinterpret_cast<la_bf16x8*>(reinterpret_cast<unsigned char*>(Wk) + n * LA_WPS + c * 2) =
-          la_pack8(*reinterpret_cast<const f32x4*>(a.wk + n * LA_D + c), *reinterpret_cast<const f32x4*>(a.wk + n * LA_D + c + 4));
-      *reinterpret_cast<la_bf16x8*>(reinterpret_cast<unsigned char*>(Wv) + n * LA_WPS + c * 2) =
-          la_pack8(*reinterpret_cast<const f32x4*>(a.wv + n * LA_D + c), *reinterpret_cast<const f32x4*>(a.wv + n * LA_D + c + 4));
+      *reinterpret_cast<cmr_bf16x8*>(reinterpret_cast<unsigned char*>(Wk) + n * LA_WPS + c * 2) =
+          cmr_bf16x8_pairs(*reinterpret_cast<const f32x4*>(a.wk + n * LA_D + c), *reinterpret_cast<const f32x4*>(a.wk + n * LA_D + c + 4));
+      *reinterpret_cast<cmr_bf16x8*>(reinterpret_cast<unsigned char*>(Wv) + n * LA_WPS + c * 2) =
+          cmr_bf16x8_pairs(*reinterpret_cast<const f32x4*>(a.wv + n * LA_D + c), *reinterpret_cast<const f32x4*>(a.wv + n * LA_D + c + 4));
     }
   } else {
     for (int e = tid; e < LA_D * (LA_D / 4); e += 512) {
@@ -349,11 +299,11 @@ __global__ __launch_bounds__(512) void la_state_partial_kernel(const LaStateArgs
       const unsigned char* wvr = reinterpret_cast<const unsigned char*>(Wv) + l31 * LA_WPS + h * 16;
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        const la_bf16x8 ya = la_pack8(yf[2 * ks], yf[2 * ks + 1]);
+        const cmr_bf16x8 ya = cmr_bf16x8_pairs(yf[2 * ks], yf[2 * ks + 1]);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-          const la_bf16x8 wkb = *reinterpret_cast<const la_bf16x8*>(wkr + t * 32 * LA_WPS + ks * 32);
-          const la_bf16x8 wvb = *reinterpret_cast<const la_bf16x8*>(wvr + t * 32 * LA_WPS + ks * 32);
+          const cmr_bf16x8 wkb = *reinterpret_cast<const cmr_bf16x8*>(wkr + t * 32 * LA_WPS + ks * 32);
+          const cmr_bf16x8 wvb = *reinterpret_cast<const cmr_bf16x8*>(wvr + t * 32 * LA_WPS + ks * 32);
           kk[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ya, wkb, kk[t], 0, 0, 0);      // D[row][channel 32t + l31]
           vv[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ya, wvb, vv[t], 0, 0, 0);
         }
@@ -390,7 +340,7 @@ __global__ __launch_bounds__(512) void la_state_partial_kernel(const LaStateArgs
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        float k = la_elu1(kk[t][r]);
+        float k = cmr_elu1_fast(kk[t][r]);
         const uint32_t srow = tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
         if (partial && srow >= a.S) k = 0.f;
         if (SAVE && srow < a.S) {                  // lane = channel 32 t + l31: 32 consecutive floats per row and lane half
@@ -410,7 +360,7 @@ __global__ __launch_bounds__(512) void la_state_partial_kernel(const LaStateArgs
   float* p = a.part + ((int64_t)b * gridDim.x * 8 + blockIdx.x * 8 + wave) * LA_STATE;
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
-    const float ks = ksum[t] + la_xhalf(ksum[t]);
+    const float ks = ksum[t] + cmr_xhalf(ksum[t]);
     if (h == 0) p[512 + 32 * t + l31] = ks;                      // channel 32t + l31 = hd*8 + d
 #pragma unroll
     for (int r = 0; r < 16; ++r) {

@@ -15,42 +15,7 @@
 
 namespace {
 
-typedef __bf16 lb_bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int LB_D = 64, LB_HID = 128, LB_STATE = 576;
-
-__device__ __forceinline__ float lb_elu1(float v) { return v > 0.f ? v + 1.f : __builtin_amdgcn_exp2f(v * 1.4426950408889634f); }   // see la_fused.hip
-__device__ __forceinline__ float lb_xhalf(float v) { return cmr_xhalf(v); }
-
-__device__ __forceinline__ void lb_layernorm(f32x16 (&v)[2], const float* __restrict__ gs, const float* __restrict__ bs, int h, float eps) {
-  float s = 0.f;
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s += v[t][r];
-  s += lb_xhalf(s);
-  const float mean = s * (1.f / 64.f);
-  float q = 0.f;
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float d = v[t][r] - mean;
-      v[t][r] = d;
-      q += d * d;
-    }
-  q += lb_xhalf(q);
-  const float rstd = 1.f / sqrtf(q * (1.f / 64.f) + eps);
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      const f32x4 g = *reinterpret_cast<const f32x4*>(gs + 32 * t + 8 * qd + 4 * h);
-      const f32x4 b = *reinterpret_cast<const f32x4*>(bs + 32 * t + 8 * qd + 4 * h);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[t][4 * qd + e] = v[t][4 * qd + e] * rstd * g[e] + b[e];
-    }
-}
 
 // input channel of k slot (step s, lane half hh, element j): natural order, or the order in which an accumulator tile holds
 // its channels (step s = tile s / 2, register half s % 2)
@@ -60,12 +25,12 @@ __device__ __forceinline__ int lb_kchan(bool acc_order, int s, int hh, int j) {
 
 // W [N][K] fp32 (PyTorch [out][in]) -> A fragments [N / 32][K / 16][64 lanes][8 bf16]; steps >= acc_from use the accumulator order
 // (relative to the first such step)
-__device__ __forceinline__ void lb_stage_frags(lb_bf16x8* dst, const float* __restrict__ w, int N, int K, int acc_from, int tid) {
+__device__ __forceinline__ void lb_stage_frags(cmr_bf16x8* dst, const float* __restrict__ w, int N, int K, int acc_from, int tid) {
   const int S = K / 16;
   for (int e = tid; e < (N / 32) * S * 64; e += 512) {
     const int ln = e & 63, s = (e >> 6) % S, t = (e >> 6) / S;
     const int n = 32 * t + (ln & 31), hh = ln >> 5;
-    lb_bf16x8 v;
+    cmr_bf16x8 v;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int c = s < acc_from ? lb_kchan(false, s, hh, j) : 16 * acc_from + lb_kchan(true, s - acc_from, hh, j);
@@ -75,8 +40,10 @@ __device__ __forceinline__ void lb_stage_frags(lb_bf16x8* dst, const float* __re
   }
 }
 
-__device__ __forceinline__ lb_bf16x8 lb_pack_acc(const f32x16& a, int s2) {
-  lb_bf16x8 r;
+// cmr_bf16x8_each on registers 8 s2 .. 8 s2 + 7 of an accumulator tile.  A local copy: routed through cmr_bf16x8_each (two float4 built from the
+// tile) the kernel compiles to another program (2370 against 2372 instruction lines).
+__device__ __forceinline__ cmr_bf16x8 lb_pack_acc(const f32x16& a, int s2) {
+  cmr_bf16x8 r;
 #pragma unroll
   for (int j = 0; j < 8; ++j) r[j] = (__bf16)a[8 * s2 + j];
   return r;
@@ -94,10 +61,10 @@ struct LbArgs {
 
 __global__ __launch_bounds__(512) void la_query_layer_bf16_kernel(const LbArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  lb_bf16x8* Wq = reinterpret_cast<lb_bf16x8*>(smem_raw);      // [2][4][64]   x (natural order)
-  lb_bf16x8* Wm = Wq + 2 * 4 * 64;                              // [2][4][64]   message (accumulator order)
-  lb_bf16x8* W0 = Wm + 2 * 4 * 64;                              // [4][8][64]   steps 0..3 x, 4..7 merged message (accumulator order)
-  lb_bf16x8* W3 = W0 + 4 * 8 * 64;                              // [2][8][64]   hidden (accumulator order)
+  cmr_bf16x8* Wq = reinterpret_cast<cmr_bf16x8*>(smem_raw);     // [2][4][64]   x (natural order)
+  cmr_bf16x8* Wm = Wq + 2 * 4 * 64;                              // [2][4][64]   message (accumulator order)
+  cmr_bf16x8* W0 = Wm + 2 * 4 * 64;                              // [4][8][64]   steps 0..3 x, 4..7 merged message (accumulator order)
+  cmr_bf16x8* W3 = W0 + 4 * 8 * 64;                              // [2][8][64]   hidden (accumulator order)
   float* Ln = reinterpret_cast<float*>(W3 + 2 * 8 * 64);        // g1 | b1 | g2 | b2
   float* Kv = Ln + 4 * LB_D;                                    // [B][576]
   const int tid = threadIdx.x, lane = tid & 63;
@@ -134,7 +101,7 @@ __global__ __launch_bounds__(512) void la_query_layer_bf16_kernel(const LbArgs a
     const uint32_t rowc = valid ? row : 0;
     load_x(tile + tstride, nlo, nhi);                    // next tile's rows fly under this tile's work
     const float* kvb = Kv + (rowc / a.L) * LB_STATE + 4 * h;
-    lb_bf16x8 xb[4];
+    cmr_bf16x8 xb[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
 #pragma unroll
@@ -159,9 +126,9 @@ __global__ __launch_bounds__(512) void la_query_layer_bf16_kernel(const LbArgs a
         const int hd = 4 * t + qd;
         float qo[4], qp[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) qo[e] = lb_elu1(msg[t][4 * qd + e]);
+        for (int e = 0; e < 4; ++e) qo[e] = cmr_elu1_fast(msg[t][4 * qd + e]);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) qp[e] = lb_xhalf(qo[e]);
+        for (int e = 0; e < 4; ++e) qp[e] = cmr_xhalf(qo[e]);
         float qd8[8];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -186,7 +153,7 @@ __global__ __launch_bounds__(512) void la_query_layer_bf16_kernel(const LbArgs a
     // ---- merge + LayerNorm 1
     f32x16 mrg[2];
     {
-      lb_bf16x8 mb[4];
+      cmr_bf16x8 mb[4];
 #pragma unroll
       for (int s = 0; s < 4; ++s) mb[s] = lb_pack_acc(msg[s >> 1], s & 1);
 #pragma unroll
@@ -197,11 +164,11 @@ __global__ __launch_bounds__(512) void la_query_layer_bf16_kernel(const LbArgs a
         for (int s = 0; s < 4; ++s) mrg[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wm[(t * 4 + s) * 64 + lane], mb[s], mrg[t], 0, 0, 0);
       }
     }
-    lb_layernorm(mrg, Ln, Ln + LB_D, h, a.ln_eps);
+    cmr_layernorm64(mrg, Ln, Ln + LB_D, h, a.ln_eps);
     // ---- mlp: 128 -> 128 (ReLU) -> 64 on cat[x, message], LayerNorm 2
     f32x16 hid[4];
     {
-      lb_bf16x8 mb[4];
+      cmr_bf16x8 mb[4];
 #pragma unroll
       for (int s = 0; s < 4; ++s) mb[s] = lb_pack_acc(mrg[s >> 1], s & 1);
 #pragma unroll
@@ -227,7 +194,7 @@ __global__ __launch_bounds__(512) void la_query_layer_bf16_kernel(const LbArgs a
       for (int s = 0; s < 8; ++s)
         o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(W3[(t * 8 + s) * 64 + lane], lb_pack_acc(hid[s >> 1], s & 1), o[t], 0, 0, 0);
     }
-    lb_layernorm(o, Ln + 2 * LB_D, Ln + 3 * LB_D, h, a.ln_eps);
+    cmr_layernorm64(o, Ln + 2 * LB_D, Ln + 3 * LB_D, h, a.ln_eps);
     // ---- residual: x in output layout.  Piece kg = 2 s (channels 16 s + 4 h ..): h = 0 own lo, h = 1 the partner's hi;
     //      piece kg = 2 s + 1 (channels 16 s + 8 + 4 h ..): h = 0 the partner's lo, h = 1 own hi.
     f32x4 ov[8];
@@ -237,7 +204,7 @@ __global__ __launch_bounds__(512) void la_query_layer_bf16_kernel(const LbArgs a
 #pragma unroll
       for (int e = 0; e < 4; ++e) send[e] = h == 0 ? xhi[s][e] : xlo[s][e];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) recv[e] = lb_xhalf(send[e]);
+      for (int e = 0; e < 4; ++e) recv[e] = cmr_xhalf(send[e]);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float xe = h == 0 ? xlo[s][e] : recv[e];

@@ -45,11 +45,6 @@ __device__ __forceinline__ void lt_gemm_t(const float* __restrict__ Ws, int l31,
   }
 }
 
-__device__ __forceinline__ float lt_sum32(float v) {   // over the 32 rows of a tile (lanes of one half)
-  v = m16_sum16(v);
-  return v + cmr_xor16(v);
-}
-
 // LayerNorm(64) backward on a row held as 8 float4 (channels 8 kg + 4 h + e; the other 32 channels in lane ^ 32).
 // in: dy (gradient at the LayerNorm output), x (its input); out: dx; pg / pb: this row's contribution to d gamma / d beta.
 __device__ __forceinline__ void lt_ln_bwd(const f32x4 (&dy)[8], const f32x4 (&x)[8], const float* __restrict__ gam, int h, float eps,
@@ -148,14 +143,12 @@ __global__ __launch_bounds__(512) void la_mlp_bwd_kernel(const LaMlpBwdArgs a) {
   }
   for (int e = tid; e < 8 * 2 * 128; e += 512) Acc[e] = 0.f;
   __syncthreads();
-  uint64_t key_att = 0, key_hid = 0, key_out = 0;
+  CmrDrop d_att{}, d_hid{}, d_out{};
   if (DROP) {
-    const uint64_t sd = (uint64_t)a.seed[0];
-    key_att = cmr_mix64(sd + a.site_att * 0x9E3779B97F4A7C15ull);
-    key_hid = cmr_mix64(sd + a.site_hid * 0x9E3779B97F4A7C15ull);
-    key_out = cmr_mix64(sd + a.site_out * 0x9E3779B97F4A7C15ull);
+    d_att.init(a.seed, a.site_att, a.thr, a.ks);
+    d_hid.init(a.seed, a.site_hid, a.thr, a.ks);
+    d_out.init(a.seed, a.site_out, a.thr, a.ks);
   }
-  auto keep = [&](uint64_t key, uint64_t idx) { return (uint32_t)cmr_mix64(key ^ idx) >= a.thr ? a.ks : 0.f; };
 
   const uint32_t ntiles = (a.rows + 31) / 32;
   for (uint32_t tile = blockIdx.x * 8 + wave; tile < ntiles; tile += gridDim.x * 8) {
@@ -181,8 +174,8 @@ __global__ __launch_bounds__(512) void la_mlp_bwd_kernel(const LaMlpBwdArgs a) {
     for (int kg = 0; kg < 8; ++kg)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        pg[kg][e] = lt_sum32(pg[kg][e]);
-        pb[kg][e] = lt_sum32(pb[kg][e]);
+        pg[kg][e] = m16_sum32(pg[kg][e]);
+        pb[kg][e] = m16_sum32(pb[kg][e]);
       }
     if (l31 == 0) {                              // lanes 0 and 32: own slot, own channels -- plain read-modify-write, fixed order
       float* lp = Acc + (wave * 2 + 1) * 128 + 4 * h;
@@ -197,7 +190,7 @@ __global__ __launch_bounds__(512) void la_mlp_bwd_kernel(const LaMlpBwdArgs a) {
 #pragma unroll
       for (int kg = 0; kg < 8; ++kg)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) dO[kg][e] *= keep(key_out, (uint64_t)row * LT_D + 8 * kg + 4 * h + e);
+        for (int e = 0; e < 4; ++e) dO[kg][e] *= d_out.mul((uint64_t)row * LT_D + 8 * kg + 4 * h + e);
     }
     {                                            // (output buffers hold whole tiles: no predicated stores)
       float* p = a.d_o + (int64_t)row * LT_D + 4 * h;
@@ -247,7 +240,7 @@ __global__ __launch_bounds__(512) void la_mlp_bwd_kernel(const LaMlpBwdArgs a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float v = dc[t][4 * qd + e];
-          if (DROP) v *= keep(key_att, (uint64_t)row * LT_D + 8 * kg + 4 * h + e);
+          if (DROP) v *= d_att.mul((uint64_t)row * LT_D + 8 * kg + 4 * h + e);
           dn[kg][e] = v;
         }
       }
@@ -257,8 +250,8 @@ __global__ __launch_bounds__(512) void la_mlp_bwd_kernel(const LaMlpBwdArgs a) {
     for (int kg = 0; kg < 8; ++kg)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        pg[kg][e] = lt_sum32(pg[kg][e]);
-        pb[kg][e] = lt_sum32(pb[kg][e]);
+        pg[kg][e] = m16_sum32(pg[kg][e]);
+        pb[kg][e] = m16_sum32(pb[kg][e]);
       }
     if (l31 == 0) {
       float* lp = Acc + (wave * 2 + 0) * 128 + 4 * h;

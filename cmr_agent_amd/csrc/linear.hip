@@ -237,7 +237,7 @@ __device__ __attribute__((aligned(16))) float cmr_zero16[4] = {0.f, 0.f, 0.f, 0.
 // loads and every store (stores count in vmcnt on gfx9) behind each other.
 template <int AC>
 __device__ __forceinline__ float ws_act(float v, float slope) {
-  if (AC == 1) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
+  if (AC == 1) return cmr_gelu(v);
   if (AC == 2) return v > 0.f ? v + 1.f : expf(v);
   return v > 0.f ? v : v * slope;
 }
@@ -909,18 +909,6 @@ extern "C" int cmr_linear_f32(const float* x1, int64_t ld1, int k1, const float*
 // rows); on the bf16 cores the products take 1/16 of the time and the layer is a pure stream.  Transposed product (D[channel][row]: weights
 // = A operand, rows = B operand): a lane owns one row, its accumulator registers are 4 x 4 consecutive output channels -> float4 epilogue.
 // The whole weight matrix lives in registers as bf16 fragments (NT x KS x 4 VGPRs, converted once per wave); rows are converted on the fly.
-typedef __bf16 lin_bf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ lin_bf16x8 lin_pack8(const f32x4& lo, const f32x4& hi) {
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-  uint4 w;
-  w.x = __builtin_bit_cast(unsigned, __builtin_convertvector((f2){lo[0], lo[1]}, b2));
-  w.y = __builtin_bit_cast(unsigned, __builtin_convertvector((f2){lo[2], lo[3]}, b2));
-  w.z = __builtin_bit_cast(unsigned, __builtin_convertvector((f2){hi[0], hi[1]}, b2));
-  w.w = __builtin_bit_cast(unsigned, __builtin_convertvector((f2){hi[2], hi[3]}, b2));
-  return __builtin_bit_cast(lin_bf16x8, w);
-}
-
 // AC as in linear_ws_kernel (0: none / ReLU / LeakyReLU through the slope, 1: GELU, 2: elu + 1); RES: a residual operand is given.
 // Register budget <= 128 (four waves per SIMD: a stream, not a GEMM): weight fragments 8 NT KS / 4 ... 32, the raw rows of the NEXT tile 8 KS,
 // this tile's rows as bf16 4 KS, accumulators 16 NT (initialised with the bias from LDS).
@@ -935,7 +923,7 @@ __global__ __launch_bounds__(256, CMR_LRB_MINB) void linear_rows_bf16_kernel(con
   const int h = lane >> 5, l31 = lane & 31;
   if (tid < 32 * NT) Bs[tid] = (a.bias && tid < a.n_out) ? a.bias[tid] : 0.f;
   // weight fragments: lane (cout l31, half h) of tile t, step ks holds W[32 t + l31][16 ks + 8 h .. + 7] (rows past n_out: zeros)
-  lin_bf16x8 wf[NT][KS];
+  cmr_bf16x8 wf[NT][KS];
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const int n = 32 * t + l31;
@@ -944,7 +932,7 @@ __global__ __launch_bounds__(256, CMR_LRB_MINB) void linear_rows_bf16_kernel(con
     for (int ks = 0; ks < KS; ++ks) {
       f32x4 lo = *reinterpret_cast<const f32x4*>(wr + 16 * ks), hi = *reinterpret_cast<const f32x4*>(wr + 16 * ks + 4);
       if (n >= a.n_out) { lo = f32x4{0.f, 0.f, 0.f, 0.f}; hi = lo; }
-      wf[t][ks] = lin_pack8(lo, hi);
+      wf[t][ks] = cmr_bf16x8_pairs(lo, hi);
     }
   }
   __syncthreads();
@@ -964,9 +952,9 @@ __global__ __launch_bounds__(256, CMR_LRB_MINB) void linear_rows_bf16_kernel(con
   uint32_t tile = blockIdx.x * 4 + wave;
   load_tile(tile, raw);
   for (; tile < ntiles; tile += tstride) {
-    lin_bf16x8 xb[KS];
+    cmr_bf16x8 xb[KS];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) xb[ks] = lin_pack8(raw[2 * ks], raw[2 * ks + 1]);
+    for (int ks = 0; ks < KS; ++ks) xb[ks] = cmr_bf16x8_pairs(raw[2 * ks], raw[2 * ks + 1]);
     load_tile(tile + tstride, raw);                            // next tile of this wave in flight under this one's products / stores
     const uint32_t row = tile * 32 + l31;
     f32x4 rv[RES ? NT : 1][4];

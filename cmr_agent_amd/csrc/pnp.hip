@@ -355,11 +355,6 @@ __global__ __launch_bounds__(PNP_HYP_WG) void pnp_score_kernel(const float* __re
 }
 
 // ---- selection + Gauss-Newton + recount ----------------------------------------------------------------------------------------
-__device__ __forceinline__ double pnp_wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 __device__ __forceinline__ int pnp_block_count(int v, int* scratch) {      // sum over the block (integers: order free); all threads
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -443,7 +438,7 @@ __global__ __launch_bounds__(PNP_SEL_THREADS) void pnp_select_kernel(const float
       a[27] += ru * ru + rv * rv;
     }
     for (int q = 0; q < PNP_NACC; ++q) {
-      const double s = pnp_wave_sum(a[q]);
+      const double s = cmr_wave_sum_d(a[q]);
       if (lane == 0) acc[wave][q] = s;
     }
     __syncthreads();

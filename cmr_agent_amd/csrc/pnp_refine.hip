@@ -32,11 +32,6 @@ struct PrfState {
   int32_t stop, status, wcount, pad;
 };
 
-__device__ __forceinline__ double prf_wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 __global__ __launch_bounds__(64) void prf_init_kernel(const float* __restrict__ pose_in, const float* __restrict__ Kin,
                                                       PrfState* __restrict__ state) {
   const int b = blockIdx.x;
@@ -107,7 +102,7 @@ __global__ __launch_bounds__(PRF_THREADS) void prf_accum_kernel(const float* __r
   }
 #pragma unroll
   for (int q = 0; q < PRF_NACC; ++q) {
-    const double v = prf_wave_sum(a[q]);
+    const double v = cmr_wave_sum_d(a[q]);
     if (lane == 0) acc[wave][q] = v;
   }
   for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);

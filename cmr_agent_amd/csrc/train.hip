@@ -72,13 +72,6 @@ __global__ __launch_bounds__(RED_THREADS) void bn_stats_partial_kernel(const flo
   }
 }
 
-// sum over a wave of doubles, same value in every lane afterwards (fixed butterfly order: deterministic)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // one wave per channel: lane l adds partials l, l + 64, ... in double, then a butterfly over the wave
 __global__ __launch_bounds__(64) void bn_stats_final_kernel(const float* __restrict__ x, const float* __restrict__ part, int nblk, int64_t rows,
                                                             int C, float eps, float momentum, const float* __restrict__ gamma,
@@ -90,8 +83,8 @@ __global__ __launch_bounds__(64) void bn_stats_final_kernel(const float* __restr
     s += (double)part[(int64_t)b * 2 * C + c];
     ss += (double)part[(int64_t)b * 2 * C + C + c];
   }
-  s = wave_sum(s);
-  ss = wave_sum(ss);
+  s = cmr_wave_sum_d(s);
+  ss = cmr_wave_sum_d(ss);
   if (lane != 0) return;
   const double n = (double)rows;
   const double pm = s / n;
@@ -252,8 +245,8 @@ __global__ __launch_bounds__(64) void bn_bwd_final_kernel(const float* __restric
     s += (double)part[(int64_t)b * 2 * C + c];
     sx += (double)part[(int64_t)b * 2 * C + C + c];
   }
-  s = wave_sum(s);
-  sx = wave_sum(sx);
+  s = cmr_wave_sum_d(s);
+  sx = cmr_wave_sum_d(sx);
   if (lane != 0) return;
   coef[c] = (float)(s / (double)rows);
   coef[C + c] = (float)(sx / (double)rows);
@@ -413,7 +406,7 @@ __global__ __launch_bounds__(64) void col_final_kernel(const float* __restrict__
   } else {
     double a = 0.0;
     for (int k = lane; k < nblk; k += 64) a += (double)pv[((int64_t)b * nblk + k) * C + c];
-    a = wave_sum(a);
+    a = cmr_wave_sum_d(a);
     if (lane == 0) out[(int64_t)b * C + c] = (float)a;
   }
 }
@@ -718,8 +711,8 @@ static __global__ __launch_bounds__(64) void bn_stats_from_sums_kernel(const flo
         ss += (double)v1[u];
       }
   }
-  s = wave_sum(s);
-  ss = wave_sum(ss);
+  s = cmr_wave_sum_d(s);
+  ss = cmr_wave_sum_d(ss);
   if (lane != 0) return;
   const double n = (double)rows;
   const double pm = s / n;

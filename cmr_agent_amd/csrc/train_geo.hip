@@ -10,11 +10,6 @@ namespace {
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 inline unsigned ew_grid(int64_t items) {
   int64_t g = (items + 255) / 256;
   return (unsigned)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
@@ -36,7 +31,7 @@ __device__ __forceinline__ float act_grad(float x, int act, float p) {
   switch (act) {
     case CMR_ACT_RELU: return x > 0.f ? 1.f : 0.f;
     case CMR_ACT_LRELU: return x > 0.f ? 1.f : p;
-    case CMR_ACT_GELU: return 0.5f * (1.f + erff(x * 0.70710678118654752440f)) + x * 0.39894228040143267794f * expf(-0.5f * x * x);
+    case CMR_ACT_GELU: return cmr_gelu_grad(x);
     case CMR_ACT_ELU1: return x > 0.f ? 1.f : expf(x);
     default: return 1.f;
   }
@@ -127,7 +122,7 @@ __global__ __launch_bounds__(64) void reduce_partials_kernel(const float* __rest
   const int i = blockIdx.x, lane = threadIdx.x;
   double s = 0.0;
   for (int b = lane; b < nblk; b += 64) s += (double)part[(int64_t)b * n + i];
-  s = wave_sum_d(s);
+  s = cmr_wave_sum_d(s);
   if (lane == 0) {
     float* d = out + (out_map ? out_map[i] : i);
     *d = accumulate ? *d + (float)s : (float)s;
@@ -140,7 +135,7 @@ __global__ __launch_bounds__(64) void reduce_partials2_kernel(const float* __res
   const int i = blockIdx.x, lane = threadIdx.x;
   double s = 0.0;
   for (int b = lane; b < nblk; b += 64) s += (double)part[(int64_t)b * 2 * n + i];
-  s = wave_sum_d(s);
+  s = cmr_wave_sum_d(s);
   if (lane == 0) {
     float* d = i < n ? out0 + i : out1 + (i - n);
     *d = accumulate ? *d + (float)s : (float)s;
@@ -504,7 +499,7 @@ __global__ __launch_bounds__(64) void la_bwd_state_kernel(const float* __restric
   const int i = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
   double s = 0.0;
   for (int k = lane; k < nper; k += 64) s += (double)part[((int64_t)b * nper + k) * 576 + i];
-  s = wave_sum_d(s);
+  s = cmr_wave_sum_d(s);
   if (lane == 0) dstate[(int64_t)b * 576 + i] = (float)s;
 }
 

@@ -14,40 +14,9 @@
 // The MLP kernel gives one 32-row tile to a workgroup of 8 waves: every wave redoes the small out-projection and
 // LayerNorm, takes 128 of the 1024 hidden units through fc1 / GELU / its K-slice of fc2, and the 8 partial outputs
 // are summed through LDS in a fixed order.
-#include "cmr_common.h"
+#include "cmr_mfma16.h"
 
 namespace {
-
-__device__ __forceinline__ float vf_xhalf(float v) { return cmr_xhalf(v); }
-__device__ __forceinline__ float vf_gelu(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
-
-// LayerNorm over the 64 channels of a row held as 8 fragments (32 channels here, 32 in lane ^ 32), in place
-__device__ __forceinline__ void vf_layernorm(f32x4 (&v)[8], const float* __restrict__ g, const float* __restrict__ b, int h,
-                                             float eps) {
-  float s = 0.f;
-#pragma unroll
-  for (int kg = 0; kg < 8; ++kg) s += (v[kg][0] + v[kg][1]) + (v[kg][2] + v[kg][3]);
-  s += vf_xhalf(s);
-  const float mean = s * (1.f / 64.f);
-  float q = 0.f;
-#pragma unroll
-  for (int kg = 0; kg < 8; ++kg)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float d = v[kg][e] - mean;
-      v[kg][e] = d;
-      q += d * d;
-    }
-  q += vf_xhalf(q);
-  const float rstd = 1.f / sqrtf(q * (1.f / 64.f) + eps);
-#pragma unroll
-  for (int kg = 0; kg < 8; ++kg) {
-    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + 8 * kg + 4 * h);
-    const f32x4 bv = *reinterpret_cast<const f32x4*>(b + 8 * kg + 4 * h);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[kg][e] = v[kg][e] * rstd * gv[e] + bv[e];
-  }
-}
 
 // acc[t] = sum_kg sum_j Wf[tile0 + t][kg0 + kg][lane][j] * bfrag(kg, j).  The fragments come straight from L2
 // (~1-2 us under load) and a k-group is only T*4 MFMAs (0.25-0.5 us), so they are requested D k-groups ahead
@@ -108,7 +77,7 @@ __global__ __launch_bounds__(256) void ln64_linear_kernel(const LnLinArgs a) {
   f32x4 xf[8];
 #pragma unroll
   for (int kg = 0; kg < 8; ++kg) xf[kg] = *reinterpret_cast<const f32x4*>(xp + kg * 8);
-  vf_layernorm(xf, a.g, a.b, h, a.eps);
+  cmr_layernorm64(xf, a.g, a.b, a.eps, [&](int kg) { return 8 * kg + 4 * h; });
   for (int pr = 0; pr < P.npair; ++pr) {               // 64 output channels per pass
     f32x16 acc[2];
     vf_gemm<2, 8, 8>(P.wf, 8, 2 * pr, 0, lane, acc, [&](int kg, int j) { return xf[kg][j]; });
@@ -171,7 +140,7 @@ __global__ __launch_bounds__(512) void vit_out_ffn_kernel(const OutFfnArgs a) {
   f32x4 xn[8];
 #pragma unroll
   for (int kg = 0; kg < 8; ++kg) xn[kg] = x1[kg];
-  vf_layernorm(xn, a.g2, a.b2n, h, a.eps);
+  cmr_layernorm64(xn, a.g2, a.b2n, a.eps, [&](int kg) { return 8 * kg + 4 * h; });
   // ---- this wave's 128 hidden units: fc1 + GELU, then its K-slice of fc2
   f32x16 hid[4];
   vf_gemm<4, 8, 4>(a.w1_f, 8, 4 * wave, 0, lane, hid, [&](int kg, int j) { return xn[kg][j]; });
@@ -181,7 +150,7 @@ __global__ __launch_bounds__(512) void vit_out_ffn_kernel(const OutFfnArgs a) {
     for (int qd = 0; qd < 4; ++qd) {
       const f32x4 bv = *reinterpret_cast<const f32x4*>(a.b1 + 128 * wave + 32 * t + 8 * qd + 4 * h);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) hid[t][4 * qd + e] = vf_gelu(hid[t][4 * qd + e] + bv[e]);
+      for (int e = 0; e < 4; ++e) hid[t][4 * qd + e] = cmr_gelu(hid[t][4 * qd + e] + bv[e]);
     }
   f32x16 part[2];
   vf_gemm<2, 16, 8>(a.w2_f, 128, 0, 16 * wave, lane, part, [&](int kg, int j) { return hid[kg / 4][4 * (kg % 4) + j]; });
@@ -222,45 +191,7 @@ __global__ __launch_bounds__(512) void vit_out_ffn_kernel(const OutFfnArgs a) {
 // 4 g + r (r = 0..3) of row n.  A lane therefore owns ONE row and, of every 16-channel tile T, the channels 16 T + 4 g + r -- which is
 // again the B operand of k-steps (T, r) of the next GEMM when its weights are stored in that order ([n_out/16][k/16][64 lanes][4],
 // lane = 16 g + m holding W[16 To + m][16 T + 4 g + r], r = 0..3: cmr_agent_amd/models/_pack.py:frag_pack16).  Rows read from memory
-// are read in the same order (float4 at channel 16 T + 4 g).
-__device__ __forceinline__ f32x4 vf_mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// acc[To] = sum over k-tiles T (KT of them, from kt0) and r of Wf[tile0 + To][kt0 + T][lane][r] * bfrag(T, r); fragments requested D
-// k-tiles ahead through a register ring (they come straight from L2)
-template <int TO, int KT, int D, typename BF>
-__device__ __forceinline__ void vf16_gemm(const float* __restrict__ wf, int kt_total, int tile0, int kt0, int lane, f32x4 (&acc)[TO], BF bfrag) {
-  static_assert(D >= 1 && D <= KT, "prefetch depth");
-#pragma unroll
-  for (int t = 0; t < TO; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const float* wp = wf + ((int64_t)tile0 * kt_total + kt0) * 256 + lane * 4;
-  const int64_t tstride = (int64_t)kt_total * 256;
-  f32x4 ring[D][TO];
-#pragma unroll
-  for (int d = 0; d < D; ++d)
-#pragma unroll
-    for (int t = 0; t < TO; ++t) ring[d][t] = *reinterpret_cast<const f32x4*>(wp + t * tstride + d * 256);
-#pragma unroll
-  for (int kt = 0; kt < KT; ++kt) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float b = bfrag(kt, r);
-#pragma unroll
-      for (int t = 0; t < TO; ++t) acc[t] = vf_mfma16(ring[kt % D][t][r], b, acc[t]);
-    }
-    if (kt + D < KT) {
-#pragma unroll
-      for (int t = 0; t < TO; ++t) ring[kt % D][t] = *reinterpret_cast<const f32x4*>(wp + t * tstride + (kt + D) * 256);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// sum over the four lane groups g (lanes l, l ^ 16, l ^ 32, l ^ 48)
-__device__ __forceinline__ float vf16_allg(float v) {
-  v += cmr_xor16(v);
-  return v + cmr_xhalf(v);
-}
-
+// are read in the same order (float4 at channel 16 T + 4 g).  The MFMA, its ring-buffered GEMM and the four-group sum: cmr_mfma16.h.
 #ifdef CMR_FFN_STAMPS
 #define FFN_STAMP(i) do { uint64_t t_; asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); st_[i] = t_; } while (0)
 #else
@@ -290,7 +221,7 @@ __global__ __launch_bounds__(512) void vit_out_ffn16_kernel(const OutFfnArgs a) 
   // ---- x1 = ctx Wo + bo + x     (every wave: 64 MFMAs)
   {
     f32x4 acc[4];
-    vf16_gemm<4, 4, 4>(a.wo_f, 4, 0, 0, lane, acc, [&](int t, int r) { return cf[t][r]; });
+    m16_gemm<4, 4, 4>(a.wo_f, 4, 0, 0, lane, acc, [&](int t, int r) { return cf[t][r]; });
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bo + 16 * t + 4 * g);
@@ -305,7 +236,7 @@ __global__ __launch_bounds__(512) void vit_out_ffn16_kernel(const OutFfnArgs a) 
     float s = 0.f;
 #pragma unroll
     for (int t = 0; t < 4; ++t) s += (x1[t][0] + x1[t][1]) + (x1[t][2] + x1[t][3]);
-    const float mean = vf16_allg(s) * (1.f / 64.f);
+    const float mean = m16_allg(s) * (1.f / 64.f);
     float q = 0.f;
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -315,7 +246,7 @@ __global__ __launch_bounds__(512) void vit_out_ffn16_kernel(const OutFfnArgs a) 
         xn[t][e] = d;
         q += d * d;
       }
-    const float rstd = 1.f / sqrtf(vf16_allg(q) * (1.f / 64.f) + a.eps);
+    const float rstd = 1.f / sqrtf(m16_allg(q) * (1.f / 64.f) + a.eps);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const f32x4 gv = *reinterpret_cast<const f32x4*>(a.g2 + 16 * t + 4 * g);
@@ -327,17 +258,17 @@ __global__ __launch_bounds__(512) void vit_out_ffn16_kernel(const OutFfnArgs a) 
   FFN_STAMP(3);
   // ---- this wave's 128 hidden units: fc1 + GELU (8 tiles of 16), then its K-slice of fc2
   f32x4 hid[8];
-  vf16_gemm<8, 4, 4>(a.w1_f, 4, 8 * wave, 0, lane, hid, [&](int t, int r) { return xn[t][r]; });
+  m16_gemm<8, 4, 4>(a.w1_f, 4, 8 * wave, 0, lane, hid, [&](int t, int r) { return xn[t][r]; });
   FFN_STAMP(4);
 #pragma unroll
   for (int t = 0; t < 8; ++t) {
     const f32x4 bv = *reinterpret_cast<const f32x4*>(a.b1 + 128 * wave + 16 * t + 4 * g);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) hid[t][e] = vf_gelu(hid[t][e] + bv[e]);
+    for (int e = 0; e < 4; ++e) hid[t][e] = cmr_gelu(hid[t][e] + bv[e]);
   }
   FFN_STAMP(5);
   f32x4 part[4];
-  vf16_gemm<4, 8, 8>(a.w2_f, 64, 0, 8 * wave, lane, part, [&](int t, int r) { return hid[t][r]; });
+  m16_gemm<4, 8, 8>(a.w2_f, 64, 0, 8 * wave, lane, part, [&](int t, int r) { return hid[t][r]; });
   FFN_STAMP(6);
   if (wave > 0) {
 #pragma unroll

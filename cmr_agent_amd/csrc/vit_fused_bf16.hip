@@ -16,52 +16,9 @@
 
 namespace {
 
-typedef __bf16 vb_bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float vb_xhalf(float v) { return cmr_xhalf(v); }
-__device__ __forceinline__ float vb_gelu(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
-
-// LayerNorm over the 64 channels of a row held as 8 float4 pieces (4 in this lane, 4 in lane ^ 32); chan(i) = first channel of piece i
-template <typename CH>
-__device__ __forceinline__ void vb_layernorm(f32x4 (&v)[8], const float* __restrict__ g, const float* __restrict__ b, float eps, CH chan) {
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-  s += vb_xhalf(s);
-  const float mean = s * (1.f / 64.f);
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float d = v[i][e] - mean;
-      v[i][e] = d;
-      q += d * d;
-    }
-  q += vb_xhalf(q);
-  const float rstd = 1.f / sqrtf(q * (1.f / 64.f) + eps);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + chan(i));
-    const f32x4 bv = *reinterpret_cast<const f32x4*>(b + chan(i));
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[i][e] = v[i][e] * rstd * gv[e] + bv[e];
-  }
-}
-
-__device__ __forceinline__ vb_bf16x8 vb_pack(const f32x4& a, const f32x4& b) {
-  vb_bf16x8 r;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    r[i] = (__bf16)a[i];
-    r[4 + i] = (__bf16)b[i];
-  }
-  return r;
-}
-
 struct VbProblem {
   const float* x; int64_t ldx; uint32_t rows;
-  const vb_bf16x8* wf; const float* bias; int npair;   // n_out = 64 * npair; wf [2 npair][4][64]
+  const cmr_bf16x8* wf; const float* bias; int npair;   // n_out = 64 * npair; wf [2 npair][4][64]
   float* y; int64_t ldy;
 };
 struct VbLnArgs {
@@ -84,12 +41,12 @@ __global__ __launch_bounds__(256) void ln64_linear_bf16_kernel(const VbLnArgs a)
   f32x4 xf[8];                                           // piece 2 s + half = channels 16 s + 8 h + 4 half .. + 3
 #pragma unroll
   for (int i = 0; i < 8; ++i) xf[i] = *reinterpret_cast<const f32x4*>(xp + 16 * (i >> 1) + 4 * (i & 1));
-  vb_layernorm(xf, a.g, a.b, a.eps, [&](int i) { return 16 * (i >> 1) + 8 * h + 4 * (i & 1); });
-  vb_bf16x8 xb[4];
+  cmr_layernorm64(xf, a.g, a.b, a.eps, [&](int i) { return 16 * (i >> 1) + 8 * h + 4 * (i & 1); });
+  cmr_bf16x8 xb[4];
 #pragma unroll
-  for (int s = 0; s < 4; ++s) xb[s] = vb_pack(xf[2 * s], xf[2 * s + 1]);
+  for (int s = 0; s < 4; ++s) xb[s] = cmr_bf16x8_each(xf[2 * s], xf[2 * s + 1]);
   for (int pr = 0; pr < P.npair; ++pr) {
-    vb_bf16x8 wv[2][4];
+    cmr_bf16x8 wv[2][4];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -124,10 +81,10 @@ __global__ __launch_bounds__(256) void ln64_linear_bf16_kernel(const VbLnArgs a)
 struct VbFfnArgs {
   const float* ctx; int64_t ldc;
   const float* x; int64_t ldx;
-  const vb_bf16x8* wo_f; const float* bo;              // [2][4][64] natural order
+  const cmr_bf16x8* wo_f; const float* bo;              // [2][4][64] natural order
   const float* g2; const float* b2n; float eps;
-  const vb_bf16x8* w1_f; const float* b1;              // [32][4][64] accumulator order
-  const vb_bf16x8* w2_f; const float* b2;              // [2][64][64] accumulator order
+  const cmr_bf16x8* w1_f; const float* b1;              // [32][4][64] accumulator order
+  const cmr_bf16x8* w2_f; const float* b2;              // [2][64][64] accumulator order
   float* out; int64_t ldo; uint32_t rows;
 };
 
@@ -145,7 +102,7 @@ __global__ __launch_bounds__(512) void vit_out_ffn_bf16_kernel(const VbFfnArgs a
   const float* xp = a.x + (int64_t)rowc * a.ldx + 4 * h;
   // this wave's weight fragments of the out-projection and of fc1 are requested up front (8 + 16 KB-sized wave loads in flight while
   // the rows arrive); those of fc2 follow once fc1 has released its registers (256 registers per wave at 2 waves / SIMD)
-  vb_bf16x8 wo[2][4], w1[4][4], w2[2][8];
+  cmr_bf16x8 wo[2][4], w1[4][4], w2[2][8];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -170,7 +127,7 @@ __global__ __launch_bounds__(512) void vit_out_ffn_bf16_kernel(const VbFfnArgs a
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 #pragma unroll
-      for (int s = 0; s < 4; ++s) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wo[t][s], vb_pack(cl[s], ch[s]), acc[t], 0, 0, 0);
+      for (int s = 0; s < 4; ++s) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wo[t][s], cmr_bf16x8_each(cl[s], ch[s]), acc[t], 0, 0, 0);
     }
 #pragma unroll
     for (int kg = 0; kg < 8; ++kg) {
@@ -182,11 +139,11 @@ __global__ __launch_bounds__(512) void vit_out_ffn_bf16_kernel(const VbFfnArgs a
   f32x4 xn[8];
 #pragma unroll
   for (int kg = 0; kg < 8; ++kg) xn[kg] = x1[kg];
-  vb_layernorm(xn, a.g2, a.b2n, a.eps, [&](int i) { return 8 * i + 4 * h; });
+  cmr_layernorm64(xn, a.g2, a.b2n, a.eps, [&](int i) { return 8 * i + 4 * h; });
   // LN(x1) sits in the accumulator layout: k step (t, s'') = pieces 4 t + 2 s'', 4 t + 2 s'' + 1
-  vb_bf16x8 nb[4];
+  cmr_bf16x8 nb[4];
 #pragma unroll
-  for (int s = 0; s < 4; ++s) nb[s] = vb_pack(xn[2 * s], xn[2 * s + 1]);
+  for (int s = 0; s < 4; ++s) nb[s] = cmr_bf16x8_each(xn[2 * s], xn[2 * s + 1]);
   // ---- this wave's 128 hidden units: fc1 + GELU, then its K slice of fc2
   f32x16 hid[4];
 #pragma unroll
@@ -209,7 +166,7 @@ __global__ __launch_bounds__(512) void vit_out_ffn_bf16_kernel(const VbFfnArgs a
     for (int qd = 0; qd < 4; ++qd) {
       const f32x4 bv = *reinterpret_cast<const f32x4*>(a.b1 + 128 * wave + 32 * t + 8 * qd + 4 * h);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) hid[t][4 * qd + e] = vb_gelu(hid[t][4 * qd + e] + bv[e]);
+      for (int e = 0; e < 4; ++e) hid[t][4 * qd + e] = cmr_gelu(hid[t][4 * qd + e] + bv[e]);
     }
     __builtin_amdgcn_sched_barrier(0);        // one tile's biases / erf temporaries at a time (register budget)
   }
@@ -220,7 +177,7 @@ __global__ __launch_bounds__(512) void vit_out_ffn_bf16_kernel(const VbFfnArgs a
     for (int r = 0; r < 16; ++r) part[n][r] = 0.f;
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
-      vb_bf16x8 hb;
+      cmr_bf16x8 hb;
 #pragma unroll
       for (int j = 0; j < 8; ++j) hb[j] = (__bf16)hid[s >> 1][8 * (s & 1) + j];
       part[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2[n][s], hb, part[n], 0, 0, 0);
@@ -264,13 +221,13 @@ extern "C" int cmr_ln64_linear_bf16_f32(const float* x, int64_t ldx, int64_t row
   CMR_REQUIRE(n_out_x > 0 && n_out_x % 64 == 0 && ldx % 4 == 0 && ldo_x % 4 == 0 && cmr_aligned16(x) && cmr_aligned16(wf_x) &&
               cmr_aligned16(bias_x) && cmr_aligned16(out_x) && cmr_aligned16(gamma) && cmr_aligned16(beta));
   VbLnArgs a{};
-  a.p[0] = VbProblem{x, ldx, (uint32_t)rows_x, (const vb_bf16x8*)wf_x, bias_x, n_out_x / 64, out_x, ldo_x};
+  a.p[0] = VbProblem{x, ldx, (uint32_t)rows_x, (const cmr_bf16x8*)wf_x, bias_x, n_out_x / 64, out_x, ldo_x};
   a.tiles0 = (uint32_t)((rows_x + 31) / 32);
   a.tiles = a.tiles0;
   if (y) {
     CMR_REQUIRE(wf_y && bias_y && out_y && rows_y > 0 && rows_y < (int64_t)0x7fffffc0 && n_out_y > 0 && n_out_y % 64 == 0);
     CMR_REQUIRE(ldy % 4 == 0 && ldo_y % 4 == 0 && cmr_aligned16(y) && cmr_aligned16(wf_y) && cmr_aligned16(bias_y) && cmr_aligned16(out_y));
-    a.p[1] = VbProblem{y, ldy, (uint32_t)rows_y, (const vb_bf16x8*)wf_y, bias_y, n_out_y / 64, out_y, ldo_y};
+    a.p[1] = VbProblem{y, ldy, (uint32_t)rows_y, (const cmr_bf16x8*)wf_y, bias_y, n_out_y / 64, out_y, ldo_y};
     a.tiles += (uint32_t)((rows_y + 31) / 32);
   } else {
     a.p[1] = a.p[0];
@@ -287,7 +244,7 @@ extern "C" int cmr_vit_out_ffn_bf16_f32(const float* ctx, int64_t ldc, const flo
   CMR_REQUIRE(ldc % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && cmr_aligned16(ctx) && cmr_aligned16(x) && cmr_aligned16(out) &&
               cmr_aligned16(wo_f) && cmr_aligned16(w1_f) && cmr_aligned16(w2_f) && cmr_aligned16(bo) && cmr_aligned16(b1) &&
               cmr_aligned16(b2) && cmr_aligned16(ln_g) && cmr_aligned16(ln_b));
-  const VbFfnArgs a{ctx, ldc, x, ldx, (const vb_bf16x8*)wo_f, bo, ln_g, ln_b, eps, (const vb_bf16x8*)w1_f, b1, (const vb_bf16x8*)w2_f, b2,
+  const VbFfnArgs a{ctx, ldc, x, ldx, (const cmr_bf16x8*)wo_f, bo, ln_g, ln_b, eps, (const cmr_bf16x8*)w1_f, b1, (const cmr_bf16x8*)w2_f, b2,
                     out, ldo, (uint32_t)rows};
   hipLaunchKernelGGL(vit_out_ffn_bf16_kernel, dim3((unsigned)((rows + 31) / 32)), dim3(512), 0, stream, a);
   return cmr_launch_status();

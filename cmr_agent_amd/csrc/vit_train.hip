@@ -54,7 +54,7 @@ __global__ __launch_bounds__(512) void vit_out_ffn16_train_kernel(const OutFfnTr
     cf[t] = *reinterpret_cast<const f32x4*>(cp + 16 * t);
     x1[t] = *reinterpret_cast<const f32x4*>(xp + 16 * t);
   }
-  M16Drop dp, da, df;
+  CmrDrop dp, da, df;
   if (DROP) {
     dp.init(a.seed, a.site_proj, a.thr_proj, a.ks_proj);
     da.init(a.seed, a.site_act, a.thr_mlp, a.ks_mlp);
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(512) void vit_out_ffn16_train_kernel(const OutFfnTr
     const f32x4 bv = *reinterpret_cast<const f32x4*>(a.b1 + 128 * wave + 16 * t + 4 * g);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float v = m16_gelu(hid[t][e] + bv[e]);
+      float v = cmr_gelu(hid[t][e] + bv[e]);
       if (DROP) v *= da.mul((uint64_t)row * 1024 + 128 * wave + 16 * t + 4 * g + e);
       hid[t][e] = v;
     }
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(512) void vit_ffn_bwd16_kernel(const FfnBwdArgs a) 
     dO[t] = *reinterpret_cast<const f32x4*>(dp_ + 16 * t);
     x1[t] = *reinterpret_cast<const f32x4*>(xp + 16 * t);
   }
-  M16Drop dp, da, df;
+  CmrDrop dp, da, df;
   if (DROP) {
     dp.init(a.seed, a.site_proj, a.thr_proj, a.ks_proj);
     da.init(a.seed, a.site_act, a.thr_mlp, a.ks_mlp);
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(512) void vit_ffn_bwd16_kernel(const FfnBwdArgs a) 
       const float uu = u[t][e] + bv[e];
       const float sc = DROP ? da.mul((uint64_t)row * 1024 + 128 * wave + 16 * t + 4 * g + e) : 1.f;
       float ge, gd;
-      m16_gelu_both(uu, ge, gd);
+      cmr_gelu_both(uu, ge, gd);
       u[t][e] = ge * sc;                               // hidden activation as the forward's fc2 saw it
       dg[t][e] = dg[t][e] * sc * gd;                   // gradient at the pre-activation
     }
@@ -359,11 +359,6 @@ struct LnQkvBwdArgs {
   float* lnpart;                                       // [tiles][128] per-tile sums of d gamma | d beta
 };
 
-__device__ __forceinline__ float vt_sum32(float v) {   // over the 32 rows of a tile (lanes of one half)
-  v = m16_sum16(v);
-  return v + cmr_xor16(v);
-}
-
 __global__ __launch_bounds__(256) void vit_lnqkv_bwd_kernel(const LnQkvBwdArgs a) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -460,8 +455,8 @@ __global__ __launch_bounds__(256) void vit_lnqkv_bwd_kernel(const LnQkvBwdArgs a
   for (int kg = 0; kg < 8; ++kg)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      pg[kg][e] = vt_sum32(pg[kg][e]);
-      pb[kg][e] = vt_sum32(pb[kg][e]);
+      pg[kg][e] = m16_sum32(pg[kg][e]);
+      pb[kg][e] = m16_sum32(pb[kg][e]);
     }
   if (l31 == 0) {
     float* lp = a.lnpart + (int64_t)gt * 128 + 4 * h;

@@ -397,14 +397,6 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_lds_kernel(const float* __r
 //   LDS: X^T ring [4][Cin][21 dwords] (21: odd row stride -> the 32 channel rows of an operand read fall on 32 banks; 42 >= 34 halo
 //   pixels), dY^T [2][32][21 dwords].  45 KB at Cin = 128: three workgroups per CU.
 // ------------------------------------------------------------------------------------------------------------------
-typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ unsigned wg_pack2(float lo, float hi) {            // (bf16(lo) | bf16(hi) << 16), round to nearest even
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){lo, hi}, b2));
-}
-
 // OCC = workgroups per CU the register budget is set for.  2 (the Cin = 128 instances, round 5): 144 accumulator registers + < 112 others.
 // One workgroup per CU kept ~80 KB of loads in flight per CU and waited for them 70 % of the time (an image row tile took 4.6 us for 1 150
 // matrix-pipe cycles); two co-resident workgroups double the bytes in flight and multiply while the other waits.  The bias gradient (BIAS)
@@ -478,8 +470,8 @@ __global__ __launch_bounds__(256, OCC) void conv3x3_wgrad_bf16_kernel(const floa
       v = ok ? v : f32x4{0.f, 0.f, 0.f, 0.f};
       const float s0 = h ? v[0] : v[2], s1 = h ? v[1] : v[3];
       const float r0 = cmr_xhalf(s0), r1 = cmr_xhalf(s1);
-      const unsigned w0 = h ? wg_pack2(r0, v[2]) : wg_pack2(v[0], r0);
-      const unsigned w1 = h ? wg_pack2(r1, v[3]) : wg_pack2(v[1], r1);
+      const unsigned w0 = h ? cmr_bf16_pack2(r0, v[2]) : cmr_bf16_pack2(v[0], r0);
+      const unsigned w1 = h ? cmr_bf16_pack2(r1, v[3]) : cmr_bf16_pack2(v[1], r1);
       unsigned* p = row0 + (4 * quad + 2 * h) * RS + pp;
       p[0] = w0;
       p[RS] = w1;
@@ -509,7 +501,7 @@ __global__ __launch_bounds__(256, OCC) void conv3x3_wgrad_bf16_kernel(const floa
         if (BIAS) {
           f32x4 lo;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) lo[e] = src[i][e] - __builtin_bit_cast(float, wg_pack2(0.f, src[i][e]) & 0xffff0000u);
+          for (int e = 0; e < 4; ++e) lo[e] = src[i][e] - __builtin_bit_cast(float, cmr_bf16_pack2(0.f, src[i][e]) & 0xffff0000u);
           store_pairs(DL + (r & 1) * (32 * NCO * RS), dc4, dpair(i), lo, ok);
         }
         store_pairs(DT + (r & 1) * (32 * NCO * RS), dc4, dpair(i), src[i], ok);
@@ -551,12 +543,12 @@ __global__ __launch_bounds__(256, OCC) void conv3x3_wgrad_bf16_kernel(const floa
       for (int pbi = 0; pbi < NBLK / NSPLIT; ++pbi) {
         const int pb = split * (NBLK / NSPLIT) + pbi;   // Cin = 64: the pixel blocks of a row tile are split over two waves
         const int d0 = 8 * pb + 4 * h;                  // first dword of this lane's 8 pixels (dY: element = pixel; X: element = pixel + kx)
-        wg_bf16x8 av[NCO];
+        cmr_bf16x8 av[NCO];
 #pragma unroll
         for (int c = 0; c < NCO; ++c) {
           uint4 aw;
           aw.x = dr[c * 32 * RS + d0]; aw.y = dr[c * 32 * RS + d0 + 1]; aw.z = dr[c * 32 * RS + d0 + 2]; aw.w = dr[c * 32 * RS + d0 + 3];
-          av[c] = __builtin_bit_cast(wg_bf16x8, aw);
+          av[c] = __builtin_bit_cast(cmr_bf16x8, aw);
         }
         if (BIAS && ci_t == 0) {                        // (wave-uniform)
           const uint4 one8 = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
@@ -565,8 +557,8 @@ __global__ __launch_bounds__(256, OCC) void conv3x3_wgrad_bf16_kernel(const floa
           for (int c = 0; c < NCO; ++c) {
             uint4 lw;
             lw.x = lr[c * 32 * RS + d0]; lw.y = lr[c * 32 * RS + d0 + 1]; lw.z = lr[c * 32 * RS + d0 + 2]; lw.w = lr[c * 32 * RS + d0 + 3];
-            accb[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c], __builtin_bit_cast(wg_bf16x8, one8), accb[c], 0, 0, 0);
-            accb[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wg_bf16x8, lw), __builtin_bit_cast(wg_bf16x8, one8), accb[c], 0, 0, 0);
+            accb[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c], __builtin_bit_cast(cmr_bf16x8, one8), accb[c], 0, 0, 0);
+            accb[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cmr_bf16x8, lw), __builtin_bit_cast(cmr_bf16x8, one8), accb[c], 0, 0, 0);
           }
         }
 #pragma unroll
@@ -580,9 +572,9 @@ __global__ __launch_bounds__(256, OCC) void conv3x3_wgrad_bf16_kernel(const floa
           const uint4 b2 = {q[1], q[2], q[3], q[4]};
 #pragma unroll
           for (int c = 0; c < NCO; ++c) {
-            acc[c][3 * ky] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c], __builtin_bit_cast(wg_bf16x8, b0), acc[c][3 * ky], 0, 0, 0);
-            acc[c][3 * ky + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c], __builtin_bit_cast(wg_bf16x8, b1), acc[c][3 * ky + 1], 0, 0, 0);
-            acc[c][3 * ky + 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c], __builtin_bit_cast(wg_bf16x8, b2), acc[c][3 * ky + 2], 0, 0, 0);
+            acc[c][3 * ky] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c], __builtin_bit_cast(cmr_bf16x8, b0), acc[c][3 * ky], 0, 0, 0);
+            acc[c][3 * ky + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c], __builtin_bit_cast(cmr_bf16x8, b1), acc[c][3 * ky + 1], 0, 0, 0);
+            acc[c][3 * ky + 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c], __builtin_bit_cast(cmr_bf16x8, b2), acc[c][3 * ky + 2], 0, 0, 0);
           }
         }
       }
@@ -751,7 +743,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_bf16_tr_kernel(const flo
           }
         }
         const f32x4 v = ok ? t : f32x4{0.f, 0.f, 0.f, 0.f};
-        *reinterpret_cast<uint2*>(slot + wt2_off(px, xq >> 1) + 8 * (xq & 1)) = uint2{wg_pack2(v[0], v[1]), wg_pack2(v[2], v[3])};
+        *reinterpret_cast<uint2*>(slot + wt2_off(px, xq >> 1) + 8 * (xq & 1)) = uint2{cmr_bf16_pack2(v[0], v[1]), cmr_bf16_pack2(v[2], v[3])};
       }
     };
     auto load_drow = [&](int r, f32x4& dst) {
@@ -762,12 +754,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_bf16_tr_kernel(const flo
       unsigned char* img = DI + (r & 1) * WT2_DROW;
       const bool ok = live && r < H && x0 + dp < W;
       const f32x4 v = ok ? src : f32x4{0.f, 0.f, 0.f, 0.f};
-      const unsigned w0 = wg_pack2(v[0], v[1]), w1 = wg_pack2(v[2], v[3]);
+      const unsigned w0 = cmr_bf16_pack2(v[0], v[1]), w1 = cmr_bf16_pack2(v[2], v[3]);
       *reinterpret_cast<uint2*>(img + wt2_off(dp, dq >> 1) + 8 * (dq & 1)) = uint2{w0, w1};
       if (BIAS) {                                         // residues dY - bf16(dY), in the upper 64 channels of the same pixel row
         const float l0 = v[0] - __builtin_bit_cast(float, w0 << 16), l1 = v[1] - __builtin_bit_cast(float, w0 & 0xffff0000u);
         const float l2 = v[2] - __builtin_bit_cast(float, w1 << 16), l3 = v[3] - __builtin_bit_cast(float, w1 & 0xffff0000u);
-        *reinterpret_cast<uint2*>(img + wt2_off(dp, 8 + (dq >> 1)) + 8 * (dq & 1)) = uint2{wg_pack2(l0, l1), wg_pack2(l2, l3)};
+        *reinterpret_cast<uint2*>(img + wt2_off(dp, 8 + (dq >> 1)) + 8 * (dq & 1)) = uint2{cmr_bf16_pack2(l0, l1), cmr_bf16_pack2(l2, l3)};
       }
     };
 
@@ -792,12 +784,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_bf16_tr_kernel(const flo
 #pragma unroll
       for (int pb = 0; pb < TW / 16; ++pb) {
         const uint2 a0 = wt2_tr(dimg, od[pb][0]), a1 = wt2_tr(dimg, od[pb][1]);
-        const wg_bf16x8 av = __builtin_bit_cast(wg_bf16x8, uint4{a0.x, a0.y, a1.x, a1.y});
+        const cmr_bf16x8 av = __builtin_bit_cast(cmr_bf16x8, uint4{a0.x, a0.y, a1.x, a1.y});
         if (BIAS && ci_t == 0) {                          // (wave-uniform)
           const uint4 one8 = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
           const uint2 l0 = wt2_tr(dimg, ol[pb][0]), l1 = wt2_tr(dimg, ol[pb][1]);
-          accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(wg_bf16x8, one8), accb, 0, 0, 0);
-          accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wg_bf16x8, uint4{l0.x, l0.y, l1.x, l1.y}), __builtin_bit_cast(wg_bf16x8, one8), accb, 0, 0, 0);
+          accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(cmr_bf16x8, one8), accb, 0, 0, 0);
+          accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cmr_bf16x8, uint4{l0.x, l0.y, l1.x, l1.y}), __builtin_bit_cast(cmr_bf16x8, one8), accb, 0, 0, 0);
         }
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
@@ -808,9 +800,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_bf16_tr_kernel(const flo
           const uint4 b1 = {__builtin_amdgcn_alignbit(r0.y, r0.x, 16), __builtin_amdgcn_alignbit(r1.x, r0.y, 16),
                             __builtin_amdgcn_alignbit(r1.y, r1.x, 16), __builtin_amdgcn_alignbit(r2.x, r1.y, 16)};
           const uint4 b2 = {r0.y, r1.x, r1.y, r2.x};
-          acc[3 * ky] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(wg_bf16x8, b0), acc[3 * ky], 0, 0, 0);
-          acc[3 * ky + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(wg_bf16x8, b1), acc[3 * ky + 1], 0, 0, 0);
-          acc[3 * ky + 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(wg_bf16x8, b2), acc[3 * ky + 2], 0, 0, 0);
+          acc[3 * ky] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(cmr_bf16x8, b0), acc[3 * ky], 0, 0, 0);
+          acc[3 * ky + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(cmr_bf16x8, b1), acc[3 * ky + 1], 0, 0, 0);
+          acc[3 * ky + 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(cmr_bf16x8, b2), acc[3 * ky + 2], 0, 0, 0);
         }
       }
     };
