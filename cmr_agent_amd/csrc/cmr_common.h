@@ -277,6 +277,14 @@ static inline unsigned cmr_fill_blocks(int64_t vecs, int threads) {
   return (unsigned)(want < 1 ? 1 : (want > 65536 ? 65536 : want));
 }
 
+// counts = 0 as a launch of its own, for an entry without a fill kernel to fold it into.  Internal to each source that launches it.
+namespace {
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void cmr_zero_kernel(int32_t* __restrict__ counts, int ncounts) {
+  for (int c = blockIdx.x * THREADS + threadIdx.x; c < ncounts; c += gridDim.x * THREADS) counts[c] = 0;
+}
+}  // namespace
+
 __device__ __forceinline__ int cmr_mfma_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 // Dropout mask, counter based (no state, no stored mask): element `idx` of dropout site `site` in the step whose seed is `seed` is KEPT

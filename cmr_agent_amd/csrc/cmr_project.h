@@ -4,6 +4,11 @@
 #pragma once
 #include "cmr_common.h"
 
+// The limits the pose operations share, each defined here and nowhere else (ops.py restates them for its messages).
+constexpr int CMR_MAX_RADIUS = 16;    // a window's radius in pixels: (2r + 1)^2 <= 1089 cells per row; also keeps centre +- r far from integer overflow
+constexpr int CMR_MAX_PLANES = 64;    // planes of an image that is sampled or of an attribute that is rendered
+constexpr int CMR_MAX_POSES = 4096;   // candidate poses per sample
+
 // X_c = R x + t, p = K X_c in fp32.  P is the sample's 4 x 4 pose, row-major (16 floats, the last row unused), K its 3 x 3 intrinsics
 // (9 floats), x its cloud as three planes of N.  Every sum is an fmaf chain from the LAST term inwards; K[2] zc, K[5] zc and K[8] zc are
 // plain products.  A restatement elsewhere (the tests' fp32 torch code) must use these operations in this order.

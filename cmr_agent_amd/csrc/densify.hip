@@ -4,7 +4,7 @@
 // difference of the guide image's colours.
 //
 // cmr_densify_f32 -- two launches on the caller's stream, no workspace:
-//   dn_zero_kernel     counts = 0.
+//   cmr_zero_kernel    counts = 0 (cmr_common.h).
 //   dn_densify_kernel  one 256-thread workgroup per DN_TW x DN_TH = 64 x 16 tile on (ceil(w / 64) ceil(h / 16), B); templated on the
 //                      number of guide planes and on "has attributes".
 //     stage   the depth tile with its halo of R pixels ((16 + 2R) x (64 + 2R) floats) and the guide planes go to LDS once, one
@@ -22,7 +22,7 @@
 //             atomic per workgroup and word.
 // LDS: (1 + Cg) (16 + 2R) (64 + 2R) 4 + (16 + 2R) 16 bytes, dynamic: 10.8 KB at R = 8 without a guide, 41.5 KB with 3 planes, 92 928 B
 // at R = 16 with 4 (one workgroup per CU; granted through cmr_grant_smem).
-#include "cmr_common.h"
+#include "cmr_project.h"   // CMR_MAX_RADIUS
 
 namespace {
 
@@ -30,12 +30,7 @@ constexpr int DN_THREADS = 256;
 constexpr int DN_TW = 64;          // tile width = one wave per tile line
 constexpr int DN_TH = 16;          // tile height: 4 waves x DN_PPT lines
 constexpr int DN_PPT = DN_TH / (DN_THREADS / 64);
-constexpr int DN_MAX_R = 16;
 constexpr int DN_MAX_C = 4;
-
-__global__ __launch_bounds__(DN_THREADS) void dn_zero_kernel(int32_t* __restrict__ counts, int ncounts) {
-  for (int c = blockIdx.x * DN_THREADS + threadIdx.x; c < ncounts; c += gridDim.x * DN_THREADS) counts[c] = 0;
-}
 
 struct DnParams {
   const float* depth;
@@ -204,7 +199,7 @@ extern "C" int cmr_densify_f32(const float* depth, const float* attr, int C, con
   CMR_REQUIRE(B > 0 && B <= 65535 && h > 0 && w > 0 && (int64_t)h * w <= (int64_t)1 << 24);
   CMR_REQUIRE((attr == nullptr) == (dense_attr == nullptr) && (attr ? (C >= 1 && C <= DN_MAX_C) : C == 0));
   CMR_REQUIRE(guide ? (Cg >= 1 && Cg <= DN_MAX_C) : Cg == 0);
-  CMR_REQUIRE(radius >= 0 && radius <= DN_MAX_R && (keep == 0 || keep == 1));
+  CMR_REQUIRE(radius >= 0 && radius <= CMR_MAX_RADIUS && (keep == 0 || keep == 1));
   CMR_REQUIRE(sigma_s > 0.f && sigma_s < __builtin_huge_valf() && min_weight >= 1e-24f && min_weight < __builtin_huge_valf());
   CMR_REQUIRE(!guide || (sigma_r > 0.f && sigma_r < __builtin_huge_valf()));
   const double log2e = 1.4426950408889634074;
@@ -216,6 +211,6 @@ extern "C" int cmr_densify_f32(const float* depth, const float* attr, int C, con
   p.kr = guide ? (float)(log2e / (2.0 * (double)sigma_r * (double)sigma_r)) : 0.f;
   p.min_weight = min_weight; p.fill = fill;
   CMR_REQUIRE(p.ks < __builtin_huge_valf() && p.kr < __builtin_huge_valf());
-  hipLaunchKernelGGL(dn_zero_kernel, dim3(1), dim3(DN_THREADS), 0, stream, counts, 3 * B);
+  hipLaunchKernelGGL(cmr_zero_kernel<DN_THREADS>, dim3(1), dim3(DN_THREADS), 0, stream, counts, 3 * B);
   return attr ? dn_dispatch<true>(p, Cg, B, stream) : dn_dispatch<false>(p, Cg, B, stream);
 }

@@ -26,7 +26,6 @@ constexpr int GM_THREADS = 256;     // 4 waves
 constexpr int GM_LANES = 16;        // lanes per row: 16 x float4 = one 256-byte feature row
 constexpr int GM_ROWS = GM_THREADS / GM_LANES;   // rows per workgroup
 constexpr int GM_AHEAD = 4;         // window pixels whose loads are in flight together per group
-constexpr int GM_MAX_RADIUS = 16;  // (2r + 1)^2 <= 1089 pixels per point; also keeps centre +- r far from integer overflow
 
 __global__ __launch_bounds__(256) void gm_project_kernel(const float* __restrict__ pts, const void* __restrict__ mask, int mask_bytes,
                                                          const float* __restrict__ pose, const float* __restrict__ Kin, int N, int h,
@@ -147,7 +146,7 @@ extern "C" int cmr_guided_match_f32(const float* pts, const float* pc_feat, cons
   CMR_REQUIRE(pts && pc_feat && img_feat && mask && pose && K && idx && keep && counts && workspace);
   CMR_REQUIRE(C == GM_C && cmr_cloud_map_ok(B, N, h, w));
   CMR_REQUIRE(mask_bytes == 1 || mask_bytes == 8);
-  CMR_REQUIRE(radius >= 0 && radius <= GM_MAX_RADIUS && max_dist >= 0.f && __builtin_isfinite(max_dist));
+  CMR_REQUIRE(radius >= 0 && radius <= CMR_MAX_RADIUS && max_dist >= 0.f && __builtin_isfinite(max_dist));
   CMR_REQUIRE(cmr_aligned16(pc_feat) && cmr_aligned16(img_feat) && cmr_aligned16(workspace));
   CMR_REQUIRE(workspace_bytes >= cmr_guided_match_workspace_bytes(B, N));
   const int64_t groups = ((int64_t)N + GM_ROWS - 1) / GM_ROWS * B;

@@ -4,35 +4,29 @@
 // the same rows and cells bit for bit.
 //
 // cmr_paint_points_f32 -- the image laid over the cloud.  Two launches on the caller's stream:
-//   pi_zero_kernel    counts = 0.
+//   cmr_zero_kernel   counts = 0 (cmr_common.h).
 //   pi_paint_kernel   one thread per row on (ceil(N / 256), B): projection (pose and K are wave-uniform: scalar loads), the in-view test
 //                     on the floats, then the C planes PI_PLANES at a time: the taps of all PI_PLANES planes (4 each when bilinear) are
 //                     loaded before the first is used, the three lerps are rounded operation by operation (cmr_lerp, under
 //                     fp contract(off): never an fma, so plain fp32 torch code gives the same bits), and colours are stored coalesced (consecutive
 //                     n within a plane), 0 for the rows that are not painted.  counts by one atomic per workgroup and word.
-// cmr_render_points_f32 -- the cloud laid over the image: a z-buffer that remembers its owner.  Three launches, no memset node:
-//   pi_fill_kernel    key map = all ones (16-byte stores; the workspace is 16-byte aligned) and counts = 0.
-//   pi_splat_kernel   one thread per row: a selected row in view lowers the 64-bit key (bits of z) << 32 | n of its cell with ONE unsigned
-//                     64-bit vector atomic min (positive floats order like their bits, so the nearest row wins and equal depths go to the
-//                     lowest n: the map does not depend on the order of arrival).
+// cmr_render_points_f32 -- the cloud laid over the image: a z-buffer that remembers its owner.  The key, its fill, its decode and the
+// attribute gather are cmr_zbuffer.h's, shared with surfel.hip.  Three launches, no memset node:
+//   pi_fill_kernel    key map = empty (cmr_zfill) and counts = 0.
+//   pi_splat_kernel   one thread per row: a selected row in view lowers the key cmr_zkey(z, n) of its cell with ONE unsigned 64-bit vector
+//                     atomic min: the map does not depend on the order of arrival.
 //   pi_resolve_kernel one thread per pixel, templated on the footprint S = splat: the least key over the (2S + 1)^2 cells round the pixel as
 //                     a gather -- compile-time loop bounds, clamped addresses and a select, all loads of a line in flight together; a
-//                     minimum is exact, so this equals (2S + 1)^2 atomics per row -- then coalesced stores of index / depth / attribute
-//                     maps; the gather attr[b, c, owner] (PI_PLANES planes in flight) is the only scattered read.
+//                     minimum is exact, so this equals (2S + 1)^2 atomics per row -- then cmr_zresolve / cmr_zgather: coalesced stores of
+//                     the index / depth / attribute maps.
 // No floating-point atomic anywhere; every output element is a plain store by the thread that owns it.
-#include "cmr_sample.h"
+#include "cmr_zbuffer.h"
 
 namespace {
 
 constexpr int PI_THREADS = 256;
-constexpr int PI_PLANES = 4;       // planes whose taps / gathers are in flight together
-constexpr int PI_MAX_C = 64;
+constexpr int PI_PLANES = 4;       // planes whose taps are in flight together
 constexpr int PI_MAX_SPLAT = 4;
-constexpr unsigned long long PI_EMPTY = ~0ull;
-
-__global__ __launch_bounds__(PI_THREADS) void pi_zero_kernel(int32_t* __restrict__ counts, int ncounts) {
-  for (int c = blockIdx.x * PI_THREADS + threadIdx.x; c < ncounts; c += gridDim.x * PI_THREADS) counts[c] = 0;
-}
 
 template <bool BILINEAR>
 __global__ __launch_bounds__(PI_THREADS) void pi_paint_kernel(const float* __restrict__ pts, const void* __restrict__ mask, int mask_bytes,
@@ -94,10 +88,7 @@ __global__ __launch_bounds__(PI_THREADS) void pi_paint_kernel(const float* __res
 __global__ __launch_bounds__(PI_THREADS) void pi_fill_kernel(unsigned long long* __restrict__ keys, int64_t cells,
                                                              int32_t* __restrict__ counts, int ncounts) {
   const int64_t i = (int64_t)blockIdx.x * PI_THREADS + threadIdx.x, stride = (int64_t)gridDim.x * PI_THREADS;
-  const int64_t nvec = cells >> 1;
-  ulonglong2* kv = reinterpret_cast<ulonglong2*>(keys);                  // the workspace is 16-byte aligned
-  for (int64_t v = i; v < nvec; v += stride) kv[v] = make_ulonglong2(PI_EMPTY, PI_EMPTY);
-  if (i == 0 && (cells & 1)) keys[cells - 1] = PI_EMPTY;
+  cmr_zfill(keys, cells, i, stride);
   for (int64_t c = i; c < ncounts; c += stride) counts[c] = 0;
 }
 
@@ -111,10 +102,7 @@ __global__ __launch_bounds__(PI_THREADS) void pi_splat_kernel(const float* __res
   if (sel) {
     const CmrProj p = cmr_project(pose + 16 * b, Kin + 9 * b, pts + (int64_t)b * 3 * N, N, n, h, w, 0);
     view = p.view;
-    if (view) {
-      const unsigned long long key = ((unsigned long long)__builtin_bit_cast(unsigned, p.z) << 32) | (unsigned)n;
-      atomicMin(keys + (int64_t)b * h * w + (p.cy * w + p.cx), key);     // cy * w + cx < h * w <= 2^24
-    }
+    if (view) atomicMin(keys + (int64_t)b * h * w + (p.cy * w + p.cx), cmr_zkey(p.z, (unsigned)n));      // cy * w + cx < h * w <= 2^24
   }
   const bool flag[2] = {sel, view};
   int cnt[2];
@@ -134,7 +122,7 @@ __global__ __launch_bounds__(PI_THREADS) void pi_resolve_kernel(const unsigned l
   const int pix = valid ? i : cells - 1;
   const int py = pix / w, px = pix - py * w;
   const unsigned long long* kb = keys + (int64_t)b * cells;
-  unsigned long long best = PI_EMPTY;
+  unsigned long long best = CMR_ZEMPTY;
 #pragma unroll
   for (int dy = -S; dy <= S; ++dy) {
     const int y = py + dy;
@@ -146,35 +134,12 @@ __global__ __launch_bounds__(PI_THREADS) void pi_resolve_kernel(const unsigned l
 #pragma unroll
     for (int dx = -S; dx <= S; ++dx) {
       const int x = px + dx;
-      const unsigned long long kk = (iny && x >= 0 && x < w) ? k[dx + S] : PI_EMPTY;
+      const unsigned long long kk = (iny && x >= 0 && x < w) ? k[dx + S] : CMR_ZEMPTY;
       best = kk < best ? kk : best;
     }
   }
-  const bool owned = valid && best != PI_EMPTY;
-  const int owner = owned ? (int)(unsigned)(best & 0xffffffffull) : -1;
-  if (valid) {
-    const int64_t o = (int64_t)b * cells + i;
-    index_map[o] = owner;
-    depth_map[o] = owned ? __builtin_bit_cast(float, (unsigned)(best >> 32)) : __builtin_huge_valf();
-  }
-  if (attr_map) {
-    const float* ab = attr + (int64_t)b * C * N;
-    float* ob = attr_map + (int64_t)b * C * cells;
-    for (int c = 0; c < C; c += PI_PLANES) {                             // wave-uniform
-      float val[PI_PLANES];
-#pragma unroll
-      for (int k = 0; k < PI_PLANES; ++k) val[k] = fill;
-      if (owned) {
-#pragma unroll
-        for (int k = 0; k < PI_PLANES; ++k) val[k] = ab[(int64_t)(c + k < C ? c + k : C - 1) * N + owner];
-      }
-      if (valid) {
-#pragma unroll
-        for (int k = 0; k < PI_PLANES; ++k)
-          if (c + k < C) ob[(int64_t)(c + k) * cells + i] = val[k];
-      }
-    }
-  }
+  const bool owned = cmr_zresolve(best, valid, b, i, cells, index_map, depth_map);
+  cmr_zgather(best, owned, valid, b, i, cells, attr, C, N, fill, attr_map);
   const bool flag[1] = {owned};
   int cnt[1];
   cmr_block_counts<1, PI_THREADS>(flag, part, cnt);
@@ -187,9 +152,9 @@ extern "C" int cmr_paint_points_f32(const float* pts, const void* mask, int mask
                                     int B, int N, int C, int H, int W, int mode, float* colors, uint8_t* painted, int32_t* counts, float* uv,
                                     hipStream_t stream) {
   CMR_REQUIRE(pts && pose && K && image && colors && painted && counts);
-  CMR_REQUIRE(cmr_cloud_map_ok(B, N, H, W) && C >= 1 && C <= PI_MAX_C);
-  CMR_REQUIRE((mask_bytes == 1 || mask_bytes == 8) && (mode == 0 || mode == 1));
-  hipLaunchKernelGGL(pi_zero_kernel, dim3(1), dim3(PI_THREADS), 0, stream, counts, 2 * B);
+  CMR_REQUIRE(cmr_cloud_map_ok(B, N, H, W) && C >= 1 && C <= CMR_MAX_PLANES);
+  CMR_REQUIRE(cmr_mask_bytes_ok(mask_bytes) && (mode == 0 || mode == 1));
+  hipLaunchKernelGGL(cmr_zero_kernel<PI_THREADS>, dim3(1), dim3(PI_THREADS), 0, stream, counts, 2 * B);
   const dim3 grid((N + PI_THREADS - 1) / PI_THREADS, B);
   if (mode == 1)
     hipLaunchKernelGGL(pi_paint_kernel<true>, grid, dim3(PI_THREADS), 0, stream, pts, mask, mask_bytes, pose, K, image, N, C, H, W, colors,
@@ -201,16 +166,15 @@ extern "C" int cmr_paint_points_f32(const float* pts, const void* mask, int mask
 }
 
 extern "C" int64_t cmr_render_points_workspace_bytes(int B, int h, int w) {
-  if (B <= 0 || h <= 0 || w <= 0) return 0;
-  return cmr_up16((int64_t)B * h * w * 8);
+  return cmr_zkeys_bytes(B, h, w);
 }
 
 extern "C" int cmr_render_points_f32(const float* pts, const void* mask, int mask_bytes, const float* pose, const float* K, const float* attr,
                                      int C, int B, int N, int h, int w, int splat, float fill, int32_t* index_map, float* depth_map,
                                      float* attr_map, int32_t* counts, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
   CMR_REQUIRE(pts && pose && K && index_map && depth_map && counts && workspace);
-  CMR_REQUIRE(cmr_cloud_map_ok(B, N, h, w) && (mask_bytes == 1 || mask_bytes == 8) && splat >= 0 && splat <= PI_MAX_SPLAT);
-  CMR_REQUIRE((attr == nullptr) == (attr_map == nullptr) && (attr ? (C >= 1 && C <= PI_MAX_C) : C == 0));
+  CMR_REQUIRE(cmr_cloud_map_ok(B, N, h, w) && cmr_mask_bytes_ok(mask_bytes) && splat >= 0 && splat <= PI_MAX_SPLAT);
+  CMR_REQUIRE(cmr_attr_ok(attr, attr_map, C));
   CMR_REQUIRE(cmr_aligned16(workspace) && workspace_bytes >= cmr_render_points_workspace_bytes(B, h, w));
   unsigned long long* keys = (unsigned long long*)workspace;
   const int64_t cells = (int64_t)B * h * w;

@@ -33,7 +33,6 @@ constexpr int PMI_AHEAD = 4;                    // rows of a thread whose pixel 
 constexpr int PMI_MAX_BINS = 64;
 constexpr int PMI_MAX_CHUNK = 8;                // poses per workgroup at nb <= 32
 constexpr int PMI_LDS_BYTES = 32 * 1024;        // the chunk's histograms: 8 poses at nb <= 32, 2 at nb = 64
-constexpr int PMI_MAX_POSES = 4096;             // pose_score.hip PS_MAX_POSES
 static_assert(PMI_ROWS % PMI_AHEAD == 0 && PMI_MAX_BINS * PMI_MAX_BINS * 4 <= PMI_LDS_BYTES, "row groups and one histogram in LDS");
 
 inline int pmi_chunk(int nb) {
@@ -223,7 +222,7 @@ extern "C" int cmr_pose_mi_f32(const float* pts, const float* attr, const void* 
                                float g_lo, float g_hi, int32_t* hist, int32_t* counts, int32_t* selected, double* entropy, double* mi,
                                hipStream_t stream) {
   CMR_REQUIRE(pts && attr && poses && K && grey && hist && counts && selected && entropy && mi);
-  CMR_REQUIRE(cmr_cloud_map_ok(B, N, H, W) && P > 0 && P <= PMI_MAX_POSES);
+  CMR_REQUIRE(cmr_cloud_map_ok(B, N, H, W) && P > 0 && P <= CMR_MAX_POSES);
   CMR_REQUIRE((mask_bytes == 1 || mask_bytes == 8) && (mode == 0 || mode == 1) && bins >= 2 && bins <= PMI_MAX_BINS);
   CMR_REQUIRE(__builtin_isfinite(a_lo) && __builtin_isfinite(a_hi) && a_lo < a_hi && __builtin_isfinite(g_lo) && __builtin_isfinite(g_hi) &&
               g_lo < g_hi);

@@ -30,8 +30,6 @@ constexpr int PS_GROUPS = PS_THREADS / PS_LANES;
 constexpr int PS_SLICE = 256;       // rows per workgroup, one per thread in the packing step.  A constant: the summation order hangs on it
 constexpr int PS_CHUNK = 32;        // poses per workgroup: 2 accumulators per lane
 constexpr int PS_AHEAD = 4;         // poses whose pixel loads are in flight together per group
-constexpr int PS_MAX_RADIUS = 16;   // guided_match.hip GM_MAX_RADIUS
-constexpr int PS_MAX_POSES = 4096;
 static_assert(PS_SLICE == PS_THREADS && PS_CHUNK % PS_LANES == 0 && PS_LANES % PS_AHEAD == 0, "packing and accumulator layout");
 
 __global__ __launch_bounds__(PS_THREADS) void ps_score_kernel(const float* __restrict__ pts, const float* __restrict__ pc,
@@ -195,9 +193,9 @@ extern "C" int cmr_pose_score_f32(const float* pts, const float* pc_feat, const 
                                   double* score, int32_t* counts, int32_t* selected, void* workspace, int64_t workspace_bytes,
                                   hipStream_t stream) {
   CMR_REQUIRE(pts && pc_feat && img_feat && mask && poses && K && score && counts && selected && workspace);
-  CMR_REQUIRE(C == PS_C && cmr_cloud_map_ok(B, N, h, w) && P > 0 && P <= PS_MAX_POSES);
+  CMR_REQUIRE(C == PS_C && cmr_cloud_map_ok(B, N, h, w) && P > 0 && P <= CMR_MAX_POSES);
   CMR_REQUIRE(mask_bytes == 1 || mask_bytes == 8);
-  CMR_REQUIRE(radius >= 0 && radius <= PS_MAX_RADIUS && tau > 0.f && __builtin_isfinite(tau));
+  CMR_REQUIRE(radius >= 0 && radius <= CMR_MAX_RADIUS && tau > 0.f && __builtin_isfinite(tau));
   CMR_REQUIRE(cmr_aligned16(pc_feat) && cmr_aligned16(img_feat) && cmr_aligned16(workspace));
   CMR_REQUIRE(workspace_bytes >= cmr_pose_score_workspace_bytes(B, N, P));
   const int nslice = (N + PS_SLICE - 1) / PS_SLICE, nchunk = (P + PS_CHUNK - 1) / PS_CHUNK;

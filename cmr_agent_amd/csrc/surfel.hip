@@ -4,39 +4,32 @@
 // cmr_project.h's (so the centre's cell and "in view" agree bit for bit with guided match, visibility, paint and render); the per-pixel
 // part is plain fp32 operators under fp contract(off), each rounded on its own, so a numpy float32 restatement gives the same bits.
 //
-// cmr_render_surfels_f32 -- three launches on the caller's stream, no memset node, whatever the data:
-//   sf_fill_kernel     key map = all ones (16-byte stores), counts[b] = (0, 0, 0, status of K[b]).
+// cmr_render_surfels_f32 -- three launches on the caller's stream, no memset node, whatever the data.  The key, its fill, its decode and
+// the attribute gather are cmr_zbuffer.h's, shared with point_image.hip:
+//   sf_fill_kernel     key map = empty (cmr_zfill), counts[b] = (0, 0, 0, status of K[b]).
 //   sf_splat_kernel    256 rows per workgroup in two phases.  Setup, one thread per row (coalesced loads, pose and K wave-uniform): the
 //                      projection, X_c, n_c, r, the drawn predicate and the window the row walks, left in LDS (11 words per row); the
 //                      `surfel` planes are stored here, coalesced; counts (selected, drawn) by one atomic per workgroup and word.
 //                      Walk, one 16-lane group per row (16 groups, 16 rows each in turn): the window a line at a time, the lanes over the
-//                      columns, so a wide footprint and a narrow one keep 16 lanes busy alike.  A covered pixel lowers the 64-bit key
-//                      (bits of tau) << 32 | n of its cell with ONE unsigned 64-bit vector atomic min -- after an L2-served load
+//                      columns, so a wide footprint and a narrow one keep 16 lanes busy alike.  A covered pixel lowers the key
+//                      cmr_zkey(tau, n) of its cell with ONE unsigned 64-bit vector atomic min -- after an L2-served load
 //                      of the cell that skips the atomic when the stored key is already lower (keys only fall, so a stale value costs an
 //                      atomic and never a result).  Why the skip: an atomic drops the line from the XCD's L2 and is one request per
 //                      lane at the memory side; where discs overlap (a wall seen by several rings) most candidates lose, and the load
 //                      keeps the line.  Not measured against unconditional atomics.
-//   sf_resolve_kernel  one thread per pixel: index / depth / attribute maps as coalesced stores; the owner's normal is recomputed from
-//                      pts and normals (two gathers of three) for normal_map; attr[b, c, owner] is gathered SF_PLANES planes at a time.
-//                      counts[2] by one atomic per workgroup.
-// cmr_depth_test_f32 -- two launches: sf_zero_kernel (counts = 0) and sf_test_kernel, visibility.hip's test with the projection in
-//   front of it: SFT_LANES = 4 lanes per row walk the (2r + 1)^2 window a line at a time with wave-uniform bounds, the four partial
-//   minima meet over two quad-permute DPP moves, bound = zmin * opr + abs_tol with two roundings.
+//   sf_resolve_kernel  one thread per pixel: cmr_zresolve (index / depth maps), then the owner's normal, recomputed from pts and normals
+//                      (two gathers of three) for normal_map, then cmr_zgather (attribute map).  counts[2] by one atomic per workgroup.
+// cmr_depth_test_f32 -- two launches: cmr_zero_kernel (counts = 0, cmr_common.h) and sf_test_kernel: the projection, then cmr_ztest_row,
+//   the test visibility.hip runs on the cell and depth it stored.
 // No floating-point atomic anywhere; every output element is a plain store by the thread that owns it.  No scratch.
-#include "cmr_sample.h"
+#include "cmr_zbuffer.h"
 
 namespace {
 
 constexpr int SF_THREADS = 256;
 constexpr int SF_LANES = 16;                       // lanes per surfel in the walk
 constexpr int SF_GROUPS = SF_THREADS / SF_LANES;   // surfels walked together per workgroup
-constexpr int SF_MAX_PX = 16;                      // guided_match.hip GM_MAX_RADIUS
-constexpr int SF_MAX_C = 64;
-constexpr int SF_PLANES = 4;                       // attribute planes whose gathers are in flight together
-constexpr int SFT_LANES = 4;                       // lanes per row in the depth test: one DPP quad
-constexpr int SFT_ROWS = SF_THREADS / SFT_LANES;
-constexpr int SFT_AHEAD = 4;
-constexpr unsigned long long SF_EMPTY = ~0ull;
+constexpr int SFT_ROWS = SF_THREADS / CMR_ZT_LANES; // rows per workgroup in the depth test
 
 // The camera model the per-pixel part assumes: K = [[fx, s, cx], [0, fy, cy], [0, 0, 1]] with fx, fy finite and > 0.
 __device__ __forceinline__ bool sf_camera_ok(const float* K) {
@@ -80,15 +73,8 @@ __device__ __forceinline__ bool sf_ray(const SfDisc& d, float fx, float s, float
 __global__ __launch_bounds__(SF_THREADS) void sf_fill_kernel(unsigned long long* __restrict__ keys, int64_t cells,
                                                              const float* __restrict__ Kin, int B, int32_t* __restrict__ counts) {
   const int64_t i = (int64_t)blockIdx.x * SF_THREADS + threadIdx.x, stride = (int64_t)gridDim.x * SF_THREADS;
-  const int64_t nvec = cells >> 1;
-  ulonglong2* kv = reinterpret_cast<ulonglong2*>(keys);                  // the workspace is 16-byte aligned
-  for (int64_t v = i; v < nvec; v += stride) kv[v] = make_ulonglong2(SF_EMPTY, SF_EMPTY);
-  if (i == 0 && (cells & 1)) keys[cells - 1] = SF_EMPTY;
+  cmr_zfill(keys, cells, i, stride);
   for (int64_t c = i; c < 4 * (int64_t)B; c += stride) counts[c] = (c & 3) == 3 ? (sf_camera_ok(Kin + 9 * (c >> 2)) ? 0 : 1) : 0;
-}
-
-__global__ __launch_bounds__(SF_THREADS) void sf_zero_kernel(int32_t* __restrict__ counts, int ncounts) {
-  for (int c = blockIdx.x * SF_THREADS + threadIdx.x; c < ncounts; c += gridDim.x * SF_THREADS) counts[c] = 0;
 }
 
 __global__ __launch_bounds__(SF_THREADS) void sf_splat_kernel(const float* __restrict__ pts, const float* __restrict__ normals,
@@ -171,7 +157,7 @@ __global__ __launch_bounds__(SF_THREADS) void sf_splat_kernel(const float* __res
       for (int x = wx0 + j; x <= wx1; x += SF_LANES) {
         float tau;
         if (sf_ray(d, fx, s, cx, fy, cy, (float)x, (float)y, tau)) {
-          const unsigned long long key = ((unsigned long long)__builtin_bit_cast(unsigned, tau) << 32) | row;
+          const unsigned long long key = cmr_zkey(tau, row);
           unsigned long long* cell = kb + (y * w + x);                   // y * w + x < h * w <= 2^24
           if (__hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > key) atomicMin(cell, key);
         }
@@ -191,16 +177,11 @@ __global__ __launch_bounds__(SF_THREADS) void sf_resolve_kernel(const unsigned l
   const int i = blockIdx.x * SF_THREADS + threadIdx.x;
   const bool valid = i < cells;
   const unsigned long long best = keys[(int64_t)b * cells + (valid ? i : cells - 1)];
-  const bool owned = valid && best != SF_EMPTY;
-  const int owner = owned ? (int)(unsigned)(best & 0xffffffffull) : -1;
-  if (valid) {
-    const int64_t o = (int64_t)b * cells + i;
-    index_map[o] = owner;
-    depth_map[o] = owned ? __builtin_bit_cast(float, (unsigned)(best >> 32)) : __builtin_huge_valf();
-  }
+  const bool owned = cmr_zresolve(best, valid, b, i, cells, index_map, depth_map);
   if (normal_map) {
     float m0 = 0.f, m1 = 0.f, m2 = 0.f;
     if (owned) {
+      const int owner = cmr_zowner(best);
       const float* x = pts + (int64_t)b * 3 * N;
       const float* nr = normals + (int64_t)b * 3 * N;
       const float* P = pose + 16 * b;
@@ -222,24 +203,7 @@ __global__ __launch_bounds__(SF_THREADS) void sf_resolve_kernel(const unsigned l
       nm[0] = m0; nm[cells] = m1; nm[2 * (int64_t)cells] = m2;
     }
   }
-  if (attr_map) {
-    const float* ab = attr + (int64_t)b * C * N;
-    float* ob = attr_map + (int64_t)b * C * cells;
-    for (int c = 0; c < C; c += SF_PLANES) {                             // wave-uniform
-      float val[SF_PLANES];
-#pragma unroll
-      for (int k = 0; k < SF_PLANES; ++k) val[k] = fill;
-      if (owned) {
-#pragma unroll
-        for (int k = 0; k < SF_PLANES; ++k) val[k] = ab[(int64_t)(c + k < C ? c + k : C - 1) * N + owner];
-      }
-      if (valid) {
-#pragma unroll
-        for (int k = 0; k < SF_PLANES; ++k)
-          if (c + k < C) ob[(int64_t)(c + k) * cells + i] = val[k];
-      }
-    }
-  }
+  cmr_zgather(best, owned, valid, b, i, cells, attr, C, N, fill, attr_map);
   const bool flag[1] = {owned};
   int cnt[1];
   cmr_block_counts<1, SF_THREADS>(flag, part, cnt);
@@ -250,8 +214,7 @@ __global__ __launch_bounds__(SF_THREADS) void sf_test_kernel(const float* __rest
                                                              const float* __restrict__ pose, const float* __restrict__ Kin,
                                                              const float* __restrict__ Z, int N, int h, int w, int radius, float opr,
                                                              float abs_tol, uint8_t* __restrict__ visible, int32_t* __restrict__ counts) {
-  __shared__ int part[3][SF_THREADS / 64];
-  const int b = blockIdx.y, j = threadIdx.x & (SFT_LANES - 1);
+  const int b = blockIdx.y;
   const int64_t n = (int64_t)blockIdx.x * SFT_ROWS + (threadIdx.x >> 2);
   const int64_t g = (int64_t)b * N + n;
   const bool valid = n < N;
@@ -263,46 +226,13 @@ __global__ __launch_bounds__(SF_THREADS) void sf_test_kernel(const float* __rest
     c = p.cell;
     z = p.z;
   }
-  const bool active = c >= 0;                                            // selected and in view
-  const int cx = active ? c % w : 0, cy = active ? c / w : 0;
-  const float* Zb = Z + (int64_t)b * h * w;
-  const float inf = __builtin_huge_valf();
-  float zmin = inf;
-  if (__ballot(active)) {                                                // wave-uniform: EXEC stays full inside
-    const int nch = (2 * radius + 1 + SFT_LANES - 1) / SFT_LANES, total = (2 * radius + 1) * nch;
-    int dy = -radius, ch = 0;                                            // wave-uniform
-    for (int k = 0; k < total; k += SFT_AHEAD) {
-      float f[SFT_AHEAD];
-      bool in[SFT_AHEAD];
-#pragma unroll
-      for (int u = 0; u < SFT_AHEAD; ++u) {
-        const int dx = -radius + ch * SFT_LANES + j;
-        const int x = cx + dx, y = cy + dy;                              // past the end of the run dy = r + 1: dropped by k + u < total
-        in[u] = k + u < total && dx <= radius && x >= 0 && x < w && y >= 0 && y < h;
-        f[u] = Zb[cmr_clampi(y, h - 1) * w + cmr_clampi(x, w - 1)];
-        if (++ch == nch) { ch = 0; ++dy; }
-      }
-#pragma unroll
-      for (int u = 0; u < SFT_AHEAD; ++u) zmin = fminf(zmin, in[u] ? f[u] : inf);      // fminf drops a NaN cell
-    }
-  }
-  zmin = fminf(zmin, cmr_fdpp<0xB1>(zmin));                               // quad_perm:[1,0,3,2]; outside every branch
-  zmin = fminf(zmin, cmr_fdpp<0x4E>(zmin));                               // quad_perm:[2,3,0,1]
-  const float bound = cmr_mul_add_rn(zmin, opr, abs_tol);                // two roundings, never one fma
-  const bool vis = active && z <= bound;
-  const bool first = j == 0;
-  if (valid && first) visible[g] = vis ? 1 : 0;
-  const bool flag[3] = {sel && first, active && first, vis && first};
-  int cnt[3];
-  cmr_block_counts<3, SF_THREADS>(flag, part, cnt);
-  if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(&counts[3 * b + threadIdx.x], cnt[threadIdx.x]);
+  cmr_ztest_row<SF_THREADS, 3>(Z, b, h, w, radius, opr, abs_tol, valid, sel, c, z, g, visible, counts);
 }
 
 }  // namespace
 
 extern "C" int64_t cmr_render_surfels_workspace_bytes(int B, int h, int w) {
-  if (B <= 0 || h <= 0 || w <= 0) return 0;
-  return cmr_up16((int64_t)B * h * w * 8);
+  return cmr_zkeys_bytes(B, h, w);
 }
 
 extern "C" int cmr_render_surfels_f32(const float* pts, const float* normals, const void* mask, int mask_bytes, const float* pose,
@@ -311,10 +241,10 @@ extern "C" int cmr_render_surfels_f32(const float* pts, const float* normals, co
                                       float* attr_map, int32_t* counts, float* surfel, void* workspace, int64_t workspace_bytes,
                                       hipStream_t stream) {
   CMR_REQUIRE(pts && normals && pose && K && index_map && depth_map && counts && workspace);
-  CMR_REQUIRE(cmr_cloud_map_ok(B, N, h, w) && (mask_bytes == 1 || mask_bytes == 8) && max_px >= 0 && max_px <= SF_MAX_PX);
+  CMR_REQUIRE(cmr_cloud_map_ok(B, N, h, w) && cmr_mask_bytes_ok(mask_bytes) && max_px >= 0 && max_px <= CMR_MAX_RADIUS);
   CMR_REQUIRE(__builtin_isfinite(radius) && radius >= 0.f && __builtin_isfinite(range_slope) && range_slope >= 0.f);
   CMR_REQUIRE(min_cos >= 0.f && min_cos <= 1.f);
-  CMR_REQUIRE((attr == nullptr) == (attr_map == nullptr) && (attr ? (C >= 1 && C <= SF_MAX_C) : C == 0));
+  CMR_REQUIRE(cmr_attr_ok(attr, attr_map, C));
   CMR_REQUIRE(cmr_aligned16(workspace) && workspace_bytes >= cmr_render_surfels_workspace_bytes(B, h, w));
   unsigned long long* keys = (unsigned long long*)workspace;
   const int64_t cells = (int64_t)B * h * w;
@@ -332,12 +262,12 @@ extern "C" int cmr_depth_test_f32(const float* pts, const void* mask, int mask_b
                                   int N, int h, int w, int radius, float rel_tol, float abs_tol, uint8_t* visible, int32_t* counts,
                                   hipStream_t stream) {
   CMR_REQUIRE(pts && mask && pose && K && Z && visible && counts);
-  CMR_REQUIRE(cmr_cloud_map_ok(B, N, h, w) && (mask_bytes == 1 || mask_bytes == 8));
-  CMR_REQUIRE(radius >= 0 && radius <= SF_MAX_PX);
-  CMR_REQUIRE(rel_tol >= 0.f && abs_tol >= 0.f && __builtin_isfinite(rel_tol) && __builtin_isfinite(abs_tol));
-  CMR_REQUIRE((reinterpret_cast<uintptr_t>(Z) & 3u) == 0);
-  const float opr = (float)(1.0 + (double)rel_tol);
-  hipLaunchKernelGGL(sf_zero_kernel, dim3(1), dim3(SF_THREADS), 0, stream, counts, 3 * B);
+  CMR_REQUIRE(cmr_cloud_map_ok(B, N, h, w) && cmr_mask_bytes_ok(mask_bytes));
+  CMR_REQUIRE(radius >= 0 && radius <= CMR_MAX_RADIUS);
+  CMR_REQUIRE(cmr_tols_ok(rel_tol, abs_tol));
+  CMR_REQUIRE(cmr_aligned4(Z));
+  const float opr = cmr_one_plus(rel_tol);
+  hipLaunchKernelGGL(cmr_zero_kernel<SF_THREADS>, dim3(1), dim3(SF_THREADS), 0, stream, counts, 3 * B);
   hipLaunchKernelGGL(sf_test_kernel, dim3((N + SFT_ROWS - 1) / SFT_ROWS, B), dim3(SF_THREADS), 0, stream, pts, mask, mask_bytes, pose, K, Z, N,
                      h, w, radius, opr, abs_tol, visible, counts);
   return cmr_launch_status();

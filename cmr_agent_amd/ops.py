@@ -1056,6 +1056,23 @@ def _row_mask(who, name, m, n, or_none=False):
     return m.view(torch.uint8) if m.dtype == torch.bool else m
 
 
+def _depth_test_args(who, radius, rel_tol, abs_tol):
+    """The window and the two tolerances of the depth test (visibility, depth_test), as the entry takes them"""
+    _int_arg(who, "radius", radius, 0, GUIDED_MAX_RADIUS)
+    _f32_arg(who, "rel_tol", rel_tol, "be finite and >= 0")
+    _f32_arg(who, "abs_tol", abs_tol, "be finite and >= 0")
+    return int(radius), float(rel_tol), float(abs_tol)
+
+
+def _render_maps(B, C, h, w, dev, workspace_bytes):
+    """render_points' and render_surfels' index_map, depth_map, attr_map (None at C = 0) and key-map workspace with its size, by that export"""
+    index_map = torch.empty((B, h, w), dtype=torch.int32, device=dev)
+    depth_map = torch.empty((B, h, w), dtype=f32, device=dev)
+    attr_map = torch.empty((B, C, h, w), dtype=f32, device=dev) if C else None
+    nb = getattr(_lib.load(), workspace_bytes)(B, h, w)
+    return index_map, depth_map, attr_map, _ws(nb, dev), nb
+
+
 def _gt_xy_arg(who, gt_xy, B, N):
     if gt_xy is not None and (not torch.is_tensor(gt_xy) or gt_xy.dtype != f32 or tuple(gt_xy.shape) != (B, 2, N)):
         raise ValueError("%s: gt_xy must be float32 [%d, 2, %d], got %s %s" % ((who, B, N) + _got(gt_xy)))
@@ -1202,7 +1219,7 @@ def pnp_ransac(pts, uv, mask, K, n_hyp=1024, thr=1.0, seed=0, refine_iters=10, w
     return (pose, inliers, status, hyp) if want_hyp_inliers else (pose, inliers, status)
 
 
-GUIDED_MAX_RADIUS = 16      # csrc/guided_match.hip GM_MAX_RADIUS
+GUIDED_MAX_RADIUS = 16      # csrc/cmr_project.h CMR_MAX_RADIUS: every window radius below
 
 
 def guided_match(pts, pc_feat_rows, img_feat_nhwc, mask, pose, K, radius, max_dist=0.0, gt_xy=None, thr=3.0, want_dist=False,
@@ -1239,7 +1256,7 @@ def guided_match(pts, pc_feat_rows, img_feat_nhwc, mask, pose, K, radius, max_di
     return idx, keep.view(torch.bool), counts, dist, proj
 
 
-POSE_SCORE_MAX_POSES = 4096  # csrc/pose_score.hip PS_MAX_POSES
+POSE_SCORE_MAX_POSES = 4096  # csrc/cmr_project.h CMR_MAX_POSES
 
 
 def pose_score(pts, pc_feat_rows, img_feat_nhwc, mask, poses, K, radius=0, tau=0.8):
@@ -1293,9 +1310,7 @@ def visibility(pts, pose, K, h, w, mask, occ_mask=None, radius=1, rel_tol=0.05, 
     B, N, h, w = _camera_args(who, pts, pose, K, h, w, "map", "float32")
     mask = _row_mask(who, "mask", mask, B * N)
     occ_mask = None if occ_mask is None else _row_mask(who, "occ_mask", occ_mask, B * N)
-    _int_arg(who, "radius", radius, 0, GUIDED_MAX_RADIUS)
-    _f32_arg(who, "rel_tol", rel_tol, "be finite and >= 0")
-    _f32_arg(who, "abs_tol", abs_tol, "be finite and >= 0")
+    radius, rel_tol, abs_tol = _depth_test_args(who, radius, rel_tol, abs_tol)
     _on_one_gpu(who, pts, pose, K, mask, occ_mask)
     dev = pts.device
     visible = torch.empty((B * N,), dtype=torch.uint8, device=dev)
@@ -1306,12 +1321,12 @@ def visibility(pts, pose, K, h, w, mask, occ_mask=None, radius=1, rel_tol=0.05, 
     nb = _lib.load().cmr_visibility_workspace_bytes(B, N, h, w)
     ws = _ws(nb, dev)
     _lib.call("cmr_visibility_f32", _p(pts), _p(mask), mask.element_size(), _p(occ_mask), 1 if occ_mask is None else occ_mask.element_size(),
-              _p(pose), _p(K), B, N, h, w, int(radius), float(rel_tol), float(abs_tol), _p(visible), _p(counts), _p(depth_map), _p(cell),
+              _p(pose), _p(K), B, N, h, w, radius, rel_tol, abs_tol, _p(visible), _p(counts), _p(depth_map), _p(cell),
               _p(depth), _p(ws), nb, _stream())
     return visible.view(torch.bool), counts, depth_map, cell, depth
 
 
-POINT_IMAGE_MAX_C = 64      # csrc/point_image.hip PI_MAX_C
+POINT_IMAGE_MAX_C = 64      # csrc/cmr_project.h CMR_MAX_PLANES
 RENDER_MAX_SPLAT = 4        # csrc/point_image.hip PI_MAX_SPLAT
 _PAINT_MODES = {"nearest": 0, "bilinear": 1}
 
@@ -1376,19 +1391,14 @@ def render_points(pts, pose, K, h, w, attr=None, mask=None, splat=0, fill=0.0):
     _int_arg(who, "splat", splat, 0, RENDER_MAX_SPLAT)
     fill = _f32_arg(who, "fill", fill, "be a number", lo=None)
     _on_one_gpu(who, pts, pose, K, attr, mask)
-    dev = pts.device
-    index_map = torch.empty((B, h, w), dtype=torch.int32, device=dev)
-    depth_map = torch.empty((B, h, w), dtype=f32, device=dev)
-    attr_map = torch.empty((B, C, h, w), dtype=f32, device=dev) if attr is not None else None
-    counts = torch.empty((B, 3), dtype=torch.int32, device=dev)
-    nb = _lib.load().cmr_render_points_workspace_bytes(B, h, w)
-    ws = _ws(nb, dev)
+    index_map, depth_map, attr_map, ws, nb = _render_maps(B, C, h, w, pts.device, "cmr_render_points_workspace_bytes")
+    counts = torch.empty((B, 3), dtype=torch.int32, device=pts.device)
     _lib.call("cmr_render_points_f32", _p(pts), _p(mask), 1 if mask is None else mask.element_size(), _p(pose), _p(K), _p(attr), C, B, N, h, w,
               int(splat), fill, _p(index_map), _p(depth_map), _p(attr_map), _p(counts), _p(ws), nb, _stream())
     return index_map, depth_map, attr_map, counts
 
 
-SURFEL_MAX_PX = 16          # csrc/surfel.hip SF_MAX_PX
+SURFEL_MAX_PX = 16          # csrc/cmr_project.h CMR_MAX_RADIUS
 
 
 def render_surfels(pts, normals, pose, K, h, w, radius=0.1, range_slope=0.004, max_px=8, min_cos=0.1, attr=None, mask=None, fill=0.0,
@@ -1421,14 +1431,10 @@ def render_surfels(pts, normals, pose, K, h, w, radius=0.1, range_slope=0.004, m
     fill = _f32_arg(who, "fill", fill, "be a number", lo=None)
     _on_one_gpu(who, pts, normals, pose, K, attr, mask)
     dev = pts.device
-    index_map = torch.empty((B, h, w), dtype=torch.int32, device=dev)
-    depth_map = torch.empty((B, h, w), dtype=f32, device=dev)
-    attr_map = torch.empty((B, C, h, w), dtype=f32, device=dev) if attr is not None else None
+    index_map, depth_map, attr_map, ws, nb = _render_maps(B, C, h, w, dev, "cmr_render_surfels_workspace_bytes")
     normal_map = torch.empty((B, 3, h, w), dtype=f32, device=dev) if want_normal_map else None
     surfel = torch.empty((B, 8, N), dtype=f32, device=dev) if want_surfel else None
     counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
-    nb = _lib.load().cmr_render_surfels_workspace_bytes(B, h, w)
-    ws = _ws(nb, dev)
     _lib.call("cmr_render_surfels_f32", _p(pts), _p(normals), _p(mask), 1 if mask is None else mask.element_size(), _p(pose), _p(K), _p(attr),
               C, B, N, h, w, radius, range_slope, int(max_px), min_cos, fill, _p(index_map), _p(depth_map), _p(normal_map), _p(attr_map),
               _p(counts), _p(surfel), _p(ws), nb, _stream())
@@ -1453,15 +1459,13 @@ def depth_test(pts, pose, K, depth_map, mask, radius=0, rel_tol=0.05, abs_tol=0.
     mask = _row_mask("depth_test", "mask", mask, B * N, or_none=True)
     if Bd != B:
         raise ValueError("depth_test: depth_map must be float32 [%d, h, w], got %s" % (B, tuple(depth_map.shape)))
-    _int_arg("depth_test", "radius", radius, 0, GUIDED_MAX_RADIUS)
-    _f32_arg("depth_test", "rel_tol", rel_tol, "be finite and >= 0")
-    _f32_arg("depth_test", "abs_tol", abs_tol, "be finite and >= 0")
+    radius, rel_tol, abs_tol = _depth_test_args("depth_test", radius, rel_tol, abs_tol)
     _on_one_gpu("depth_test", pts, pose, K, depth_map, mask)
     dev = pts.device
     visible = torch.empty((B * N,), dtype=torch.uint8, device=dev)
     counts = torch.empty((B, 3), dtype=torch.int32, device=dev)
-    _lib.call("cmr_depth_test_f32", _p(pts), _p(mask), mask.element_size(), _p(pose), _p(K), _p(depth_map), B, N, h, w, int(radius),
-              float(rel_tol), float(abs_tol), _p(visible), _p(counts), _stream())
+    _lib.call("cmr_depth_test_f32", _p(pts), _p(mask), mask.element_size(), _p(pose), _p(K), _p(depth_map), B, N, h, w, radius, rel_tol,
+              abs_tol, _p(visible), _p(counts), _stream())
     return visible.view(torch.bool), counts
 
 
@@ -1531,7 +1535,7 @@ def pose_mi(pts, attr, grey, mask, poses, K, bins=32, mode='nearest', attr_range
     return mi, entropy, counts, selected, hist if want_hist else None
 
 
-DENSIFY_MAX_RADIUS = 16     # csrc/densify.hip DN_MAX_R
+DENSIFY_MAX_RADIUS = 16     # csrc/cmr_project.h CMR_MAX_RADIUS
 DENSIFY_MAX_C = 4           # csrc/densify.hip DN_MAX_C: attribute planes, and guide planes
 DENSIFY_TILE_W = 64         # csrc/densify.hip DN_TW x DN_TH: the pixels of one workgroup (tests put their shapes round these)
 DENSIFY_TILE_H = 16

@@ -90,8 +90,9 @@ def _touched(*a, **kw):
 def test_constants():
     assert ops.DENSIFY_MAX_RADIUS == 16 and ops.DENSIFY_MAX_C == 4 and ops.DENSIFY_TILE_W == 64 and ops.DENSIFY_TILE_H == 16
     src = open(os.path.join(ROOT, "cmr_agent_amd", "csrc", "densify.hip")).read()
-    for text in ("DN_MAX_R = 16", "DN_MAX_C = 4", "DN_TW = 64", "DN_TH = 16", "cmr_densify_f32"):
+    for text in ("radius <= CMR_MAX_RADIUS", "DN_MAX_C = 4", "DN_TW = 64", "DN_TH = 16", "cmr_densify_f32"):
         assert text in src
+    assert "constexpr int CMR_MAX_RADIUS = 16;" in open(os.path.join(ROOT, "cmr_agent_amd", "csrc", "cmr_project.h")).read()
     assert "not tuned on real data" in " ".join(ops.densify.__doc__.split()) and "NOT checked" in ops.densify.__doc__
     protos = _lib.parse_header()
     assert protos["cmr_densify_f32"][2] == ["depth", "attr", "C", "guide", "Cg", "B", "h", "w", "radius", "sigma_s", "sigma_r", "min_weight", "keep",

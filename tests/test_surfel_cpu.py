@@ -150,8 +150,12 @@ def _touched(*a, **kw):
 def test_constants_and_prototypes():
     assert ops.SURFEL_MAX_PX == 16
     src = open(os.path.join(ROOT, "cmr_agent_amd", "csrc", "surfel.hip")).read()
-    for text in ("SF_MAX_PX = 16", "SF_MAX_C = 64", "cmr_render_surfels_f32", "cmr_depth_test_f32", "fp contract(off)"):
+    for text in ("max_px <= CMR_MAX_RADIUS", "cmr_attr_ok(attr, attr_map, C)", "cmr_render_surfels_f32", "cmr_depth_test_f32", "fp contract(off)"):
         assert text in src
+    csrc = os.path.join(ROOT, "cmr_agent_amd", "csrc")
+    assert "constexpr int CMR_MAX_RADIUS = 16;" in open(os.path.join(csrc, "cmr_project.h")).read()      # the limits' one definition
+    assert "constexpr int CMR_MAX_PLANES = 64;" in open(os.path.join(csrc, "cmr_project.h")).read()
+    assert "C <= CMR_MAX_PLANES" in open(os.path.join(csrc, "cmr_zbuffer.h")).read() and ops.POINT_IMAGE_MAX_C == 64
     assert "atomicAdd(float" not in src and "atomicAdd((float" not in src
     for fn in (ops.render_surfels, ops.depth_test):
         assert "not tuned on real data" in " ".join(fn.__doc__.split())

@@ -285,6 +285,52 @@ def test_depth_test_on_visibilitys_own_map_gives_its_flags(name, radius):
         assert torch.equal(got64, vis) and torch.equal(gcounts64, counts[:, :3])
 
 
+# include/cmr_hip.h, cmr_depth_test_f32: "a NaN cell is ignored".  Two 5 x 7 maps and eight rows each, placed by hand: K and the pose are
+# identities, so the row (x z, y z, z) lands on the cell (x, y) at depth z exactly; every depth is dyadic and both tolerances are 0, so a
+# row in view is visible iff z <= the least cell of its window that is not NaN.  (x, y, z, queried, the flag expected at radius (0, 2)).
+_NAN_ROWS = [
+    [(1, 2, 4.0, True, (True, True)),        # A: its own cell holds 4; the only other cells of its window that hold anything hold NaN
+     (0, 0, 4.0, True, (True, True)),        # B: its own cell is NaN; A's 4 is in its window at radius 2, and is not nearer
+     (6, 4, 4.0, True, (True, False)),       # C: the 2 at (4, 4) stands next to the NaN at (5, 4), two columns to its left
+     (6, 0, 4.0, True, (False, False)),      # D: its own cell holds 2, the NaN at (5, 0) beside it changes nothing
+     (1, 1, -4.0, True, (False, False)),     # behind the camera
+     (9, 2, 4.0, True, (False, False)),      # beside the map
+     (1, 2, 1.0, False, (False, False)),     # not queried
+     (4, 4, 1.0, True, (True, True))],       # L: nearer than the 2 of its own cell
+    [(3, 2, 4.0, True, (True, False)),       # E: the 2 at (5, 2) is the LAST column of its window: lane 0 of the second lane chunk
+     (2, 2, 4.0, True, (True, True)),        # F: the same 2 is one column past its window: lane 1 of that chunk, cut by dx <= radius
+     (1, 0, 4.0, True, (True, True)),        # G: the NaN at (3, 0) in the last column of its window
+     (3, 2, 1.0, False, (False, False)),     # not queried
+     (0, 4, 4.0, True, (True, True)),        # M: NaN right of it and above it, nothing else
+     (5, 2, 2.0, True, (True, True)),        # P: as deep as its own cell
+     (5, 2, 2.5, True, (False, False)),      # Q: behind its own cell, the NaN at (6, 2) beside it
+     (2, 2, -4.0, True, (False, False))]]    # behind the camera
+_NAN_CELLS = [{(1, 2): 4.0, (4, 4): 2.0, (6, 0): 2.0, (2, 2): math.nan, (2, 3): math.nan, (0, 0): math.nan, (5, 4): math.nan, (5, 0): math.nan},
+              {(5, 2): 2.0, (6, 2): math.nan, (3, 0): math.nan, (1, 4): math.nan, (0, 3): math.nan}]      # (x, y): value; +inf elsewhere
+
+
+@pytest.mark.parametrize("mask_dtype", [torch.bool, torch.int64])
+@pytest.mark.parametrize("radius", [0, 2])
+def test_depth_test_ignores_nan_cells(radius, mask_dtype):
+    h, w = 5, 7
+    pts = F([[[x * z for x, _, z, _, _ in rows], [y * z for _, y, z, _, _ in rows], [z for _, _, z, _, _ in rows]] for rows in _NAN_ROWS])
+    mask = torch.tensor([[s for _, _, _, s, _ in rows] for rows in _NAN_ROWS]).to(DEV).to(mask_dtype)
+    pose, K = torch.eye(4, device=DEV).repeat(2, 1, 1), torch.eye(3, device=DEV).repeat(2, 1, 1)
+    planted = torch.full((2, h, w), INF)
+    for b, cells in enumerate(_NAN_CELLS):
+        for (x, y), v in cells.items():
+            planted[b, y, x] = v
+    assert int(torch.isnan(planted).sum()) == 9
+    vis, counts = ops.depth_test(pts, pose, K, planted.to(DEV), mask, radius=radius, rel_tol=0.0, abs_tol=0.0)
+    emptied, ecounts = ops.depth_test(pts, pose, K, torch.nan_to_num(planted, nan=INF, posinf=INF).to(DEV), mask, radius=radius, rel_tol=0.0,
+                                      abs_tol=0.0)
+    print("radius", radius, "visible", vis.view(2, -1).int().tolist(), "counts", counts.tolist())
+    assert torch.equal(vis, emptied) and torch.equal(counts, ecounts)                                   # (a) NaN = empty
+    want = torch.tensor([[e[radius // 2] for _, _, _, _, e in rows] for rows in _NAN_ROWS])
+    assert vis.dtype == torch.bool and torch.equal(vis.cpu().view(2, -1), want)                         # (b), (c): by hand, row by row
+    assert counts.cpu().tolist() == [[7, 5, int(want[0].sum())], [7, 6, int(want[1].sum())]]
+
+
 # ---- 3. against float64 ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", [s[0] for s in vr.SCENES])
 def test_against_float64(name):
