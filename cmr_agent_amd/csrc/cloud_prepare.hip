@@ -4,35 +4,19 @@
 //   cmr_voxel_keys_f32       one int64 key per row from its grid cell (the contract of include/cmr_hip.h, bit for bit)
 //   (the caller sorts the keys, stable: the rows of a cell become one run, in ascending input index)
 //   cmr_segment_heads_i64    runs of equal keys -> CSR offsets, counts, the int32 row order cmr_segment_reduce_f32 takes, the inverse map
+//   cmr_cloud_gather4_f32    the kept rows as float4 in key order: the rows of a grid index (ops.cloud_index; cloud_icp.hip searches them)
 //   cmr_point_normals_f32    fixed-radius neighbourhoods over the sorted cells, 3x3 covariance, its smallest eigenvector
 //
 // No float atomics anywhere: min / max and the integer counts are order free, every float sum runs in a fixed order.
-#include "cmr_common.h"
-
-#include <math.h>
+#include "cmr_cloud_grid.h"
 
 namespace {
 
-constexpr int CELL_BITS = 21;                                   // per axis; the key is cz << 42 | cy << 21 | cx
-constexpr int64_t CELL_MAX = ((int64_t)1 << CELL_BITS) - 1;
 constexpr int64_t KEY_DROPPED = INT64_MAX;                      // rows with a non-finite coordinate sort behind every cell
 constexpr int BOUNDS_BLOCKS = 256;                              // partial results of cmr_cloud_bounds_f32: 8 words each
 constexpr int SCAN_TILE = 1024;                                 // rows per workgroup of the head scan: 256 threads x 4
 
 __device__ __forceinline__ bool row_finite(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
-// (x - origin) / cell: one IEEE subtraction, one IEEE division (hipcc divides fp32 correctly rounded by default; nothing here can contract)
-__device__ __forceinline__ float cell_coord(float x, float origin, float cell) {
-#pragma clang fp contract(off)
-  const float d = x - origin;
-  return d / cell;
-}
-// the cell index; the host has checked the cloud's bounds, the clamp only keeps a key well formed whatever it is handed
-__device__ __forceinline__ int64_t cell_index(float x, float origin, float cell) {
-  const float c = floorf(cell_coord(x, origin, cell));
-  return c >= 0.f ? (c <= (float)CELL_MAX ? (int64_t)c : CELL_MAX) : 0;          // NaN -> 0
-}
-__device__ __forceinline__ int64_t pack_key(int64_t cx, int64_t cy, int64_t cz) { return cz << (2 * CELL_BITS) | cy << CELL_BITS | cx; }
 
 // ------------------------------------------------------------------------------------------------------------------------ bounds
 struct Bounds {
@@ -187,45 +171,6 @@ __global__ __launch_bounds__(256) void gather_points4_kernel(const float* __rest
   if (i >= kept) return;
   const float* p = pts + order[i] * ld;
   out[i] = f32x4{p[0], p[1], p[2], 0.f};
-}
-
-// the cells a query searches along one axis: its own and one to either side -- and a second one on the side whose face the query sits on to
-// within the rounding of cell_coord (a neighbour at distance radius there may round into the cell after next)
-__device__ __forceinline__ void axis_cells(float x, float origin, float cell, int& lo, int& hi) {
-  const float t = cell_coord(x, origin, cell);
-  const float c = floorf(t);
-  const float tol = (t + 2.f) * 9.5367431640625e-07f;           // 16 * 2^-24 (t + 2)
-  const float frac = t - c;
-  const int64_t ci = cell_index(x, origin, cell);
-  const int64_t l = ci - 1 - (frac < tol ? 1 : 0), h = ci + 1 + (frac > 1.f - tol ? 1 : 0);
-  lo = (int)(l < 0 ? 0 : l);
-  hi = (int)(h > CELL_MAX ? CELL_MAX : h);
-}
-// first index in keys[0, n) whose key is >= k (upper = false) or > k (upper = true)
-__device__ __forceinline__ int64_t key_bound(const int64_t* __restrict__ keys, int64_t n, int64_t k, bool upper) {
-  int64_t lo = 0;
-  while (n > 0) {
-    const int64_t half = n >> 1;
-    const int64_t v = keys[lo + half];
-    if (upper ? v <= k : v < k) {
-      lo += half + 1;
-      n -= half + 1;
-    } else {
-      n = half;
-    }
-  }
-  return lo;
-}
-__device__ __forceinline__ bool within(float dx, float dy, float dz, float r2) {
-#pragma clang fp contract(off)
-  return (dx * dx + dy * dy) + dz * dz <= r2;
-}
-__device__ __forceinline__ int isum16(int s) {
-  s += cmr_dpp<0xB1>(s);
-  s += cmr_dpp<0x4E>(s);
-  s += cmr_dpp<0x141>(s);
-  s += cmr_dpp<0x140>(s);
-  return s;
 }
 
 // one Jacobi rotation that clears a[p][q] of the symmetric 3x3 a (r is the third index); v collects the rotations in its columns
@@ -411,6 +356,12 @@ extern "C" int cmr_segment_heads_i64(const int64_t* keys_sorted, const int64_t* 
   hipLaunchKernelGGL(heads_write_kernel, dim3(blocks_of(inverse ? N : kept, SCAN_TILE)), dim3(256), 0, stream, keys_sorted, order,
                      inverse ? N : kept, kept, tile_sum, tiles, order32, offsets, inverse);
   hipLaunchKernelGGL(heads_count_rows_kernel, dim3(blocks_of(kept, 256)), dim3(256), 0, stream, offsets, nseg, count);
+  return cmr_launch_status();
+}
+
+extern "C" int cmr_cloud_gather4_f32(const float* points, int64_t ld, const int64_t* order, int64_t kept, float* points4, hipStream_t stream) {
+  CMR_REQUIRE(points && order && points4 && ld >= 3 && kept > 0 && kept < ((int64_t)1 << 31) && cmr_aligned16(points4));
+  hipLaunchKernelGGL(gather_points4_kernel, dim3(blocks_of(kept, 256)), dim3(256), 0, stream, points, ld, order, kept, (f32x4*)points4);
   return cmr_launch_status();
 }
 

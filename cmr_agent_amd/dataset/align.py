@@ -1,0 +1,133 @@
+"""Prepared clouds of a sequence -> the motion between consecutive scans, by point-to-plane ICP.
+
+    <root>/<data_velodyne>/sequences/<seq>/voxel0.1-SNr0.6/<i>.npy        float32 [7, n]: x, y, z, reflectance, nx, ny, nz   (read)
+
+Frame i + 1 (the source) is registered onto frame i (the target, with the normals `prepare` wrote into rows 4-6) by
+`ops.icp_point_to_plane` (HIP, csrc/cloud_icp.hip); the start pose of a pair is the previous pair's result -- a vehicle moves much like it
+did a scan ago -- and the identity for the first pair.  One line per pair:
+
+    pair <i> <i+1>: pairs <n> rmse <m> iterations <k> status <s> t <x y z> r <degrees>
+
+pairs and rmse are those of the last iteration (at the pose it started from), status is the op's (0 converged, 1 iterations exhausted,
+2 fewer than 6 pairs, 3 singular system), t and r are the translation in metres and the rotation angle of the pair's pose.  --out FILE
+writes the chained poses, 12 numbers per line (the upper 3 x 4, row-major, KITTI's layout): line j maps frame A + j into frame A, the first
+line is the identity, all in the velodyne frame.
+
+    python -m cmr_agent_amd.dataset.align --root DIR --sequence S [--frames A:B --max-dist 1.0 --huber 0.1 --iters 30 --out FILE]
+"""
+import argparse
+import math
+import os
+
+import numpy as np
+import torch
+
+from .. import ops
+from . import prepare
+
+
+def read_prepared(path):
+    """<i>.npy of a prepared folder -> float32 [7, n]; ValueError for anything else (a [4, n] file has no normals)."""
+    cloud = np.load(path)
+    if cloud.dtype != np.float32 or cloud.ndim != 2 or cloud.shape[0] != 7:
+        raise ValueError("%s: need float32 [7, n] (x, y, z, reflectance, nx, ny, nz), got %s %s" % (path, cloud.dtype, cloud.shape))
+    return cloud
+
+
+def register_pair(target7, source7, pose=None, max_dist=1.0, huber=0.1, iters=30, device=None):
+    """Two prepared clouds float32 [7, n] (numpy) -> ops.IcpResult of the source onto the target."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    rows = lambda a: torch.from_numpy(np.ascontiguousarray(a.T)).to(device)            # noqa: E731
+    return ops.icp_point_to_plane(rows(source7[0:3]), rows(target7[0:3]), rows(target7[4:7]), pose=pose, max_dist=max_dist, huber=huber,
+                                  iters=iters)
+
+
+def rotation_degrees(pose):
+    c = (float(pose[0, 0]) + float(pose[1, 1]) + float(pose[2, 2]) - 1.0) / 2.0
+    return math.degrees(math.acos(min(1.0, max(-1.0, c))))
+
+
+def align_sequence(files, max_dist=1.0, huber=0.1, iters=30, device=None, report=print):
+    """files: the prepared clouds of consecutive frames as (frame number, path).  -> float64 [len(files), 4, 4]: frame j in frame 0's
+    coordinates.  `report` receives one line per pair."""
+    chain = [np.eye(4)]
+    pose = None
+    target = read_prepared(files[0][1]) if files else None
+    for (i, _), (j, path) in zip(files[:-1], files[1:]):
+        source = read_prepared(path)
+        res = register_pair(target, source, pose, max_dist, huber, iters, device)
+        pose = res.pose
+        T = pose.cpu().numpy().astype(np.float64)
+        report("pair %d %d: pairs %d rmse %.4f iterations %d status %d t %.4f %.4f %.4f r %.4f" % (
+            i, j, res.pairs, res.rmse, res.iterations, res.status, T[0, 3], T[1, 3], T[2, 3], rotation_degrees(T)))
+        chain.append(chain[-1] @ T)
+        target = source
+    return np.stack(chain[:len(files)]) if files else np.zeros((0, 4, 4))
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m cmr_agent_amd.dataset.align", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--root", required=True, help="dataset root: <root>/<data_velodyne>/sequences/<seq>/<subdir>/*.npy is read")
+    ap.add_argument("--sequence", required=True, type=int, help="the sequence number")
+    ap.add_argument("--frames", default=":", help="A:B, the frames A <= i < B of the sequence (default: all of them)")
+    ap.add_argument("--data-velodyne", default=None, help="the velodyne folder under --root (default: the KITTI configuration's data_velodyne)")
+    ap.add_argument("--subdir", default=prepare.subdir(), help="the prepared folder of the sequence (default %s)" % prepare.subdir())
+    ap.add_argument("--max-dist", type=float, default=1.0, help="largest distance of a pair in metres, and the grid's cell (default 1.0)")
+    ap.add_argument("--huber", type=float, default=0.1, help="residuals above this many metres are down-weighted; 0 = off (default 0.1)")
+    ap.add_argument("--iters", type=int, default=30, help="most iterations per pair (default 30)")
+    ap.add_argument("--out", default=None, help="write the chained poses here, 12 numbers per line")
+    args = ap.parse_args(argv)
+    if not 0 <= args.sequence <= 99:
+        ap.error("--sequence must lie in [0, 99]")
+    if not (0.0 < args.max_dist < float("inf")):
+        ap.error("--max-dist must be finite and > 0, got %r" % (args.max_dist,))
+    if not (0.0 <= args.huber < float("inf")):
+        ap.error("--huber must be finite and >= 0, got %r" % (args.huber,))
+    if not 0 <= args.iters <= ops.ICP_MAX_ITERS:
+        ap.error("--iters must lie in [0, %d]" % ops.ICP_MAX_ITERS)
+    try:
+        a, b = args.frames.split(":")
+        args.frames = (int(a) if a else 0, int(b) if b else None)
+        if args.frames[0] < 0 or (args.frames[1] is not None and args.frames[1] < args.frames[0]):
+            raise ValueError
+    except ValueError:
+        ap.error("--frames must be A:B with integers 0 <= A <= B (either may be left out)")
+    if args.data_velodyne is None:
+        from ..config.KittiConfig import KittiConfiguration
+        args.data_velodyne = KittiConfiguration(None).data_velodyne
+    return ap, args
+
+
+def main(argv=None, device=None):
+    ap, args = parse_args(argv)
+    folder = os.path.join(args.root, args.data_velodyne, "sequences", "%02d" % args.sequence, args.subdir)
+    if not os.path.isdir(folder):
+        ap.error("%s is not a directory; python -m cmr_agent_amd.dataset.prepare writes it" % folder)
+    a, b = args.frames
+    files = []
+    for name in sorted(os.listdir(folder)):
+        stem, ext = os.path.splitext(name)
+        if ext == ".npy" and stem.isdigit() and a <= int(stem) and (b is None or int(stem) < b):
+            files.append((int(stem), os.path.join(folder, name)))
+    files.sort()
+    for (i, _), (j, _) in zip(files[:-1], files[1:]):
+        if j != i + 1:
+            ap.error("frame %d is missing between %d and %d in %s" % (i + 1, i, j, folder))
+    for _, path in files:                                # the headers only: a wrong layout ends the run before any work
+        shape = np.load(path, mmap_mode="r").shape
+        if len(shape) == 2 and shape[0] == 4:
+            ap.error("%s holds [4, n] rows and no normals; write [7, n] files with python -m cmr_agent_amd.dataset.prepare "
+                     "(without --no-normals)" % path)
+    try:
+        chain = align_sequence(files, args.max_dist, args.huber, args.iters, device)
+    except ValueError as e:
+        ap.error(str(e))
+    if args.out is not None:
+        with open(args.out, "w") as fh:
+            for T in chain:
+                fh.write(" ".join("%.9e" % v for v in T[:3].reshape(-1)) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -2651,3 +2651,138 @@ def point_normals(points, radius=0.6, viewpoint=(0, 0, 0), min_neighbors=3, want
               viewpoint[0], viewpoint[1], viewpoint[2], min(max(min_neighbors, 3), CLOUD_MAX_ROWS), _p(pts4), _p(normals), _p(count), _p(eig),
               _stream())
     return PointNormals(normals, count, eig)
+
+
+# ---- cloud against cloud: nearest row and point-to-plane ICP on a grid index (csrc/cloud_icp.hip) ---------------------------
+ICP_MAX_ITERS = 1000
+ICP_STATUS = ("converged", "iterations exhausted", "fewer than 6 pairs", "singular or non-finite system")
+
+
+class CloudIndex(collections.namedtuple("CloudIndex", "pts4 keys order origin cell kept n")):
+    """cloud_index's result, the grid index of one cloud: pts4 float32 [kept, 4] = the rows with finite coordinates in key order, keys int64
+    [n] sorted, order int64 [n] = the row each key came from, origin = the grid's origin (three python floats holding fp32 values), cell,
+    kept, n = the cloud's rows.  Built once, read by every cloud_nearest / icp_point_to_plane call on that cloud."""
+
+
+class CloudNearest(collections.namedtuple("CloudNearest", "idx dist2")):
+    """cloud_nearest's result: idx int32 [M] = the nearest target row in the target's own order (-1: none within max_dist), dist2 float32
+    [M] = its squared distance (NaN where idx is -1)."""
+
+
+class IcpResult(collections.namedtuple("IcpResult", "pose pairs rmse iterations status trace system")):
+    """icp_point_to_plane's result: pose float32 [4, 4] on the device; pairs and rmse of the last executed iteration (those of the pose it
+    started from); iterations executed; status 0 .. 3 (ICP_STATUS); trace float64 [iters, 4] = pairs, rmse, |omega|, |v| per iteration (host);
+    system float64 [iters, 28] = H upper, g, cost per iteration (host; None unless asked for)."""
+
+
+def _cloud_index_arg(index, max_dist, who):
+    if not isinstance(index, CloudIndex):
+        raise ValueError("%s: index must be a CloudIndex (ops.cloud_index), got %s" % (who, type(index).__name__))
+    if max_dist is None:
+        return index.cell
+    max_dist = _cloud_scalar(max_dist, "max_dist")
+    if np.float32(max_dist) > np.float32(index.cell):
+        raise ValueError("%s: max_dist %g exceeds the index's cell %g (a match must lie in the query's cell or one next to it)"
+                         % (who, max_dist, index.cell))
+    return max_dist
+
+
+def _cloud_pose(pose, dev, who):
+    if pose is None:
+        return None
+    if not isinstance(pose, torch.Tensor) or pose.dtype != f32 or tuple(pose.shape) != (4, 4):
+        raise ValueError("%s: pose must be a float32 [4, 4] tensor or None, got %s %s" % ((who,) + _got(pose)))
+    return pose.to(dev).contiguous()
+
+
+def cloud_index(points, cell):
+    """The sorted-key grid index of one cloud, the prologue of point_normals on its own: bounds (one host read), keys on the grid of `cell`
+    with the origin at the cloud's minimum, a stable sort, the kept rows gathered into key order (cmr_cloud_gather4_f32).  points float32
+    [n, 3] -> CloudIndex.  A cloud without a finite row gives an empty index (kept = 0) and no launch."""
+    cell = _cloud_scalar(cell, "cell")
+    points = _cloud_points(points)
+    n, dev = points.shape[0], points.device
+    lo, hi, kept = _cloud_bounds(points) if n else (None, None, 0)
+    if kept == 0:
+        return CloudIndex(torch.empty((0, 4), dtype=f32, device=dev), torch.empty((0,), dtype=torch.int64, device=dev),
+                          torch.empty((0,), dtype=torch.int64, device=dev), (0.0, 0.0, 0.0), cell, 0, n)
+    _cloud_cells(hi, lo, cell, "cloud_index")
+    keys, order = _sorted_keys(points, lo, cell)
+    pts4 = torch.empty((kept, 4), dtype=f32, device=dev)
+    _lib.call("cmr_cloud_gather4_f32", _p(points), 3, _p(order), kept, _p(pts4), _stream())
+    return CloudIndex(pts4, keys, order, tuple(float(v) for v in lo), cell, kept, n)
+
+
+def cloud_nearest(index, queries, max_dist=None, pose=None):
+    """The nearest row of an indexed cloud for every query row (cmr_cloud_nearest_f32; the contract is the header's): exact, the lowest
+    row on equal distances.  index: ops.cloud_index of the target; queries float32 [M, 3]; max_dist <= index.cell (default: the cell); pose
+    float32 [4, 4] or None: the queries are moved by it first, in fp32.  -> CloudNearest(idx int32 [M], dist2 float32 [M])."""
+    who = "cloud_nearest"
+    max_dist = _cloud_index_arg(index, max_dist, who)
+    queries = _cloud_points(queries, "queries")
+    M, dev = queries.shape[0], queries.device
+    pose = _cloud_pose(pose, dev, who)
+    if index.pts4.device != dev:
+        raise ValueError("%s: queries must be on the device of the index" % who)
+    if M == 0 or index.kept == 0:
+        return CloudNearest(torch.full((M,), -1, dtype=torch.int32, device=dev), torch.full((M,), float("nan"), dtype=f32, device=dev))
+    idx = torch.empty((M,), dtype=torch.int32, device=dev)
+    dist2 = torch.empty((M,), dtype=f32, device=dev)
+    o = index.origin
+    _lib.call("cmr_cloud_nearest_f32", _p(queries), 3, M, _p(pose), _p(index.pts4), _p(index.keys), _p(index.order), index.kept, o[0], o[1], o[2],
+              index.cell, max_dist, _p(idx), _p(dist2), _stream())
+    return CloudNearest(idx, dist2)
+
+
+def icp_point_to_plane(source, target, target_normals, pose=None, max_dist=1.0, huber=0.0, iters=30, tol_rot=1e-6, tol_trans=1e-6, index=None,
+                       want_system=False):
+    """Point-to-plane ICP of one cloud onto another (cmr_icp_point_to_plane_f32; the contract is the header's): the pose that maps the
+    source rows onto the planes through their nearest target rows, Gauss-Newton from `pose` (identity by default), every iteration on the
+    device and one host read at the end.  source float32 [M, 3]; target float32 [n, 3] (may be None when `index` is given);
+    target_normals float32 [n, 3] in the target's row order, zero rows take no part; index: ops.cloud_index(target, cell >= max_dist),
+    built here with cell = max_dist when None -- pass one to register several sources, or several start poses, against one target.
+    huber: residuals above it are down-weighted by huber / |r| (0: off).  -> IcpResult.  An empty source or target returns the start pose
+    with status 2 and no launch."""
+    who = "icp_point_to_plane"
+    max_dist = _cloud_scalar(max_dist, "max_dist")
+    huber = _f32_arg(who, "huber", huber, "be a finite number >= 0")
+    tol_rot = _f32_arg(who, "tol_rot", tol_rot, "be a finite number >= 0")
+    tol_trans = _f32_arg(who, "tol_trans", tol_trans, "be a finite number >= 0")
+    iters = _int_arg(who, "iters", iters, 0, ICP_MAX_ITERS)
+    if index is not None:
+        _cloud_index_arg(index, max_dist, who)
+    elif target is None:
+        raise ValueError("%s: give the target cloud or its index" % who)
+    source = _cloud_points(source, "source")
+    dev = source.device
+    target_normals = _cloud_points(target_normals, "target_normals")
+    if target is not None:
+        target = _cloud_points(target, "target")
+    n = index.n if index is not None else target.shape[0]
+    if target_normals.shape[0] != n or (target is not None and target.shape[0] != n):
+        raise ValueError("%s: the target has %d rows, target_normals %d%s" % (
+            who, target.shape[0] if target is not None else n, target_normals.shape[0], "" if index is None else ", the index %d" % n))
+    pose = _cloud_pose(pose, dev, who)
+    if target_normals.device != dev or (target is not None and target.device != dev) or (index is not None and index.pts4.device != dev):
+        raise ValueError("%s: source, target, target_normals and the index must be on one device" % who)
+    if pose is None:
+        pose = torch.eye(4, dtype=f32, device=dev)
+    M = source.shape[0]
+    if index is None and M and n:
+        index = cloud_index(target, max_dist)
+    trace = torch.zeros((iters, 4), dtype=torch.float64, device=dev)
+    system = torch.zeros((iters, 28), dtype=torch.float64, device=dev) if want_system else None
+    if M == 0 or n == 0 or index.kept == 0:
+        return IcpResult(pose.clone(), 0, 0.0, 0, 2, trace.cpu(), None if system is None else system.cpu())
+    out = torch.empty((4, 4), dtype=f32, device=dev)
+    status = torch.empty((2,), dtype=torch.int32, device=dev)
+    nb = _lib.load().cmr_icp_point_to_plane_workspace_bytes(M)
+    ws = _ws(nb, dev)
+    o = index.origin
+    _lib.call("cmr_icp_point_to_plane_f32", _p(source), 3, M, _p(index.pts4), _p(index.keys), _p(index.order), index.kept, o[0], o[1], o[2],
+              index.cell, _p(target_normals), _p(pose), max_dist, huber, iters, tol_rot, tol_trans, _p(out), _p(trace), _p(system), _p(status),
+              _p(ws), nb, _stream())
+    code, executed = (int(v) for v in status.cpu())                    # the one host read (trace and system ride behind it)
+    trace = trace.cpu()
+    last = trace[executed - 1] if executed else torch.zeros(4, dtype=torch.float64)
+    return IcpResult(out, int(last[0]), float(last[1]), executed, code, trace, None if system is None else system.cpu())

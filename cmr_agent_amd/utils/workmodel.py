@@ -284,6 +284,12 @@ WORK = {
     "cmr_fps_f32": lambda a: (0, a["B"] * (16 * a["N"] + 8 * a["npoint"])),
     "cmr_fps_ws_f32": lambda a: (0, a["B"] * (16 * a["N"] + 8 * a["npoint"])),
     "cmr_ball_query_f32": lambda a: (0, a["B"] * (16 * a["N"] + a["S"] * (16 + 8 * a["nsample"]))),
+    # DESIGN.md 4ae, latency-class like the rows above and priced on compulsory bytes: the query rows (12 B) and the index once (16 B of
+    # float4, 8 B of key, 8 B of order per kept row), 8 B of result per query; ICP reads the same per iteration plus 12 B of normal per
+    # source row, and ~9 FLOP per candidate are not counted (the candidate count is data).  ~250 float64 FLOP per pair for the sums.
+    "cmr_cloud_gather4_f32": lambda a: (0, a["kept"] * (12 + 8 + 16)),
+    "cmr_cloud_nearest_f32": lambda a: (0, a["M"] * (12 + 8) + a["kept"] * 32),
+    "cmr_icp_point_to_plane_f32": lambda a: (250.0 * a["iters"] * a["M"], a["iters"] * (a["M"] * 24 + a["kept"] * 32)),
 }
 
 # Multiplies the kernel ISSUES on the matrix cores per algorithmic multiply: F(2x2,3x3) Winograd computes 2x2 outputs with 16

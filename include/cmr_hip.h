@@ -1353,6 +1353,62 @@ int cmr_segment_heads_i64(const int64_t* keys_sorted, const int64_t* order, int6
 int cmr_point_normals_f32(const float* points, int64_t ld, const int64_t* keys_sorted, const int64_t* order, int64_t N, int64_t kept,
                           float ox, float oy, float oz, float radius, float vx, float vy, float vz, int min_neighbors, float* points4,
                           float* normals, int32_t* count, float* eigenvalues, hipStream_t stream);
+/* The first step of cmr_point_normals_f32 on its own: points4[i] = (x, y, z, 0) of row order[i], i < kept -- the kept rows in key order as
+ * float4 (16-byte aligned).  With keys_sorted and order these are the rows of a GRID INDEX of the cloud (below).  0 < kept < 2^31. */
+int cmr_cloud_gather4_f32(const float* points, int64_t ld, const int64_t* order, int64_t kept, float* points4, hipStream_t stream);
+
+/* ---- cloud against cloud: nearest row and point-to-plane ICP on a grid index (csrc/cloud_icp.hip) --------------------
+ * Port extension: every pose operation of the reference goes through a camera; these relate one cloud to another.
+ *
+ * The TARGET is handed over as a grid index, built once and searched by every call: keys_sorted / order = the keys of the target's rows
+ * on the grid (origin (ox, oy, oz), cell) in ascending order and the row each came from (cmr_voxel_keys_f32 and a stable sort, as for
+ * cmr_point_normals_f32), kept = the number of rows with finite coordinates, points4 = those rows in key order (cmr_cloud_gather4_f32).
+ * Rows with a non-finite coordinate are not in the index and are never a match.
+ *
+ * cmr_cloud_nearest_f32.  Query row i of queries [M][ld >= 3], 0 < M < 2^31:
+ *   q      with pose (fp32 [4][4], row-major; its upper 3 x 4 is read) q = R p + t in fp32, every operation rounded on its own, left to
+ *          right:  q_x = ((R00 p_x + R01 p_y) + R02 p_z) + t_x  and likewise q_y, q_z;  with pose = null q = p;
+ *   d2     of a target row c:  d = c - q in fp32,  d2 = (dx dx + dy dy) + dz dz,  each product and sum rounded on its own (the arithmetic
+ *          of cmr_point_normals_f32's neighbour test);
+ *   match  the target row with the least d2 among those with d2 <= max_dist max_dist (the square rounded on its own); on equal d2 the
+ *          LOWEST row in the target's original order;
+ *   idx[i] = that row in the target's original order and d2[i] = its d2;  idx[i] = -1 and d2[i] = NaN when there is none, or when q has a
+ *          non-finite coordinate.
+ * 0 < max_dist <= cell: a match then lies in the query's cell or one next to it.  One 16-lane group serves a query; per (z, y) pair of
+ * cells it reads ONE run of the sorted rows, 9 runs, more for a query within rounding of a cell face, as for cmr_point_normals_f32, so the
+ * candidate set holds every row within max_dist whatever the rounding of the cell coordinate.  Queries need not lie inside the target's
+ * grid: per axis the cells searched are clamped to [0, 2^21), an empty range on any axis means no candidates, and no key is formed from
+ * an index outside that range.  (d2, row) is ordered lexicographically and every output has one writer: the result is exact, and two
+ * calls agree bit for bit. */
+int cmr_cloud_nearest_f32(const float* queries, int64_t ld, int64_t M, const float* pose, const float* points4,
+                          const int64_t* keys_sorted, const int64_t* order, int64_t kept, float ox, float oy, float oz, float cell,
+                          float max_dist, int32_t* idx, float* d2, hipStream_t stream);
+/* cmr_icp_point_to_plane_f32: the pose T (fp32 [4][4], maps source rows into the target's frame) that minimises the point-to-plane
+ * distances of the source rows [M][ld >= 3] to their nearest target rows, by Gauss-Newton from pose_in; the whole loop runs on the device,
+ * 2 iters + 2 launches whatever the data.  normals [n][3]: the target's normals in its ORIGINAL row order (n > every entry of order).
+ * The working pose is float64.  Iteration k = 0 .. iters - 1 (0 <= iters <= 1000):
+ *   match   the working pose rounded to fp32, then every source row as cmr_cloud_nearest_f32 states (q, the matched row c, fp32);
+ *   pairs   the rows with a match whose normal n is not the zero vector;
+ *   terms   in float64 from the fp32 q, c, n, each operation rounded on its own:  r = (nx (qx - cx) + ny (qy - cy)) + nz (qz - cz),
+ *           J = [(q x n)^T, n^T],  w = 1, or with huber > 0:  w = 1 for |r| <= huber, huber / |r| above it  (huber >= 0; 0 = off);
+ *   sums    H = sum w J^T J (21 upper-triangle entries, row by row, as (w J_a) J_b),  g = sum (w J) r,  cost = sum (w r) r,  the number of
+ *           pairs -- float64 in a fixed order: the rows of a slice of 32 consecutive source rows in 16 interleaved sequences, those added
+ *           in order, then the slices in order.  No atomics;
+ *   step    H xi = -g by 6 x 6 Cholesky (a pivot must exceed 1e-13 of its diagonal entry), xi = (omega, v);  T <- [exp(omega) | v] T;
+ *   stop    when |omega| < tol_rot and |v| < tol_trans: status 0, and every later launch of the call returns at once.
+ * Outputs: pose;  trace float64 [iters][4] = {pairs, sqrt(cost / pairs) (0 without pairs), |omega|, |v|} of every executed iteration -- cost
+ * and pairs are those of the pose the iteration STARTED from -- and zero rows after the last executed one;  system float64 [iters][28] (or
+ * null) = H upper, g, cost per executed iteration, zero after;  status int32 [2] = {code, iterations executed}:
+ *   0 converged;  1 iterations exhausted (iters = 0: pose = pose_in);  2 fewer than 6 pairs at some iteration;  3 non-finite sums, a failed
+ *   factorisation or a non-finite update.  With 2 and 3 the pose is the one the failing iteration started from; that iteration counts as
+ *   executed, its trace row holds pairs and the root mean square and zeros for the step.
+ * Workspace of cmr_icp_point_to_plane_workspace_bytes(M), 16-byte aligned.  Two calls agree bit for bit. */
+int64_t cmr_icp_point_to_plane_workspace_bytes(int64_t M);
+int cmr_icp_point_to_plane_f32(const float* source, int64_t ld, int64_t M, const float* points4, const int64_t* keys_sorted,
+                               const int64_t* order, int64_t kept, float ox, float oy, float oz, float cell, const float* normals,
+                               const float* pose_in, float max_dist, float huber, int iters, float tol_rot, float tol_trans, float* pose,
+                               double* trace, double* system, int32_t* status, void* workspace, int64_t workspace_bytes,
+                               hipStream_t stream);
 
 #ifdef __cplusplus
 }

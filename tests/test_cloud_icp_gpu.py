@@ -1,0 +1,287 @@
+"""GPU tier of the cloud-against-cloud operations (ops.cloud_index / ops.cloud_nearest / ops.icp_point_to_plane, csrc/cloud_icp.hip,
+dataset/align.py), against the restatement of cloud_icp_reference.py.
+
+Nearest row: idx is EXACT and d2 is BIT-EXACT (the header states every fp32 operation and the tie rule).
+
+One iteration from an fp32 start pose (the matches are then exact, asserted through the pair count and the sums): every entry of H, g and
+cost within pairs * 2^-52 * sum |terms of that entry| of the float64 restatement -- the terms themselves are the same float64 numbers on
+both sides, the two sums differ in their order only, and (pairs - 1) 2^-53 sum |terms| bounds either one's distance from the exact sum;
+|omega| and |v| of the trace within 4 cond2(H) (bound(H) / |H| + bound(g) / |g|) |xi| of the restatement's -- the first-order perturbation
+bound of a linear system, with a factor of 4, which bounds the difference of the vectors and so that of their norms; the fp32 pose within
+2^-23 max(1, |entry|) of the float64 update (one rounding to fp32 is 2^-24 |entry|; the rest is room for the xi above).
+
+The loop: the bars of the issue, stated at the tests."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import cloud_icp_reference as R
+from cmr_agent_amd import ops
+from cmr_agent_amd.dataset import align
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+F = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)      # noqa: E731
+SIZES = (1, 2, 15, 16, 17, 255, 256, 257)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
+
+
+# ---- nearest row ------------------------------------------------------------------------------------------------------------------------
+def _check_nearest(target, queries, cell, max_dist=None, pose=None, index=None):
+    target = np.asarray(target, np.float32).reshape(-1, 3)
+    queries = np.asarray(queries, np.float32).reshape(-1, 3)
+    index = ops.cloud_index(F(target), cell) if index is None else index
+    tp = None if pose is None else F(pose)
+    got = ops.cloud_nearest(index, F(queries), max_dist, tp)
+    again = ops.cloud_nearest(index, F(queries), max_dist, tp)
+    ref_idx, ref_d2, _ = R.nearest(target, queries, cell if max_dist is None else max_dist, pose)
+    idx, d2 = got.idx.cpu().numpy(), got.dist2.cpu().numpy()
+    assert got.idx.dtype == torch.int32 and got.dist2.dtype == torch.float32 and idx.shape == d2.shape == (queries.shape[0],)
+    assert np.array_equal(idx, ref_idx), np.nonzero(idx != ref_idx)[0][:8]
+    assert np.array_equal(np.isnan(d2), ref_idx < 0)
+    assert np.array_equal(_bits(d2)[ref_idx >= 0], _bits(ref_d2)[ref_idx >= 0])
+    assert np.array_equal(again.idx.cpu().numpy(), idx) and np.array_equal(_bits(again.dist2.cpu().numpy()), _bits(d2))
+    return idx, index
+
+
+@pytest.mark.parametrize("cell,max_dist", [(1.0, None), (1.0, 0.5), (0.5, None), (0.3, 0.25)])
+def test_nearest_scene_pair(cell, max_dist):
+    case = R.pair_case()
+    idx, index = _check_nearest(case["target"], case["other"], cell, max_dist)
+    assert index.kept == index.n == case["target"].shape[0] and (idx >= 0).sum() > 4000
+    pose = R.pose_matrix(*R.TRUE_POSES[0]).astype(np.float32)
+    moved, _ = _check_nearest(case["target"], case["other"], cell, max_dist, pose, index)
+    assert (moved != idx).sum() > 1000                                                  # the pose is not a formality
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_nearest_small_sizes(n):
+    r = np.random.default_rng(300 + n)
+    target = r.uniform(-1, 1, (n, 3)).astype(np.float32)
+    index = None
+    for M in SIZES:
+        queries = r.uniform(-1.3, 1.3, (M, 3)).astype(np.float32)
+        queries[::3] = target[r.integers(0, n, len(queries[::3]))]                      # some queries are target rows: d2 = 0
+        _, index = _check_nearest(target, queries, 0.5, None, None, index)
+        _check_nearest(target, queries, 0.5, 0.375, R.pose_matrix((0.1, 0.2, -0.1), (0.05, 0, -0.05)).astype(np.float32), index)
+
+
+def test_nearest_lattice_every_row_on_a_face_every_neighbour_at_the_radius():
+    s = 0.5                                                                             # spacing = cell = max_dist, exact in fp32
+    g = np.arange(7, dtype=np.float32) * s - 1.0
+    lat = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
+    ijk = np.stack(np.meshgrid(*[np.arange(7)] * 3, indexing="ij"), -1).reshape(-1, 3).sum(1)
+    even, odd = lat[ijk % 2 == 0], lat[ijk % 2 == 1]
+    perm = np.random.default_rng(5).permutation(even.shape[0])
+    idx, index = _check_nearest(even[perm], odd, s)                                     # up to six rows tie at d2 = cell^2 exactly
+    assert (idx >= 0).all()
+    idx, _ = _check_nearest(even[perm], lat, s, None, None, index)
+    assert (idx >= 0).all()
+    _check_nearest(even[perm], lat + np.float32(0.25), s, None, None, index)            # mid-cell: sqrt(3) / 4 < 0.5 from eight rows
+    # a lattice off the powers of two: the cell coordinate rounds, the face rule has to cover it
+    t = (np.stack(np.meshgrid(*[np.arange(9, dtype=np.float32)] * 3, indexing="ij"), -1).reshape(-1, 3) * np.float32(0.3) + np.float32(7.1)).astype(np.float32)
+    _check_nearest(t[::2], t[1::2], np.float32(0.3))
+    _check_nearest(t[::2], t[1::2], np.float32(0.3) * np.float32(1.0000001))
+
+
+def test_nearest_duplicated_rows_tie_to_the_lowest():
+    r = np.random.default_rng(8)
+    base = r.uniform(-2, 2, (300, 3)).astype(np.float32)
+    target = np.concatenate([base, base, base[:100]])[r.permutation(700)]
+    idx, _ = _check_nearest(target, base + r.normal(0, 0.05, base.shape).astype(np.float32), 0.5)
+    assert (idx >= 0).sum() > 250
+    idx, _ = _check_nearest(target, base, 0.5)
+    first = {}
+    for row, p in enumerate(target):
+        first.setdefault(p.tobytes(), row)
+    assert idx.tolist() == [first[p.tobytes()] for p in base]
+
+
+def test_nearest_queries_outside_the_grid():
+    r = np.random.default_rng(9)
+    target = r.uniform(0, 4, (500, 3)).astype(np.float32)
+    qs = []
+    for axis in range(3):
+        for off in (0.1, 0.4, 0.6, 1.1, 2.6, 50.0, 1e6, 3e6, 1e12, 1e30, 3e38):
+            for side in (-1, 1):
+                q = r.uniform(0, 4, (6, 3)).astype(np.float32)
+                q[:, axis] = np.float32(side * off + (4 if side > 0 else 0))
+                qs.append(q)
+    qs.append(np.float32([[-3e38, 3e38, 0], [3e38, 3e38, 3e38], [-1e30, -1e30, -1e30]]))
+    queries = np.concatenate(qs)
+    for cell, md in ((0.5, None), (0.5, 0.45), (1e-5, None), (1.0, None)):
+        idx, _ = _check_nearest(target, queries, cell, md)
+    assert (idx >= 0).any() and (idx < 0).any()
+    # the grid's last cells: a target that ends near cell 2^21 - 1, queries beyond it
+    far = (np.float32(2 ** 21 - 3) + r.uniform(0, 2.5, (200, 3))).astype(np.float32)
+    far[0] = 0.0
+    _check_nearest(far, np.concatenate([far[1:50] + np.float32(0.5), far[1:50] + np.float32(4.0), queries]), 1.0)
+
+
+def test_nearest_non_finite_rows_and_empty_clouds():
+    r = np.random.default_rng(10)
+    target = r.uniform(-1, 1, (400, 3)).astype(np.float32)
+    queries = r.uniform(-1, 1, (64, 3)).astype(np.float32)
+    queries[[3, 17, 18], [0, 1, 2]] = np.nan
+    queries[[5, 40], [2, 0]] = [np.inf, -np.inf]
+    idx, _ = _check_nearest(target, queries, 0.5)
+    assert (idx[[3, 17, 18, 5, 40]] == -1).all() and (idx >= 0).sum() > 40
+    _check_nearest(target, queries, 0.5, None, np.eye(4, dtype=np.float32))             # 0 * inf = NaN under a pose: still -1
+    holes = target.copy()
+    holes[::5, 1] = np.nan
+    holes[7] = [np.inf, 0, 0]
+    idx, index = _check_nearest(holes, queries, 0.5)
+    assert index.n == 400 and index.kept == 400 - 80 - 1 and not np.isin(idx, np.arange(0, 400, 5)).any()
+    for empty in (np.zeros((0, 3), np.float32), np.full((5, 3), np.nan, np.float32)):
+        idx, index = _check_nearest(empty, queries, 0.5)
+        assert index.kept == 0 and (idx == -1).all()
+    none = ops.cloud_nearest(index, torch.zeros((0, 3), device=DEV))
+    assert none.idx.shape == (0,) and none.dist2.shape == (0,)
+    with pytest.raises(ValueError, match="exceeds the index's cell"):
+        ops.cloud_nearest(ops.cloud_index(F(target), 0.5), F(queries), 0.6)
+
+
+# ---- one iteration ----------------------------------------------------------------------------------------------------------------------
+def _start_pose(kind, k, start):
+    truth = R.pose_matrix(*R.TRUE_POSES[k])
+    if start == "identity":
+        return np.eye(4, dtype=np.float32)
+    if start == "truth":
+        return truth.astype(np.float32)
+    return (R.pose_matrix((0.004, -0.003, 0.002), (0.03, 0.02, -0.01)) @ truth).astype(np.float32)
+
+
+@pytest.mark.parametrize("kind,k,max_dist,start", [("same", 0, 1.0, "identity"), ("same", 1, 0.5, "truth"), ("other", 1, 1.0, "identity"),
+                                                   ("other", 2, 0.5, "near"), ("other", 0, 1.0, "truth")])
+def test_one_iteration_system_step_and_pose(kind, k, max_dist, start):
+    case, L = R.pair_case(), R.loop_case(kind, k, max_dist)
+    T0 = _start_pose(kind, k, start)
+    ref = R.iteration(L["source"], case["target"], case["normals"], T0.astype(np.float64), max_dist, L["huber"])
+    got = ops.icp_point_to_plane(F(L["source"]), F(case["target"]), F(case["normals"]), pose=F(T0), max_dist=max_dist, huber=L["huber"],
+                                 iters=1, tol_rot=0.0, tol_trans=0.0, want_system=True)
+    pairs = ref["pairs"]
+    assert got.status == 1 and got.iterations == 1 and got.pairs == pairs and pairs > 4000
+    assert got.trace.shape == (1, 4) and got.system.shape == (1, 28) and got.trace.dtype == got.system.dtype == torch.float64
+    sums, bound = got.system[0].numpy(), pairs * 2.0 ** -52 * ref["abs_sums"]
+    err = np.abs(sums - ref["sums"])
+    ratio_sum = float((err / bound).max())
+    assert np.all(err <= bound), (ratio_sum, int(np.argmax(err / bound)))
+    assert abs(got.trace[0, 1].item() - np.sqrt(ref["sums"][27] / pairs)) <= 1e-12 * max(1.0, got.trace[0, 1].item())
+
+    H, g, xi = R.full_matrix(ref["sums"][:21]), ref["sums"][21:27], ref["xi"]
+    bH, bg = R.full_matrix(bound[:21]), bound[21:27]
+    bar = 4.0 * np.linalg.cond(H) * (np.linalg.norm(bH, 2) / np.linalg.norm(H, 2) + np.linalg.norm(bg) / np.linalg.norm(g)) * np.linalg.norm(xi)
+    d_rot = abs(got.trace[0, 2].item() - np.linalg.norm(xi[:3]))
+    d_trans = abs(got.trace[0, 3].item() - np.linalg.norm(xi[3:]))
+    ratio_xi = max(d_rot, d_trans) / bar
+    assert d_rot <= bar and d_trans <= bar, (d_rot, d_trans, bar)
+
+    pose = got.pose.cpu().numpy().astype(np.float64)
+    perr = np.abs(pose - ref["pose"]) / np.maximum(1.0, np.abs(ref["pose"]))
+    ratio_pose = float(perr.max() / 2.0 ** -23)
+    assert ratio_pose <= 1.0 and np.array_equal(pose[3], [0, 0, 0, 1])
+    print("one iteration %s %d %.1f %s: pairs %d cond %.1f |xi| %.3g  measured / bar: sums %.2e  xi %.2e  pose %.3f"
+          % (kind, k, max_dist, start, pairs, np.linalg.cond(H), np.linalg.norm(xi), ratio_sum, ratio_xi, ratio_pose))
+
+
+# ---- the loop ---------------------------------------------------------------------------------------------------------------------------
+def _run_loop(kind, k, max_dist, index=None):
+    case, L = R.pair_case(), R.loop_case(kind, k, max_dist)
+    return L, ops.icp_point_to_plane(F(L["source"]), F(case["target"]), F(case["normals"]), max_dist=max_dist, huber=L["huber"],
+                                     iters=R.LOOP_ITERS, index=index)
+
+
+@pytest.mark.parametrize("max_dist", R.MAX_DISTS)
+@pytest.mark.parametrize("k", range(3))
+def test_loop_same_cloud_finds_the_truth(k, max_dist):
+    L, got = _run_loop("same", k, max_dist)
+    rot, trans = R.pose_error(got.pose.cpu().numpy(), L["truth"])
+    print("same %d %.1f: status %d iterations %d (restatement %d) pairs %d rmse %.3g error %.3g rad %.3g m" % (
+        k, max_dist, got.status, got.iterations, L["ref"]["iterations"], got.pairs, got.rmse, rot, trans))
+    assert got.status == 0 and rot <= 1e-5 and trans <= 1e-5
+    assert not got.trace[got.iterations:].any() and got.trace[0, 0] == L["ref"]["trace"][0, 0] and got.system is None
+    assert got.pairs == L["ref"]["pairs"] == 4447                                       # every row with a normal, at the end
+
+
+@pytest.mark.parametrize("max_dist", R.MAX_DISTS)
+@pytest.mark.parametrize("k", range(3))
+def test_loop_other_cloud_agrees_with_the_restatement(k, max_dist):
+    L, got = _run_loop("other", k, max_dist)
+    ref = L["ref"]
+    ref_rot, ref_trans = R.pose_error(ref["pose"], L["truth"])
+    rot, trans = R.pose_error(got.pose.cpu().numpy(), ref["pose"])
+    print("other %d %.1f: status %d iterations %d (restatement %d) pairs %d rmse %.4g  to the restatement %.3g rad %.3g m = %.4f / %.4f of "
+          "its error to the truth" % (k, max_dist, got.status, got.iterations, ref["iterations"], got.pairs, got.rmse, rot, trans,
+                                      rot / ref_rot, trans / ref_trans))
+    assert got.status == 0 and ref["status"] == 0
+    assert rot <= 0.1 * ref_rot and trans <= 0.1 * ref_trans
+    assert abs(got.iterations - ref["iterations"]) <= 2
+
+
+def test_loop_two_calls_agree_bit_for_bit_and_an_index_is_reusable():
+    case = R.pair_case()
+    index = ops.cloud_index(F(case["target"]), 1.0)
+    for kind, md in (("other", 1.0), ("same", 0.5)):
+        L, a = _run_loop(kind, 2, md)
+        _, b = _run_loop(kind, 2, md, index)                                            # cell 1.0 serves max_dist 0.5 too: same matches
+        src, tgt, nrm = F(L["source"]), F(case["target"]), F(case["normals"])
+        c = ops.icp_point_to_plane(src, None, nrm, max_dist=md, huber=L["huber"], iters=R.LOOP_ITERS, index=index, want_system=True)
+        for other in (b, c):
+            assert torch.equal(a.pose, other.pose) and torch.equal(a.trace, other.trace)
+            assert (a.status, a.iterations, a.pairs, a.rmse) == (other.status, other.iterations, other.pairs, other.rmse)
+        assert c.system[:c.iterations].abs().sum() > 0 and not c.system[c.iterations:].any()
+        with pytest.raises(ValueError, match="exceeds the index's cell"):
+            ops.icp_point_to_plane(src, tgt, nrm, max_dist=1.5, index=index)
+
+
+# ---- status codes -----------------------------------------------------------------------------------------------------------------------
+def test_status_codes():
+    g = np.arange(12, dtype=np.float32) * np.float32(0.25)
+    plane = np.concatenate([np.stack(np.meshgrid(g, g, indexing="ij"), -1).reshape(-1, 2), np.zeros((144, 1), np.float32)], 1)
+    up = np.tile(np.float32([[0, 0, 1]]), (144, 1))
+    start = R.pose_matrix((0, 0, 0.01), (0.01, 0, 0)).astype(np.float32)
+    shifted = plane + np.float32([0.05, 0.03, 0.02])
+    for pose in (None, start):
+        got = ops.icp_point_to_plane(F(shifted), F(plane), F(up), pose=None if pose is None else F(pose), max_dist=0.5, iters=5, want_system=True)
+        assert got.status == 3 and got.iterations == 1 and got.pairs == 144                # H is exactly of rank 3: omega_z, v_x, v_y unseen
+        assert np.array_equal(got.pose.cpu().numpy(), np.eye(4, dtype=np.float32) if pose is None else pose)
+        assert got.system[0, 0] > 0 and got.system[0, 11] == 0 and not got.trace[1:].any() and not got.trace[0, 2:].any()
+    case = R.pair_case()
+    tgt, nrm = F(case["target"]), F(case["normals"])
+    away = ops.icp_point_to_plane(F(case["other"] + np.float32([0, 0, 10])), tgt, nrm, pose=F(start), max_dist=1.0, iters=5)
+    assert away.status == 2 and away.iterations == 1 and away.pairs < 6 and np.array_equal(away.pose.cpu().numpy(), start)
+    zero = ops.icp_point_to_plane(F(case["other"]), tgt, torch.zeros_like(nrm), pose=F(start), max_dist=1.0, iters=5)
+    assert zero.status == 2 and zero.pairs == 0 and zero.rmse == 0.0 and np.array_equal(zero.pose.cpu().numpy(), start)
+    none = ops.icp_point_to_plane(F(case["other"]), tgt, nrm, pose=F(start), iters=0, want_system=True)
+    assert none.status == 1 and none.iterations == 0 and np.array_equal(none.pose.cpu().numpy(), start)
+    assert none.trace.shape == (0, 4) and none.system.shape == (0, 28)
+    for src, t3, n3 in ((torch.zeros((0, 3), device=DEV), tgt, nrm), (F(case["other"]), tgt[:0], nrm[:0])):
+        e = ops.icp_point_to_plane(src, t3, n3, pose=F(start), iters=3)
+        assert e.status == 2 and e.iterations == 0 and e.pairs == 0 and np.array_equal(e.pose.cpu().numpy(), start) and not e.trace.any()
+    bad = case["normals"].copy()
+    bad[100] = np.nan
+    nan = ops.icp_point_to_plane(F(case["target"]), tgt, F(bad), max_dist=0.5, iters=3)
+    assert nan.status == 3 and nan.iterations == 1 and np.array_equal(nan.pose.cpu().numpy(), np.eye(4, dtype=np.float32))
+
+
+# ---- the command ------------------------------------------------------------------------------------------------------------------------
+def test_align_command(tmp_path, capsys):
+    case = R.pair_case()
+    folder = tmp_path / "vel" / "sequences" / "07" / "voxel0.1-SNr0.6"
+    os.makedirs(folder)
+    truth = R.pose_matrix(*R.TRUE_POSES[0])
+    seven = lambda xyz, nrm: np.concatenate([xyz.T, np.zeros((1, xyz.shape[0]), np.float32), nrm.T]).astype(np.float32)   # noqa: E731
+    np.save(folder / "000004.npy", seven(case["target"], case["normals"]))
+    np.save(folder / "000005.npy", seven(R.moved(case["target"], truth), case["normals"] @ np.linalg.inv(truth)[:3, :3].T.astype(np.float32)))
+    out = tmp_path / "poses.txt"
+    align.main(["--root", str(tmp_path), "--data-velodyne", "vel", "--sequence", "7", "--huber", "0", "--out", str(out)])
+    line = capsys.readouterr().out
+    assert line.startswith("pair 4 5: pairs 4447 rmse 0.0000 iterations ") and " status 0 t 0.3000 -0.2000 0.1000 r " in line
+    chain = np.loadtxt(out)
+    assert chain.shape == (2, 12) and np.array_equal(chain[0], np.eye(4)[:3].reshape(-1))
+    assert np.abs(chain[1].reshape(3, 4) - truth[:3]).max() < 1e-5
