@@ -4,6 +4,22 @@
 #pragma once
 #include "cmr_common.h"
 
+// The draws of a RANSAC hypothesis (pnp.hip; cloud_global.hip with b = 0).
+// lowbias32 (C. Wellons' integer hash, constants 0x21f0aaad / 0xd35a2d97); draw c of hypothesis h of sample b:
+// mix(mix(mix(mix(seed ^ 0x9e3779b9) ^ b) ^ h) ^ c) % count.
+__host__ __device__ __forceinline__ uint32_t pnp_mix(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x21f0aaadu;
+  x ^= x >> 15;
+  x *= 0xd35a2d97u;
+  x ^= x >> 15;
+  return x;
+}
+
+__device__ __forceinline__ uint32_t pnp_hash(uint32_t seed, uint32_t b, uint32_t h, uint32_t c) {
+  return pnp_mix(pnp_mix(pnp_mix(pnp_mix(seed ^ 0x9e3779b9u) ^ b) ^ h) ^ c);
+}
+
 // The inlier test (scoring, selection, recount and the refinement's working set: the same operations in the same order).
 // M = K[R|t] row-major fp32; inlier iff z > 0 and (x - u z)^2 + (y - v z)^2 <= thr^2 z^2 (no division).
 __device__ __forceinline__ bool cmr_pnp_inlier(const float* M, float X, float Y, float Z, float u, float v, float thr2) {

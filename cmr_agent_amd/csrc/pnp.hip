@@ -24,21 +24,7 @@ constexpr int PNP_MAX_DRAWS = 32;    // hash counters a hypothesis may use for i
 constexpr int PNP_NACC = 28;         // J^T J (21 upper-triangle entries), J^T r (6), cost
 constexpr double PNP_ORTH_TOL = 1e-5;  // a P3P solution is kept only if max |R R^T - I| <= this
 
-// ---- hash ----------------------------------------------------------------------------------------------------------------------
-// lowbias32 (C. Wellons' integer hash, constants 0x21f0aaad / 0xd35a2d97); draw c of hypothesis h of sample b:
-// mix(mix(mix(mix(seed ^ 0x9e3779b9) ^ b) ^ h) ^ c) % count.
-__host__ __device__ __forceinline__ uint32_t pnp_mix(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x21f0aaadu;
-  x ^= x >> 15;
-  x *= 0xd35a2d97u;
-  x ^= x >> 15;
-  return x;
-}
-
-__device__ __forceinline__ uint32_t pnp_hash(uint32_t seed, uint32_t b, uint32_t h, uint32_t c) {
-  return pnp_mix(pnp_mix(pnp_mix(pnp_mix(seed ^ 0x9e3779b9u) ^ b) ^ h) ^ c);
-}
+// ---- hash: pnp_hash, stated once in cmr_pnp.h (cloud_global.hip draws its hypotheses with it too) ------------------------------------
 
 // ---- compaction ----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(PNP_CHUNK) void pnp_chunk_count_kernel(const void* __restrict__ mask, int mask_bytes, int N, int nchunk,

@@ -13,7 +13,15 @@ pairs and rmse are those of the last iteration (at the pose it started from), st
 writes the chained poses, 12 numbers per line (the upper 3 x 4, row-major, KITTI's layout): line j maps frame A + j into frame A, the first
 line is the identity, all in the velodyne frame.
 
+--init says where a pair's start pose comes from.  `previous` (the default) is the rule above.  `global` starts every pair
+from `ops.register_global(refine=False)`: FPFH descriptors of both clouds (the source's normals are rows 4-6 of its own file), mutual
+nearest descriptors, RANSAC -- no start pose needed, so a gap, a dropped frame or a revisit does not matter.  `auto` tries `previous` and
+repeats the pair from `global` when ICP ends with status 2 or 3; one more line is then printed ahead of the pair's:
+
+    pair <i> <i+1>: global inliers <n> of <L> status <s>
+
     python -m cmr_agent_amd.dataset.align --root DIR --sequence S [--frames A:B --max-dist 1.0 --huber 0.1 --iters 30 --out FILE]
+                                          [--init previous|global|auto --fpfh-radius 1.0 --ransac-hyp 4096 --ransac-thr 0.3 --seed 0]
 """
 import argparse
 import math
@@ -43,20 +51,37 @@ def register_pair(target7, source7, pose=None, max_dist=1.0, huber=0.1, iters=30
                                   iters=iters)
 
 
+def global_start(target7, source7, radius=1.0, n_hyp=4096, thr=0.3, seed=0, device=None):
+    """Two prepared clouds float32 [7, n] (numpy) -> ops.GlobalResult of the source onto the target without a start pose, not polished."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    rows = lambda a: torch.from_numpy(np.ascontiguousarray(a.T)).to(device)            # noqa: E731
+    return ops.register_global(rows(source7[0:3]), rows(source7[4:7]), rows(target7[0:3]), rows(target7[4:7]), radius=radius, n_hyp=n_hyp,
+                               thr=thr, seed=seed, refine=False)
+
+
 def rotation_degrees(pose):
     c = (float(pose[0, 0]) + float(pose[1, 1]) + float(pose[2, 2]) - 1.0) / 2.0
     return math.degrees(math.acos(min(1.0, max(-1.0, c))))
 
 
-def align_sequence(files, max_dist=1.0, huber=0.1, iters=30, device=None, report=print):
+def align_sequence(files, max_dist=1.0, huber=0.1, iters=30, device=None, report=print, init="previous", fpfh_radius=1.0, ransac_hyp=4096,
+                   ransac_thr=0.3, seed=0):
     """files: the prepared clouds of consecutive frames as (frame number, path).  -> float64 [len(files), 4, 4]: frame j in frame 0's
-    coordinates.  `report` receives one line per pair."""
+    coordinates.  `report` receives one line per pair (two for a pair that `auto` repeats from a global start)."""
     chain = [np.eye(4)]
     pose = None
     target = read_prepared(files[0][1]) if files else None
     for (i, _), (j, path) in zip(files[:-1], files[1:]):
         source = read_prepared(path)
-        res = register_pair(target, source, pose, max_dist, huber, iters, device)
+        res = None
+        if init != "global":
+            res = register_pair(target, source, pose, max_dist, huber, iters, device)
+        if init == "global" or (init == "auto" and res.status in (2, 3)):
+            g = global_start(target, source, fpfh_radius, ransac_hyp, ransac_thr, seed, device)
+            if init == "auto":
+                report("pair %d %d: global inliers %d of %d status %d" % (i, j, g.inliers, g.correspondences, g.status))
+            res = register_pair(target, source, g.pose, max_dist, huber, iters, device)
         pose = res.pose
         T = pose.cpu().numpy().astype(np.float64)
         report("pair %d %d: pairs %d rmse %.4f iterations %d status %d t %.4f %.4f %.4f r %.4f" % (
@@ -77,6 +102,13 @@ def parse_args(argv=None):
     ap.add_argument("--huber", type=float, default=0.1, help="residuals above this many metres are down-weighted; 0 = off (default 0.1)")
     ap.add_argument("--iters", type=int, default=30, help="most iterations per pair (default 30)")
     ap.add_argument("--out", default=None, help="write the chained poses here, 12 numbers per line")
+    ap.add_argument("--init", default="previous", choices=("previous", "global", "auto"),
+                    help="a pair's start pose: the previous pair's result (default), a global registration from FPFH descriptors and RANSAC, "
+                         "or the first and, when ICP ends with status 2 or 3, the second")
+    ap.add_argument("--fpfh-radius", type=float, default=1.0, help="radius of the FPFH descriptors in metres (default 1.0)")
+    ap.add_argument("--ransac-hyp", type=int, default=4096, help="RANSAC hypotheses of a global registration (default 4096)")
+    ap.add_argument("--ransac-thr", type=float, default=0.3, help="RANSAC inlier distance in metres (default 0.3)")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the RANSAC draws (default 0)")
     args = ap.parse_args(argv)
     if not 0 <= args.sequence <= 99:
         ap.error("--sequence must lie in [0, 99]")
@@ -86,6 +118,14 @@ def parse_args(argv=None):
         ap.error("--huber must be finite and >= 0, got %r" % (args.huber,))
     if not 0 <= args.iters <= ops.ICP_MAX_ITERS:
         ap.error("--iters must lie in [0, %d]" % ops.ICP_MAX_ITERS)
+    if not (0.0 < args.fpfh_radius < float("inf")):
+        ap.error("--fpfh-radius must be finite and > 0, got %r" % (args.fpfh_radius,))
+    if not 1 <= args.ransac_hyp <= ops.RANSAC_MAX_HYP:
+        ap.error("--ransac-hyp must lie in [1, %d]" % ops.RANSAC_MAX_HYP)
+    if not (0.0 < args.ransac_thr < float("inf")):
+        ap.error("--ransac-thr must be finite and > 0, got %r" % (args.ransac_thr,))
+    if not 0 <= args.seed < 1 << 32:
+        ap.error("--seed must lie in [0, 2^32)")
     try:
         a, b = args.frames.split(":")
         args.frames = (int(a) if a else 0, int(b) if b else None)
@@ -120,7 +160,8 @@ def main(argv=None, device=None):
             ap.error("%s holds [4, n] rows and no normals; write [7, n] files with python -m cmr_agent_amd.dataset.prepare "
                      "(without --no-normals)" % path)
     try:
-        chain = align_sequence(files, args.max_dist, args.huber, args.iters, device)
+        chain = align_sequence(files, args.max_dist, args.huber, args.iters, device, init=args.init, fpfh_radius=args.fpfh_radius,
+                               ransac_hyp=args.ransac_hyp, ransac_thr=args.ransac_thr, seed=args.seed)
     except ValueError as e:
         ap.error(str(e))
     if args.out is not None:

@@ -2786,3 +2786,178 @@ def icp_point_to_plane(source, target, target_normals, pose=None, max_dist=1.0, 
     trace = trace.cpu()
     last = trace[executed - 1] if executed else torch.zeros(4, dtype=torch.float64)
     return IcpResult(out, int(last[0]), float(last[1]), executed, code, trace, None if system is None else system.cpu())
+
+
+# ---- registration without a start pose: FPFH, nearest descriptors, RANSAC (csrc/cloud_fpfh.hip, csrc/cloud_global.hip) -------
+FPFH_DIM = 33
+DESCRIPTOR_MAX_WIDTH = 64
+RANSAC_MAX_HYP = 1 << 20
+RANSAC_MAX_CORR = 1 << 24
+RANSAC_STATUS = ("ok", "fewer than 3 correspondences", "no valid hypothesis")
+
+
+class PointFpfh(collections.namedtuple("PointFpfh", "fpfh count spfh")):
+    """point_fpfh's result: fpfh float32 [N, 33], count int32 [N] = the neighbours that take part (the row itself not counted), spfh int32
+    [N, 33] = the row's own three histograms as integer counts (None unless asked for).  All in the input's row order."""
+
+
+class DescriptorNearest(collections.namedtuple("DescriptorNearest", "idx dist2")):
+    """descriptor_nearest's result: idx int32 [M] = the nearest selected target row (-1: none), dist2 float32 [M] (NaN where idx is -1)."""
+
+
+class RansacRigid(collections.namedtuple("RansacRigid", "pose inliers status best hyp_inliers")):
+    """ransac_rigid's result: pose float32 [4, 4] on the device (source -> target); inliers; status 0 .. 2 (RANSAC_STATUS); best = the
+    winning hypothesis (-1 without one); hyp_inliers int32 [n_hyp] on the device, -1 for an invalid hypothesis (None unless asked for)."""
+
+
+class GlobalResult(collections.namedtuple("GlobalResult", "pose inliers correspondences status icp")):
+    """register_global's result: pose float32 [4, 4] on the device; inliers and status of the RANSAC stage; correspondences = the number
+    handed to it; icp = the IcpResult of the polish (None with refine=False or when RANSAC found nothing)."""
+
+
+def point_fpfh(points, normals, radius, index=None, want_spfh=False):
+    """FPFH descriptors of one cloud from its normals (cmr_point_fpfh_f32; the contract is the header's): Open3D's ComputeFPFHFeature with a
+    pure radius search.  points, normals float32 [N, 3]; a row takes part when it is finite and its normal is finite and not zero, any
+    other row gets zeros and is nobody's neighbour.  index: ops.cloud_index(points, cell >= radius), built here with cell = radius when
+    None.  -> PointFpfh.  Two launches; no host read beyond cloud_index's."""
+    who = "point_fpfh"
+    radius = _cloud_scalar(radius, "radius")
+    if index is not None:
+        if not isinstance(index, CloudIndex):
+            raise ValueError("%s: index must be a CloudIndex (ops.cloud_index), got %s" % (who, type(index).__name__))
+        if np.float32(index.cell) < np.float32(radius):
+            raise ValueError("%s: radius %g exceeds the index's cell %g (a neighbour must lie in the row's cell or one next to it)"
+                             % (who, radius, index.cell))
+    points = _cloud_points(points)
+    normals = _cloud_points(normals, "normals")
+    N, dev = points.shape[0], points.device
+    if normals.shape[0] != N or (index is not None and index.n != N):
+        raise ValueError("%s: points has %d rows, normals %d%s" % (who, N, normals.shape[0], "" if index is None else ", the index %d" % index.n))
+    if normals.device != dev or (index is not None and index.pts4.device != dev):
+        raise ValueError("%s: points, normals and the index must be on one device" % who)
+    if index is None and N:
+        index = cloud_index(points, radius)
+    if N == 0 or index.kept == 0:
+        return PointFpfh(torch.zeros((N, FPFH_DIM), dtype=f32, device=dev), torch.zeros((N,), dtype=torch.int32, device=dev),
+                         torch.zeros((N, FPFH_DIM), dtype=torch.int32, device=dev) if want_spfh else None)
+    fpfh = torch.empty((N, FPFH_DIM), dtype=f32, device=dev)
+    count = torch.empty((N,), dtype=torch.int32, device=dev)
+    spfh = torch.empty((N, FPFH_DIM), dtype=torch.int32, device=dev) if want_spfh else None
+    nb = _lib.load().cmr_point_fpfh_workspace_bytes(index.kept)
+    ws = _ws(nb, dev)
+    o = index.origin
+    _lib.call("cmr_point_fpfh_f32", _p(index.pts4), _p(index.keys), _p(index.order), N, index.kept, o[0], o[1], o[2], index.cell, _p(normals),
+              radius, _p(fpfh), _p(count), _p(spfh), _p(ws), nb, _stream())
+    return PointFpfh(fpfh, count, spfh)
+
+
+def _descriptor_rows(who, name, t):
+    if not isinstance(t, torch.Tensor) or t.dtype != f32 or t.dim() != 2 or t.shape[1] < 1:
+        raise ValueError("%s: %s must be a float32 [rows, C >= 1] tensor, got %s %s" % ((who, name) + _got(t)))
+    if t.shape[0] > CLOUD_MAX_ROWS:
+        raise ValueError("%s: %s holds %d rows; at most 2^31 - 1 (int32 row ids)" % (who, name, t.shape[0]))
+    return t
+
+
+def _byte_mask(who, name, m, n):
+    if m is None:
+        return None
+    if not isinstance(m, torch.Tensor) or m.dtype not in (torch.bool, torch.uint8) or tuple(m.shape) != (n,):
+        raise ValueError("%s: %s must be None or bool / uint8 [%d], got %s %s" % ((who, name, n) + _got(m)))
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+def descriptor_nearest(queries, targets, query_mask=None, target_mask=None):
+    """The nearest target descriptor of every query descriptor by brute force (cmr_descriptor_nearest_f32; the contract is the header's):
+    the plain fp32 sum of squared differences in channel order, the lowest row on equal distances -- exact against float32 numpy.  queries
+    float32 [M, C], targets float32 [N, C], C <= 64; masks bool / uint8 [M] / [N] or None = every row.  -> DescriptorNearest; -1 / NaN for an
+    unselected query, a query with a non-finite entry and when no target is selected."""
+    who = "descriptor_nearest"
+    queries = _descriptor_rows(who, "queries", queries)
+    targets = _descriptor_rows(who, "targets", targets)
+    M, C = queries.shape
+    N = targets.shape[0]
+    if targets.shape[1] != C:
+        raise ValueError("%s: queries have %d channels, targets %d" % (who, C, targets.shape[1]))
+    if C > DESCRIPTOR_MAX_WIDTH:
+        raise ValueError("%s: %d channels; the kernel serves at most %d (the entry point answers CMR_EUNSUPPORTED)" % (who, C, DESCRIPTOR_MAX_WIDTH))
+    query_mask = _byte_mask(who, "query_mask", query_mask, M)
+    target_mask = _byte_mask(who, "target_mask", target_mask, N)
+    if not queries.is_cuda:
+        raise ValueError("%s: queries must be a device tensor (there is no CPU path)" % who)
+    queries, targets = queries.contiguous(), targets.contiguous()
+    query_mask = None if query_mask is None else query_mask.contiguous()
+    target_mask = None if target_mask is None else target_mask.contiguous()
+    _on_one_gpu(who, queries, targets, query_mask, target_mask)
+    dev = queries.device
+    if M == 0 or N == 0:
+        return DescriptorNearest(torch.full((M,), -1, dtype=torch.int32, device=dev), torch.full((M,), float("nan"), dtype=f32, device=dev))
+    idx = torch.empty((M,), dtype=torch.int32, device=dev)
+    dist2 = torch.empty((M,), dtype=f32, device=dev)
+    _lib.call("cmr_descriptor_nearest_f32", _p(queries), M, _p(targets), N, C, _p(query_mask), _p(target_mask), _p(idx), _p(dist2), _stream())
+    return DescriptorNearest(idx, dist2)
+
+
+def ransac_rigid(source_pts, target_pts, corr, n_hyp=4096, thr=0.3, edge_ratio=0.9, seed=0, want_hyp_inliers=False):
+    """The rigid transform that most correspondences agree on, by RANSAC over 3-point hypotheses (cmr_ransac_rigid_f32; the contract is the
+    header's).  source_pts float32 [M, 3], target_pts float32 [N, 3], corr int32 [L, 2] = (source row, target row); rows of corr with an
+    index out of range (-1 included) are dropped on the device.  -> RansacRigid.  Everything is enqueued on the stream; the one host read is
+    status / inliers / best."""
+    who = "ransac_rigid"
+    n_hyp = _int_arg(who, "n_hyp", n_hyp, 1, RANSAC_MAX_HYP)
+    thr = _cloud_scalar(thr, "thr")
+    edge_ratio = _f32_arg(who, "edge_ratio", edge_ratio, "be a number in [0, 1]", 0.0, 1.0, bools=False)
+    seed = _int_arg(who, "seed", seed, 0, (1 << 32) - 1)
+    if not isinstance(corr, torch.Tensor) or corr.dtype != torch.int32 or corr.dim() != 2 or corr.shape[1] != 2:
+        raise ValueError("%s: corr must be an int32 [L, 2] tensor, got %s %s" % ((who,) + _got(corr)))
+    L = corr.shape[0]
+    if L > RANSAC_MAX_CORR:
+        raise ValueError("%s: corr holds %d rows; at most 2^24" % (who, L))
+    source_pts = _cloud_points(source_pts, "source_pts")
+    target_pts = _cloud_points(target_pts, "target_pts")
+    corr = corr.contiguous()
+    _on_one_gpu(who, source_pts, target_pts, corr)
+    dev = source_pts.device
+    hyp = torch.full((n_hyp,), -1, dtype=torch.int32, device=dev) if want_hyp_inliers else None
+    if L == 0 or source_pts.shape[0] == 0 or target_pts.shape[0] == 0:
+        return RansacRigid(torch.eye(4, dtype=f32, device=dev), 0, 1, -1, hyp)
+    pose = torch.empty((4, 4), dtype=f32, device=dev)
+    result = torch.empty((3,), dtype=torch.int32, device=dev)
+    nb = _lib.load().cmr_ransac_rigid_workspace_bytes(L, n_hyp)
+    ws = _ws(nb, dev)
+    _lib.call("cmr_ransac_rigid_f32", _p(source_pts), source_pts.shape[0], _p(target_pts), target_pts.shape[0], _p(corr), L, n_hyp, thr,
+              edge_ratio, seed, _p(pose), _p(result), _p(hyp), _p(ws), nb, _stream())
+    inliers, status, best = (int(v) for v in result.cpu())             # the one host read
+    return RansacRigid(pose, inliers, status, best, hyp)
+
+
+def register_global(source, source_normals, target, target_normals, radius=1.0, mutual=True, n_hyp=4096, thr=0.3, edge_ratio=0.9, seed=0,
+                    refine=True, **icp):
+    """One cloud onto another without a start pose: point_fpfh on both, descriptor_nearest source -> target (with `mutual` also target ->
+    source, a correspondence is kept when the two agree; rows without a neighbour are masked out), ransac_rigid on the kept
+    correspondences and, with `refine`, icp_point_to_plane from the RANSAC pose (keywords `icp`, defaults max_dist=1.0, huber=0.1).  ->
+    GlobalResult; pose is the polish's when its status is 0 or 1, RANSAC's otherwise."""
+    who = "register_global"
+    if not isinstance(mutual, bool) or not isinstance(refine, bool):
+        raise ValueError("%s: mutual and refine must be True or False, got %r / %r" % (who, mutual, refine))
+    unknown = set(icp) - {"max_dist", "huber", "iters", "tol_rot", "tol_trans"}
+    if unknown:
+        raise ValueError("%s: unknown keyword(s) %s" % (who, ", ".join(sorted(unknown))))
+    fs = point_fpfh(source, source_normals, radius)
+    ft = point_fpfh(target, target_normals, radius)
+    sm, tm = fs.count > 0, ft.count > 0
+    fwd = descriptor_nearest(fs.fpfh, ft.fpfh, sm, tm)
+    keep = fwd.idx >= 0
+    if mutual and ft.fpfh.shape[0]:
+        back = descriptor_nearest(ft.fpfh, fs.fpfh, tm, sm)
+        rows = torch.arange(fs.fpfh.shape[0], dtype=torch.int32, device=fs.fpfh.device)
+        keep = keep & (back.idx[fwd.idx.clamp(min=0).long()] == rows)
+    src_rows = torch.nonzero(keep).reshape(-1)                          # the compaction: torch plumbing, in row order
+    corr = torch.stack([src_rows.to(torch.int32), fwd.idx[src_rows]], 1).contiguous()
+    rr = ransac_rigid(source, target, corr, n_hyp, thr, edge_ratio, seed)
+    if not refine or rr.status != 0:
+        return GlobalResult(rr.pose, rr.inliers, corr.shape[0], rr.status, None)
+    kw = dict(max_dist=1.0, huber=0.1)
+    kw.update(icp)
+    res = icp_point_to_plane(source, target, target_normals, pose=rr.pose, **kw)
+    return GlobalResult(res.pose if res.status in (0, 1) else rr.pose, rr.inliers, corr.shape[0], rr.status, res)

@@ -290,6 +290,13 @@ WORK = {
     "cmr_cloud_gather4_f32": lambda a: (0, a["kept"] * (12 + 8 + 16)),
     "cmr_cloud_nearest_f32": lambda a: (0, a["M"] * (12 + 8) + a["kept"] * 32),
     "cmr_icp_point_to_plane_f32": lambda a: (250.0 * a["iters"] * a["M"], a["iters"] * (a["M"] * 24 + a["kept"] * 32)),
+    # DESIGN.md 4af.  FPFH: the index and the normals once, the SPFH table written and read, 33 floats of result per row; its ~120 float64
+    # FLOP per neighbour pair are not counted (the pair count is data).  The descriptor sweep is compute: a subtraction, a product and a sum
+    # per pair and channel, unfused by contract.  RANSAC: the three-operation residual of every hypothesis against every list entry in
+    # float64 (~30 FLOP), the list once per 256 hypotheses.
+    "cmr_point_fpfh_f32": lambda a: (0, a["kept"] * (32 + 12 + 2 * 136) + a["N"] * (132 + 4)),
+    "cmr_descriptor_nearest_f32": lambda a: (3.0 * a["M"] * a["N"] * a["C"], F * (a["M"] + a["N"]) * a["C"] + 8 * a["M"]),
+    "cmr_ransac_rigid_f32": lambda a: (30.0 * a["n_hyp"] * a["L"], a["L"] * 8 + (a["n_hyp"] + 255) // 256 * a["L"] * 32 + a["n_hyp"] * 100),
 }
 
 # Multiplies the kernel ISSUES on the matrix cores per algorithmic multiply: F(2x2,3x3) Winograd computes 2x2 outputs with 16

@@ -1410,6 +1410,67 @@ int cmr_icp_point_to_plane_f32(const float* source, int64_t ld, int64_t M, const
                                double* trace, double* system, int32_t* status, void* workspace, int64_t workspace_bytes,
                                hipStream_t stream);
 
+/* ---- registration without a start pose: FPFH descriptors, nearest descriptors, RANSAC over rigid hypotheses (csrc/cloud_fpfh.hip,
+ * csrc/cloud_global.hip) ------------------------------------------------------------------------------------------------
+ * Port extension.  cmr_icp_point_to_plane_f32 needs a start pose inside its basin; these three find one from the clouds alone.
+ *
+ * cmr_point_fpfh_f32: the FPFH descriptor (Rusu 2009; the definition is Open3D's ComputeFPFHFeature with a pure radius search) of every row
+ * of a cloud handed over as a grid index (above: points4, keys_sorted, order, N rows of which kept are in the index, origin, cell) with its
+ * normals [N][3] in the ORIGINAL row order.  0 < radius <= cell.
+ *   rows        row i TAKES PART when it is in the index and its normal is finite and not the zero vector; any other row gets all-zero
+ *               outputs and is nobody's neighbour;
+ *   neighbours  of a row i that takes part: the rows j != i that take part with fp32  (dx dx + dy dy) + dz dz <= radius radius,  d = p_j - p_i
+ *               (cmr_point_normals_f32's test); count[i] = their number k;
+ *   pair        features in fp64 from the fp32 inputs, EVERY +, -, *, / and sqrt rounded on its own, a dot product summed as (x + y) + z:
+ *               d = p_j - p_i, l = sqrt(d . d), l = 0 skips the pair;  a1 = n_i . d / l,  a2 = n_j . d / l;  when |a1| < |a2|:  n1 = n_j,
+ *               n2 = n_i, d <- -d, f3 = -a2;  otherwise n1 = n_i, n2 = n_j, f3 = a1;  v = d x n1, |v| = sqrt(v . v), |v| = 0 skips the pair,
+ *               v <- v / |v|;  w = n1 x v;  f2 = v . n2;  f1 = atan2(w . n2, n1 . n2)  (a x b = (ay bz - az by, az bx - ax bz, ax by - ay bx));
+ *   bins        min(10, max(0, floor(11 x)))  of  x = (f1 + pi) / (2 pi),  (f2 + 1) / 2,  (f3 + 1) / 2  with pi and 2 pi the nearest doubles;
+ *   spfh        int32 [N][33] (or null): per row three groups of 11 INTEGER counts over its pairs that were not skipped;  the SPFH VALUE
+ *               of a row is (100 count) / k in fp64 (k = 0: zero);
+ *   fpfh        float [N][33]:  S[b] = sum over the neighbours j with d2_j > 0 of  value_j[b] / d2_j,  d2 the fp32 number of the
+ *               neighbour test widened, the sum in fp64 in a fixed order (every lane of a 16-lane group adds what it meets in sorted
+ *               order, then a balanced tree over the lanes; no atomics);  per group of 11  tot = the sum of its S in bin order,
+ *               fpfh[b] = fp32(S[b] (100 / tot) + value_i[b]),  with 0 in place of 100 / tot when tot = 0.
+ * Outputs are in the input's row order; two launches (SPFH, FPFH); two calls agree bit for bit.  Workspace of
+ * cmr_point_fpfh_workspace_bytes(kept), 16-byte aligned: the SPFH table. */
+int64_t cmr_point_fpfh_workspace_bytes(int64_t kept);
+int cmr_point_fpfh_f32(const float* points4, const int64_t* keys_sorted, const int64_t* order, int64_t N, int64_t kept, float ox, float oy,
+                       float oz, float cell, const float* normals, float radius, float* fpfh, int32_t* count, int32_t* spfh,
+                       void* workspace, int64_t workspace_bytes, hipStream_t stream);
+/* cmr_descriptor_nearest_f32: for every row of queries [M][C] the nearest row of targets [N][C] by brute force, 0 < C <= 64
+ * (CMR_EUNSUPPORTED above), M, N > 0.  query_mask / target_mask: bytes [M] / [N], non-zero = selected, null = every row.
+ *   d2      in fp32 over c = 0 .. C - 1 in order:  acc = acc + (q_c - t_c) (q_c - t_c),  each operation rounded on its own, from acc = 0;
+ *   idx[i]  the selected target row of least d2, the LOWEST row on equal d2;  a target whose d2 is NaN or infinite is no candidate;
+ *   d2[i]   its d2;  idx = -1 and d2 = NaN for an unselected query, a query with a non-finite entry, and when no target is a candidate.
+ * The targets pass through LDS in tiles; the four waves of a workgroup share 64 queries and split a tile's rows, a lane keeps the least
+ * (d2, row) of its query while its rows go by in ascending order, and the four meet in a lexicographic minimum of (d2, row), so the result
+ * does not depend on the tiling.  Every output is a plain store by its owner. */
+int cmr_descriptor_nearest_f32(const float* queries, int64_t M, const float* targets, int64_t N, int C, const void* query_mask,
+                               const void* target_mask, int32_t* idx, float* d2, hipStream_t stream);
+/* cmr_ransac_rigid_f32: the rigid transform (R, t) with R a + t = b for most of the correspondences corr int32 [L][2] = (row of source
+ * [M][3], row of target [N][3]), 0 < L <= 2^24, by RANSAC over n_hyp (<= 2^20) 3-point hypotheses.  Everything runs on the stream.
+ *   list    the rows of corr with 0 <= source row < M, 0 <= target row < N and finite coordinates on both sides, in corr's order; the
+ *           others are dropped before anything else;  fewer than 3: status 1;
+ *   draws   hypothesis h takes 3 distinct list positions  hash(seed, 0, h, c) % count,  c = 0, 1, ... (at most 32), cmr_pnp_ransac_f32's
+ *           hash;  all that follows is fp64 from the fp32 coordinates;
+ *   checks  h is INVALID (inlier count -1) when it has no 3 distinct draws; when for one of its edges (0-1, 1-2, 2-0) the shorter of the two
+ *           corresponding lengths is below edge_ratio (0 .. 1) times the longer (Open3D's CorrespondenceCheckerBasedOnEdgeLength); when
+ *           the triple is collinear on either side:  |e1 x e2|^2 <= 1e-4 |e1|^2 |e2|^2  for e1, e2 the edges from its first point;
+ *   fit     the (R, t) minimising sum |R a + t - b|^2 over the three pairs with det R = +1 (Horn's unit quaternion: the top eigenvector
+ *           of a symmetric 4 x 4 by cyclic Jacobi, ten sweeps), t = mean b - R mean a;
+ *   inlier  a list entry with  |R a + t - b|^2 <= thr thr,  residual and square in fp64 (thr > 0 widened first);
+ *   best    the valid hypothesis with most inliers, the lowest h on ties;  none valid: status 2;
+ *   refit   the same least squares over best's inlier set -- means, then the centred sums, fp64 in a fixed order without atomics -- and a
+ *           recount of the whole list;  the refit is kept when its count is not below best's.
+ * Outputs: pose fp32 [4][4];  result int32 [3] = {inliers, status, best h (-1 with status 1 or 2)};  hyp_inliers int32 [n_hyp] (or null).
+ * status 0 ok; with 1 and 2 the pose is the identity and inliers 0.  Workspace of cmr_ransac_rigid_workspace_bytes(L, n_hyp), 16-byte
+ * aligned.  Integer counts are added atomically (order free); two calls agree bit for bit. */
+int64_t cmr_ransac_rigid_workspace_bytes(int64_t L, int n_hyp);
+int cmr_ransac_rigid_f32(const float* source, int64_t M, const float* target, int64_t N, const int32_t* corr, int64_t L, int n_hyp,
+                         float thr, float edge_ratio, uint32_t seed, float* pose, int32_t* result, int32_t* hyp_inliers, void* workspace,
+                         int64_t workspace_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

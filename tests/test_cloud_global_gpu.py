@@ -1,0 +1,311 @@
+"""GPU tier of the registration without a start pose (ops.point_fpfh / ops.descriptor_nearest / ops.ransac_rigid / ops.register_global,
+csrc/cloud_fpfh.hip, csrc/cloud_global.hip), against the restatement of cloud_global_reference.py.
+
+SPFH: `count` and the integer histograms are EXACT on every row without an `edge` pair (11 x1 within 1e-9 of an integer, where the two
+atan2 may disagree); on the others the L1 difference is at most 2 per `edge` pair (one count leaves a bin, one enters its neighbour).
+
+FPFH: the second stage is judged alone, fed the device's own counts: every entry within 2^-23 max(1, |entry|) (one rounding to fp32 is
+2^-24 |entry|, the restatement's own rounding may fall on the other side) plus k 2^-52 sum |terms| (two float64 sums of the same k terms in
+different orders are each within (k - 1) 2^-53 sum |terms| of the exact one).  The whole operation is compared on the rows with no `edge`
+row in their neighbourhood, themselves included.
+
+Descriptor nearest: idx and dist2 BIT-EXACT.  RANSAC: hyp_inliers equal on every hypothesis the restatement does not flag; best / inliers /
+pose when best and runner-up are unflagged.  End to end: the bars of the issue, stated at the tests."""
+import numpy as np
+import pytest
+import torch
+
+import cloud_global_reference as G
+import cloud_icp_reference as I
+from cmr_agent_amd import _lib, ops
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+F = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)      # noqa: E731
+SIZES = (1, 2, 15, 16, 17, 255, 256, 257)
+U23 = 2.0 ** -23
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
+
+
+# ---- SPFH and FPFH ----------------------------------------------------------------------------------------------------------------------
+def _check_fpfh(points, normals, radius, cell=None, ref=None):
+    points = np.asarray(points, np.float32).reshape(-1, 3)
+    normals = np.asarray(normals, np.float32).reshape(-1, 3)
+    N = points.shape[0]
+    index = None if cell is None else ops.cloud_index(F(points), cell)
+    got = ops.point_fpfh(F(points), F(normals), radius, index, want_spfh=True)
+    again = ops.point_fpfh(F(points), F(normals), radius, index, want_spfh=True)
+    plain = ops.point_fpfh(F(points), F(normals), radius, index)
+    ref = G.fpfh(points, normals, radius) if ref is None else ref
+    fp, cnt, hist = got.fpfh.cpu().numpy(), got.count.cpu().numpy(), got.spfh.cpu().numpy()
+    assert got.fpfh.dtype == torch.float32 and got.count.dtype == torch.int32 and got.spfh.dtype == torch.int32
+    assert fp.shape == hist.shape == (N, 33) and cnt.shape == (N,) and plain.spfh is None
+    # stage 1
+    assert np.array_equal(cnt, ref["count"]), np.nonzero(cnt != ref["count"])[0][:8]
+    clean = ref["edge"] == 0
+    assert np.array_equal(hist[clean], ref["spfh"][clean]), np.nonzero((hist != ref["spfh"]).any(1) & clean)[0][:8]
+    l1 = np.abs(hist - ref["spfh"]).sum(1)
+    assert (l1 <= 2 * ref["edge"]).all()
+    assert not hist[~ref["part"]].any() and not fp[~ref["part"]].any() and not cnt[~ref["part"]].any()
+    # two calls, bit for bit; want_spfh changes nothing
+    assert np.array_equal(_bits(again.fpfh.cpu().numpy()), _bits(fp)) and np.array_equal(again.spfh.cpu().numpy(), hist)
+    assert np.array_equal(_bits(plain.fpfh.cpu().numpy()), _bits(fp)) and np.array_equal(plain.count.cpu().numpy(), cnt)
+    # stage 2 alone: the restatement fed the device's counts
+    st = G.fpfh_stage(hist, cnt, ref["pairs"], N)
+    bound = U23 * np.maximum(1.0, np.abs(st["fpfh"])) + st["k"][:, None] * 2.0 ** -52 * st["terms"]
+    err = np.abs(fp.astype(np.float64) - st["fpfh"])
+    assert (err <= bound).all(), (err / bound).max()
+    # the whole operation where no `edge` row is near
+    i, j, _ = ref["pairs"]
+    tainted = ref["edge"] > 0
+    tainted[i[ref["edge"][j] > 0]] = True
+    bound = U23 * np.maximum(1.0, np.abs(ref["fpfh"])) + ref["k"][:, None] * 2.0 ** -52 * ref["terms"]
+    assert (np.abs(fp.astype(np.float64) - ref["fpfh"]) <= bound)[~tainted].all()
+    # a group of the neighbours' part sums to 100, or to 0 without a neighbour at a distance > 0
+    part = (fp.astype(np.float64) - st["value"]).reshape(N, 3, 11).sum(2)
+    assert (np.minimum(np.abs(part - 100.0), np.abs(part)) <= 1e-3).all()
+    return got, ref
+
+
+def _random_cloud(seed, n, side=3.0):
+    r = np.random.default_rng(seed)
+    p = r.uniform(0, side, (n, 3)).astype(np.float32)
+    v = r.standard_normal((n, 3))
+    return p, (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32)
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_fpfh_sizes(n):
+    p, v = _random_cloud(100 + n, n)
+    got, ref = _check_fpfh(p, v, 1.0)
+    if n >= 15:
+        assert ref["count"].max() >= 2 and got.fpfh.abs().sum() > 0
+
+
+def test_fpfh_scene_pair():
+    case = I.pair_case()
+    got, ref = _check_fpfh(case["target"], case["normals"], G.RADIUS, ref=G.target_features())
+    assert ref["part"].sum() == 4447 and ref["count"].max() > 256
+    g = G.global_case("other", 3)
+    _check_fpfh(g["source"], g["source_normals"], G.RADIUS, ref=g["feat"])
+
+
+def test_fpfh_neighbours_on_the_radius_duplicates_and_a_larger_cell():
+    g = np.stack(np.meshgrid(np.arange(5), np.arange(5), np.arange(3), indexing="ij"), -1).reshape(-1, 3)
+    _, v = _random_cloud(7, g.shape[0])
+    for spacing in (1.0, 0.3):
+        for off in (0.0, 0.1, 1000.0):
+            pts = (g * np.float32(spacing) + np.float32(off)).astype(np.float32)
+            _, ref = _check_fpfh(pts, v, spacing)
+            if spacing == 1.0 and off == 0.0:
+                assert ref["count"].max() == 6 and ref["count"].min() == 3            # the lattice neighbours lie ON the radius
+    p, v = _random_cloud(8, 200)
+    dup = np.concatenate([p, p[:40], p[:10]])
+    dv = np.concatenate([v, v[40:80], v[:10]])
+    _, ref = _check_fpfh(dup, dv, 1.0)
+    assert (ref["pairs"][2] == 0).sum() >= 100
+    for cell in (1.0, 1.5, 4.0):
+        _check_fpfh(p, v, 1.0, cell=cell)
+    _check_fpfh(p, v, 0.75, cell=1.0)
+    with pytest.raises(ValueError, match="exceeds the index's cell"):
+        ops.point_fpfh(F(p), F(v), 1.0, ops.cloud_index(F(p), 0.5))
+
+
+def test_fpfh_rows_that_take_no_part():
+    p, v = _random_cloud(9, 300)
+    p[5], p[17, 1], p[100, 2] = np.nan, np.inf, -np.inf
+    v[8], v[30, 0], v[31, 2] = np.nan, np.inf, np.nan
+    v[40:60] = 0.0
+    got, ref = _check_fpfh(p, v, 1.0)
+    assert (~ref["part"]).sum() == 26 and ref["count"][ref["part"]].min() > 0
+    got, _ = _check_fpfh(p, np.zeros_like(v), 1.0)                                        # nobody takes part
+    assert not got.fpfh.any() and not got.count.any()
+    got = ops.point_fpfh(F(np.full((4, 3), np.nan)), F(v[:4]), 1.0, want_spfh=True)       # no finite row: no launch
+    assert not got.fpfh.any() and got.spfh.shape == (4, 33)
+
+
+# ---- nearest descriptor -----------------------------------------------------------------------------------------------------------------
+def _check_desc(q, t, qm=None, tm=None):
+    B = lambda m: None if m is None else torch.from_numpy(m).to(DEV)                      # noqa: E731
+    got = ops.descriptor_nearest(F(q), F(t), B(qm), B(tm))
+    ref_idx, ref_d2 = G.descriptor_nearest(q, t, qm, tm)
+    idx, d2 = got.idx.cpu().numpy(), got.dist2.cpu().numpy()
+    assert got.idx.dtype == torch.int32 and got.dist2.dtype == torch.float32 and idx.shape == d2.shape == (q.shape[0],)
+    assert np.array_equal(idx, ref_idx), np.nonzero(idx != ref_idx)[0][:8]
+    assert np.array_equal(np.isnan(d2), ref_idx < 0)
+    assert np.array_equal(_bits(d2)[ref_idx >= 0], _bits(ref_d2)[ref_idx >= 0])
+    return idx
+
+
+@pytest.mark.parametrize("C", (1, 33, 64))
+def test_descriptor_nearest_shapes_ties_and_masks(C):
+    r = np.random.default_rng(C)
+    shapes = (1, 2, 63, 64, 65, 257)
+    ties = 0
+    for M in shapes:
+        for N in shapes:
+            q = r.uniform(0, 100, (M, C)).astype(np.float32)
+            t = r.uniform(0, 100, (N, C)).astype(np.float32)
+            _check_desc(q, t)
+            # few distinct values: equal distances everywhere, the lowest row must win
+            qi = r.integers(0, 3, (M, C)).astype(np.float32)
+            ti = r.integers(0, 3, (N, C)).astype(np.float32)
+            if N > 2:
+                ti[N // 2:] = ti[:N - N // 2]                                            # every row of the first half has a twin further down
+            idx = _check_desc(qi, ti)
+            ties += int((idx < N // 2).sum()) if N > 2 else 0
+            qm, tm = r.uniform(size=M) < 0.7, r.uniform(size=N) < 0.5
+            _check_desc(q, t, qm, tm)
+            _check_desc(qi, ti, qm.astype(np.uint8), tm.astype(np.uint8))
+            _check_desc(q, t, None, np.zeros(N, bool))                                   # nothing selected
+    assert ties > 100
+
+
+def test_descriptor_nearest_special_values_and_limits():
+    r = np.random.default_rng(3)
+    q = r.uniform(0, 1, (70, 33)).astype(np.float32)
+    t = r.uniform(0, 1, (130, 33)).astype(np.float32)
+    q[3, 5], q[9, 32], q[11, 0] = np.nan, np.inf, -np.inf
+    t[7, 2], t[64, 30] = np.nan, np.inf                                                   # never a candidate
+    idx = _check_desc(q, t)
+    assert idx[3] == idx[9] == idx[11] == -1 and 7 not in idx and 64 not in idx
+    big = np.full((2, 33), 3e38, np.float32)                                              # every d2 overflows: no candidate
+    assert _check_desc(-big, big).tolist() == [-1, -1]
+    e = ops.descriptor_nearest(F(q), F(t[:0]))                                            # an empty target
+    assert e.idx.tolist() == [-1] * 70 and e.dist2.isnan().all()
+    e = ops.descriptor_nearest(F(q[:0]), F(t))
+    assert e.idx.shape == (0,) and e.idx.dtype == torch.int32
+    with pytest.raises(ValueError, match="at most 64"):
+        ops.descriptor_nearest(F(np.zeros((4, 65))), F(np.zeros((4, 65))))
+    a, out, d2 = F(np.zeros((4, 65))), torch.zeros(4, dtype=torch.int32, device=DEV), torch.zeros(4, device=DEV)
+    rc = _lib.load().cmr_descriptor_nearest_f32(a.data_ptr(), 4, a.data_ptr(), 4, 65, None, None, out.data_ptr(), d2.data_ptr(), None)
+    assert rc == _lib.UNSUPPORTED
+
+
+def test_descriptor_nearest_on_the_scene_descriptors():
+    g, ft = G.global_case("other", 3), G.target_features()
+    sm, tm = g["feat"]["count"] > 0, ft["count"] > 0
+    fwd = _check_desc(g["feat"]["fpfh32"], ft["fpfh32"], sm, tm)
+    assert (fwd >= 0).sum() == sm.sum()
+
+
+# ---- RANSAC -----------------------------------------------------------------------------------------------------------------------------
+def _check_ransac(source, target, corr, n_hyp=4096, seed=0, ref=None, **kw):
+    c = torch.from_numpy(np.ascontiguousarray(corr, dtype=np.int32)).to(DEV)
+    got = ops.ransac_rigid(F(source), F(target), c, n_hyp=n_hyp, seed=seed, want_hyp_inliers=True, **kw)
+    again = ops.ransac_rigid(F(source), F(target), c, n_hyp=n_hyp, seed=seed, want_hyp_inliers=True, **kw)
+    ref = G.ransac(source, target, corr, n_hyp=n_hyp, seed=seed, **kw) if ref is None else ref
+    hyp = got.hyp_inliers.cpu().numpy()
+    pose = got.pose.cpu().numpy()
+    assert got.pose.dtype == torch.float32 and pose.shape == (4, 4) and hyp.shape == (n_hyp,) and got.hyp_inliers.dtype == torch.int32
+    assert np.array_equal(_bits(again.pose.cpu().numpy()), _bits(pose)) and np.array_equal(again.hyp_inliers.cpu().numpy(), hyp)
+    assert (again.inliers, again.status, again.best) == (got.inliers, got.status, got.best)
+    clean = ~ref["edge"]
+    assert np.array_equal(hyp[clean], ref["hyp_inliers"][clean]), np.nonzero((hyp != ref["hyp_inliers"]) & clean)[0][:8]
+    assert got.status == ref["status"]
+    if ref["status"] != 0:
+        assert got.inliers == 0 and got.best == -1 and np.array_equal(pose, np.eye(4, dtype=np.float32))
+    elif clean[ref["best"]] and (ref["runner_up"] < 0 or clean[ref["runner_up"]]):
+        assert got.best == ref["best"]
+        if not ref["refit_edge"]:
+            assert got.inliers == ref["inliers"]
+            assert (np.abs(pose.astype(np.float64) - ref["pose"]) <= U23 * np.maximum(1.0, np.abs(ref["pose"]))).all()
+    return got, ref
+
+
+@pytest.mark.parametrize("seed", G.SEEDS[:2])
+def test_ransac_on_the_far_pose(seed):
+    g, case = G.global_case("other", 3), I.pair_case()
+    got, ref = _check_ransac(g["source"], case["target"], g["corr"], seed=seed, ref=G.ransac_case("other", 3, seed))
+    rot, trans = I.pose_error(got.pose.cpu().numpy(), g["truth"])
+    print("seed %d: L %d valid %d inliers %d best %d error %.4f rad %.4f m" % (seed, len(g["corr"]), (ref["hyp_inliers"] >= 0).sum(),
+                                                                                 got.inliers, got.best, rot, trans))
+    assert got.status == 0 and rot <= G.BAR_ROT and trans <= G.BAR_TRANS and ref["edge"].mean() <= 0.01
+
+
+def test_ransac_depends_on_the_seed_and_keeps_the_list_order():
+    g, case = G.global_case("other", 3), I.pair_case()
+    a, _ = _check_ransac(g["source"], case["target"], g["corr"], n_hyp=512, seed=0)
+    b, _ = _check_ransac(g["source"], case["target"], g["corr"], n_hyp=512, seed=7)
+    assert not np.array_equal(a.hyp_inliers.cpu().numpy(), b.hyp_inliers.cpu().numpy())
+    # rows out of range and -1 are dropped before anything else: the same draws, the same result
+    corr = g["corr"]
+    M, N = g["source"].shape[0], case["target"].shape[0]
+    junk = np.array([[-1, 0], [0, -1], [M, 0], [0, N], [2 ** 31 - 1, 3], [-2 ** 31, 3]], dtype=np.int32)
+    mixed = np.concatenate([junk[:2], corr[:500], junk[2:4], corr[500:], junk[4:]])
+    c, _ = _check_ransac(g["source"], case["target"], mixed, n_hyp=512, seed=0)
+    assert np.array_equal(c.hyp_inliers.cpu().numpy(), a.hyp_inliers.cpu().numpy())
+    assert np.array_equal(_bits(c.pose.cpu().numpy()), _bits(a.pose.cpu().numpy()))
+
+
+@pytest.mark.parametrize("L", (3, 4, 1281))
+def test_ransac_list_lengths(L):
+    g, case = G.global_case("other", 3), I.pair_case()
+    corr = g["corr"]
+    res = np.linalg.norm(g["source"][corr[:, 0]].astype(np.float64) @ g["truth"][:3, :3].T + g["truth"][:3, 3]
+                         - case["target"][corr[:, 1]], axis=1)
+    good = corr[np.argsort(res, kind="stable")]
+    assert len(corr) >= 1281
+    sub = corr[:L] if L > 4 else good[[0, 80, 160, 240][:L]]
+    got, ref = _check_ransac(g["source"], case["target"], sub, n_hyp=256, seed=1)
+    assert ref["count"] == L and (got.status != 0 or got.inliers >= 3)
+
+
+def test_ransac_status_one_and_two():
+    r = np.random.default_rng(5)
+    s, t = r.uniform(0, 5, (40, 3)).astype(np.float32), r.uniform(0, 5, (40, 3)).astype(np.float32)
+    two = np.array([[0, 0], [1, 1]], dtype=np.int32)
+    got, _ = _check_ransac(s, t, two, n_hyp=64)
+    assert got.status == 1
+    got, _ = _check_ransac(s, t, np.array([[0, 0], [1, 1], [-1, 2], [40, 3]], dtype=np.int32), n_hyp=64)      # two are left
+    assert got.status == 1
+    e = ops.ransac_rigid(F(s), F(t), torch.zeros((0, 2), dtype=torch.int32, device=DEV), want_hyp_inliers=True)
+    assert e.status == 1 and e.inliers == 0 and e.best == -1 and (e.hyp_inliers == -1).all() and torch.equal(e.pose.cpu(), torch.eye(4))
+    line = np.stack([np.arange(40), np.zeros(40), np.zeros(40)], 1).astype(np.float32)                        # every triple is collinear
+    got, _ = _check_ransac(line, line, np.stack([np.arange(40), np.arange(40)], 1), n_hyp=64)
+    assert got.status == 2
+    got, _ = _check_ransac(s, (2 * s).astype(np.float32), np.stack([np.arange(40), np.arange(40)], 1), n_hyp=64)   # every edge is doubled
+    assert got.status == 2
+    got, _ = _check_ransac(s, (2 * s).astype(np.float32), np.stack([np.arange(40), np.arange(40)], 1), n_hyp=64, edge_ratio=0.5, thr=10.0)
+    assert got.status == 0
+
+
+# ---- end to end -------------------------------------------------------------------------------------------------------------------------
+def _register(kind, k, **kw):
+    g, case = G.global_case(kind, k), I.pair_case()
+    return g, ops.register_global(F(g["source"]), F(g["source_normals"]), F(case["target"]), F(case["normals"]), radius=G.RADIUS, **kw)
+
+
+def test_todays_icp_alone_fails_on_the_far_pose():
+    g, case = G.global_case("other", 3), I.pair_case()
+    res = ops.icp_point_to_plane(F(g["source"]), F(case["target"]), F(case["normals"]), max_dist=1.0, huber=0.1)
+    rot, _ = I.pose_error(res.pose.cpu().numpy(), g["truth"])
+    assert res.status == 2 or rot > 1.0
+
+
+@pytest.mark.parametrize("k", range(4))
+def test_register_global_other_cloud(k):
+    g, got = _register("other", k, refine=False)
+    rot, trans = I.pose_error(got.pose.cpu().numpy(), g["truth"])
+    print("other %d: correspondences %d (restatement %d) inliers %d RANSAC error %.4f rad %.4f m" % (
+        k, got.correspondences, len(g["corr"]), got.inliers, rot, trans))
+    assert got.status == 0 and got.icp is None and rot <= G.BAR_ROT and trans <= G.BAR_TRANS
+    g, got = _register("other", k)
+    ref = G.refined_case("other", k)
+    ref_rot, ref_trans = I.pose_error(ref["pose"], g["truth"])
+    rot, trans = I.pose_error(got.pose.cpu().numpy(), ref["pose"])
+    print("other %d: ICP status %d iterations %d (restatement %d)  to the restatement %.3g rad %.3g m = %.4f / %.4f of its error to the truth"
+          % (k, got.icp.status, got.icp.iterations, ref["iterations"], rot, trans, rot / ref_rot, trans / ref_trans))
+    assert got.icp.status == 0 and ref["status"] == 0 and torch.equal(got.pose, got.icp.pose)
+    assert rot <= 0.1 * ref_rot and trans <= 0.1 * ref_trans
+
+
+def test_register_global_same_cloud():
+    g, got = _register("same", 3, huber=0.0)
+    rot, trans = I.pose_error(got.pose.cpu().numpy(), g["truth"])
+    print("same: correspondences %d inliers %d ICP status %d iterations %d error %.3g rad %.3g m" % (
+        got.correspondences, got.inliers, got.icp.status, got.icp.iterations, rot, trans))
+    assert got.status == 0 and got.icp.status == 0 and rot <= 1e-5 and trans <= 1e-5
