@@ -1,7 +1,7 @@
 // FPFH descriptors of a prepared cloud on the sorted-key grid (port extension): Open3D's ComputeFPFHFeature with a pure radius
 // search, from the normals every prepared file carries.  The cloud is a grid index as ops.cloud_index builds it (cmr_cloud_grid.h), cell >=
-// radius, so a row's neighbours lie in its own cell or one next to it; the walk is point_normals_kernel's: one 16-lane group per row in key
-// order, one run of sorted rows per (z, y) pair of cells.
+// radius, so a row's neighbours lie in its own cell or one next to it; both kernels walk them with walk16 of cmr_cloud_grid.h: one 16-lane
+// group per row in key order, one run of sorted rows per (z, y) pair of cells.
 //
 //   cmr_point_fpfh_f32   two launches on the caller's stream:
 //     spfh_kernel   per row: its neighbours' pair features in fp64 (every operation rounded on its own), binned into 3 x 11 INTEGER counts --
@@ -18,15 +18,9 @@ constexpr int FP_BINS = 11;
 constexpr int FP_DIM = 3 * FP_BINS;
 constexpr int FP_GROUPS = 16;        // 16-lane groups (rows) per workgroup
 
-// the run of sorted rows behind the cells [xlo, xhi] of one (y, z) pair
-__device__ __forceinline__ void cell_run(const int64_t* __restrict__ keys, int64_t kept, int xlo, int xhi, int yy, int zz, int64_t& b, int64_t& e) {
-  b = key_bound(keys, kept, pack_key(xlo, yy, zz), false);
-  e = b + key_bound(keys + b, kept - b, pack_key(xhi, yy, zz), true);
-}
-
 // a row takes part when its normal is finite and not the zero vector
 __device__ __forceinline__ bool takes_part(float nx, float ny, float nz) {
-  return isfinite(nx) && isfinite(ny) && isfinite(nz) && (nx != 0.f || ny != 0.f || nz != 0.f);
+  return cmr_finite3(nx, ny, nz) && (nx != 0.f || ny != 0.f || nz != 0.f);
 }
 
 __device__ __forceinline__ double dot3(double ax, double ay, double az, double bx, double by, double bz) {
@@ -66,25 +60,9 @@ __device__ __forceinline__ bool pair_bins(const f32x4& pi, float nix, float niy,
   return true;
 }
 
-struct Walk {                        // the cells round a row, uniform over its 16-lane group
-  int xlo, xhi, ylo, ny, zlo, nruns;
-};
-__device__ __forceinline__ Walk walk_of(const f32x4& p, bool live, float ox, float oy, float oz, float cell) {
-  Walk w;
-  int yhi, zhi;
-  axis_cells(p.x, ox, cell, w.xlo, w.xhi);
-  axis_cells(p.y, oy, cell, w.ylo, yhi);
-  axis_cells(p.z, oz, cell, w.zlo, zhi);
-  w.ny = yhi - w.ylo + 1;
-  w.nruns = live ? w.ny * (zhi - w.zlo + 1) : 0;
-  return w;
-}
-
 // ------------------------------------------------------------------------------------------------------------------------------ SPFH
 // table[q] (key order) = 33 counts, tcount[q] = k, or -1 for a row that takes no part.  Rows q in [kept, N) are the dropped ones: zeros.
-__global__ __launch_bounds__(256) void spfh_kernel(const f32x4* __restrict__ pts4, const int64_t* __restrict__ keys,
-                                                   const int64_t* __restrict__ order, int64_t N, int64_t kept,
-                                                   const float* __restrict__ normals, float ox, float oy, float oz, float cell, float radius,
+__global__ __launch_bounds__(256) void spfh_kernel(GridIndex index, int64_t N, const float* __restrict__ normals, float radius,
                                                    int32_t* __restrict__ table, int32_t* __restrict__ tcount, int32_t* __restrict__ count,
                                                    int32_t* __restrict__ spfh) {
   __shared__ int hist[FP_GROUPS][FP_DIM];
@@ -92,37 +70,28 @@ __global__ __launch_bounds__(256) void spfh_kernel(const f32x4* __restrict__ pts
   const int64_t q = (int64_t)blockIdx.x * FP_GROUPS + g;
   for (int b = lane; b < FP_DIM; b += 16) hist[g][b] = 0;
   __syncthreads();
-  const bool inidx = q < kept;
-  const f32x4 p = pts4[inidx ? q : 0];
-  const int64_t row = q < N ? order[q] : 0;
+  const bool inidx = q < index.kept;
+  const f32x4 p = index.pts4[inidx ? q : 0];
+  const int64_t row = q < N ? index.order[q] : 0;
   const float nx = normals[row * 3], ny = normals[row * 3 + 1], nz = normals[row * 3 + 2];
   const bool live = inidx && takes_part(nx, ny, nz);
-  const Walk w = walk_of(p, live, ox, oy, oz, cell);
+  const Walk w(p, live, index);
   const float r2 = radius * radius;
   int k = 0;
-  for (int base = 0; base < w.nruns; base += 16) {
-    int64_t b = 0, e = 0;                                           // lane r of the group finds run base + r
-    if (base + lane < w.nruns) cell_run(keys, kept, w.xlo, w.xhi, w.ylo + (base + lane) % w.ny, w.zlo + (base + lane) / w.ny, b, e);
-    const int here = w.nruns - base < 16 ? w.nruns - base : 16;
-    for (int r = 0; r < here; ++r) {
-      const int64_t rb = __shfl(b, r, 16), re = __shfl(e, r, 16);
-      for (int64_t j = rb + lane; j < re; j += 16) {
-        if (j == q) continue;
-        const f32x4 c = pts4[j];
-        if (!within(c.x - p.x, c.y - p.y, c.z - p.z, r2)) continue;
-        const int64_t jr = order[j];
-        const float mx = normals[jr * 3], my = normals[jr * 3 + 1], mz = normals[jr * 3 + 2];
-        if (!takes_part(mx, my, mz)) continue;
-        ++k;
-        int b1, b2, b3;
-        if (pair_bins(p, nx, ny, nz, c, mx, my, mz, b1, b2, b3)) {
-          atomicAdd(&hist[g][b1], 1);
-          atomicAdd(&hist[g][FP_BINS + b2], 1);
-          atomicAdd(&hist[g][2 * FP_BINS + b3], 1);
-        }
-      }
+  walk16(index, w, lane, [&](int64_t j, const f32x4& c) {
+    if (j == q) return;
+    if (!within(c.x - p.x, c.y - p.y, c.z - p.z, r2)) return;
+    const int64_t jr = index.order[j];
+    const float mx = normals[jr * 3], my = normals[jr * 3 + 1], mz = normals[jr * 3 + 2];
+    if (!takes_part(mx, my, mz)) return;
+    ++k;
+    int b1, b2, b3;
+    if (pair_bins(p, nx, ny, nz, c, mx, my, mz, b1, b2, b3)) {
+      atomicAdd(&hist[g][b1], 1);
+      atomicAdd(&hist[g][FP_BINS + b2], 1);
+      atomicAdd(&hist[g][2 * FP_BINS + b3], 1);
     }
-  }
+  });
   k = isum16(k);
   asm volatile("" : "+v"(k));
   __syncthreads();
@@ -143,42 +112,31 @@ __device__ __forceinline__ double spfh_value(int c, int k) {
   return (100.0 * (double)c) / (double)k;
 }
 
-__global__ __launch_bounds__(256) void fpfh_kernel(const f32x4* __restrict__ pts4, const int64_t* __restrict__ keys,
-                                                   const int64_t* __restrict__ order, int64_t N, int64_t kept, float ox, float oy, float oz,
-                                                   float cell, float radius, const int32_t* __restrict__ table,
+__global__ __launch_bounds__(256) void fpfh_kernel(GridIndex index, int64_t N, float radius, const int32_t* __restrict__ table,
                                                    const int32_t* __restrict__ tcount, float* __restrict__ fpfh) {
 #pragma clang fp contract(off)
   const int lane = threadIdx.x & 15;
   const int64_t q = (int64_t)blockIdx.x * FP_GROUPS + (threadIdx.x >> 4);
-  const bool inidx = q < kept;
-  const f32x4 p = pts4[inidx ? q : 0];
+  const bool inidx = q < index.kept;
+  const f32x4 p = index.pts4[inidx ? q : 0];
   const int kq = inidx ? tcount[q] : -1;
-  const Walk w = walk_of(p, kq > 0, ox, oy, oz, cell);             // a row without neighbours has nothing to add
+  const Walk w(p, kq > 0, index);                                  // a row without neighbours has nothing to add
   const float r2 = radius * radius;
   double s[FP_DIM];
 #pragma unroll
   for (int b = 0; b < FP_DIM; ++b) s[b] = 0.0;
-  for (int base = 0; base < w.nruns; base += 16) {
-    int64_t b = 0, e = 0;
-    if (base + lane < w.nruns) cell_run(keys, kept, w.xlo, w.xhi, w.ylo + (base + lane) % w.ny, w.zlo + (base + lane) / w.ny, b, e);
-    const int here = w.nruns - base < 16 ? w.nruns - base : 16;
-    for (int r = 0; r < here; ++r) {
-      const int64_t rb = __shfl(b, r, 16), re = __shfl(e, r, 16);
-      for (int64_t j = rb + lane; j < re; j += 16) {
-        if (j == q) continue;
-        const f32x4 c = pts4[j];
-        const float dx = c.x - p.x, dy = c.y - p.y, dz = c.z - p.z;
-        if (!within(dx, dy, dz, r2)) continue;
-        const float d2 = (dx * dx + dy * dy) + dz * dz;
-        const int kj = tcount[j];
-        if (kj <= 0 || !(d2 > 0.f)) continue;                       // takes no part (a neighbour of q has k >= 1: q itself), or d2 = 0
-        const double D2 = (double)d2;
-        const int32_t* t = table + j * FP_DIM;
+  walk16(index, w, lane, [&](int64_t j, const f32x4& c) {
+    if (j == q) return;
+    const float dx = c.x - p.x, dy = c.y - p.y, dz = c.z - p.z;
+    if (!within(dx, dy, dz, r2)) return;
+    const float d2 = dist2(dx, dy, dz);
+    const int kj = tcount[j];
+    if (kj <= 0 || !(d2 > 0.f)) return;                             // takes no part (a neighbour of q has k >= 1: q itself), or d2 = 0
+    const double D2 = (double)d2;
+    const int32_t* t = table + j * FP_DIM;
 #pragma unroll
-        for (int bb = 0; bb < FP_DIM; ++bb) s[bb] += spfh_value(t[bb], kj) / D2;
-      }
-    }
-  }
+    for (int bb = 0; bb < FP_DIM; ++bb) s[bb] += spfh_value(t[bb], kj) / D2;
+  });
   // every lane of the wave is here again: the balanced tree over the 16 lanes
 #pragma unroll
   for (int bb = 0; bb < FP_DIM; ++bb) {
@@ -186,7 +144,7 @@ __global__ __launch_bounds__(256) void fpfh_kernel(const f32x4* __restrict__ pts
     for (int o = 1; o < 16; o <<= 1) s[bb] += __shfl_xor(s[bb], o, 16);
   }
   if (lane != 0 || q >= N) return;
-  float* out = fpfh + order[q] * FP_DIM;
+  float* out = fpfh + index.order[q] * FP_DIM;
 #pragma unroll
   for (int grp = 0; grp < 3; ++grp) {
     double tot = 0.0;
@@ -209,15 +167,15 @@ extern "C" int64_t cmr_point_fpfh_workspace_bytes(int64_t kept) { return kept > 
 extern "C" int cmr_point_fpfh_f32(const float* points4, const int64_t* keys_sorted, const int64_t* order, int64_t N, int64_t kept, float ox,
                                   float oy, float oz, float cell, const float* normals, float radius, float* fpfh, int32_t* count,
                                   int32_t* spfh, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
-  CMR_REQUIRE(points4 && keys_sorted && order && normals && fpfh && count && workspace && cmr_aligned16(points4) && cmr_aligned16(workspace));
-  CMR_REQUIRE(N > 0 && N < ((int64_t)1 << 31) && kept > 0 && kept <= N && isfinite(ox) && isfinite(oy) && isfinite(oz) && cell > 0.f &&
-              isfinite(cell) && radius > 0.f && radius <= cell && workspace_bytes >= cmr_point_fpfh_workspace_bytes(kept));
+  const GridIndex index{(const f32x4*)points4, keys_sorted, order, kept, ox, oy, oz, cell};
+  CMR_REQUIRE(grid_index_ok(index) && normals && fpfh && count && workspace && cmr_aligned16(workspace));
+  CMR_REQUIRE(N > 0 && N < ((int64_t)1 << 31) && kept <= N && radius > 0.f && radius <= cell &&
+              workspace_bytes >= cmr_point_fpfh_workspace_bytes(kept));
   int32_t* table = (int32_t*)workspace;
   int32_t* tcount = (int32_t*)((char*)workspace + cmr_up16(kept * FP_DIM * 4));
   const unsigned blocks = (unsigned)((N + FP_GROUPS - 1) / FP_GROUPS);
-  hipLaunchKernelGGL(spfh_kernel, dim3(blocks), dim3(256), 0, stream, (const f32x4*)points4, keys_sorted, order, N, kept, normals, ox, oy, oz,
-                     cell, radius, table, tcount, count, spfh);
-  hipLaunchKernelGGL(fpfh_kernel, dim3(blocks), dim3(256), 0, stream, (const f32x4*)points4, keys_sorted, order, N, kept, ox, oy, oz, cell,
-                     radius, (const int32_t*)table, (const int32_t*)tcount, fpfh);
+  hipLaunchKernelGGL(spfh_kernel, dim3(blocks), dim3(256), 0, stream, index, N, normals, radius, table, tcount, count, spfh);
+  hipLaunchKernelGGL(fpfh_kernel, dim3(blocks), dim3(256), 0, stream, index, N, radius, (const int32_t*)table,
+                     (const int32_t*)tcount, fpfh);
   return cmr_launch_status();
 }

@@ -9,11 +9,13 @@
 //   cmr_ransac_rigid_f32         four launches on the caller's stream:
 //     rr_pack_kernel     one workgroup: the valid rows of corr IN LIST ORDER (draws index the list) as two float4 planes, and their count;
 //     rr_hyp_kernel      one lane per hypothesis: 3 hashed draws (pnp_hash of cmr_pnp.h), the edge-length and collinearity checks, the
-//                        least-squares rigid transform of the three pairs in fp64 (Horn's quaternion, a 4 x 4 Jacobi eigen-solve);
+//                        least-squares rigid transform of the three pairs in fp64 (Horn's quaternion, a 4 x 4 Jacobi eigen-solve on
+//                        cmr_jacobi_rotate of cmr_common.h);
 //     rr_score_kernel    a workgroup = 256 hypotheses x one 512-entry slice of the list staged in LDS; INTEGER partial counts added
 //                        atomically (order free, exact);
 //     rr_select_kernel   one workgroup: most inliers, ties to the lowest hypothesis; the same least squares over its inlier set, fp64 sums in
-//                        a fixed order (thread t adds entries t, t + 256, ..., then a tree over the threads); recount; outputs.
+//                        a fixed order (thread t adds entries t, t + 256, ..., then a tree over the threads); recount; outputs (the
+//                        pose's fp32 4x4 form is cmr_pose_entry of cmr_pnp.h).
 #include "cmr_cloud_grid.h"
 #include "cmr_pnp.h"
 
@@ -115,8 +117,6 @@ constexpr int RR_MAX_DRAWS = 32;     // hash counters a hypothesis may use for i
 constexpr int RR_JACOBI_SWEEPS = 10; // cyclic Jacobi on a 4 x 4 in fp64: six sweeps reach the last bit, ten are fixed
 constexpr double RR_COLLINEAR = 1e-4;  // a triple is collinear when sin^2 of the angle at its first point is at most this, on either side
 
-__device__ __forceinline__ bool rr_finite(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
 // The valid rows of corr in list order.  One workgroup walks the list 1024 rows at a time: ballot ranks inside a wave, the 16 wave counts
 // through LDS.
 __global__ __launch_bounds__(RR_PACK_THREADS) void rr_pack_kernel(const float* __restrict__ src, int64_t M, const float* __restrict__ tgt,
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(RR_PACK_THREADS) void rr_pack_kernel(const float* _
       if (s >= 0 && s < M && t >= 0 && t < N) {
         a = f32x4{src[3 * (int64_t)s], src[3 * (int64_t)s + 1], src[3 * (int64_t)s + 2], 0.f};
         b = f32x4{tgt[3 * (int64_t)t], tgt[3 * (int64_t)t + 1], tgt[3 * (int64_t)t + 2], 0.f};
-        ok = rr_finite(a.x, a.y, a.z) && rr_finite(b.x, b.y, b.z);
+        ok = cmr_finite3(a.x, a.y, a.z) && cmr_finite3(b.x, b.y, b.z);
       }
     }
     const unsigned long long bal = __ballot(ok);
@@ -162,31 +162,6 @@ __device__ __forceinline__ V3d sub(const V3d& a, const V3d& b) { return V3d{a.x 
 __device__ __forceinline__ double dot(const V3d& a, const V3d& b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ V3d cross(const V3d& a, const V3d& b) { return V3d{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 
-template <int P, int Q>
-__device__ __forceinline__ void jacobi4_rotate(double (&a)[4][4], double (&v)[4][4]) {
-  const double apq = a[P][Q];
-  if (apq == 0.0) return;
-  const double theta = (a[Q][Q] - a[P][P]) / (2.0 * apq);
-  const double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-  a[P][P] -= t * apq;
-  a[Q][Q] += t * apq;
-  a[P][Q] = a[Q][P] = 0.0;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    if (r == P || r == Q) continue;
-    const double arp = a[r][P], arq = a[r][Q];
-    a[r][P] = a[P][r] = c * arp - s * arq;
-    a[r][Q] = a[Q][r] = s * arp + c * arq;
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double vp = v[k][P], vq = v[k][Q];
-    v[k][P] = c * vp - s * vq;
-    v[k][Q] = s * vp + c * vq;
-  }
-}
-
 // The rotation R (row-major) maximising trace(R S^T) over det R = +1 for S = sum a b^T (centred), i.e. minimising sum |R a - b|^2: Horn's
 // unit quaternion, the eigenvector of the largest eigenvalue of a symmetric 4 x 4.  Proper for a rank-2 S (three pairs) as for a full one.
 __device__ void rr_rotation(const double (&S)[3][3], double (&R)[9]) {
@@ -206,12 +181,12 @@ __device__ void rr_rotation(const double (&S)[3][3], double (&R)[9]) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[i][j] = i == j ? 1.0 : 0.0;
   for (int sweep = 0; sweep < RR_JACOBI_SWEEPS; ++sweep) {
-    jacobi4_rotate<0, 1>(a, v);
-    jacobi4_rotate<0, 2>(a, v);
-    jacobi4_rotate<0, 3>(a, v);
-    jacobi4_rotate<1, 2>(a, v);
-    jacobi4_rotate<1, 3>(a, v);
-    jacobi4_rotate<2, 3>(a, v);
+    cmr_jacobi_rotate<0, 1>(a, v);
+    cmr_jacobi_rotate<0, 2>(a, v);
+    cmr_jacobi_rotate<0, 3>(a, v);
+    cmr_jacobi_rotate<1, 2>(a, v);
+    cmr_jacobi_rotate<1, 3>(a, v);
+    cmr_jacobi_rotate<2, 3>(a, v);
   }
   double qw = v[0][0], qx = v[1][0], qy = v[2][0], qz = v[3][0], top = a[0][0];
 #pragma unroll
@@ -324,17 +299,8 @@ __global__ __launch_bounds__(RR_HYP_WG) void rr_score_kernel(const f32x4* __rest
 }
 
 // the sum of v over the workgroup in a fixed order, valid in every thread: a tree over the threads in LDS
-__device__ __forceinline__ double rr_block_sum(double v, double* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = RR_SEL_THREADS / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  return red[0];
-}
-__device__ __forceinline__ int rr_block_isum(int v, int* red) {
+template <typename T>
+__device__ __forceinline__ T rr_block_sum(T v, T* red) {
   __syncthreads();
   red[threadIdx.x] = v;
   __syncthreads();
@@ -426,13 +392,9 @@ __global__ __launch_bounds__(RR_SEL_THREADS) void rr_select_kernel(const f32x4* 
   int again = 0;
   if (keep)                                                         // uniform: LDS
     for (int e = tid; e < count; e += RR_SEL_THREADS) again += rr_inlier(Tn, la[e], lb[e], thr2) ? 1 : 0;
-  again = rr_block_isum(again, ired);
+  again = rr_block_sum(again, ired);
   const bool take = keep && again >= best_inl;                      // the refit is kept if the count does not drop
-  if (tid < 16) {
-    const int r = tid >> 2, cc = tid & 3;
-    const double* U = take ? Tn : T;
-    pose_out[tid] = r == 3 ? (cc == 3 ? 1.f : 0.f) : (float)(cc < 3 ? U[3 * r + cc] : U[9 + r]);
-  }
+  if (tid < 16) pose_out[tid] = cmr_pose_entry(take ? Tn : T, tid);
   if (tid == 16) out3[0] = take ? again : best_inl;
   if (tid == 17) out3[1] = 0;
   if (tid == 18) out3[2] = best;

@@ -12,17 +12,19 @@
 //                          slice one after the other: match under the working pose rounded to fp32, then lane 0 of the group adds the
 //                          pair's w J^T J (21), w J r (6) and w r^2 in float64.  The 16 group sums are added in group order into the
 //                          slice's own slot, the pair counts next to them;
-//       icp_step_kernel    one workgroup: adds the slots IN SLICE ORDER, 6x6 Cholesky (cmr_pnp.h), T <- [exp(w) | v] T, trace, the stop flag;
+//       icp_step_kernel    one workgroup: adds the slots IN SLICE ORDER, 6x6 Cholesky, T <- [exp(w) | v] T (all three of cmr_pnp.h), trace,
+//                          the stop flag;
 //     icp_final_kernel   the working pose as fp32, status.
 // A call that has stopped turns its remaining launches into early returns read from its state in the workspace.  No atomics: every slot,
-// state and output has one writer.
+// state and output has one writer.  The index (GridIndex), the cells round a query (Walk) and the walk over their runs (walk16) are
+// cmr_cloud_grid.h's; the working pose's load, left update and fp32 4x4 form and the slice-order sum are cmr_pnp.h's.
 #include "cmr_cloud_grid.h"
 #include "cmr_pnp.h"
 
 namespace {
 
 constexpr int ICP_SLICE = 32;        // source rows per accumulation workgroup: 2 per group.  A constant: the summation order rests on it
-constexpr int ICP_NACC = 28;         // H upper triangle (21), g (6), cost
+constexpr int ICP_NACC = CMR_GN_NACC; // H upper triangle (21), g (6), cost
 constexpr int NO_ROW = INT32_MAX;
 
 struct IcpState {
@@ -37,70 +39,26 @@ __device__ __forceinline__ void pose_apply(const float (&T)[12], float px, float
   qy = ((T[3] * px + T[4] * py) + T[5] * pz) + T[10];
   qz = ((T[6] * px + T[7] * py) + T[8] * pz) + T[11];
 }
-// the value that `within` compares
-__device__ __forceinline__ float dist2(float dx, float dy, float dz) {
-#pragma clang fp contract(off)
-  return (dx * dx + dy * dy) + dz * dz;
-}
-
-// The cells of the TARGET's grid that a query searches along one axis.  A query inside the grid: axis_cells.  A query outside it has no
-// cell of its own; up to two cells below cell 0 (above CELL_MAX) it can still reach cell 0 and, from a face, cell 1 -- both are searched,
-// the distance test decides -- and beyond that nothing: lo > hi, no runs.  No index outside [0, CELL_MAX] leaves this function.
-__device__ __forceinline__ void query_cells(float x, float origin, float cell, int& lo, int& hi) {
-  const float c = floorf(cell_coord(x, origin, cell));
-  if (c >= 0.f && c <= (float)CELL_MAX) {
-    axis_cells(x, origin, cell, lo, hi);
-  } else if (c >= -2.f && c < 0.f) {
-    lo = 0;
-    hi = 1;
-  } else if (c > (float)CELL_MAX && c <= (float)(CELL_MAX + 2)) {
-    lo = (int)CELL_MAX - 1;
-    hi = (int)CELL_MAX;
-  } else {                                                        // far outside, or not a number
-    lo = 1;
-    hi = 0;
-  }
-}
-
-// The nearest target row of q for one 16-lane group (every lane of the wave calls it; `live` is uniform over the group): the least d2 among
-// the rows with d2 <= r2, on equal d2 the lowest original row.  -> row (NO_ROW: none), d2, and pos = its place in key order.
-__device__ __forceinline__ void nearest16(float qx, float qy, float qz, bool live, const f32x4* __restrict__ pts4,
-                                          const int64_t* __restrict__ keys, const int64_t* __restrict__ order, int64_t kept, float ox,
-                                          float oy, float oz, float cell, float r2, int lane, int& row, float& best, int& pos) {
-  int xlo, xhi, ylo, yhi, zlo, zhi;
-  query_cells(qx, ox, cell, xlo, xhi);
-  query_cells(qy, oy, cell, ylo, yhi);
-  query_cells(qz, oz, cell, zlo, zhi);
-  const int ny = yhi - ylo + 1, nz = zhi - zlo + 1;
-  const int nruns = live && xhi >= xlo && ny > 0 && nz > 0 ? ny * nz : 0;
+// The nearest target row of q for one 16-lane group (every lane of the wave calls it; `live` is uniform over the group, as walk16 asks):
+// the least d2 among the rows with d2 <= r2, on equal d2 the lowest original row.  -> row (NO_ROW: none), d2, and pos = its place in key order.
+__device__ __forceinline__ void nearest16(float qx, float qy, float qz, bool live, const GridIndex& index, float r2, int lane, int& row,
+                                          float& best, int& pos) {
+  const Walk w(qx, qy, qz, live, index);
   row = NO_ROW;
   best = INFINITY;
   pos = 0;
-  for (int base = 0; base < nruns; base += 16) {
-    int64_t b = 0, e = 0;                                           // lane r of the group finds run base + r
-    if (base + lane < nruns) {
-      const int zz = zlo + (base + lane) / ny, yy = ylo + (base + lane) % ny;
-      b = key_bound(keys, kept, pack_key(xlo, yy, zz), false);
-      e = b + key_bound(keys + b, kept - b, pack_key(xhi, yy, zz), true);
-    }
-    const int here = nruns - base < 16 ? nruns - base : 16;
-    for (int r = 0; r < here; ++r) {
-      const int64_t rb = __shfl(b, r, 16), re = __shfl(e, r, 16);
-      for (int64_t j = rb + lane; j < re; j += 16) {
-        const f32x4 c = pts4[j];
-        const float dx = c.x - qx, dy = c.y - qy, dz = c.z - qz;
-        const float d2 = dist2(dx, dy, dz);
-        if (within(dx, dy, dz, r2) && d2 <= best) {
-          const int cand = (int)order[j];
-          if (d2 < best || cand < row) {
-            best = d2;
-            row = cand;
-            pos = (int)j;
-          }
-        }
+  walk16(index, w, lane, [&](int64_t j, const f32x4& c) {
+    const float dx = c.x - qx, dy = c.y - qy, dz = c.z - qz;
+    const float d2 = dist2(dx, dy, dz);
+    if (within(dx, dy, dz, r2) && d2 <= best) {
+      const int cand = (int)index.order[j];
+      if (d2 < best || cand < row) {
+        best = d2;
+        row = cand;
+        pos = (int)j;
       }
     }
-  }
+  });
   // every lane of the wave is here again: the 16-lane minimum of (d2, row)
 #pragma unroll
   for (int o = 8; o > 0; o >>= 1) {
@@ -114,12 +72,8 @@ __device__ __forceinline__ void nearest16(float qx, float qy, float qz, bool liv
   }
 }
 
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
 __global__ __launch_bounds__(256) void cloud_nearest_kernel(const float* __restrict__ queries, int64_t ld, int64_t M,
-                                                            const float* __restrict__ pose, const f32x4* __restrict__ pts4,
-                                                            const int64_t* __restrict__ keys, const int64_t* __restrict__ order,
-                                                            int64_t kept, float ox, float oy, float oz, float cell, float r2,
+                                                            const float* __restrict__ pose, GridIndex index, float r2,
                                                             int32_t* __restrict__ idx, float* __restrict__ d2out) {
   const int lane = threadIdx.x & 15;
   const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
@@ -138,7 +92,7 @@ __global__ __launch_bounds__(256) void cloud_nearest_kernel(const float* __restr
   }
   int row, pos;
   float best;
-  nearest16(qx, qy, qz, have && finite3(qx, qy, qz), pts4, keys, order, kept, ox, oy, oz, cell, r2, lane, row, best, pos);
+  nearest16(qx, qy, qz, have && cmr_finite3(qx, qy, qz), index, r2, lane, row, best, pos);
   if (lane != 0 || !have) return;
   idx[i] = row == NO_ROW ? -1 : row;
   d2out[i] = row == NO_ROW ? NAN : best;
@@ -151,10 +105,7 @@ __global__ __launch_bounds__(256) void icp_init_kernel(const float* __restrict__
   if (system)
     for (int i = threadIdx.x; i < iters * ICP_NACC; i += 256) system[i] = 0.0;
   if (threadIdx.x != 0) return;
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) st->cur[3 * i + j] = (double)pose_in[4 * i + j];
-    st->cur[9 + i] = (double)pose_in[4 * i + 3];
-  }
+  cmr_pose_load(pose_in, st->cur);
   st->stop = 0;
   st->code = 1;                      // iterations exhausted, until a step says otherwise
   st->executed = 0;
@@ -181,12 +132,10 @@ __device__ __forceinline__ void icp_pair(float qx, float qy, float qz, const f32
   a[27] += (w * r) * r;
 }
 
-__global__ __launch_bounds__(256) void icp_accum_kernel(const float* __restrict__ src, int64_t ld, int64_t M,
-                                                        const f32x4* __restrict__ pts4, const int64_t* __restrict__ keys,
-                                                        const int64_t* __restrict__ order, int64_t kept,
-                                                        const float* __restrict__ normals, float ox, float oy, float oz, float cell,
-                                                        float r2, float huber, const IcpState* __restrict__ st,
-                                                        double* __restrict__ slots, int32_t* __restrict__ cslots) {
+__global__ __launch_bounds__(256) void icp_accum_kernel(const float* __restrict__ src, int64_t ld, int64_t M, GridIndex index,
+                                                        const float* __restrict__ normals, float r2, float huber,
+                                                        const IcpState* __restrict__ st, double* __restrict__ slots,
+                                                        int32_t* __restrict__ cslots) {
   __shared__ double acc[16][ICP_NACC];
   __shared__ int cnt[16];
   if (st->stop) return;
@@ -205,11 +154,11 @@ __global__ __launch_bounds__(256) void icp_accum_kernel(const float* __restrict_
     pose_apply(T, p[0], p[1], p[2], qx, qy, qz);
     int row, pos;
     float best;
-    nearest16(qx, qy, qz, have && finite3(qx, qy, qz), pts4, keys, order, kept, ox, oy, oz, cell, r2, lane, row, best, pos);
+    nearest16(qx, qy, qz, have && cmr_finite3(qx, qy, qz), index, r2, lane, row, best, pos);
     if (lane == 0 && row != NO_ROW) {
       const float nx = normals[(int64_t)row * 3], ny = normals[(int64_t)row * 3 + 1], nz = normals[(int64_t)row * 3 + 2];
       if (nx != 0.f || ny != 0.f || nz != 0.f) {
-        icp_pair(qx, qy, qz, pts4[pos], nx, ny, nz, (double)huber, a);
+        icp_pair(qx, qy, qz, index.pts4[pos], nx, ny, nz, (double)huber, a);
         ++pairs;
       }
     }
@@ -240,17 +189,7 @@ __global__ __launch_bounds__(64) void icp_step_kernel(int it, int nslice, float 
   const int tid = threadIdx.x;
   if (st->stop) return;
   if (tid < ICP_NACC) {
-    double v = 0.0;
-    int s = 0;
-    for (; s + 8 <= nslice; s += 8) {                                 // slice order; eight loads in flight, added in that order
-      double t[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) t[u] = slots[(int64_t)(s + u) * ICP_NACC + tid];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v += t[u];
-    }
-    for (; s < nslice; ++s) v += slots[(int64_t)s * ICP_NACC + tid];
-    tot[tid] = v;
+    tot[tid] = cmr_slot_sum(slots, nslice, tid);
   } else if (tid == ICP_NACC) {
     long long c = 0;
     for (int s = 0; s < nslice; ++s) c += cslots[s];
@@ -272,15 +211,7 @@ __global__ __launch_bounds__(64) void icp_step_kernel(int it, int nslice, float 
     for (int r = 0; r < 6; ++r) g[r] = -tot[21 + r];
     ok = cmr_pnp_chol6<true>(tot, g, xi);
   }
-  if (ok) {
-    double E[9];
-    cmr_pnp_expso3(xi, E);
-    for (int i = 0; i < 3; ++i) {
-      for (int j = 0; j < 3; ++j) nw[3 * i + j] = E[3 * i] * st->cur[j] + E[3 * i + 1] * st->cur[3 + j] + E[3 * i + 2] * st->cur[6 + j];
-      nw[9 + i] = E[3 * i] * st->cur[9] + E[3 * i + 1] * st->cur[10] + E[3 * i + 2] * st->cur[11] + xi[3 + i];
-    }
-    for (int i = 0; i < 12; ++i) ok = ok && isfinite(nw[i]);
-  }
+  ok = ok && cmr_pose_left_update(st->cur, xi, nw);
   if (!ok) { st->code = 3; st->stop = 1; return; }                  // the pose stays the one before this iteration
   for (int i = 0; i < 12; ++i) st->cur[i] = nw[i];
   const double rot = sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]), trans = sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
@@ -292,10 +223,7 @@ __global__ __launch_bounds__(64) void icp_step_kernel(int it, int nslice, float 
 __global__ __launch_bounds__(64) void icp_final_kernel(const IcpState* __restrict__ st, float* __restrict__ pose,
                                                        int32_t* __restrict__ status) {
   const int tid = threadIdx.x;
-  if (tid < 16) {
-    const int r = tid >> 2, c = tid & 3;
-    pose[tid] = r == 3 ? (c == 3 ? 1.f : 0.f) : (float)(c < 3 ? st->cur[3 * r + c] : st->cur[9 + r]);
-  }
+  if (tid < 16) pose[tid] = cmr_pose_entry(st->cur, tid);
   if (tid == 16) status[0] = st->code;
   if (tid == 17) status[1] = st->executed;
 }
@@ -312,21 +240,15 @@ inline IcpWs icp_layout(int64_t M) {
   return L;
 }
 
-inline bool index_ok(const void* pts4, const void* keys, const void* order, int64_t kept, float ox, float oy, float oz, float cell,
-                     float max_dist) {
-  return pts4 && keys && order && cmr_aligned16(pts4) && kept > 0 && kept < ((int64_t)1 << 31) && isfinite(ox) && isfinite(oy) &&
-         isfinite(oz) && cell > 0.f && isfinite(cell) && max_dist > 0.f && max_dist <= cell;
-}
-
 }  // namespace
 
 extern "C" int cmr_cloud_nearest_f32(const float* queries, int64_t ld, int64_t M, const float* pose, const float* points4,
                                      const int64_t* keys_sorted, const int64_t* order, int64_t kept, float ox, float oy, float oz,
                                      float cell, float max_dist, int32_t* idx, float* d2, hipStream_t stream) {
-  CMR_REQUIRE(queries && idx && d2 && ld >= 3 && M > 0 && M < ((int64_t)1 << 31) &&
-              index_ok(points4, keys_sorted, order, kept, ox, oy, oz, cell, max_dist));
-  hipLaunchKernelGGL(cloud_nearest_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, stream, queries, ld, M, pose,
-                     (const f32x4*)points4, keys_sorted, order, kept, ox, oy, oz, cell, max_dist * max_dist, idx, d2);
+  const GridIndex index{(const f32x4*)points4, keys_sorted, order, kept, ox, oy, oz, cell};
+  CMR_REQUIRE(queries && idx && d2 && ld >= 3 && M > 0 && M < ((int64_t)1 << 31) && grid_index_ok(index) && max_dist > 0.f && max_dist <= cell);
+  hipLaunchKernelGGL(cloud_nearest_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, stream, queries, ld, M, pose, index,
+                     max_dist * max_dist, idx, d2);
   return cmr_launch_status();
 }
 
@@ -337,8 +259,9 @@ extern "C" int cmr_icp_point_to_plane_f32(const float* source, int64_t ld, int64
                                           const float* normals, const float* pose_in, float max_dist, float huber, int iters,
                                           float tol_rot, float tol_trans, float* pose, double* trace, double* system, int32_t* status,
                                           void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  const GridIndex index{(const f32x4*)points4, keys_sorted, order, kept, ox, oy, oz, cell};
   CMR_REQUIRE(source && normals && pose_in && pose && status && workspace && ld >= 3 && M > 0 && M < ((int64_t)1 << 31) &&
-              index_ok(points4, keys_sorted, order, kept, ox, oy, oz, cell, max_dist));
+              grid_index_ok(index) && max_dist > 0.f && max_dist <= cell);
   CMR_REQUIRE(huber >= 0.f && isfinite(huber) && iters >= 0 && iters <= 1000 && (iters == 0 || trace) && tol_rot == tol_rot &&
               tol_trans == tol_trans);
   CMR_REQUIRE(cmr_aligned16(workspace) && workspace_bytes >= cmr_icp_point_to_plane_workspace_bytes(M));
@@ -349,8 +272,8 @@ extern "C" int cmr_icp_point_to_plane_f32(const float* source, int64_t ld, int64
   const int nslice = (int)icp_slices(M);
   hipLaunchKernelGGL(icp_init_kernel, dim3(1), dim3(256), 0, stream, pose_in, iters, st, trace, system);
   for (int it = 0; it < iters; ++it) {
-    hipLaunchKernelGGL(icp_accum_kernel, dim3(nslice), dim3(256), 0, stream, source, ld, M, (const f32x4*)points4, keys_sorted, order,
-                       kept, normals, ox, oy, oz, cell, max_dist * max_dist, huber, (const IcpState*)st, slots, cslots);
+    hipLaunchKernelGGL(icp_accum_kernel, dim3(nslice), dim3(256), 0, stream, source, ld, M, index, normals, max_dist * max_dist, huber,
+                       (const IcpState*)st, slots, cslots);
     hipLaunchKernelGGL(icp_step_kernel, dim3(1), dim3(64), 0, stream, it, nslice, tol_rot, tol_trans, st, (const double*)slots,
                        (const int32_t*)cslots, trace, system);
   }

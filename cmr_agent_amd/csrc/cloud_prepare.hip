@@ -6,6 +6,8 @@
 //   cmr_segment_heads_i64    runs of equal keys -> CSR offsets, counts, the int32 row order cmr_segment_reduce_f32 takes, the inverse map
 //   cmr_cloud_gather4_f32    the kept rows as float4 in key order: the rows of a grid index (ops.cloud_index; cloud_icp.hip searches them)
 //   cmr_point_normals_f32    fixed-radius neighbourhoods over the sorted cells, 3x3 covariance, its smallest eigenvector
+// The index, the walk over a neighbourhood's runs and the membership test live in cmr_cloud_grid.h (GridIndex, Walk, walk16), the Jacobi
+// rotation and the finite test in cmr_common.h.
 //
 // No float atomics anywhere: min / max and the integer counts are order free, every float sum runs in a fixed order.
 #include "cmr_cloud_grid.h"
@@ -15,8 +17,6 @@ namespace {
 constexpr int64_t KEY_DROPPED = INT64_MAX;                      // rows with a non-finite coordinate sort behind every cell
 constexpr int BOUNDS_BLOCKS = 256;                              // partial results of cmr_cloud_bounds_f32: 8 words each
 constexpr int SCAN_TILE = 1024;                                 // rows per workgroup of the head scan: 256 threads x 4
-
-__device__ __forceinline__ bool row_finite(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
 // ------------------------------------------------------------------------------------------------------------------------ bounds
 struct Bounds {
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void bounds_partial_kernel(const float* __rest
   Bounds b{{INFINITY, INFINITY, INFINITY}, {-INFINITY, -INFINITY, -INFINITY}, 0};
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256) {
     const float x = pts[i * ld], y = pts[i * ld + 1], z = pts[i * ld + 2];
-    if (row_finite(x, y, z)) bounds_merge(b, Bounds{{x, y, z}, {x, y, z}, 1});
+    if (cmr_finite3(x, y, z)) bounds_merge(b, Bounds{{x, y, z}, {x, y, z}, 1});
   }
   bounds_block(b, sh);
   if (threadIdx.x == 0) bounds_write(b, part + (int64_t)blockIdx.x * 8);
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void voxel_keys_kernel(const float* __restrict
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
   const float x = pts[i * ld], y = pts[i * ld + 1], z = pts[i * ld + 2];
-  keys[i] = row_finite(x, y, z) ? pack_key(cell_index(x, ox, cell), cell_index(y, oy, cell), cell_index(z, oz, cell)) : KEY_DROPPED;
+  keys[i] = cmr_finite3(x, y, z) ? pack_key(cell_index(x, ox, cell), cell_index(y, oy, cell), cell_index(z, oz, cell)) : KEY_DROPPED;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------- heads
@@ -173,27 +173,6 @@ __global__ __launch_bounds__(256) void gather_points4_kernel(const float* __rest
   out[i] = f32x4{p[0], p[1], p[2], 0.f};
 }
 
-// one Jacobi rotation that clears a[p][q] of the symmetric 3x3 a (r is the third index); v collects the rotations in its columns
-template <int P, int Q, int R>
-__device__ __forceinline__ void jacobi_rotate(double (&a)[3][3], double (&v)[3][3]) {
-  const double apq = a[P][Q];
-  if (apq == 0.0) return;
-  const double theta = (a[Q][Q] - a[P][P]) / (2.0 * apq);
-  const double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));        // theta^2 = inf gives t = 0
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-  a[P][P] -= t * apq;
-  a[Q][Q] += t * apq;
-  a[P][Q] = a[Q][P] = 0.0;
-  const double arp = a[R][P], arq = a[R][Q];
-  a[R][P] = a[P][R] = c * arp - s * arq;
-  a[R][Q] = a[Q][R] = s * arp + c * arq;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double vp = v[k][P], vq = v[k][Q];
-    v[k][P] = c * vp - s * vq;
-    v[k][Q] = s * vp + c * vq;
-  }
-}
 template <int I, int J>
 __device__ __forceinline__ void eig_order(double (&w)[3], double (&v)[3][3]) {
   if (w[J] < w[I]) {
@@ -211,57 +190,35 @@ __device__ __forceinline__ void eig_order(double (&w)[3], double (&v)[3][3]) {
 
 constexpr int JACOBI_SWEEPS = 8;      // cyclic Jacobi on a 3x3 in fp64 converges quadratically: five sweeps reach the last bit, eight are fixed
 
-// One 16-lane group per query, in key order: the four queries of a wave are neighbours in space and read nearly the same runs.  The cells of a
-// (z, y) pair that a query searches are consecutive along x, i.e. ONE range of keys and, the rows being sorted, one run of rows: 9 runs (up to
-// 16 for a query on a cell face, where axis_cells adds a cell on one side of an axis; 25 only beyond some 2^18 cells from the origin,
-// where the rounding of cell_coord reaches half a cell and both sides are added), each found by two binary searches, one run per lane.
-__global__ __launch_bounds__(256) void point_normals_kernel(const f32x4* __restrict__ pts4, const int64_t* __restrict__ keys,
-                                                            const int64_t* __restrict__ order, int64_t N, int64_t kept, float ox, float oy,
-                                                            float oz, float radius, float vx, float vy, float vz, int kmin,
+// One 16-lane group per query, in key order: the four queries of a wave are neighbours in space and read nearly the same runs.  The walk over
+// the runs of the cells round the query is walk16 (cmr_cloud_grid.h); the grid's cell is the radius here.
+__global__ __launch_bounds__(256) void point_normals_kernel(GridIndex index, int64_t N, float vx, float vy, float vz, int kmin,
                                                             float* __restrict__ normals, int32_t* __restrict__ count,
                                                             float* __restrict__ eig) {
   const int lane = threadIdx.x & 15;
   const int64_t q = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-  const bool live = q < kept;
-  const f32x4 p = pts4[live ? q : 0];
-  int xlo, xhi, ylo, yhi, zlo, zhi;
-  axis_cells(p.x, ox, radius, xlo, xhi);
-  axis_cells(p.y, oy, radius, ylo, yhi);
-  axis_cells(p.z, oz, radius, zlo, zhi);
-  const int ny = yhi - ylo + 1;
-  const int nruns = live ? ny * (zhi - zlo + 1) : 0;
-  const float r2 = radius * radius;
+  const bool live = q < index.kept;
+  const f32x4 p = index.pts4[live ? q : 0];
+  const Walk walk(p, live, index);
+  const float r2 = index.cell * index.cell;
 
   float s[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // sum d (3), sum d d^T (xx xy xz yy yz zz)
   int k = 0;
-  for (int base = 0; base < nruns; base += 16) {                    // one pass, save for the 25 runs far from the origin (above)
-    int64_t b = 0, e = 0;                                           // lane r of the group finds run base + r
-    if (base + lane < nruns) {
-      const int zz = zlo + (base + lane) / ny, yy = ylo + (base + lane) % ny;
-      b = key_bound(keys, kept, pack_key(xlo, yy, zz), false);
-      e = b + key_bound(keys + b, kept - b, pack_key(xhi, yy, zz), true);
+  walk16(index, walk, lane, [&](int64_t, const f32x4& c) {
+    const float dx = c.x - p.x, dy = c.y - p.y, dz = c.z - p.z;
+    if (within(dx, dy, dz, r2)) {
+      s[0] += dx;
+      s[1] += dy;
+      s[2] += dz;
+      s[3] += dx * dx;
+      s[4] += dx * dy;
+      s[5] += dx * dz;
+      s[6] += dy * dy;
+      s[7] += dy * dz;
+      s[8] += dz * dz;
+      ++k;
     }
-    const int here = nruns - base < 16 ? nruns - base : 16;
-    for (int r = 0; r < here; ++r) {
-      const int64_t rb = __shfl(b, r, 16), re = __shfl(e, r, 16);
-      for (int64_t j = rb + lane; j < re; j += 16) {
-        const f32x4 c = pts4[j];
-        const float dx = c.x - p.x, dy = c.y - p.y, dz = c.z - p.z;
-        if (within(dx, dy, dz, r2)) {
-          s[0] += dx;
-          s[1] += dy;
-          s[2] += dz;
-          s[3] += dx * dx;
-          s[4] += dx * dy;
-          s[5] += dx * dz;
-          s[6] += dy * dy;
-          s[7] += dy * dz;
-          s[8] += dz * dz;
-          ++k;
-        }
-      }
-    }
-  }
+  });
   // every lane of the wave is here again: the lane sums in the fixed order of the DPP butterfly, pinned in front of the branches below
 #pragma unroll
   for (int c = 0; c < 9; ++c) {
@@ -286,9 +243,9 @@ __global__ __launch_bounds__(256) void point_normals_kernel(const f32x4* __restr
     a[1][2] = a[2][1] = s[7] * inv - my * mz;
     a[2][2] = s[8] * inv - mz * mz;
     for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
-      jacobi_rotate<0, 1, 2>(a, v);
-      jacobi_rotate<0, 2, 1>(a, v);
-      jacobi_rotate<1, 2, 0>(a, v);
+      cmr_jacobi_rotate<0, 1>(a, v);
+      cmr_jacobi_rotate<0, 2>(a, v);
+      cmr_jacobi_rotate<1, 2>(a, v);
     }
     w[0] = a[0][0];
     w[1] = a[1][1];
@@ -298,7 +255,7 @@ __global__ __launch_bounds__(256) void point_normals_kernel(const f32x4* __restr
     eig_order<0, 1>(w, v);
   }
   if (lane != 0 || q >= N) return;
-  const int64_t row = order[q];
+  const int64_t row = index.order[q];
   float n[3] = {0.f, 0.f, 0.f};
   if (valid) {
     double nx = v[0][0], nyv = v[1][0], nz = v[2][0];
@@ -369,11 +326,11 @@ extern "C" int cmr_point_normals_f32(const float* points, int64_t ld, const int6
                                      int64_t kept, float ox, float oy, float oz, float radius, float vx, float vy, float vz,
                                      int min_neighbors, float* points4, float* normals, int32_t* count, float* eigenvalues,
                                      hipStream_t stream) {
-  CMR_REQUIRE(points && keys_sorted && order && points4 && normals && count && ld >= 3 && N > 0 && N < ((int64_t)1 << 31) && kept > 0 &&
-              kept <= N && radius > 0.f && isfinite(radius) && isfinite(ox) && isfinite(oy) && isfinite(oz) && isfinite(vx) &&
-              isfinite(vy) && isfinite(vz) && cmr_aligned16(points4));
+  const GridIndex index{(const f32x4*)points4, keys_sorted, order, kept, ox, oy, oz, radius};      // the keys were taken with the radius as the cell
+  CMR_REQUIRE(points && normals && count && ld >= 3 && N > 0 && N < ((int64_t)1 << 31) && grid_index_ok(index) && kept <= N && isfinite(vx) &&
+              isfinite(vy) && isfinite(vz));
   hipLaunchKernelGGL(gather_points4_kernel, dim3(blocks_of(kept, 256)), dim3(256), 0, stream, points, ld, order, kept, (f32x4*)points4);
-  hipLaunchKernelGGL(point_normals_kernel, dim3(blocks_of(N, 16)), dim3(256), 0, stream, (const f32x4*)points4, keys_sorted, order, N, kept,
-                     ox, oy, oz, radius, vx, vy, vz, min_neighbors < 3 ? 3 : min_neighbors, normals, count, eigenvalues);
+  hipLaunchKernelGGL(point_normals_kernel, dim3(blocks_of(N, 16)), dim3(256), 0, stream, index, N, vx, vy, vz,
+                     min_neighbors < 3 ? 3 : min_neighbors, normals, count, eigenvalues);
   return cmr_launch_status();
 }

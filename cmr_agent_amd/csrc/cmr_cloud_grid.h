@@ -1,6 +1,8 @@
 // The sorted-key uniform grid that the cloud kernels share (cloud_prepare.hip: keys and normals; cloud_icp.hip: nearest row
-// and point-to-plane ICP), stated once: the cell of a coordinate, the key of a cell, the cells a fixed-radius query
-// searches along an axis, the run of sorted rows behind a range of keys, the membership test.  Device code only.
+// and point-to-plane ICP; cloud_fpfh.hip: SPFH and FPFH), stated once: the cell of a coordinate, the key of a
+// cell, the cells a fixed-radius query searches along an axis, the run of sorted rows behind a range of keys, the membership test -- and the
+// index as the kernels take it (GridIndex), the cells round a row or a free query (Walk) and the one loop over them (walk16), DESIGN.md 4ag.
+// Device code, and the host's check of a GridIndex.
 #pragma once
 #include "cmr_common.h"
 
@@ -49,14 +51,106 @@ __device__ __forceinline__ int64_t key_bound(const int64_t* __restrict__ keys, i
   }
   return lo;
 }
-__device__ __forceinline__ bool within(float dx, float dy, float dz, float r2) {
+// the squared distance, every operation rounded on its own, and the membership test on it
+__device__ __forceinline__ float dist2(float dx, float dy, float dz) {
 #pragma clang fp contract(off)
-  return (dx * dx + dy * dy) + dz * dz <= r2;
+  return (dx * dx + dy * dy) + dz * dz;
 }
+__device__ __forceinline__ bool within(float dx, float dy, float dz, float r2) { return dist2(dx, dy, dz) <= r2; }
 __device__ __forceinline__ int isum16(int s) {
   s += cmr_dpp<0xB1>(s);
   s += cmr_dpp<0x4E>(s);
   s += cmr_dpp<0x141>(s);
   s += cmr_dpp<0x140>(s);
   return s;
+}
+
+// ---- the index ---------------------------------------------------------------------------------------------------------------------------
+// A grid index as ops.cloud_index builds it, passed to the kernels by value: the kept rows as float4 in key order, their sorted keys, their
+// original row numbers, and the grid the keys were taken on.
+struct GridIndex {
+  const f32x4* __restrict__ pts4;
+  const int64_t* __restrict__ keys;
+  const int64_t* __restrict__ order;
+  int64_t kept;
+  float ox, oy, oz, cell;
+};
+// the host's check of an index; what an entry point asks on top of it (radius <= cell, max_dist <= cell, kept <= N) stays with the entry point
+static inline bool grid_index_ok(const GridIndex& g) {
+  return g.pts4 && g.keys && g.order && cmr_aligned16(g.pts4) && g.kept > 0 && g.kept < ((int64_t)1 << 31) && isfinite(g.ox) && isfinite(g.oy) &&
+         isfinite(g.oz) && g.cell > 0.f && isfinite(g.cell);
+}
+
+// The cells of the grid that a FREE query searches along one axis.  A query inside the grid: axis_cells.  A query outside it has no
+// cell of its own; up to two cells below cell 0 (above CELL_MAX) it can still reach cell 0 and, from a face, cell 1 -- both are searched,
+// the distance test decides -- and beyond that nothing: lo > hi, no runs.  No index outside [0, CELL_MAX] leaves this function.
+__device__ __forceinline__ void query_cells(float x, float origin, float cell, int& lo, int& hi) {
+  const float c = floorf(cell_coord(x, origin, cell));
+  if (c >= 0.f && c <= (float)CELL_MAX) {
+    axis_cells(x, origin, cell, lo, hi);
+  } else if (c >= -2.f && c < 0.f) {
+    lo = 0;
+    hi = 1;
+  } else if (c > (float)CELL_MAX && c <= (float)(CELL_MAX + 2)) {
+    lo = (int)CELL_MAX - 1;
+    hi = (int)CELL_MAX;
+  } else {                                                        // far outside, or not a number
+    lo = 1;
+    hi = 0;
+  }
+}
+
+// the run of sorted rows behind the cells [xlo, xhi] of one (y, z) pair
+__device__ __forceinline__ void cell_run(const int64_t* __restrict__ keys, int64_t kept, int xlo, int xhi, int yy, int zz, int64_t& b, int64_t& e) {
+  b = key_bound(keys, kept, pack_key(xlo, yy, zz), false);
+  e = b + key_bound(keys + b, kept - b, pack_key(xhi, yy, zz), true);
+}
+
+// ---- the walk ----------------------------------------------------------------------------------------------------------------------------
+// The cells a 16-lane group searches, uniform over the group.  The cells of a (z, y) pair are consecutive along x, i.e. ONE range of keys
+// and, the rows being sorted, one run of rows: nruns = ny * nz of them, 9 for a query inside a cell, up to 16 for one on a cell face (where
+// axis_cells adds a cell on one side of an axis), 20 or 25 only beyond some 2^18 cells from the origin, where the rounding of cell_coord
+// reaches half a cell and both sides are added.  `live` = false gives no runs.
+struct Walk {
+  int xlo, xhi, ylo, ny, zlo, nruns;
+  // round a row of the cloud itself: it lies inside the grid
+  __device__ __forceinline__ Walk(const f32x4& p, bool live, const GridIndex& g) {
+    int yhi, zhi;
+    axis_cells(p.x, g.ox, g.cell, xlo, xhi);
+    axis_cells(p.y, g.oy, g.cell, ylo, yhi);
+    axis_cells(p.z, g.oz, g.cell, zlo, zhi);
+    ny = yhi - ylo + 1;
+    nruns = live ? ny * (zhi - zlo + 1) : 0;
+  }
+  // round a free query, which may lie outside the grid (query_cells): no runs where an axis has no cells
+  __device__ __forceinline__ Walk(float qx, float qy, float qz, bool live, const GridIndex& g) {
+    int yhi, zhi;
+    query_cells(qx, g.ox, g.cell, xlo, xhi);
+    query_cells(qy, g.oy, g.cell, ylo, yhi);
+    query_cells(qz, g.oz, g.cell, zlo, zhi);
+    ny = yhi - ylo + 1;
+    const int nz = zhi - zlo + 1;
+    nruns = live && xhi >= xlo && ny > 0 && nz > 0 ? ny * nz : 0;
+  }
+};
+
+// The walk of one 16-lane group: visit(j, pts4[j]) for every row j of every run, the runs in (z, y) order, lane l taking rows b + l, b + l +
+// 16, ... of a run.  Lane r of the group finds run base + r with two binary searches, the group then reads every lane's (b, e) by shuffle.
+// Entry conditions:
+//   * EVERY lane of the wave calls it (the shuffles need every lane inside the loop), and is there again when it returns;
+//   * w is uniform over the group -- nruns above all: a lane that left the loop early would be missing from the others' shuffles.
+// One pass over `base`, save for the 20 or 25 runs far from the origin (above).  What happens to a visited row, the state it is added to and
+// the 16-lane reduction after the walk are the caller's.  (g, w and the visitor go by value: taken by reference, spfh_kernel came out at
+// 144 VGPRs instead of 128 and lost a wave per SIMD.)
+template <typename Visit>
+__device__ __forceinline__ void walk16(GridIndex g, Walk w, int lane, Visit visit) {
+  for (int base = 0; base < w.nruns; base += 16) {
+    int64_t b = 0, e = 0;                                           // lane r of the group finds run base + r
+    if (base + lane < w.nruns) cell_run(g.keys, g.kept, w.xlo, w.xhi, w.ylo + (base + lane) % w.ny, w.zlo + (base + lane) / w.ny, b, e);
+    const int here = w.nruns - base < 16 ? w.nruns - base : 16;
+    for (int r = 0; r < here; ++r) {
+      const int64_t rb = __shfl(b, r, 16), re = __shfl(e, r, 16);
+      for (int64_t j = rb + lane; j < re; j += 16) visit(j, g.pts4[j]);
+    }
+  }
 }

@@ -262,6 +262,36 @@ __device__ __forceinline__ float cmr_lerp(float a, float b, float t) {
   return cmr_mul_add_rn(t, d, a);
 }
 
+// three finite coordinates: a row of a cloud that takes part
+__device__ __forceinline__ bool cmr_finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+
+// One Jacobi rotation that clears a[P][Q] of the symmetric N x N a in fp64 (N = 3: cloud_prepare.hip's covariance, N = 4: cloud_global.hip's
+// quaternion matrix); v collects the rotations in its columns.  Sweep counts and sweep orders are the callers'.
+template <int P, int Q, int N>
+__device__ __forceinline__ void cmr_jacobi_rotate(double (&a)[N][N], double (&v)[N][N]) {
+  const double apq = a[P][Q];
+  if (apq == 0.0) return;
+  const double theta = (a[Q][Q] - a[P][P]) / (2.0 * apq);
+  const double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));        // theta^2 = inf gives t = 0
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+  a[P][P] -= t * apq;
+  a[Q][Q] += t * apq;
+  a[P][Q] = a[Q][P] = 0.0;
+#pragma unroll
+  for (int r = 0; r < N; ++r) {
+    if (r == P || r == Q) continue;
+    const double arp = a[r][P], arq = a[r][Q];
+    a[r][P] = a[P][r] = c * arp - s * arq;
+    a[r][Q] = a[Q][r] = s * arp + c * arq;
+  }
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const double vp = v[k][P], vq = v[k][Q];
+    v[k][P] = c * vp - s * vq;
+    v[k][Q] = s * vp + c * vq;
+  }
+}
+
 // ---- host helpers shared by the entries of the pose operations -------------------------------------------------------------------
 // workspace sections start on 16 bytes
 static inline int64_t cmr_up16(int64_t v) { return (v + 15) & ~(int64_t)15; }

@@ -1,6 +1,7 @@
 // The pieces that PnP-RANSAC (pnp.hip) and the refinement from a given pose (pnp_refine.hip) must agree
-// on, stated once: the working set of the refinement IS RANSAC's inlier set, and its step is RANSAC's Gauss-Newton step.  Device code
-// only.
+// on, stated once: the working set of the refinement IS RANSAC's inlier set, and its step is RANSAC's Gauss-Newton step.  The working
+// pose of that step -- its load, left update, fp32 4x4 form and the slice-order sum of a step's slots -- serves point-to-plane ICP
+// (cloud_icp.hip) as well.  Device code only.
 #pragma once
 #include "cmr_common.h"
 
@@ -53,6 +54,79 @@ static __device__ void cmr_pnp_expso3(const double* w, double* E) {
       for (int k = 0; k < 3; ++k) ww += W[3 * i + k] * W[3 * k + j];
       E[3 * i + j] = (i == j ? 1.0 : 0.0) + a * W[3 * i + j] + c * ww;
     }
+}
+
+// ---- the working pose of a Gauss-Newton loop: 12 doubles, R row-major then t (pnp.hip, pnp_refine.hip, cloud_icp.hip) ----------------
+// What a loop does with a step -- PnP's accept / undo, ICP's stop and status -- differs on purpose and stays in its kernel.
+constexpr int CMR_GN_NACC = 28;      // the sums of a step: J^T J (21 upper-triangle entries, row by row), J^T r (6), cost
+
+// from a row-major fp32 4x4
+__device__ __forceinline__ void cmr_pose_load(const float* P, double* cur) {
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) cur[3 * i + j] = (double)P[4 * i + j];
+    cur[9 + i] = (double)P[4 * i + 3];
+  }
+}
+// the left update nw = [Exp(w) | v] cur with xi = (w, v); -> whether every entry of nw is finite (nw is written either way).  The three
+// arrays do not overlap, and say so: without it prf_step_kernel took 76 VGPRs instead of 72 and lost a wave per SIMD.
+__device__ __forceinline__ bool cmr_pose_left_update(const double* __restrict__ cur, const double* __restrict__ xi,
+                                                     double* __restrict__ nw) {
+  double E[9];
+  cmr_pnp_expso3(xi, E);
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) nw[3 * i + j] = E[3 * i] * cur[j] + E[3 * i + 1] * cur[3 + j] + E[3 * i + 2] * cur[6 + j];
+    nw[9 + i] = E[3 * i] * cur[9] + E[3 * i + 1] * cur[10] + E[3 * i + 2] * cur[11] + xi[3 + i];
+  }
+  bool ok = true;
+  for (int i = 0; i < 12; ++i) ok = ok && isfinite(nw[i]);
+  return ok;
+}
+// element e < 16 of the pose as a row-major fp32 4x4: threads 0..15 write one each
+__device__ __forceinline__ float cmr_pose_entry(const double* cur, int e) {
+  const int r = e >> 2, c = e & 3;
+  return r == 3 ? (c == 3 ? 1.f : 0.f) : (float)(c < 3 ? cur[3 * r + c] : cur[9 + r]);
+}
+// entry `q` of the step's sums: the slices' slots added IN SLICE ORDER; eight loads in flight, added in that same order
+__device__ __forceinline__ double cmr_slot_sum(const double* __restrict__ slots, int nslice, int q) {
+  double v = 0.0;
+  int s = 0;
+  for (; s + 8 <= nslice; s += 8) {
+    double t[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) t[u] = slots[(int64_t)(s + u) * CMR_GN_NACC + q];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v += t[u];
+  }
+  for (; s < nslice; ++s) v += slots[(int64_t)s * CMR_GN_NACC + q];
+  return v;
+}
+
+// One correspondence's reprojection terms under the pose (R, t) and the intrinsics K (row-major 3x3), added into a: J^T J (upper triangle),
+// J^T r and the cost, for the residual (pu - u, pv - v) and a left increment of the pose.  false, and nothing added, for a point that does
+// not project in front of the camera (p2 <= 0, or not a number).
+__device__ __forceinline__ bool cmr_pnp_terms(const double* K, const double* R, const double* t, float X, float Y, float Z, float u, float v,
+                                              double (&a)[CMR_GN_NACC]) {
+  const double xc0 = R[0] * X + R[1] * Y + R[2] * Z + t[0], xc1 = R[3] * X + R[4] * Y + R[5] * Z + t[1],
+               xc2 = R[6] * X + R[7] * Y + R[8] * Z + t[2];
+  const double p0 = K[0] * xc0 + K[1] * xc1 + K[2] * xc2, p1 = K[3] * xc0 + K[4] * xc1 + K[5] * xc2,
+               p2 = K[6] * xc0 + K[7] * xc1 + K[8] * xc2;
+  if (!(p2 > 0.0)) return false;
+  const double iz = 1.0 / p2, pu = p0 * iz, pv = p1 * iz;
+  const double ru = pu - u, rv = pv - v;
+  const double ga[3] = {(K[0] - K[6] * pu) * iz, (K[1] - K[7] * pu) * iz, (K[2] - K[8] * pu) * iz};     // d pu / d xc
+  const double gb[3] = {(K[3] - K[6] * pv) * iz, (K[4] - K[7] * pv) * iz, (K[5] - K[8] * pv) * iz};
+  // d / d omega (left increment): xc x g
+  const double ja[6] = {xc1 * ga[2] - xc2 * ga[1], xc2 * ga[0] - xc0 * ga[2], xc0 * ga[1] - xc1 * ga[0], ga[0], ga[1], ga[2]};
+  const double jb[6] = {xc1 * gb[2] - xc2 * gb[1], xc2 * gb[0] - xc0 * gb[2], xc0 * gb[1] - xc1 * gb[0], gb[0], gb[1], gb[2]};
+  int q = 0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int cc = r; cc < 6; ++cc) a[q++] += ja[r] * ja[cc] + jb[r] * jb[cc];
+#pragma unroll
+  for (int r = 0; r < 6; ++r) a[21 + r] += ja[r] * ru + jb[r] * rv;
+  a[27] += ru * ru + rv * rv;
+  return true;
 }
 
 // Cholesky solve of the 6x6 H x = g (H from the 21 upper-triangle entries, row by row); false if H is not positive definite.  With

@@ -10,7 +10,8 @@
 //   pnp_score_kernel        a workgroup = 256 hypotheses x one 512-entry slice of the correspondence list, the slice staged in LDS and
 //                           read as broadcasts; integer partial counts added atomically (order free);
 //   pnp_select_kernel       one workgroup per sample: most inliers (ties to the lowest hypothesis index), Gauss-Newton on that
-//                           hypothesis' inlier set in float64, inlier recount, output.
+//                           hypothesis' inlier set in float64, inlier recount, output.  A correspondence's terms, the left update of
+//                           the pose and its fp32 4x4 form are cmr_pnp.h's, shared with pnp_refine.hip and cloud_icp.hip.
 // The row order of the list is kept (not fm_compact_kernel's atomic order): draws index the list, so its order is part of the result.
 #include "cmr_pnp.h"
 
@@ -21,7 +22,7 @@ constexpr int PNP_SLICE = 512;       // list entries per scoring workgroup
 constexpr int PNP_HYP_WG = 256;      // hypotheses per scoring workgroup
 constexpr int PNP_SEL_THREADS = 1024;
 constexpr int PNP_MAX_DRAWS = 32;    // hash counters a hypothesis may use for its 4 distinct draws
-constexpr int PNP_NACC = 28;         // J^T J (21 upper-triangle entries), J^T r (6), cost
+constexpr int PNP_NACC = CMR_GN_NACC; // J^T J (21 upper-triangle entries), J^T r (6), cost
 constexpr double PNP_ORTH_TOL = 1e-5;  // a P3P solution is kept only if max |R R^T - I| <= this
 
 // ---- hash: pnp_hash, stated once in cmr_pnp.h (cloud_global.hip draws its hypotheses with it too) ------------------------------------
@@ -408,20 +409,7 @@ __global__ __launch_bounds__(PNP_SEL_THREADS) void pnp_select_kernel(const float
     for (int i = tid; i < cnt; i += PNP_SEL_THREADS) {
       const float X = cb[i], Y = cb[N + i], Z = cb[2 * N + i], u = cb[3 * N + i], v = cb[4 * N + i];
       if (!cmr_pnp_inlier(Mh, X, Y, Z, u, v, thr2)) continue;
-      const V3 xc = v3(R[0] * X + R[1] * Y + R[2] * Z + t[0], R[3] * X + R[4] * Y + R[5] * Z + t[1], R[6] * X + R[7] * Y + R[8] * Z + t[2]);
-      const V3 p = mulv(K, xc);
-      if (!(p.z > 0.0)) continue;
-      const double iz = 1.0 / p.z, pu = p.x * iz, pv = p.y * iz;
-      const double ru = pu - u, rv = pv - v;
-      const V3 ga = scl(sub(v3(K[0], K[1], K[2]), scl(v3(K[6], K[7], K[8]), pu)), iz);   // d pu / d xc
-      const V3 gb = scl(sub(v3(K[3], K[4], K[5]), scl(v3(K[6], K[7], K[8]), pv)), iz);
-      const V3 wa = cross(xc, ga), wb = cross(xc, gb);                                     // d / d omega (left increment)
-      const double ja[6] = {wa.x, wa.y, wa.z, ga.x, ga.y, ga.z}, jb[6] = {wb.x, wb.y, wb.z, gb.x, gb.y, gb.z};
-      int q = 0;
-      for (int r = 0; r < 6; ++r)
-        for (int c = r; c < 6; ++c) a[q++] += ja[r] * ja[c] + jb[r] * jb[c];
-      for (int r = 0; r < 6; ++r) a[21 + r] += ja[r] * ru + jb[r] * rv;
-      a[27] += ru * ru + rv * rv;
+      cmr_pnp_terms(K, R, t, X, Y, Z, u, v, a);
     }
     for (int q = 0; q < PNP_NACC; ++q) {
       const double s = cmr_wave_sum_d(a[q]);
@@ -450,15 +438,9 @@ __global__ __launch_bounds__(PNP_SEL_THREADS) void pnp_select_kernel(const float
         } else {
           for (int i = 0; i < 12; ++i) prev[i] = sh_pose[i];
           cost_prev = cost;
-          double E[9];
-          cmr_pnp_expso3(dx, E);
-          double Rn[9], tn[3];
-          for (int i = 0; i < 3; ++i) {
-            for (int j = 0; j < 3; ++j) Rn[3 * i + j] = E[3 * i] * prev[j] + E[3 * i + 1] * prev[3 + j] + E[3 * i + 2] * prev[6 + j];
-            tn[i] = E[3 * i] * prev[9] + E[3 * i + 1] * prev[10] + E[3 * i + 2] * prev[11] + dx[3 + i];
-          }
-          for (int i = 0; i < 9; ++i) sh_pose[i] = Rn[i];
-          for (int i = 0; i < 3; ++i) sh_pose[9 + i] = tn[i];
+          double nw[12];
+          cmr_pose_left_update(prev, dx, nw);              // a pose that is not finite fails the next pass' cost test and is undone there
+          for (int i = 0; i < 12; ++i) sh_pose[i] = nw[i];
         }
       }
       sh_stop = stop;
@@ -478,14 +460,7 @@ __global__ __launch_bounds__(PNP_SEL_THREADS) void pnp_select_kernel(const float
     for (int i = tid; i < cnt; i += PNP_SEL_THREADS) n += cmr_pnp_inlier(Mr, cb[i], cb[N + i], cb[2 * N + i], cb[3 * N + i], cb[4 * N + i], thr2);
   const int rc = refine_iters > 0 ? pnp_block_count(n, scratch) : -1;
   const bool use_ref = refine_iters > 0 && rc >= bc;
-  if (tid < 16) {
-    const int r = tid >> 2, c = tid & 3;
-    float val;
-    if (r == 3) val = c == 3 ? 1.f : 0.f;
-    else if (use_ref) val = (float)(c < 3 ? Rf[3 * r + c] : sh_pose[9 + r]);
-    else val = (float)hyp_pose[bhi * 12 + (c < 3 ? 3 * r + c : 9 + r)];
-    out[tid] = val;
-  }
+  if (tid < 16) out[tid] = use_ref ? cmr_pose_entry(sh_pose, tid) : cmr_pose_entry(hyp_pose + bhi * 12, tid);
   if (tid == 0) { inliers[b] = use_ref ? rc : bc; status[b] = 0; }
 }
 

@@ -1,6 +1,7 @@
 // Gauss-Newton pose refinement from a GIVEN pose (port extension): the refinement step of cmr_pnp_ransac_f32 (DESIGN.md
-// 4l, csrc/pnp.hip pnp_select_kernel) restated so that it starts from any pose, with the accumulation split over the correspondences
-// instead of running in one workgroup per sample.
+// 4l, csrc/pnp.hip pnp_select_kernel) from any start pose, with the accumulation split over the correspondences instead of running in
+// one workgroup per sample.  The two share their pieces through cmr_pnp.h: the inlier test, one correspondence's terms (cmr_pnp_terms),
+// the Cholesky solve, the working pose's load, left update and fp32 4x4 form, and the slice-order sum.
 //
 // Launches, all on the caller's stream; the sequence depends on `iters` alone (3 + 2 (iters + 1) launches), a sample that has stopped
 // turns its remaining launches into early returns read from its state in the workspace:
@@ -22,7 +23,7 @@ namespace {
 
 constexpr int PRF_THREADS = 256;
 constexpr int PRF_SLICE = 1024;      // rows per accumulation workgroup: 4 per thread.  A constant: the summation order must not depend on B
-constexpr int PRF_NACC = 28;         // J^T J (21 upper-triangle entries), J^T r (6), cost
+constexpr int PRF_NACC = CMR_GN_NACC; // J^T J (21 upper-triangle entries), J^T r (6), cost
 
 struct PrfState {
   double cur[12];                    // the working pose: R row-major, t
@@ -40,10 +41,7 @@ __global__ __launch_bounds__(64) void prf_init_kernel(const float* __restrict__ 
   const float* P = pose_in + 16 * b;
   double K[9];
   for (int i = 0; i < 9; ++i) K[i] = (double)Kin[9 * b + i];
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) st.cur[3 * i + j] = (double)P[4 * i + j];
-    st.cur[9 + i] = (double)P[4 * i + 3];
-  }
+  cmr_pose_load(P, st.cur);
   for (int i = 0; i < 12; ++i) st.prev[i] = st.cur[i];
   st.cost_prev = 0.0;
   cmr_pnp_kmat(K, st.cur, st.cur + 9, st.Min);
@@ -79,26 +77,7 @@ __global__ __launch_bounds__(PRF_THREADS) void prf_accum_kernel(const float* __r
     const float X = pb[i], Y = pb[N + i], Z = pb[2 * N + i], u = qb[i], v = qb[N + i];
     if (!cmr_pnp_inlier(Min, X, Y, Z, u, v, thr2)) continue;
     ++c;
-    const double xc0 = R[0] * X + R[1] * Y + R[2] * Z + t[0], xc1 = R[3] * X + R[4] * Y + R[5] * Z + t[1],
-                 xc2 = R[6] * X + R[7] * Y + R[8] * Z + t[2];
-    const double p0 = K[0] * xc0 + K[1] * xc1 + K[2] * xc2, p1 = K[3] * xc0 + K[4] * xc1 + K[5] * xc2,
-                 p2 = K[6] * xc0 + K[7] * xc1 + K[8] * xc2;
-    if (!(p2 > 0.0)) continue;
-    const double iz = 1.0 / p2, pu = p0 * iz, pv = p1 * iz;
-    const double ru = pu - u, rv = pv - v;
-    const double ga[3] = {(K[0] - K[6] * pu) * iz, (K[1] - K[7] * pu) * iz, (K[2] - K[8] * pu) * iz};     // d pu / d xc
-    const double gb[3] = {(K[3] - K[6] * pv) * iz, (K[4] - K[7] * pv) * iz, (K[5] - K[8] * pv) * iz};
-    // d / d omega (left increment): xc x g
-    const double ja[6] = {xc1 * ga[2] - xc2 * ga[1], xc2 * ga[0] - xc0 * ga[2], xc0 * ga[1] - xc1 * ga[0], ga[0], ga[1], ga[2]};
-    const double jb[6] = {xc1 * gb[2] - xc2 * gb[1], xc2 * gb[0] - xc0 * gb[2], xc0 * gb[1] - xc1 * gb[0], gb[0], gb[1], gb[2]};
-    int q = 0;
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int cc = r; cc < 6; ++cc) a[q++] += ja[r] * ja[cc] + jb[r] * jb[cc];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) a[21 + r] += ja[r] * ru + jb[r] * rv;
-    a[27] += ru * ru + rv * rv;
+    cmr_pnp_terms(K, R, t, X, Y, Z, u, v, a);
   }
 #pragma unroll
   for (int q = 0; q < PRF_NACC; ++q) {
@@ -125,9 +104,7 @@ __global__ __launch_bounds__(64) void prf_step_kernel(int it, int iters, int nsl
   PrfState& st = state[b];
   if (st.stop) return;
   if (tid < PRF_NACC) {
-    double v = 0.0;
-    for (int s = 0; s < nslice; ++s) v += slots[((int64_t)b * nslice + s) * PRF_NACC + tid];       // slice order
-    tot[tid] = v;
+    tot[tid] = cmr_slot_sum(slots + (int64_t)b * nslice * PRF_NACC, nslice, tid);
   } else if (tid == PRF_NACC) {
     int c = 0;
     for (int s = 0; s < nslice; ++s) c += cslots[(int64_t)b * nslice + s];
@@ -151,18 +128,8 @@ __global__ __launch_bounds__(64) void prf_step_kernel(int it, int iters, int nsl
   if (it == iters) { st.stop = 1; return; }
   double g[6], dx[6];
   for (int r = 0; r < 6; ++r) g[r] = -tot[21 + r];
-  bool ok = cmr_pnp_chol6<true>(tot, g, dx);
   double nw[12];
-  if (ok) {
-    double E[9];
-    cmr_pnp_expso3(dx, E);
-    for (int i = 0; i < 3; ++i) {
-      for (int j = 0; j < 3; ++j) nw[3 * i + j] = E[3 * i] * st.cur[j] + E[3 * i + 1] * st.cur[3 + j] + E[3 * i + 2] * st.cur[6 + j];
-      nw[9 + i] = E[3 * i] * st.cur[9] + E[3 * i + 1] * st.cur[10] + E[3 * i + 2] * st.cur[11] + dx[3 + i];
-    }
-    for (int i = 0; i < 12; ++i) ok = ok && isfinite(nw[i]);
-  }
-  if (!ok) {
+  if (!(cmr_pnp_chol6<true>(tot, g, dx) && cmr_pose_left_update(st.cur, dx, nw))) {
     if (it == 0) st.status = 2;                                          // nothing to refine with: the call returns pose_in
     st.stop = 1;
     return;
@@ -215,12 +182,7 @@ __global__ __launch_bounds__(64) void prf_final_kernel(const float* __restrict__
     status[b] = st.status != 0 ? st.status : (use ? 0 : 2);
   }
   __syncthreads();
-  if (tid < 16) {
-    const int r = tid >> 2, c = tid & 3;
-    float val = pose_in[16 * b + tid];
-    if (sh_use) val = r == 3 ? (c == 3 ? 1.f : 0.f) : (float)(c < 3 ? st.cur[3 * r + c] : st.cur[9 + r]);
-    pose[16 * b + tid] = val;
-  }
+  if (tid < 16) pose[16 * b + tid] = sh_use ? cmr_pose_entry(st.cur, tid) : pose_in[16 * b + tid];
 }
 
 struct PrfWs { int64_t state, slots, cslots, total; };

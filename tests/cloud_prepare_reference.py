@@ -169,6 +169,38 @@ def scene_case(seed):
     return dict(raw=raw, down=down, cloud=cloud, normals=point_normals(cloud))
 
 
+# ---- a cloud whose second cluster lies beyond 2^19 cells from the grid's origin ---------------------------------------------------------------
+FAR_RADIUS = 1.0
+
+
+def walk_runs(points, cell, origin=None):
+    """The number of runs of sorted rows that the kernels' walk (csrc/cmr_cloud_grid.h: axis_cells, Walk) searches for every row of the
+    cloud on the grid of `cell` whose origin is the cloud's minimum: (cells along y) * (cells along z), in the header's fp32 arithmetic.
+    A 16-lane group takes 16 runs in one pass; more need the second one."""
+    p = np.asarray(points, dtype=np.float32)
+    o = p.min(0) if origin is None else np.asarray(origin, dtype=np.float32)
+    t = (p - o) / np.float32(cell)
+    c = np.floor(t)
+    tol = (t + np.float32(2.0)) * np.float32(9.5367431640625e-07)
+    frac = t - c
+    lo = np.maximum(c.astype(np.int64) - 1 - (frac < tol), 0)
+    hi = np.minimum(c.astype(np.int64) + 1 + (frac > np.float32(1.0) - tol), CELL_LIMIT - 1)
+    n = hi - lo + 1
+    return n[:, 1] * n[:, 2]
+
+
+@functools.lru_cache(maxsize=None)
+def far_case():
+    """-> dict(cloud float32 [120, 3]: 60 rows in [0, 2)^3 and 60 rows on a lattice of 1/16 at 700 000, where a cell coordinate of the
+    radius-1 grid is rounded to 1/16 and axis_cells adds a cell on both sides of an axis: 16, 20 or 25 runs, the walk's second pass; normals
+    = point_normals(cloud, 1.0)).  Callers must not modify it."""
+    r = np.random.default_rng(5)
+    first = r.uniform(0.0, 2.0, (60, 3))
+    second = np.float32(700000) + r.integers(0, 33, (60, 3)) * 0.0625
+    cloud = np.concatenate([first, second]).astype(np.float32)
+    return dict(cloud=cloud, normals=point_normals(cloud, FAR_RADIUS))
+
+
 # ---- the ops' interface on the restatement (CPU stand-ins for tests of the file layer) -----------------------------------------------------
 def ops_voxel_downsample(points, attr=None, voxel=VOXEL, origin=None, want_inverse=False):
     import torch

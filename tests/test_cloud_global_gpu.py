@@ -17,6 +17,7 @@ import torch
 
 import cloud_global_reference as G
 import cloud_icp_reference as I
+import cloud_prepare_reference as P
 from cmr_agent_amd import _lib, ops
 
 pytestmark = pytest.mark.gpu
@@ -91,6 +92,32 @@ def test_fpfh_scene_pair():
     assert ref["part"].sum() == 4447 and ref["count"].max() > 256
     g = G.global_case("other", 3)
     _check_fpfh(g["source"], g["source_normals"], G.RADIUS, ref=g["feat"])
+
+
+def test_fpfh_far_from_the_origin_takes_the_walks_second_pass():
+    """Rows beyond 2^19 cells from the grid's origin search 20 or 25 runs, more than the 16 lanes of a group take in one pass
+    (cloud_prepare_reference.far_case; tests/test_cloud_prepare_cpu.py asserts the run counts), in both kernels."""
+    case = P.far_case()
+    got, ref = _check_fpfh(case["cloud"], case["normals"]["normals"].astype(np.float32), P.FAR_RADIUS)
+    assert ref["part"].all() and ref["count"][60:].min() >= 3 and not ref["edge"].any()
+
+
+@pytest.mark.parametrize("which", ("far", "scene"))
+def test_fpfh_and_normals_count_the_same_neighbourhood(which):
+    """The users of the walk agree on it: where a row and all of its neighbours have a normal, point_fpfh counts the row's neighbours and
+    point_normals counts them and the row itself, through the same walk and the same fp32 membership test -- count == count - 1, exactly."""
+    cloud, radius = (P.far_case()["cloud"], P.FAR_RADIUS) if which == "far" else (P.scene_case(P.SEEDS[0])["cloud"], P.RADIUS)
+    nrm = ops.point_normals(F(cloud), radius=radius)
+    fp = ops.point_fpfh(F(cloud), nrm.normals, radius)
+    zero = ~nrm.normals.cpu().numpy().any(1)
+    r2 = np.float32(radius) * np.float32(radius)
+    beside_zero = np.zeros(len(cloud), bool)                            # a row without a normal within the radius, the row itself included
+    for z in cloud[zero]:
+        d = cloud - z
+        beside_zero |= (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2] <= r2
+    rows = ~beside_zero
+    assert rows.sum() >= 100 and (which == "far") == rows.all()
+    assert np.array_equal(fp.count.cpu().numpy()[rows], nrm.count.cpu().numpy()[rows] - 1)
 
 
 def test_fpfh_neighbours_on_the_radius_duplicates_and_a_larger_cell():

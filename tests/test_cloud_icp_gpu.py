@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import cloud_icp_reference as R
+import cloud_prepare_reference as P
 from cmr_agent_amd import ops
 from cmr_agent_amd.dataset import align
 
@@ -87,6 +88,15 @@ def test_nearest_lattice_every_row_on_a_face_every_neighbour_at_the_radius():
     t = (np.stack(np.meshgrid(*[np.arange(9, dtype=np.float32)] * 3, indexing="ij"), -1).reshape(-1, 3) * np.float32(0.3) + np.float32(7.1)).astype(np.float32)
     _check_nearest(t[::2], t[1::2], np.float32(0.3))
     _check_nearest(t[::2], t[1::2], np.float32(0.3) * np.float32(1.0000001))
+
+
+def test_nearest_far_from_the_origin_takes_the_walks_second_pass():
+    """Queries beyond 2^19 cells from the grid's origin search 20 or 25 runs, more than the 16 lanes of a group take in one pass
+    (cloud_prepare_reference.far_case; tests/test_cloud_prepare_cpu.py asserts the run counts)."""
+    cloud = P.far_case()["cloud"]
+    queries = np.concatenate([cloud[:60] + np.float32(0.01), cloud[60:] + np.float32(0.0625) * np.float32([1, 0, 1])]).astype(np.float32)
+    idx, _ = _check_nearest(cloud, queries, P.FAR_RADIUS, P.FAR_RADIUS)
+    assert (idx >= 0).all() and (idx[60:] >= 60).all()
 
 
 def test_nearest_duplicated_rows_tie_to_the_lowest():

@@ -97,6 +97,17 @@ def test_scene_conditions(seed):
     assert 3000 <= down["count"].size < case["raw"].shape[0]
 
 
+def test_far_case_reaches_the_walks_second_pass():
+    """What the GPU tier's far-cloud cases assume: the rows of the second cluster search more than 16 runs (a 16-lane group's second pass,
+    csrc/cmr_cloud_grid.h walk16) or exactly 16, and every row is compared -- none near the radius, none without a normal."""
+    case = R.far_case()
+    cloud, ref = case["cloud"], case["normals"]
+    runs = R.walk_runs(cloud, R.FAR_RADIUS)
+    assert cloud.shape == (120, 3) and set(runs[60:].tolist()) == {16, 20, 25} and (runs[60:] > 16).sum() >= 30 and runs[:60].max() <= 9
+    assert not ref["near"].any() and not ref["zero"].any() and R.excluded_share(ref) == 0 and R.kept_rows(ref).all()
+    assert R.walk_runs(R.scene_case(R.SEEDS[0])["cloud"], R.RADIUS).max() <= 16                    # no row of a scene gets there
+
+
 def test_fp32_sums_sit_inside_the_angle_bar():
     """The bar the GPU tier asserts (4 k 2^-24 / gap) against an emulation of what a kernel may do: covariance sums in float32,
     accumulated row by row, the solve in float64."""

@@ -158,6 +158,14 @@ def test_normals_scenes(seed):
     assert ops.point_normals(F(case["cloud"])).eigenvalues is None
 
 
+def test_normals_far_from_the_origin_take_the_walks_second_pass():
+    """Rows beyond 2^19 cells from the grid's origin search 20 or 25 runs, more than the 16 lanes of a group take in one pass
+    (tests/test_cloud_prepare_cpu.py asserts that of the case).  Every row is compared."""
+    case = R.far_case()
+    got = ops.point_normals(F(case["cloud"]), radius=R.FAR_RADIUS, want_eigenvalues=True)
+    _check_normals(case["cloud"], case["normals"], got, "far cloud", max_excluded=0)
+
+
 def test_normals_of_a_permuted_cloud():
     case = R.scene_case(R.SEEDS[0])
     cloud, ref = case["cloud"], case["normals"]
