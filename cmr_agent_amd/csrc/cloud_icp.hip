@@ -32,13 +32,6 @@ struct IcpState {
   int32_t stop, code, executed, pad;
 };
 
-// q = R p + t in fp32, every operation rounded on its own, left to right
-__device__ __forceinline__ void pose_apply(const float (&T)[12], float px, float py, float pz, float& qx, float& qy, float& qz) {
-#pragma clang fp contract(off)
-  qx = ((T[0] * px + T[1] * py) + T[2] * pz) + T[9];
-  qy = ((T[3] * px + T[4] * py) + T[5] * pz) + T[10];
-  qz = ((T[6] * px + T[7] * py) + T[8] * pz) + T[11];
-}
 // The nearest target row of q for one 16-lane group (every lane of the wave calls it; `live` is uniform over the group, as walk16 asks):
 // the least d2 among the rows with d2 <= r2, on equal d2 the lowest original row.  -> row (NO_ROW: none), d2, and pos = its place in key order.
 __device__ __forceinline__ void nearest16(float qx, float qy, float qz, bool live, const GridIndex& index, float r2, int lane, int& row,
@@ -82,12 +75,7 @@ __global__ __launch_bounds__(256) void cloud_nearest_kernel(const float* __restr
   float qx = p[0], qy = p[1], qz = p[2];
   if (pose) {
     float T[12];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) T[3 * r + c] = pose[4 * r + c];
-      T[9 + r] = pose[4 * r + 3];
-    }
+    pose_load(pose, T);
     pose_apply(T, qx, qy, qz, qx, qy, qz);
   }
   int row, pos;

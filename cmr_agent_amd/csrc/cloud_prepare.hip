@@ -6,7 +6,7 @@
 //   cmr_segment_heads_i64    runs of equal keys -> CSR offsets, counts, the int32 row order cmr_segment_reduce_f32 takes, the inverse map
 //   cmr_cloud_gather4_f32    the kept rows as float4 in key order: the rows of a grid index (ops.cloud_index; cloud_icp.hip searches them)
 //   cmr_point_normals_f32    fixed-radius neighbourhoods over the sorted cells, 3x3 covariance, its smallest eigenvector
-// The index, the walk over a neighbourhood's runs and the membership test live in cmr_cloud_grid.h (GridIndex, Walk, walk16), the Jacobi
+// The index, the walk over a neighbourhood's runs, the membership test and the workgroup scan live in cmr_cloud_grid.h (GridIndex, Walk, walk16, scan256), the Jacobi
 // rotation and the finite test in cmr_common.h.
 //
 // No float atomics anywhere: min / max and the integer counts are order free, every float sum runs in a fixed order.
@@ -93,22 +93,6 @@ __global__ __launch_bounds__(256) void voxel_keys_kernel(const float* __restrict
 // 1024 rows, an exclusive scan of the tile totals by one workgroup, then every row's run number.
 __device__ __forceinline__ int head_at(const int64_t* __restrict__ keys, int64_t i, int64_t kept) {
   return i < kept && (i == 0 || keys[i] != keys[i - 1]) ? 1 : 0;
-}
-// exclusive scan of one int per thread over the workgroup of 256 (Hillis-Steele in LDS); `total` is the workgroup's sum
-__device__ __forceinline__ int scan256(int v, int (&buf)[256], int& total) {
-  const int t = threadIdx.x;
-  buf[t] = v;
-  __syncthreads();
-  for (int off = 1; off < 256; off <<= 1) {
-    const int a = t >= off ? buf[t - off] : 0;
-    __syncthreads();
-    buf[t] += a;
-    __syncthreads();
-  }
-  const int incl = buf[t];
-  total = buf[255];
-  __syncthreads();
-  return incl - v;
 }
 __global__ __launch_bounds__(256) void heads_count_kernel(const int64_t* __restrict__ keys, int64_t kept, int32_t* __restrict__ tile_sum) {
   __shared__ int buf[256];
@@ -273,8 +257,6 @@ __global__ __launch_bounds__(256) void point_normals_kernel(GridIndex index, int
   }
   count[row] = live ? k : 0;
 }
-
-inline unsigned blocks_of(int64_t items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
 
 }  // namespace
 

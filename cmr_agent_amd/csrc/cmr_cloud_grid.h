@@ -1,7 +1,8 @@
 // The sorted-key uniform grid that the cloud kernels share (cloud_prepare.hip: keys and normals; cloud_icp.hip: nearest row
 // and point-to-plane ICP; cloud_fpfh.hip: SPFH and FPFH), stated once: the cell of a coordinate, the key of a
 // cell, the cells a fixed-radius query searches along an axis, the run of sorted rows behind a range of keys, the membership test -- and the
-// index as the kernels take it (GridIndex), the cells round a row or a free query (Walk) and the one loop over them (walk16), DESIGN.md 4ag.
+// index as the kernels take it (GridIndex), the cells round a row or a free query (Walk) and the one loop over them (walk16), DESIGN.md 4ag;
+// and what else more than one cloud source states (voxel_map.hip): the fp32 pose step, the workgroup scan, the block count.
 // Device code, and the host's check of a GridIndex.
 #pragma once
 #include "cmr_common.h"
@@ -64,6 +65,41 @@ __device__ __forceinline__ int isum16(int s) {
   s += cmr_dpp<0x140>(s);
   return s;
 }
+
+// ---- what the cloud sources share beside the grid ----------------------------------------------------------------------------------------
+// a pose as the kernels apply it: R row-major, then t -- from the upper 3 x 4 of a row-major fp32 [4][4]
+__device__ __forceinline__ void pose_load(const float* __restrict__ pose, float (&T)[12]) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) T[3 * r + c] = pose[4 * r + c];
+    T[9 + r] = pose[4 * r + 3];
+  }
+}
+// q = R p + t in fp32, every operation rounded on its own, left to right
+__device__ __forceinline__ void pose_apply(const float (&T)[12], float px, float py, float pz, float& qx, float& qy, float& qz) {
+#pragma clang fp contract(off)
+  qx = ((T[0] * px + T[1] * py) + T[2] * pz) + T[9];
+  qy = ((T[3] * px + T[4] * py) + T[5] * pz) + T[10];
+  qz = ((T[6] * px + T[7] * py) + T[8] * pz) + T[11];
+}
+// exclusive scan of one int per thread over the workgroup of 256 (Hillis-Steele in LDS); `total` is the workgroup's sum
+__device__ __forceinline__ int scan256(int v, int (&buf)[256], int& total) {
+  const int t = threadIdx.x;
+  buf[t] = v;
+  __syncthreads();
+  for (int off = 1; off < 256; off <<= 1) {
+    const int a = t >= off ? buf[t - off] : 0;
+    __syncthreads();
+    buf[t] += a;
+    __syncthreads();
+  }
+  const int incl = buf[t];
+  total = buf[255];
+  __syncthreads();
+  return incl - v;
+}
+static inline unsigned blocks_of(int64_t items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
 
 // ---- the index ---------------------------------------------------------------------------------------------------------------------------
 // A grid index as ops.cloud_index builds it, passed to the kernels by value: the kept rows as float4 in key order, their sorted keys, their

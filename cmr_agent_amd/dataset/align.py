@@ -20,8 +20,18 @@ repeats the pair from `global` when ICP ends with status 2 or 3; one more line i
 
     pair <i> <i+1>: global inliers <n> of <L> status <s>
 
+--map K (0, the default, is all of the above unchanged) registers frame j against the voxel map of the last K registered
+frames, kept in frame A's coordinates by `ops.voxel_map_insert` (HIP, csrc/voxel_map.hip), instead of against frame i alone: the map's
+normals are `ops.point_normals` of its points seen from frame i's position, the start pose is frame i's pose times the previous relative
+motion, and ICP's result is frame j's pose in frame A directly.  t and r of the pair's line stay those of the relative pose; a `global` or
+`auto` fallback registers against frame i as above and is moved into frame A.  The map's grid starts at -extent / 2 on each axis; when c
+of frame j's n rows fall off it, one more line follows the pair's:
+
+    pair <i> <i+1>: outside <c> of <n>
+
     python -m cmr_agent_amd.dataset.align --root DIR --sequence S [--frames A:B --max-dist 1.0 --huber 0.1 --iters 30 --out FILE]
                                           [--init previous|global|auto --fpfh-radius 1.0 --ransac-hyp 4096 --ransac-thr 0.3 --seed 0]
+                                          [--map K --map-voxel 0.1 --map-extent 8192 --map-normal-radius 0.6]
 """
 import argparse
 import math
@@ -91,56 +101,50 @@ def align_sequence(files, max_dist=1.0, huber=0.1, iters=30, device=None, report
     return np.stack(chain[:len(files)]) if files else np.zeros((0, 4, 4))
 
 
-def parse_args(argv=None):
-    ap = argparse.ArgumentParser(prog="python -m cmr_agent_amd.dataset.align", description=__doc__.split("\n\n")[0])
-    ap.add_argument("--root", required=True, help="dataset root: <root>/<data_velodyne>/sequences/<seq>/<subdir>/*.npy is read")
-    ap.add_argument("--sequence", required=True, type=int, help="the sequence number")
-    ap.add_argument("--frames", default=":", help="A:B, the frames A <= i < B of the sequence (default: all of them)")
-    ap.add_argument("--data-velodyne", default=None, help="the velodyne folder under --root (default: the KITTI configuration's data_velodyne)")
-    ap.add_argument("--subdir", default=prepare.subdir(), help="the prepared folder of the sequence (default %s)" % prepare.subdir())
-    ap.add_argument("--max-dist", type=float, default=1.0, help="largest distance of a pair in metres, and the grid's cell (default 1.0)")
-    ap.add_argument("--huber", type=float, default=0.1, help="residuals above this many metres are down-weighted; 0 = off (default 0.1)")
-    ap.add_argument("--iters", type=int, default=30, help="most iterations per pair (default 30)")
-    ap.add_argument("--out", default=None, help="write the chained poses here, 12 numbers per line")
-    ap.add_argument("--init", default="previous", choices=("previous", "global", "auto"),
-                    help="a pair's start pose: the previous pair's result (default), a global registration from FPFH descriptors and RANSAC, "
-                         "or the first and, when ICP ends with status 2 or 3, the second")
-    ap.add_argument("--fpfh-radius", type=float, default=1.0, help="radius of the FPFH descriptors in metres (default 1.0)")
-    ap.add_argument("--ransac-hyp", type=int, default=4096, help="RANSAC hypotheses of a global registration (default 4096)")
-    ap.add_argument("--ransac-thr", type=float, default=0.3, help="RANSAC inlier distance in metres (default 0.3)")
-    ap.add_argument("--seed", type=int, default=0, help="seed of the RANSAC draws (default 0)")
-    args = ap.parse_args(argv)
-    if not 0 <= args.sequence <= 99:
-        ap.error("--sequence must lie in [0, 99]")
-    if not (0.0 < args.max_dist < float("inf")):
-        ap.error("--max-dist must be finite and > 0, got %r" % (args.max_dist,))
-    if not (0.0 <= args.huber < float("inf")):
-        ap.error("--huber must be finite and >= 0, got %r" % (args.huber,))
-    if not 0 <= args.iters <= ops.ICP_MAX_ITERS:
-        ap.error("--iters must lie in [0, %d]" % ops.ICP_MAX_ITERS)
-    if not (0.0 < args.fpfh_radius < float("inf")):
-        ap.error("--fpfh-radius must be finite and > 0, got %r" % (args.fpfh_radius,))
-    if not 1 <= args.ransac_hyp <= ops.RANSAC_MAX_HYP:
-        ap.error("--ransac-hyp must lie in [1, %d]" % ops.RANSAC_MAX_HYP)
-    if not (0.0 < args.ransac_thr < float("inf")):
-        ap.error("--ransac-thr must be finite and > 0, got %r" % (args.ransac_thr,))
-    if not 0 <= args.seed < 1 << 32:
-        ap.error("--seed must lie in [0, 2^32)")
-    try:
-        a, b = args.frames.split(":")
-        args.frames = (int(a) if a else 0, int(b) if b else None)
-        if args.frames[0] < 0 or (args.frames[1] is not None and args.frames[1] < args.frames[0]):
-            raise ValueError
-    except ValueError:
-        ap.error("--frames must be A:B with integers 0 <= A <= B (either may be left out)")
-    if args.data_velodyne is None:
-        from ..config.KittiConfig import KittiConfiguration
-        args.data_velodyne = KittiConfiguration(None).data_velodyne
-    return ap, args
+def align_to_map(files, k, max_dist=1.0, huber=0.1, iters=30, device=None, report=print, init="previous", fpfh_radius=1.0, ransac_hyp=4096,
+                 ransac_thr=0.3, seed=0, map_voxel=0.1, map_extent=8192.0, map_normal_radius=0.6):
+    """align_sequence against a map: the target of pair (i, j) is the voxel map of the last k registered frames in the first
+    frame's coordinates (ops.voxel_map_insert with stamp = the frame number and min_stamp = j - k), its normals ops.point_normals of the
+    map's points seen from frame i's position, and ICP's result is frame j's pose in the first frame directly.  Same lines as
+    align_sequence, t and r those of the pose relative to frame i; `pair <i> <j>: outside <c> of <n>` follows when c of frame j's n rows
+    fell off the map's grid."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    rows = lambda a: torch.from_numpy(np.ascontiguousarray(a.T)).to(device)            # noqa: E731
+    tensor = lambda T: torch.from_numpy(T.astype(np.float32)).to(device)               # noqa: E731
+    chain, rel = [np.eye(4)], np.eye(4)
+    vmap = ops.voxel_map(map_voxel, (-map_extent / 2,) * 3, device=device)
+    target = None
+    for n, (j, path) in enumerate(files):
+        source = read_prepared(path)
+        xyz = rows(source[0:3])
+        if n:
+            i = j - 1
+            normals = ops.point_normals(vmap.points, radius=map_normal_radius, viewpoint=tuple(chain[-1][:3, 3])).normals
+            icp = lambda start: ops.icp_point_to_plane(xyz, vmap.points, normals, pose=tensor(start), max_dist=max_dist, huber=huber,  # noqa: E731
+                                                       iters=iters)
+            res = None
+            if init != "global":
+                res = icp(chain[-1] @ rel)
+            if init == "global" or (init == "auto" and res.status in (2, 3)):
+                g = global_start(target, source, fpfh_radius, ransac_hyp, ransac_thr, seed, device)
+                if init == "auto":
+                    report("pair %d %d: global inliers %d of %d status %d" % (i, j, g.inliers, g.correspondences, g.status))
+                res = icp(chain[-1] @ g.pose.cpu().numpy().astype(np.float64))
+            T = res.pose.cpu().numpy().astype(np.float64)
+            rel = np.linalg.inv(chain[-1]) @ T
+            report("pair %d %d: pairs %d rmse %.4f iterations %d status %d t %.4f %.4f %.4f r %.4f" % (
+                i, j, res.pairs, res.rmse, res.iterations, res.status, rel[0, 3], rel[1, 3], rel[2, 3], rotation_degrees(rel)))
+            chain.append(T)
+        ins = ops.voxel_map_insert(vmap, xyz, pose=tensor(chain[-1]), stamp=j, min_stamp=max(0, j + 1 - k))
+        if n and ins.outside:
+            report("pair %d %d: outside %d of %d" % (j - 1, j, ins.outside, xyz.shape[0]))
+        vmap, target = ins.map, source
+    return np.stack(chain) if files else np.zeros((0, 4, 4))
 
 
-def main(argv=None, device=None):
-    ap, args = parse_args(argv)
+def sequence_files(ap, args):
+    """The prepared files of the frames --frames names as (frame number, path), consecutive; anything else is an argparse error."""
     folder = os.path.join(args.root, args.data_velodyne, "sequences", "%02d" % args.sequence, args.subdir)
     if not os.path.isdir(folder):
         ap.error("%s is not a directory; python -m cmr_agent_amd.dataset.prepare writes it" % folder)
@@ -159,9 +163,86 @@ def main(argv=None, device=None):
         if len(shape) == 2 and shape[0] == 4:
             ap.error("%s holds [4, n] rows and no normals; write [7, n] files with python -m cmr_agent_amd.dataset.prepare "
                      "(without --no-normals)" % path)
+    return files
+
+
+def sequence_flags(ap):
+    """the flags that name the prepared files of a sequence"""
+    ap.add_argument("--root", required=True, help="dataset root: <root>/<data_velodyne>/sequences/<seq>/<subdir>/*.npy is read")
+    ap.add_argument("--sequence", required=True, type=int, help="the sequence number")
+    ap.add_argument("--frames", default=":", help="A:B, the frames A <= i < B of the sequence (default: all of them)")
+    ap.add_argument("--data-velodyne", default=None, help="the velodyne folder under --root (default: the KITTI configuration's data_velodyne)")
+    ap.add_argument("--subdir", default=prepare.subdir(), help="the prepared folder of the sequence (default %s)" % prepare.subdir())
+
+
+def check_sequence_flags(ap, args):
+    if not 0 <= args.sequence <= 99:
+        ap.error("--sequence must lie in [0, 99]")
     try:
-        chain = align_sequence(files, args.max_dist, args.huber, args.iters, device, init=args.init, fpfh_radius=args.fpfh_radius,
-                               ransac_hyp=args.ransac_hyp, ransac_thr=args.ransac_thr, seed=args.seed)
+        a, b = args.frames.split(":")
+        args.frames = (int(a) if a else 0, int(b) if b else None)
+        if args.frames[0] < 0 or (args.frames[1] is not None and args.frames[1] < args.frames[0]):
+            raise ValueError
+    except ValueError:
+        ap.error("--frames must be A:B with integers 0 <= A <= B (either may be left out)")
+    if args.data_velodyne is None:
+        from ..config.KittiConfig import KittiConfiguration
+        args.data_velodyne = KittiConfiguration(None).data_velodyne
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m cmr_agent_amd.dataset.align", description=__doc__.split("\n\n")[0])
+    sequence_flags(ap)
+    ap.add_argument("--max-dist", type=float, default=1.0, help="largest distance of a pair in metres, and the grid's cell (default 1.0)")
+    ap.add_argument("--huber", type=float, default=0.1, help="residuals above this many metres are down-weighted; 0 = off (default 0.1)")
+    ap.add_argument("--iters", type=int, default=30, help="most iterations per pair (default 30)")
+    ap.add_argument("--out", default=None, help="write the chained poses here, 12 numbers per line")
+    ap.add_argument("--init", default="previous", choices=("previous", "global", "auto"),
+                    help="a pair's start pose: the previous pair's result (default), a global registration from FPFH descriptors and RANSAC, "
+                         "or the first and, when ICP ends with status 2 or 3, the second")
+    ap.add_argument("--fpfh-radius", type=float, default=1.0, help="radius of the FPFH descriptors in metres (default 1.0)")
+    ap.add_argument("--ransac-hyp", type=int, default=4096, help="RANSAC hypotheses of a global registration (default 4096)")
+    ap.add_argument("--ransac-thr", type=float, default=0.3, help="RANSAC inlier distance in metres (default 0.3)")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the RANSAC draws (default 0)")
+    ap.add_argument("--map", type=int, default=0, metavar="K",
+                    help="register every frame against the voxel map of the last K registered frames instead of the frame before it (default 0: off)")
+    ap.add_argument("--map-voxel", type=float, default=0.1, help="the map's voxel in metres (default 0.1)")
+    ap.add_argument("--map-extent", type=float, default=8192.0, help="the map's grid starts at -extent / 2 on each axis, in metres (default 8192)")
+    ap.add_argument("--map-normal-radius", type=float, default=0.6, help="radius of the map's normals in metres (default 0.6)")
+    args = ap.parse_args(argv)
+    check_sequence_flags(ap, args)
+    if not (0.0 < args.max_dist < float("inf")):
+        ap.error("--max-dist must be finite and > 0, got %r" % (args.max_dist,))
+    if not (0.0 <= args.huber < float("inf")):
+        ap.error("--huber must be finite and >= 0, got %r" % (args.huber,))
+    if not 0 <= args.iters <= ops.ICP_MAX_ITERS:
+        ap.error("--iters must lie in [0, %d]" % ops.ICP_MAX_ITERS)
+    if not (0.0 < args.fpfh_radius < float("inf")):
+        ap.error("--fpfh-radius must be finite and > 0, got %r" % (args.fpfh_radius,))
+    if not 1 <= args.ransac_hyp <= ops.RANSAC_MAX_HYP:
+        ap.error("--ransac-hyp must lie in [1, %d]" % ops.RANSAC_MAX_HYP)
+    if not (0.0 < args.ransac_thr < float("inf")):
+        ap.error("--ransac-thr must be finite and > 0, got %r" % (args.ransac_thr,))
+    if not 0 <= args.seed < 1 << 32:
+        ap.error("--seed must lie in [0, 2^32)")
+    if not 0 <= args.map < 1 << 31:
+        ap.error("--map must lie in [0, 2^31)")
+    for name in ("map_voxel", "map_extent", "map_normal_radius"):
+        if not (0.0 < getattr(args, name) < float("inf")):
+            ap.error("--%s must be finite and > 0, got %r" % (name.replace("_", "-"), getattr(args, name)))
+    return ap, args
+
+
+def main(argv=None, device=None):
+    ap, args = parse_args(argv)
+    files = sequence_files(ap, args)
+    kw = dict(init=args.init, fpfh_radius=args.fpfh_radius, ransac_hyp=args.ransac_hyp, ransac_thr=args.ransac_thr, seed=args.seed)
+    try:
+        if args.map:
+            chain = align_to_map(files, args.map, args.max_dist, args.huber, args.iters, device, map_voxel=args.map_voxel,
+                                 map_extent=args.map_extent, map_normal_radius=args.map_normal_radius, **kw)
+        else:
+            chain = align_sequence(files, args.max_dist, args.huber, args.iters, device, **kw)
     except ValueError as e:
         ap.error(str(e))
     if args.out is not None:

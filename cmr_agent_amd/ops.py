@@ -2961,3 +2961,145 @@ def register_global(source, source_normals, target, target_normals, radius=1.0, 
     kw.update(icp)
     res = icp_point_to_plane(source, target, target_normals, pose=rr.pose, **kw)
     return GlobalResult(res.pose if res.status in (0, 1) else rr.pose, rr.inliers, corr.shape[0], rr.status, res)
+
+
+# ---- a voxel map of registered scans: insert, merge, forget (csrc/voxel_map.hip) --------------------------------------------
+VOXEL_MAP_MAX_STAMP = (1 << 31) - 1
+
+
+class VoxelMap(collections.namedtuple("VoxelMap", "keys points attr count stamp origin voxel")):
+    """A voxel map: keys int64 [n] ascending and unique, points float32 [n, 3] and attr float32 [n, C] = the running means of the rows that
+    fell into each voxel, count int32 [n] = their number, stamp int32 [n] = the stamp of the last insert that touched the voxel; origin =
+    the grid's origin (three python floats holding fp32 values, fixed for the map's life), voxel = its cell.  ops.voxel_map makes the empty
+    one, ops.voxel_map_insert a new one from an old one; nothing changes a map in place."""
+
+
+class MapInsert(collections.namedtuple("MapInsert", "map new merged removed dropped outside")):
+    """voxel_map_insert's result: the new map; new = voxels the scan added, merged = voxels of the map the scan touched, removed = rows
+    forgotten (stamp below min_stamp after the insert); dropped = input rows with a non-finite coordinate before or after the pose, outside
+    = finite input rows off the grid on some axis."""
+
+
+def voxel_map(voxel, origin, channels=0, device=None):
+    """The empty map on the grid (origin, voxel) with `channels` attribute columns.  origin: three finite fp32 values, required -- a map
+    that grows cannot take its origin from the first scan's corner, and every later key depends on it."""
+    who = "voxel_map"
+    voxel = _cloud_scalar(voxel, "voxel")
+    origin = tuple(float(np.float32(v)) for v in _cloud_triple(origin, "origin"))
+    channels = _int_arg(who, "channels", channels, 0, 1 << 16)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    return VoxelMap(torch.empty((0,), dtype=torch.int64, device=dev), torch.empty((0, 3), dtype=f32, device=dev),
+                    torch.empty((0, channels), dtype=f32, device=dev), torch.empty((0,), dtype=torch.int32, device=dev),
+                    torch.empty((0,), dtype=torch.int32, device=dev), origin, voxel)
+
+
+def _voxel_map_arg(map, who):
+    """-> (rows, channels, device) of a well-formed VoxelMap; ValueError for anything else.  That the keys ascend is the map's contract and is
+    not read back."""
+    if not isinstance(map, VoxelMap):
+        raise ValueError("%s: map must be a VoxelMap (ops.voxel_map), got %s" % (who, type(map).__name__))
+    want = (("keys", torch.int64, 1), ("points", f32, 2), ("attr", f32, 2), ("count", torch.int32, 1), ("stamp", torch.int32, 1))
+    for name, dtype, dim in want:
+        t = getattr(map, name)
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != dim:
+            raise ValueError("%s: malformed VoxelMap: %s must be a %s tensor of %d dimension(s), got %s %s" % ((who, name, dtype, dim) + _got(t)))
+    n = map.keys.shape[0]
+    if tuple(map.points.shape) != (n, 3) or map.attr.shape[0] != n or map.count.shape[0] != n or map.stamp.shape[0] != n:
+        raise ValueError("%s: malformed VoxelMap: %d keys, points %s, attr %s, count %s, stamp %s" % (
+            who, n, tuple(map.points.shape), tuple(map.attr.shape), tuple(map.count.shape), tuple(map.stamp.shape)))
+    if n > CLOUD_MAX_ROWS:
+        raise ValueError("%s: malformed VoxelMap: %d rows; at most 2^31 - 1" % (who, n))
+    if any(getattr(map, name).device != map.keys.device for name, _, _ in want):
+        raise ValueError("%s: malformed VoxelMap: its tensors are on different devices" % who)
+    try:
+        _cloud_scalar(map.voxel, "voxel")
+        if tuple(float(np.float32(v)) for v in _cloud_triple(map.origin, "origin")) != tuple(map.origin):
+            raise ValueError("origin must hold float32 values, got %r" % (map.origin,))
+    except (TypeError, ValueError) as e:
+        raise ValueError("%s: malformed VoxelMap: %s" % (who, e))
+    return n, map.attr.shape[1], map.keys.device
+
+
+def voxel_map_insert(map, points=None, attr=None, pose=None, stamp=0, min_stamp=None):
+    """One scan into a voxel map (cmr_voxel_map_keys_f32 / cmr_segment_heads_i64 / cmr_segment_reduce_f32 / cmr_voxel_map_plan_i64 /
+    cmr_voxel_map_write_f32; the contract is the header's) -> MapInsert with a NEW map; `map` is not changed.  points float32 [N, 3] in
+    the scan's frame, attr float32 [N, C] with the map's C channels (None when C = 0), pose float32 [4, 4] or None: the scan's pose in the
+    map's frame, applied in fp32.  Rows with a non-finite coordinate are dropped and rows off the grid counted as outside; neither is an
+    error.  Touched and new voxels get `stamp`; with min_stamp, voxels whose stamp is then below it are forgotten.  points=None (or an empty
+    scan) with min_stamp is a pure prune.  The host reads back sizes only, three times: the dropped and outside counts, the scan's voxel
+    count, the new map's sizes (a scan without a kept row: two; without rows: one) -- not capturable in a graph."""
+    who = "voxel_map_insert"
+    M, C, dev = _voxel_map_arg(map, who)
+    stamp = _int_arg(who, "stamp", stamp, 0, VOXEL_MAP_MAX_STAMP)
+    if min_stamp is not None:
+        min_stamp = _int_arg(who, "min_stamp", min_stamp, 0, VOXEL_MAP_MAX_STAMP)
+    if points is None:
+        if attr is not None:
+            raise ValueError("%s: attr without points" % who)
+    else:
+        if attr is None and C:
+            raise ValueError("%s: the map has %d attribute channel(s), attr is None" % (who, C))
+        if attr is not None:
+            if not isinstance(attr, torch.Tensor) or attr.dtype != f32 or attr.dim() != 2:
+                raise ValueError("%s: attr must be a float32 [N, C] tensor or None, got %s %s" % ((who,) + _got(attr)))
+            if attr.shape[1] != C:
+                raise ValueError("%s: attr has %d channel(s), the map %d" % (who, attr.shape[1], C))
+            if isinstance(points, torch.Tensor) and points.dim() == 2 and attr.shape[0] != points.shape[0]:
+                raise ValueError("%s: attr has %d rows, points %d" % (who, attr.shape[0], points.shape[0]))
+    pose = _cloud_pose(pose, dev, who)
+    if points is not None:
+        points = _cloud_points(points)
+        if points.device != dev or (attr is not None and attr.device != dev):
+            raise ValueError("%s: points and attr must be on the map's device" % who)
+        if attr is not None:
+            attr = attr.contiguous().view(-1).view(attr.shape)      # row strides as the kernels take them, whatever an [N, 1] tensor came with
+    if not map.keys.is_cuda:
+        raise ValueError("%s: the map must hold device tensors (there is no CPU path)" % who)
+    N = 0 if points is None else points.shape[0]
+    if M + N > CLOUD_MAX_ROWS:
+        raise ValueError("%s: the map's %d rows and the scan's %d exceed 2^31 - 1 together" % (who, M, N))
+    lib = _lib.load()
+    o = map.origin
+    i32, i64 = torch.int32, torch.int64
+    dropped = outside = S = 0
+    keys = offsets = scan_points = scan_attr = scan_count = None
+    if N:
+        keys = torch.empty((N,), dtype=i64, device=dev)
+        moved = torch.empty((N, 3), dtype=f32, device=dev)
+        counts = torch.empty((2,), dtype=i64, device=dev)
+        nb = lib.cmr_voxel_map_keys_workspace_bytes(N)
+        ws = _ws(nb, dev)
+        _lib.call("cmr_voxel_map_keys_f32", _p(points), 3, N, _p(pose), o[0], o[1], o[2], map.voxel, _p(keys), _p(moved), _p(counts), _p(ws), nb,
+                  _stream())
+        keys, order = torch.sort(keys, stable=True)               # plumbing, as in voxel_downsample
+        dropped, outside = (int(v) for v in counts.cpu())       # host read 1
+        kept = N - dropped - outside
+        keys, order = keys[N - kept:], order[N - kept:]           # both marks sort in front of every cell
+        if kept:
+            order32 = torch.empty((kept,), dtype=i32, device=dev)
+            offsets = torch.empty((kept + 1,), dtype=i32, device=dev)
+            scan_count = torch.empty((kept,), dtype=i32, device=dev)
+            nseg = torch.empty((1,), dtype=i64, device=dev)
+            nb = lib.cmr_segment_heads_workspace_bytes(kept)
+            ws = torch.empty((nb,), dtype=torch.uint8, device=dev)
+            _lib.call("cmr_segment_heads_i64", _p(keys), _p(order), kept, kept, _p(order32), _p(offsets), _p(scan_count), None, _p(nseg), _p(ws),
+                      nb, _stream())
+            S = int(nseg.item())                                  # host read 2
+            offsets = offsets[:S + 1]
+            scan_points = segment_reduce(moved, order32, offsets, S, "mean")
+            scan_attr = segment_reduce(attr, order32, offsets, S, "mean") if C else None
+    if M + S == 0:
+        return MapInsert(VoxelMap(*(t.clone() for t in map[:5]), map.origin, map.voxel), 0, 0, 0, dropped, outside)
+    low = 0 if min_stamp is None else min_stamp
+    sizes = torch.empty((4,), dtype=i64, device=dev)
+    nb = lib.cmr_voxel_map_plan_workspace_bytes(M, S)
+    ws = _ws(nb, dev)
+    _lib.call("cmr_voxel_map_plan_i64", _p(map.keys), _p(map.stamp), M, _p(keys), _p(offsets), S, stamp, low, _p(sizes), _p(ws), nb, _stream())
+    rows, new, merged, removed = (int(v) for v in sizes.cpu())  # host read 3
+    out = VoxelMap(torch.empty((rows,), dtype=i64, device=dev), torch.empty((rows, 3), dtype=f32, device=dev),
+                   torch.empty((rows, C), dtype=f32, device=dev), torch.empty((rows,), dtype=i32, device=dev),
+                   torch.empty((rows,), dtype=i32, device=dev), map.origin, map.voxel)
+    _lib.call("cmr_voxel_map_write_f32", _p(map.keys), _p(map.points.contiguous()), _p(map.attr.contiguous()), _p(map.count), _p(map.stamp), M,
+              _p(scan_points), _p(scan_attr), _p(scan_count), S, C, stamp, low, _p(ws), nb, rows, _p(out.keys), _p(out.points), _p(out.attr),
+              _p(out.count), _p(out.stamp), _stream())
+    return MapInsert(out, new, merged, removed, dropped, outside)

@@ -297,6 +297,14 @@ WORK = {
     "cmr_point_fpfh_f32": lambda a: (0, a["kept"] * (32 + 12 + 2 * 136) + a["N"] * (132 + 4)),
     "cmr_descriptor_nearest_f32": lambda a: (3.0 * a["M"] * a["N"] * a["C"], F * (a["M"] + a["N"]) * a["C"] + 8 * a["M"]),
     "cmr_ransac_rigid_f32": lambda a: (30.0 * a["n_hyp"] * a["L"], a["L"] * 8 + (a["n_hyp"] + 255) // 256 * a["L"] * 32 + a["n_hyp"] * 100),
+    # DESIGN.md 4ah, latency-class and priced on compulsory bytes.  Keys: a row read (12 B), its key (8 B) and the moved row (12 B) written.
+    # Plan: per map row its key and stamp (12 B), per scan voxel its key twice (16 B), and for both the rank and the prefix sum written and
+    # read back (12 B); the binary searches' reads are not counted (they hit the cache).  Write: the plan read again (8 B per item), every
+    # map row and scan voxel read and every row of the new map written (key, three means, C attributes, count and stamp: 28 + 4 C bytes).
+    "cmr_voxel_map_keys_f32": lambda a: (0, a["N"] * 32),
+    "cmr_voxel_map_plan_i64": lambda a: (0, a["M"] * 24 + a["S"] * 28),
+    "cmr_voxel_map_write_f32": lambda a: (3.0 * (3 + a["C"]) * min(a["M"], a["S"]),
+                                          (a["M"] + a["S"]) * (8 + 28 + 4 * a["C"]) + a["rows"] * (28 + 4 * a["C"])),
 }
 
 # Multiplies the kernel ISSUES on the matrix cores per algorithmic multiply: F(2x2,3x3) Winograd computes 2x2 outputs with 16

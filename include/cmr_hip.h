@@ -1471,6 +1471,58 @@ int cmr_ransac_rigid_f32(const float* source, int64_t M, const float* target, in
                          float thr, float edge_ratio, uint32_t seed, float* pose, int32_t* result, int32_t* hyp_inliers, void* workspace,
                          int64_t workspace_bytes, hipStream_t stream);
 
+/* ---- a voxel map of registered scans: insert, merge, forget (csrc/voxel_map.hip) -------------------------------------
+ * Port extension.  A MAP is one row per occupied voxel of a fixed grid (origin (ox, oy, oz), voxel; the keys of the section "raw scan ->
+ * prepared cloud" above): keys int64 [M] ascending and unique, points fp32 [M][3] and attr fp32 [M][C] = the running means of the rows
+ * that fell into the voxel, count int32 [M] = their number, stamp int32 [M] = the stamp of the last insert that touched the voxel.  The
+ * library keeps no state: an insert reads a map and a scan and writes a NEW map.  One insert is, in order: cmr_voxel_map_keys_f32, the
+ * caller's stable sort of the keys, cmr_segment_heads_i64 and cmr_segment_reduce_f32 (mode 2) over the moved rows and over attr -- the
+ * scan's own voxels in ascending key order, exactly as the voxel downsample makes them -- then cmr_voxel_map_plan_i64, a read of its
+ * sizes, and cmr_voxel_map_write_f32.  No re-sort of the map and no atomics; every output has one writer; two calls agree bit for bit.
+ *
+ * cmr_voxel_map_keys_f32.  Row i of points [N][ld >= 3], 0 < N < 2^31, in one pass:
+ *   q        with pose (fp32 [4][4], row-major, upper 3 x 4 read) q = R p + t as cmr_cloud_nearest_f32 states it, every operation rounded
+ *            on its own;  with pose = null q = p;  moved[i] = q  (fp32 [N][3], written for every row);
+ *   dropped  p or q has a non-finite coordinate:  keys[i] = -1;
+ *   outside  else, on some axis  floorf((q - origin) / voxel)  -- one IEEE subtraction, one IEEE division, the arithmetic of the keys above --
+ *            is below 0 or above 2^21 - 1, the comparison made on the float (so +-inf is outside):  keys[i] = -2;
+ *   key      else cz << 42 | cy << 21 | cx of the three cells.
+ * Both marks sort in FRONT of every cell (a key takes all 63 bits: 2^63 - 1 is the key of the last cell, so nothing sorts behind them):
+ * after the sort the kept rows are the last N - dropped - outside entries, and those are what cmr_segment_heads_i64 is handed.
+ * counts int64 [2] = {dropped, outside}, summed without atomics.  Workspace of cmr_voxel_map_keys_workspace_bytes(N). */
+int64_t cmr_voxel_map_keys_workspace_bytes(int64_t N);
+int cmr_voxel_map_keys_f32(const float* points, int64_t ld, int64_t N, const float* pose, float ox, float oy, float oz, float voxel,
+                           int64_t* keys, float* moved, int64_t* counts, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+/* cmr_voxel_map_plan_i64: where the rows of a map (M >= 0 rows) and of a scan (S >= 0 voxels: run s of cmr_segment_heads_i64 over
+ * keys_sorted, its key keys_sorted[offsets[s]]) go in the new map;  0 < M + S < 2^31.  0 <= stamp, min_stamp < 2^31.
+ *   hit      a scan voxel whose key the map holds, and that map row;  every scan voxel is located in the map's keys and every map row in
+ *            the scan's by binary search;  a scan voxel that is no hit is a MISS;
+ *   stamps   after the insert a hit map row and a miss carry `stamp`, every other map row its own;
+ *   kept     a map row or a miss whose stamp after the insert is not below min_stamp (min_stamp = 0 keeps everything);  the new map is
+ *            the kept rows of both sides in ascending key order, a row's place the number of kept rows with a smaller key, from exclusive
+ *            prefix sums of the keep flags of either side (tiles of 1024, int32, 64-bit row arithmetic);
+ *   sizes    int64 [4] = {rows of the new map, new = misses, merged = hits, removed = M + new - rows}.
+ * The caller reads sizes back to allocate the new map, so an insert cannot be part of a captured graph.  Workspace of
+ * cmr_voxel_map_plan_workspace_bytes(M, S), 16-byte aligned; it holds the plan and is handed on, unchanged, to cmr_voxel_map_write_f32.
+ * S = 0 with min_stamp > 0 is a pure prune.  The map's keys are taken as ascending and unique; whatever they are, no write of either
+ * call leaves the new map's rows. */
+int64_t cmr_voxel_map_plan_workspace_bytes(int64_t M, int64_t S);
+int cmr_voxel_map_plan_i64(const int64_t* map_keys, const int32_t* map_stamp, int64_t M, const int64_t* keys_sorted, const int32_t* offsets,
+                           int64_t S, int stamp, int min_stamp, int64_t* sizes, void* workspace, int64_t workspace_bytes,
+                           hipStream_t stream);
+/* cmr_voxel_map_write_f32: the new map's `rows` rows (sizes[0] of the plan in `workspace`; the other arguments as the plan took them),
+ * each written once by the thread that owns it, with plain stores.  scan_points [S][3], scan_attr [S][C], scan_count int32 [S]: the scan's
+ * voxels (means and run lengths).  C >= 0 attribute channels (attr pointers may be null when C = 0).
+ *   a kept map row that is no hit     copied, with its count and stamp;
+ *   a kept miss                       the scan voxel's means and count, and `stamp`;
+ *   a kept hit (ca, ma | cb, mb)      n = min(ca + cb, 2^31 - 1) taken in int64,  w = (float) cb / (float) n  (one IEEE division),  and per
+ *                                     component of points and attr  m' = ma + w (mb - ma):  a subtraction, a product and a sum, each
+ *                                     rounded on its own (no fused operation);  count n, and `stamp`. */
+int cmr_voxel_map_write_f32(const int64_t* map_keys, const float* map_points, const float* map_attr, const int32_t* map_count,
+                            const int32_t* map_stamp, int64_t M, const float* scan_points, const float* scan_attr, const int32_t* scan_count,
+                            int64_t S, int C, int stamp, int min_stamp, const void* workspace, int64_t workspace_bytes, int64_t rows,
+                            int64_t* keys, float* points, float* attr, int32_t* count, int32_t* stamps, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,347 @@
+"""GPU tier of the voxel map (ops.voxel_map / ops.voxel_map_insert, csrc/voxel_map.hip, dataset/accumulate.py, align --map),
+against the restatement of voxel_map_reference.py.
+
+Every integer is EXACT: keys, count, stamp, new, merged, removed, dropped, outside (the header states every fp32 operation behind a key).
+A scan voxel of one row (or of copies of one row on a coarse lattice) has the row itself as its mean, so there the combine is checked BIT FOR
+BIT against the float32 restatement -- with weights 1/2 in the size cases, and with general weights and distances, where a fused form, a
+swapped weight or a reciprocal give other bits, in test_the_combine_with_general_weights_and_distances.
+Means in general: every component within (rows + 8 inserts) 2^-23 absmax of the float64 mean of all rows ever inserted into the voxel --
+the project's sequential-sum bound rows 2^-23 absmax for each scan mean, and per combine six roundings of at most 2^-24 of at most
+2 absmax, rounded up to 8.  No voxel is left out of any comparison."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import cloud_icp_reference as R
+import cloud_prepare_reference as P
+import voxel_map_reference as V
+from cmr_agent_amd import ops
+from cmr_agent_amd.dataset import accumulate, align
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+F = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)      # noqa: E731
+SIZES = (0, 1, 2, 255, 256, 257, 1023, 1024, 1025, 2049)             # round the scan tile (1024) and the workgroup (256)
+ORIGIN = (-8.0, -8.0, -8.0)
+WORST = [0.0]                                                        # the largest share of the bound on the means met so far
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
+
+
+def _np(m):
+    return dict(keys=m.keys.cpu().numpy(), points=m.points.cpu().numpy(), attr=m.attr.cpu().numpy(), count=m.count.cpu().numpy(),
+                stamp=m.stamp.cpu().numpy())
+
+
+def _same(a, b):
+    a, b = _np(a), _np(b)
+    return all(np.array_equal(a[k], b[k]) for k in ("keys", "count", "stamp")) and all(
+        np.array_equal(_bits(a[k]), _bits(b[k])) for k in ("points", "attr"))
+
+
+def _insert(gmap, rmap, points=None, attr=None, pose=None, exact=False, **kw):
+    """One insert on both sides, compared.  -> (the op's new map, the restatement's)"""
+    before = [t.clone() for t in gmap[:5]]
+    ins = ops.voxel_map_insert(gmap, F(points), F(attr), F(pose), **kw)
+    again = ops.voxel_map_insert(gmap, F(points), F(attr), F(pose), **kw)
+    ref, info = V.insert(rmap, points, attr, pose, **kw)
+    got = _np(ins.map)
+    assert all(torch.equal(a, b) for a, b in zip(before, gmap[:5])), "the input map was changed"
+    assert (ins.new, ins.merged, ins.removed, ins.dropped, ins.outside) == tuple(info[k] for k in ("new", "merged", "removed", "dropped", "outside"))
+    assert ins.map.keys.dtype == torch.int64 and ins.map.count.dtype == ins.map.stamp.dtype == torch.int32
+    assert ins.map.origin == gmap.origin and ins.map.voxel == gmap.voxel and got["attr"].shape == (ref["keys"].size, rmap["attr"].shape[1])
+    for k in ("keys", "count", "stamp"):
+        assert np.array_equal(got[k], ref[k]), (k, np.nonzero(got[k] != ref[k])[0][:8] if got[k].shape == ref[k].shape else got[k].shape)
+    val = np.concatenate([got["points"], got["attr"]], 1).astype(np.float64)
+    err, bound = np.abs(val - V.mean64(ref)), V.bound(ref)
+    assert (err <= bound).all(), (err.max(), np.nonzero(err > bound)[0][:8])
+    WORST[0] = max(WORST[0], float((err / np.maximum(bound, 1e-300)).max()) if err.size else 0.0)
+    if exact:
+        assert np.array_equal(_bits(got["points"]), _bits(ref["points"])) and np.array_equal(_bits(got["attr"]), _bits(ref["attr"]))
+    assert _same(again.map, ins.map) and again[1:] == ins[1:]
+    return ins.map, ref
+
+
+def _cells(n, z0, rng):
+    """n distinct cells of a 32 x 32 x 8 block whose lowest layer is z0, in random order"""
+    flat = rng.permutation(32 * 32 * 8)[:n]
+    return np.stack([flat % 32, flat // 32 % 32, flat // 1024 + z0], 1)
+
+
+def _rows(cells, rng, channels):
+    """one row in every cell of the grid (ORIGIN, voxel 0.5), away from the faces, and its attributes"""
+    xyz = (np.asarray(ORIGIN) + (cells + rng.uniform(0.1, 0.9, cells.shape)) * 0.5).astype(np.float32)
+    return xyz, rng.uniform(-2, 2, (cells.shape[0], channels)).astype(np.float32)
+
+
+@pytest.mark.parametrize("overlap", ["hits", "misses", "interleaved", "below", "above"])
+def test_sizes_and_overlap(overlap):
+    """Map voxel count M x scan voxel count S over SIZES, one row per voxel on both sides: integers exact, means bit for bit."""
+    rng = np.random.default_rng(len(overlap))
+    C = 2
+    for M in SIZES:
+        pool = _cells(4100, 8, rng)
+        for S in SIZES:
+            if overlap == "hits":                                            # the smaller side lies inside the larger one
+                mc, sc = pool[:M], pool[:S]
+            elif overlap == "misses":
+                mc, sc = pool[:M], pool[2049:2049 + S][::-1]
+            elif overlap == "interleaved":                                   # every third scan voxel is one of the map's
+                mc = pool[:M]
+                sc = np.concatenate([pool[:M][::3][:S // 3], pool[2049:2049 + S - min(S // 3, (M + 2) // 3)]])
+            else:                                                            # all of the scan's keys below, or above, all of the map's
+                mc, sc = pool[:M], _cells(S, 0 if overlap == "below" else 16, rng)
+            gmap, rmap = ops.voxel_map(0.5, ORIGIN, C, DEV), V.empty(0.5, ORIGIN, C)
+            gmap, rmap = _insert(gmap, rmap, *_rows(mc, rng, C), exact=True, stamp=1)
+            assert gmap.keys.shape[0] == M
+            out, ref = _insert(gmap, rmap, *_rows(sc, rng, C), exact=True, stamp=2)
+            hits = np.isin(ref["keys"], rmap["keys"]) & (ref["stamp"] == 2)
+            if overlap == "hits":
+                assert hits.sum() == min(M, S) and out.keys.shape[0] == max(M, S)
+            elif overlap == "interleaved":
+                assert hits.sum() == min(S // 3, (M + 2) // 3) and out.keys.shape[0] == M + sc.shape[0] - hits.sum()
+            else:
+                assert hits.sum() == 0 and out.keys.shape[0] == M + S
+            if overlap in ("below", "above") and M and S:
+                lo, hi = (ref["stamp"] == 2, ref["stamp"] == 1) if overlap == "below" else (ref["stamp"] == 1, ref["stamp"] == 2)
+                assert ref["keys"][lo].max() < ref["keys"][hi].min()
+
+
+def _scans(n=4, channels=1):
+    """n scans of the scene (many rows per voxel in its clump), each under a pose of its own; columns 3.. are the attributes"""
+    out = []
+    for j in range(n):
+        raw = P.scene(30 + j, n=1600, clump=200, far=10, scale=0.5)
+        attr = np.concatenate([raw[:, 3:4], 50 * raw[:, 0:1] - 7, raw[:, 2:3] ** 2], 1)[:, :channels]
+        pose = R.pose_matrix(*R.TRUE_POSES[j % 3]).astype(np.float32) if j else None
+        out.append((raw[:, :3], np.ascontiguousarray(attr, dtype=np.float32), pose))
+    return out
+
+
+@pytest.mark.parametrize("channels", [0, 1, 3])
+def test_many_rows_per_voxel(channels):
+    gmap, rmap = ops.voxel_map(0.5, (-64, -64, -64), channels, DEV), V.empty(0.5, (-64, -64, -64), channels)
+    for j, (xyz, attr, pose) in enumerate(_scans(4, channels)):
+        gmap, rmap = _insert(gmap, rmap, xyz, attr if channels else None, pose, stamp=j)
+    assert rmap["count"].max() > 250 and (rmap["inserts"] == 4).sum() > 80 and (rmap["inserts"] == 1).sum() > 300
+    assert rmap["keys"].size > 700 and rmap["rows"].sum() == sum(s[0].shape[0] for s in _scans(4))
+    print("%d channels: the largest share of the bound on a mean so far %.3f" % (channels, WORST[0]))
+
+
+def test_edges_of_the_grid_outside_and_non_finite_rows():
+    top = 2.0 ** 21
+    inside = [[0.5, 0.5, 0.5], [top - 0.5, 0.5, 0.5], [0.5, top - 0.5, 0.5], [0.5, 0.5, top - 0.5], [top - 0.5] * 3, [0.0, 0.0, 0.0],
+              [top - 0.125, 3.0, 3.0]]
+    outside = [[-0.5, 1, 1], [1, -0.5, 1], [1, 1, -0.5], [top + 0.5, 1, 1], [1, top + 0.5, 1], [1, 1, top + 0.5], [top, 1, 1],
+               [-1e-3, 1, 1], [3e38, 1, 1], [1, -3e38, 1], [1, 1, 3e38], [-3e38, -3e38, -3e38]]
+    nonfinite = [[np.nan, 1, 1], [1, np.inf, 1], [1, 1, -np.inf], [np.nan] * 3]
+    rows = np.float32(inside + outside + nonfinite)
+    gmap, rmap = ops.voxel_map(1.0, (0, 0, 0), 1, DEV), V.empty(1.0, (0, 0, 0), 1)
+    attr = np.arange(rows.shape[0], dtype=np.float32)[:, None]
+    out, ref = _insert(gmap, rmap, rows, attr, exact=True, stamp=4)
+    ins = ops.voxel_map_insert(gmap, F(rows), F(attr), stamp=4)
+    assert (ins.new, ins.dropped, ins.outside) == (6, 4, 12)
+    cm = (1 << 21) - 1
+    assert out.keys.cpu().tolist() == sorted([0, cm, cm << 21, cm << 42, cm << 42 | cm << 21 | cm, 3 << 42 | 3 << 21 | cm])
+    assert out.count.cpu().tolist() == [2, 1, 1, 1, 1, 1]
+    # rows a pose makes non-finite, or moves on and off the grid
+    pose = np.eye(4, dtype=np.float32)
+    pose[0, 3] = 3e38
+    src = np.float32([[3e38, 1, 1], [1, 1, 1], [-3e38, 0.5, 0.5], [-3e38 + 1e32, 2, 2]])
+    _, ref2 = _insert(out, ref, src, np.zeros((4, 1), np.float32), pose, exact=True, stamp=5)
+    ins = ops.voxel_map_insert(out, F(src), F(np.zeros((4, 1))), F(pose), stamp=5)
+    assert (ins.dropped, ins.outside, ins.new, ins.merged) == (1, 2, 0, 1)                 # -3e38 + 3e38 = 0: cell 0
+    big = np.float32([[1e38, 1e38, 1e38]])
+    spin = np.float32([[2, 2, 2, 0], [0, 1, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]])            # (2 + 2) 1e38 overflows on the way
+    ins = ops.voxel_map_insert(out, F(big), F(np.zeros((1, 1))), F(spin), stamp=5)
+    assert (ins.dropped, ins.outside) == (1, 0) and _same(ins.map, out)
+    # counts at the top of int32: the sum is taken in int64 and capped, and the weight follows the CAPPED count.  The voxel's means are 0,
+    # so m' = w mb and its bits show w; 1 000 rows of 0.375, 0.625, 0.875 and of attribute 1.75 sum exactly, so mb is those numbers
+    full = ops.VoxelMap(out.keys[:1], torch.zeros((1, 3), device=DEV), torch.zeros((1, 1), device=DEV),
+                        torch.full((1,), 2 ** 31 - 1, dtype=torch.int32, device=DEV), out.stamp[:1], out.origin, out.voxel)
+    mb = np.float32([0.375, 0.625, 0.875, 1.75])
+    ins = ops.voxel_map_insert(full, F(np.tile(mb[:3], (1000, 1))), F(np.full((1000, 1), mb[3])), stamp=9)
+    assert ins.map.count.cpu().tolist() == [2 ** 31 - 1] and ins.merged == 1 and ins.new == 0
+    w = np.float32(1000) / np.float32(2 ** 31 - 1)
+    loose = np.float32(1000) / np.float32(2 ** 31 + 999)                                   # the weight of the uncapped count
+    got = np.concatenate([ins.map.points.cpu().numpy(), ins.map.attr.cpu().numpy()], 1)[0]
+    assert np.array_equal(_bits(got), _bits(w * mb)) and (_bits(loose * mb) != _bits(w * mb)).all()
+    ref, n = V.combine(np.zeros((1, 4), np.float32), mb[None], np.int64([2 ** 31 - 1]), np.int64([1000]))
+    assert n.tolist() == [2 ** 31 - 1] and np.array_equal(_bits(ref[0]), _bits(got))
+
+
+def _fused(ma, mb, w):
+    """what a fused multiply-add would give: the product exact (24 x 24 bits fit a float64), one rounding of the sum"""
+    return (ma.astype(np.float64) + w.astype(np.float64)[:, None] * (mb.astype(np.float64) - ma.astype(np.float64))).astype(np.float32)
+
+
+def test_the_combine_with_general_weights_and_distances():
+    """Scans into voxels whose counts are not 1 and whose means lie at general distances: w = 1/3, 2/5, 3/7, ... and w (mb - ma)
+    rounds.  A scan voxel holds 1 .. 8 copies of one row whose coordinates are multiples of 2^-10, so its sum and its mean are exact and
+    the scan mean is the row itself whatever the count.  Bit for bit with the float32 restatement -- where a fused multiply-add, a weight from the map's count instead of the
+    scan's, or a reciprocal in place of the division each give other bits in a share of the components that the test asserts."""
+    rng = np.random.default_rng(7)
+    C, K = 3, 1500
+    cells = _cells(K, 8, rng)
+    # a map handed over with counts set by hand: 1 .. 40
+    xyz, attr = _rows(cells, rng, C)
+    _, keys = V.scan_rows(xyz, None, ORIGIN, 0.5)
+    order = np.argsort(keys)
+    count = rng.integers(1, 41, K)
+    rmap = V.empty(0.5, ORIGIN, C)
+    val = np.concatenate([xyz, attr], 1)[order]
+    rmap.update(keys=keys[order], points=xyz[order], attr=attr[order], count=count.astype(np.int64), stamp=np.full(K, 3, np.int64),
+                sum=val.astype(np.float64) * count[:, None], absmax=np.abs(val).astype(np.float64), rows=count.astype(np.int64),
+                inserts=np.ones(K, np.int64))
+    gmap = ops.VoxelMap(torch.from_numpy(keys[order]).to(DEV), F(xyz[order]), F(attr[order]), torch.from_numpy(count.astype(np.int32)).to(DEV),
+                        torch.full((K,), 3, dtype=torch.int32, device=DEV), tuple(float(v) for v in ORIGIN), 0.5)
+    hit = rng.permutation(K)[:1200]
+    sx, sa = (np.round(v * 1024) / 1024 for v in _rows(np.concatenate([cells[hit], _cells(300, 16, rng)]), rng, C))
+    copies = rng.integers(1, 9, 1500)
+    out, ref = _insert(gmap, rmap, np.repeat(sx, copies, 0), np.repeat(sa, copies, 0), exact=True, stamp=4)
+    assert ref["keys"].size == K + 300 and (ref["stamp"] == 4).sum() == 1500
+    # the case tells the stated arithmetic from its neighbours
+    rows = np.searchsorted(rmap["keys"], V.scan_rows(sx[:1200], None, ORIGIN, 0.5)[1])
+    ma, mb = val[rows], np.concatenate([sx, sa], 1)[:1200]
+    ca, cb = count[rows].astype(np.int64), copies[:1200].astype(np.int64)
+    stated, n = V.combine(ma, mb, ca, cb)
+    w = cb.astype(np.float32) / n.astype(np.float32)
+    got = np.concatenate([out.points.cpu().numpy(), out.attr.cpu().numpy()], 1)[np.searchsorted(ref["keys"], rmap["keys"][rows])]
+    assert np.array_equal(_bits(got), _bits(stated))
+    fused = _fused(ma, mb, w)
+    swapped = V.combine(ma, mb, cb, ca)[0]                                                # w = ca / n
+    recip = (ma + (cb.astype(np.float32) * (np.float32(1) / n.astype(np.float32)))[:, None] * (mb - ma)).astype(np.float32)
+    shares = [float((_bits(x) != _bits(stated)).mean()) for x in (fused, swapped, recip)]
+    print("components that differ from the stated combine: fused %.3f, weight from the map's count %.3f, reciprocal %.3f" % tuple(shares))
+    assert shares[0] > 0.05 and shares[1] > 0.9 and shares[2] > 0.01
+    # and counts that grow insert by insert: four one-row scans into the same voxels, w = 1/2, 1/3, 1/4
+    gmap, rmap = ops.voxel_map(0.5, ORIGIN, C, DEV), V.empty(0.5, ORIGIN, C)
+    for j in range(4):
+        gmap, rmap = _insert(gmap, rmap, *_rows(cells[:700 + 100 * j], rng, C), exact=True, stamp=j)
+    assert sorted(set(rmap["count"].tolist())) == [1, 2, 3, 4]
+
+
+def test_pose_none_is_the_identity():
+    xyz, attr, _ = _scans(1)[0]
+    gmap = ops.voxel_map(0.1, (-64, -64, -64), 1, DEV)
+    a = ops.voxel_map_insert(gmap, F(xyz), F(attr), None, stamp=1)
+    b = ops.voxel_map_insert(gmap, F(xyz), F(attr), torch.eye(4, device=DEV), stamp=1)
+    assert _same(a.map, b.map) and a[1:] == b[1:] and a.new > 1000
+
+
+def test_order_of_two_scans():
+    (xa, aa, _), (xb, ab, pb) = _scans(2)
+    maps = []
+    for order in ((0, 1), (1, 0)):
+        gmap, rmap = ops.voxel_map(0.5, (-64, -64, -64), 1, DEV), V.empty(0.5, (-64, -64, -64), 1)
+        for j in order:
+            gmap, rmap = _insert(gmap, rmap, *((xa, aa, None), (xb, ab, pb))[j], stamp=7)
+        maps.append((_np(gmap), rmap))
+    (a, ra), (b, rb) = maps
+    assert np.array_equal(a["keys"], b["keys"]) and np.array_equal(a["count"], b["count"]) and (ra["inserts"] == 2).sum() > 150
+    diff = np.abs(np.concatenate([a["points"], a["attr"]], 1).astype(np.float64) - np.concatenate([b["points"], b["attr"]], 1))
+    assert (diff <= 2 * V.bound(ra)).all() and np.array_equal(V.bound(ra), V.bound(rb))
+
+
+def test_four_scans_one_by_one_against_the_downsample_of_their_rows():
+    scans = _scans(4)
+    origin = (-64.0, -64.0, -64.0)
+    gmap = ops.voxel_map(0.1, origin, 1, DEV)
+    moved = []
+    for j, (xyz, attr, pose) in enumerate(scans):
+        gmap = ops.voxel_map_insert(gmap, F(xyz), F(attr), F(pose), stamp=j).map
+        moved.append(xyz if pose is None else R.pose_apply32(pose, xyz))
+    rows, attrs = np.concatenate(moved), np.concatenate([s[1] for s in scans])
+    down = ops.voxel_downsample(F(rows), F(attrs), 0.1, origin)
+    ref = P.voxel_downsample(rows, attrs, 0.1, origin)
+    assert np.array_equal(gmap.keys.cpu().numpy(), ref["keys"]) and torch.equal(gmap.count, down.count)
+    assert np.array_equal(gmap.count.cpu().numpy(), ref["count"])
+
+
+def test_prune():
+    scans = _scans(3) + _scans(3)[::-1]
+    origin = (-64.0, -64.0, -64.0)
+    shift = lambda xyz, j: xyz + np.float32([3.0 * j, 0, 0])                # noqa: E731  scans 3 .. 5 reach ground the earlier ones do not
+    gmap, rmap = ops.voxel_map(0.1, origin, 1, DEV), V.empty(0.1, origin, 1)
+    late, rlate = gmap, rmap
+    for j, (xyz, attr, pose) in enumerate(scans):
+        if j == 5:
+            unpruned, runpruned = _insert(gmap, rmap, shift(xyz, j), attr, pose, stamp=j)
+        gmap, rmap = _insert(gmap, rmap, shift(xyz, j), attr, pose, stamp=j, min_stamp=3 if j == 5 else None)
+        if j >= 3:
+            late, rlate = _insert(late, rlate, shift(xyz, j), attr, pose, stamp=j)
+    removed = runpruned["keys"].size - rmap["keys"].size
+    assert removed > 300 and np.array_equal(rmap["keys"], rlate["keys"]) and rmap["stamp"].min() == 3
+    a, b = _np(gmap), _np(late)
+    assert np.array_equal(a["keys"], b["keys"]) and np.array_equal(a["stamp"], b["stamp"])
+    own = rmap["rows"] == rlate["rows"]                                      # voxels that scans 3 .. 5 alone touched
+    assert 500 < own.sum() < own.size and np.array_equal(a["count"][own], b["count"][own])
+    assert np.array_equal(_bits(a["points"][own]), _bits(b["points"][own])) and np.array_equal(_bits(a["attr"][own]), _bits(b["attr"][own]))
+    # a pure prune of the unpruned map gives the same map, with points=None and with an empty scan
+    pure, _ = _insert(unpruned, runpruned, min_stamp=3)
+    assert _same(pure, gmap)
+    ins = ops.voxel_map_insert(unpruned, torch.zeros((0, 3), device=DEV), torch.zeros((0, 1), device=DEV), min_stamp=3)
+    assert _same(ins.map, gmap) and (ins.new, ins.merged, ins.removed, ins.dropped, ins.outside) == (0, 0, removed, 0, 0)
+    # forgetting everything, a scan below min_stamp included; nothing to forget; an empty map
+    ins = ops.voxel_map_insert(gmap, F(scans[0][0]), F(scans[0][1]), stamp=2, min_stamp=6)
+    assert ins.map.keys.shape == (0,) and ins.map.attr.shape == (0, 1) and ins.removed == gmap.keys.shape[0] + ins.new
+    ins = ops.voxel_map_insert(gmap, min_stamp=3)
+    assert _same(ins.map, gmap) and ins.removed == 0 and ins.map.keys.data_ptr() != gmap.keys.data_ptr()
+    ins = ops.voxel_map_insert(ops.voxel_map(0.1, origin, 1, DEV), min_stamp=3)
+    assert ins.map.keys.shape == (0,) and ins[1:] == (0, 0, 0, 0, 0)
+
+
+def test_align_to_a_map_and_accumulate(tmp_path, capsys):
+    """align --map 2 on four synthetic frames, Huber 0.1, max_dist 1.0, 40 iterations, against the float64 restatement of the chain (status
+    0 on all three pairs, 12 .. 26 iterations, 4.0 .. 4.4 mrad and 3.3 .. 5.1 mm from the truth): status 0, the iteration counts within 2 of
+    the restatement's, each pose within 10 % of the restatement's own error of the restatement's pose.  Then accumulate on the written
+    poses: keys and counts equal the restatement's map, means within the bound."""
+    case = V.chain_case()
+    V.write_frames(str(tmp_path), case["frames"])
+    out, cloud = str(tmp_path / "poses.txt"), str(tmp_path / "map.npy")
+    base = ["--root", str(tmp_path), "--data-velodyne", "vel", "--sequence", "9"]
+    align.main(base + ["--map", "2", "--huber", "0.1", "--max-dist", "1.0", "--iters", "40", "--out", out])
+    lines = capsys.readouterr().out.splitlines()
+    assert [ln.split(":")[0] for ln in lines] == ["pair 3 4", "pair 4 5", "pair 5 6"]
+    chain = np.loadtxt(out).reshape(4, 3, 4)
+    assert np.array_equal(chain[0], np.eye(4)[:3])
+    figures = []
+    for j, (ln, res) in enumerate(zip(lines, case["results"])):
+        words = ln.split()
+        T = np.concatenate([chain[j + 1], [[0, 0, 0, 1]]])
+        own = R.pose_error(case["poses"][j + 1], case["truth"][j + 1])
+        err = R.pose_error(T, case["poses"][j + 1])
+        figures.append("pair %d: iterations %s (restatement %d), %.3e rad %.3e m from the restatement, whose own error is %.3e rad %.3e m" % (
+            j, words[8], res["iterations"], err[0], err[1], own[0], own[1]))
+        with capsys.disabled():
+            print(figures[-1])
+        assert res["status"] == 0 and words[9:11] == ["status", "0"] and abs(int(words[8]) - res["iterations"]) <= 2
+        assert err[0] <= 0.1 * own[0] and err[1] <= 0.1 * own[1]
+        rel = np.linalg.inv(np.concatenate([chain[j], [[0, 0, 0, 1]]])) @ T
+        assert np.allclose([float(w) for w in words[12:15]], rel[:3, 3], atol=6e-5)
+    accumulate.main(base + ["--poses", out, "--out", cloud])
+    lines = capsys.readouterr().out.splitlines()
+    ref = V.accumulate(case["frames"], accumulate.read_poses(out), V.CHAIN_FIRST)
+    got = np.load(cloud)
+    n = ref["keys"].size
+    assert got.dtype == np.float32 and got.shape == (7, n) and lines[-1] == "map: %d voxels from %d rows of 4 frames" % (
+        n, sum(f.shape[1] for f in case["frames"]))
+    m = V.empty(V.MAP_VOXEL, (-V.MAP_EXTENT / 2,) * 3, 1)
+    for j, (f, T) in enumerate(zip(case["frames"], accumulate.read_poses(out))):
+        m, info = V.insert(m, f[:3].T, f[3:4].T, T.astype(np.float32), stamp=V.CHAIN_FIRST + j)
+        assert lines[j] == "frame %d: rows %d new %d merged %d outside 0" % (V.CHAIN_FIRST + j, f.shape[1], info["new"], info["merged"])
+    assert info["merged"] > 300
+    err = np.abs(got[:4].T.astype(np.float64) - V.mean64(ref))
+    assert (err <= V.bound(ref)).all(), err.max()
+    # the file's rows are the map's, in key order: the map itself has the restatement's keys and counts
+    folder = os.path.join(str(tmp_path), "vel", "sequences", "09", align.prepare.subdir())
+    files = [(V.CHAIN_FIRST + j, os.path.join(folder, "%06d.npy" % (V.CHAIN_FIRST + j))) for j in range(4)]
+    vmap, total = accumulate.accumulate_sequence(files, accumulate.read_poses(out), report=lambda ln: None)
+    assert np.array_equal(vmap.keys.cpu().numpy(), ref["keys"]) and np.array_equal(vmap.count.cpu().numpy(), ref["count"])
+    assert np.array_equal(_bits(vmap.points.cpu().numpy()), _bits(got[:3].T)) and np.array_equal(_bits(vmap.attr.cpu().numpy()), _bits(got[3:4].T))
+    normal = np.linalg.norm(got[4:7].astype(np.float64), axis=0)
+    assert (np.abs(normal[normal > 0] - 1) < 1e-5).all() and (normal > 0).sum() > 0.9 * n
