@@ -23,33 +23,18 @@ import numpy as np
 import torch
 
 from .. import ops
-from . import align
-
-
-def read_poses(path):
-    """The file `align --out` writes -> float64 [F, 4, 4]; ValueError for anything else."""
-    try:
-        rows = np.loadtxt(path, dtype=np.float64, ndmin=2)
-    except (OSError, ValueError) as e:
-        raise ValueError("%s: %s" % (path, e))
-    if rows.shape[1:] != (12,) or not np.isfinite(rows).all():
-        raise ValueError("%s: need 12 finite numbers per line (the upper 3 x 4 of a pose, row-major)" % path)
-    poses = np.tile(np.eye(4), (rows.shape[0], 1, 1))
-    poses[:, :3, :] = rows.reshape(-1, 3, 4)
-    return poses
+from . import align, prepare
+from .align import device_pose, device_rows, read_poses            # read_poses stays a name of this module: its callers read it here
 
 
 def accumulate_sequence(files, poses, voxel=0.1, extent=8192.0, device=None, report=print):
     """files: the prepared clouds as (frame number, path); poses float64 [len(files), 4, 4].  -> (ops.VoxelMap with one attribute, the
     rows read).  `report` receives one line per frame."""
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    rows = lambda a: torch.from_numpy(np.ascontiguousarray(a.T)).to(device)            # noqa: E731
     vmap = ops.voxel_map(voxel, (-extent / 2,) * 3, channels=1, device=device)
     total = 0
     for (i, path), T in zip(files, poses):
         cloud = align.read_prepared(path)
-        ins = ops.voxel_map_insert(vmap, rows(cloud[0:3]), rows(cloud[3:4]), pose=torch.from_numpy(T.astype(np.float32)).to(device), stamp=i)
+        ins = ops.voxel_map_insert(vmap, device_rows(cloud[0:3], device), device_rows(cloud[3:4], device), pose=device_pose(T, device), stamp=i)
         report("frame %d: rows %d new %d merged %d outside %d" % (i, cloud.shape[1], ins.new, ins.merged, ins.outside))
         total += cloud.shape[1]
         vmap = ins.map
@@ -75,9 +60,7 @@ def parse_args(argv=None):
     ap.add_argument("--out", default=None, help="write the map here, float32 [7, n]")
     args = ap.parse_args(argv)
     align.check_sequence_flags(ap, args)
-    for name in ("voxel", "extent", "normal_radius"):
-        if not (0.0 < getattr(args, name) < float("inf")):
-            ap.error("--%s must be finite and > 0, got %r" % (name.replace("_", "-"), getattr(args, name)))
+    prepare.check_positive(ap, args, "voxel", "extent", "normal_radius")
     if not 1 <= args.min_count < 1 << 31:
         ap.error("--min-count must lie in [1, 2^31)")
     return ap, args

@@ -10,15 +10,13 @@ did a scan ago -- and the identity for the first pair.  One line per pair:
 
 pairs and rmse are those of the last iteration (at the pose it started from), status is the op's (0 converged, 1 iterations exhausted,
 2 fewer than 6 pairs, 3 singular system), t and r are the translation in metres and the rotation angle of the pair's pose.  --out FILE
-writes the chained poses, 12 numbers per line (the upper 3 x 4, row-major, KITTI's layout): line j maps frame A + j into frame A, the first
-line is the identity, all in the velodyne frame.
+writes the chained poses (`write_poses`): line j maps frame A + j into frame A, the first line is the identity, all in the velodyne frame.
 
 --init says where a pair's start pose comes from.  `previous` (the default) is the rule above.  `global` starts every pair
 from `ops.register_global(refine=False)`: FPFH descriptors of both clouds (the source's normals are rows 4-6 of its own file), mutual
 nearest descriptors, RANSAC -- no start pose needed, so a gap, a dropped frame or a revisit does not matter.  `auto` tries `previous` and
-repeats the pair from `global` when ICP ends with status 2 or 3; one more line is then printed ahead of the pair's:
-
-    pair <i> <i+1>: global inliers <n> of <L> status <s>
+repeats the pair from `global` when ICP ends with status 2 or 3; one more line is then printed ahead of the pair's, with RANSAC's inliers,
+the correspondences it was given and its status (`register_from`).
 
 --map K (0, the default, is all of the above unchanged) registers frame j against the voxel map of the last K registered
 frames, kept in frame A's coordinates by `ops.voxel_map_insert` (HIP, csrc/voxel_map.hip), instead of against frame i alone: the map's
@@ -52,27 +50,70 @@ def read_prepared(path):
     return cloud
 
 
+def read_poses(path):
+    """A poses file (write_poses; KITTI's layout) -> float64 [F, 4, 4]; ValueError for anything else."""
+    try:
+        rows = np.loadtxt(path, dtype=np.float64, ndmin=2)
+    except (OSError, ValueError) as e:
+        raise ValueError("%s: %s" % (path, e))
+    if rows.shape[1:] != (12,) or not np.isfinite(rows).all():
+        raise ValueError("%s: need 12 finite numbers per line (the upper 3 x 4 of a pose, row-major)" % path)
+    poses = np.tile(np.eye(4), (rows.shape[0], 1, 1))
+    poses[:, :3, :] = rows.reshape(-1, 3, 4)
+    return poses
+
+
+def write_poses(path, poses):
+    """float64 [F, 4, 4] -> the file read_poses reads: the upper 3 x 4 of each, row-major, 12 numbers per line; %.9e carries a float32 exactly."""
+    np.savetxt(path, np.asarray(poses)[:, :3].reshape(-1, 12), fmt="%.9e")
+
+
+def on_device(device):
+    return torch.device("cuda", torch.cuda.current_device()) if device is None else device
+
+
+def device_rows(a, device=None):
+    """rows of a prepared cloud, numpy float32 [c, n] -> the device tensor [n, c] the ops read"""
+    return torch.from_numpy(np.ascontiguousarray(a.T)).to(on_device(device))
+
+
+def device_pose(T, device=None):
+    return torch.from_numpy(T.astype(np.float32)).to(on_device(device))                # float64 [4, 4] -> the float32 the ops read
+
+
 def register_pair(target7, source7, pose=None, max_dist=1.0, huber=0.1, iters=30, device=None):
     """Two prepared clouds float32 [7, n] (numpy) -> ops.IcpResult of the source onto the target."""
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    rows = lambda a: torch.from_numpy(np.ascontiguousarray(a.T)).to(device)            # noqa: E731
-    return ops.icp_point_to_plane(rows(source7[0:3]), rows(target7[0:3]), rows(target7[4:7]), pose=pose, max_dist=max_dist, huber=huber,
-                                  iters=iters)
+    return ops.icp_point_to_plane(device_rows(source7[0:3], device), device_rows(target7[0:3], device), device_rows(target7[4:7], device),
+                                  pose=pose, max_dist=max_dist, huber=huber, iters=iters)
 
 
 def global_start(target7, source7, radius=1.0, n_hyp=4096, thr=0.3, seed=0, device=None):
     """Two prepared clouds float32 [7, n] (numpy) -> ops.GlobalResult of the source onto the target without a start pose, not polished."""
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    rows = lambda a: torch.from_numpy(np.ascontiguousarray(a.T)).to(device)            # noqa: E731
-    return ops.register_global(rows(source7[0:3]), rows(source7[4:7]), rows(target7[0:3]), rows(target7[4:7]), radius=radius, n_hyp=n_hyp,
-                               thr=thr, seed=seed, refine=False)
+    return ops.register_global(device_rows(source7[0:3], device), device_rows(source7[4:7], device), device_rows(target7[0:3], device),
+                               device_rows(target7[4:7], device), radius=radius, n_hyp=n_hyp, thr=thr, seed=seed, refine=False)
 
 
 def rotation_degrees(pose):
     c = (float(pose[0, 0]) + float(pose[1, 1]) + float(pose[2, 2]) - 1.0) / 2.0
     return math.degrees(math.acos(min(1.0, max(-1.0, c))))
+
+
+def register_from(init, i, j, report, icp, previous, from_global):
+    """--init for pair (i, j): icp(start) -> ops.IcpResult, `previous` = the start `previous` means, from_global() -> ops.GlobalResult with the
+    start as its pose.  `auto` repeats a pair that ends with status 2 or 3 from the global start, after one more line.  -> ops.IcpResult."""
+    if init != "global":
+        res = icp(previous)
+    if init == "global" or (init == "auto" and res.status in (2, 3)):
+        g = from_global()
+        if init == "auto":
+            report("pair %d %d: global inliers %d of %d status %d" % (i, j, g.inliers, g.correspondences, g.status))
+        res = icp(g.pose)
+    return res
+
+
+def report_pair(report, i, j, res, rel):
+    report("pair %d %d: pairs %d rmse %.4f iterations %d status %d t %.4f %.4f %.4f r %.4f" % (
+        i, j, res.pairs, res.rmse, res.iterations, res.status, rel[0, 3], rel[1, 3], rel[2, 3], rotation_degrees(rel)))
 
 
 def align_sequence(files, max_dist=1.0, huber=0.1, iters=30, device=None, report=print, init="previous", fpfh_radius=1.0, ransac_hyp=4096,
@@ -84,18 +125,11 @@ def align_sequence(files, max_dist=1.0, huber=0.1, iters=30, device=None, report
     target = read_prepared(files[0][1]) if files else None
     for (i, _), (j, path) in zip(files[:-1], files[1:]):
         source = read_prepared(path)
-        res = None
-        if init != "global":
-            res = register_pair(target, source, pose, max_dist, huber, iters, device)
-        if init == "global" or (init == "auto" and res.status in (2, 3)):
-            g = global_start(target, source, fpfh_radius, ransac_hyp, ransac_thr, seed, device)
-            if init == "auto":
-                report("pair %d %d: global inliers %d of %d status %d" % (i, j, g.inliers, g.correspondences, g.status))
-            res = register_pair(target, source, g.pose, max_dist, huber, iters, device)
+        res = register_from(init, i, j, report, lambda start: register_pair(target, source, start, max_dist, huber, iters, device), pose,
+                            lambda: global_start(target, source, fpfh_radius, ransac_hyp, ransac_thr, seed, device))
         pose = res.pose
         T = pose.cpu().numpy().astype(np.float64)
-        report("pair %d %d: pairs %d rmse %.4f iterations %d status %d t %.4f %.4f %.4f r %.4f" % (
-            i, j, res.pairs, res.rmse, res.iterations, res.status, T[0, 3], T[1, 3], T[2, 3], rotation_degrees(T)))
+        report_pair(report, i, j, res, T)
         chain.append(chain[-1] @ T)
         target = source
     return np.stack(chain[:len(files)]) if files else np.zeros((0, 4, 4))
@@ -108,35 +142,27 @@ def align_to_map(files, k, max_dist=1.0, huber=0.1, iters=30, device=None, repor
     map's points seen from frame i's position, and ICP's result is frame j's pose in the first frame directly.  Same lines as
     align_sequence, t and r those of the pose relative to frame i; `pair <i> <j>: outside <c> of <n>` follows when c of frame j's n rows
     fell off the map's grid."""
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    rows = lambda a: torch.from_numpy(np.ascontiguousarray(a.T)).to(device)            # noqa: E731
-    tensor = lambda T: torch.from_numpy(T.astype(np.float32)).to(device)               # noqa: E731
     chain, rel = [np.eye(4)], np.eye(4)
     vmap = ops.voxel_map(map_voxel, (-map_extent / 2,) * 3, device=device)
     target = None
     for n, (j, path) in enumerate(files):
         source = read_prepared(path)
-        xyz = rows(source[0:3])
+        xyz = device_rows(source[0:3], device)
         if n:
-            i = j - 1
             normals = ops.point_normals(vmap.points, radius=map_normal_radius, viewpoint=tuple(chain[-1][:3, 3])).normals
-            icp = lambda start: ops.icp_point_to_plane(xyz, vmap.points, normals, pose=tensor(start), max_dist=max_dist, huber=huber,  # noqa: E731
-                                                       iters=iters)
-            res = None
-            if init != "global":
-                res = icp(chain[-1] @ rel)
-            if init == "global" or (init == "auto" and res.status in (2, 3)):
+            icp = lambda start: ops.icp_point_to_plane(xyz, vmap.points, normals, pose=device_pose(start, device), max_dist=max_dist,  # noqa: E731
+                                                       huber=huber, iters=iters)
+
+            def from_global():                               # frame j against frame i from the files, moved into the first frame
                 g = global_start(target, source, fpfh_radius, ransac_hyp, ransac_thr, seed, device)
-                if init == "auto":
-                    report("pair %d %d: global inliers %d of %d status %d" % (i, j, g.inliers, g.correspondences, g.status))
-                res = icp(chain[-1] @ g.pose.cpu().numpy().astype(np.float64))
+                return g._replace(pose=chain[-1] @ g.pose.cpu().numpy().astype(np.float64))
+
+            res = register_from(init, j - 1, j, report, icp, chain[-1] @ rel, from_global)
             T = res.pose.cpu().numpy().astype(np.float64)
             rel = np.linalg.inv(chain[-1]) @ T
-            report("pair %d %d: pairs %d rmse %.4f iterations %d status %d t %.4f %.4f %.4f r %.4f" % (
-                i, j, res.pairs, res.rmse, res.iterations, res.status, rel[0, 3], rel[1, 3], rel[2, 3], rotation_degrees(rel)))
+            report_pair(report, j - 1, j, res, rel)
             chain.append(T)
-        ins = ops.voxel_map_insert(vmap, xyz, pose=tensor(chain[-1]), stamp=j, min_stamp=max(0, j + 1 - k))
+        ins = ops.voxel_map_insert(vmap, xyz, pose=device_pose(chain[-1], device), stamp=j, min_stamp=max(0, j + 1 - k))
         if n and ins.outside:
             report("pair %d %d: outside %d of %d" % (j - 1, j, ins.outside, xyz.shape[0]))
         vmap, target = ins.map, source
@@ -211,25 +237,17 @@ def parse_args(argv=None):
     ap.add_argument("--map-normal-radius", type=float, default=0.6, help="radius of the map's normals in metres (default 0.6)")
     args = ap.parse_args(argv)
     check_sequence_flags(ap, args)
-    if not (0.0 < args.max_dist < float("inf")):
-        ap.error("--max-dist must be finite and > 0, got %r" % (args.max_dist,))
+    prepare.check_positive(ap, args, "max_dist", "fpfh_radius", "ransac_thr", "map_voxel", "map_extent", "map_normal_radius")
     if not (0.0 <= args.huber < float("inf")):
         ap.error("--huber must be finite and >= 0, got %r" % (args.huber,))
     if not 0 <= args.iters <= ops.ICP_MAX_ITERS:
         ap.error("--iters must lie in [0, %d]" % ops.ICP_MAX_ITERS)
-    if not (0.0 < args.fpfh_radius < float("inf")):
-        ap.error("--fpfh-radius must be finite and > 0, got %r" % (args.fpfh_radius,))
     if not 1 <= args.ransac_hyp <= ops.RANSAC_MAX_HYP:
         ap.error("--ransac-hyp must lie in [1, %d]" % ops.RANSAC_MAX_HYP)
-    if not (0.0 < args.ransac_thr < float("inf")):
-        ap.error("--ransac-thr must be finite and > 0, got %r" % (args.ransac_thr,))
     if not 0 <= args.seed < 1 << 32:
         ap.error("--seed must lie in [0, 2^32)")
     if not 0 <= args.map < 1 << 31:
         ap.error("--map must lie in [0, 2^31)")
-    for name in ("map_voxel", "map_extent", "map_normal_radius"):
-        if not (0.0 < getattr(args, name) < float("inf")):
-            ap.error("--%s must be finite and > 0, got %r" % (name.replace("_", "-"), getattr(args, name)))
     return ap, args
 
 
@@ -246,9 +264,7 @@ def main(argv=None, device=None):
     except ValueError as e:
         ap.error(str(e))
     if args.out is not None:
-        with open(args.out, "w") as fh:
-            for T in chain:
-                fh.write(" ".join("%.9e" % v for v in T[:3].reshape(-1)) + "\n")
+        write_poses(args.out, chain)
 
 
 if __name__ == "__main__":

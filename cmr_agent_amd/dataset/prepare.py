@@ -71,6 +71,13 @@ def prepare_sequence(velodyne_dir, out_dir, voxel=0.1, sn_radius=0.6, normals=Tr
     return frames, raw_points, kept_points
 
 
+def check_positive(ap, args, *names):
+    """the rule of the three drivers' lengths in metres, for the flags whose attributes are `names`"""
+    for name in names:
+        if not (0.0 < getattr(args, name) < float("inf")):
+            ap.error("--%s must be finite and > 0, got %r" % (name.replace("_", "-"), getattr(args, name)))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="python -m cmr_agent_amd.dataset.prepare", description=__doc__.split("\n\n")[0])
     ap.add_argument("--root", required=True, help="dataset root: <root>/<data_velodyne>/sequences/<seq>/velodyne/*.bin is read")
@@ -81,10 +88,7 @@ def parse_args(argv=None):
     ap.add_argument("--no-normals", action="store_true", help="write [4, n] files (x, y, z, reflectance): what the loaders read")
     ap.add_argument("--overwrite", action="store_true", help="write files that exist again (default: keep them)")
     args = ap.parse_args(argv)
-    if not (0.0 < args.voxel < float("inf")):
-        ap.error("--voxel must be finite and > 0, got %r" % (args.voxel,))
-    if not (0.0 < args.sn_radius < float("inf")):
-        ap.error("--sn-radius must be finite and > 0, got %r" % (args.sn_radius,))
+    check_positive(ap, args, "voxel", "sn_radius")
     if args.sequences is not None:
         try:
             args.sequences = tuple(int(s) for s in args.sequences.split(","))

@@ -2558,25 +2558,44 @@ def _cloud_bounds(points):
     return b[0:3].copy(), b[3:6].copy(), int(b[6:8].view(np.int64)[0])
 
 
-def _cloud_cells(hi, origin, cell, what):
-    """The largest cell index per axis, in the kernel's fp32 arithmetic (the index is monotone in x, so the corners decide); ValueError when a
-    kept row would fall outside [0, 2^21) on an axis."""
-    with np.errstate(over="ignore", invalid="ignore"):
-        top = np.floor((hi.astype(np.float32) - origin) / np.float32(cell))
+def _cloud_grid(points, cell, who, origin=lambda lo: lo):
+    """The prologue of every grid over one cloud: the bounds of its rows with finite coordinates (one host read; none without rows), the grid's
+    origin = origin(their float32 minimum), the check that the keys fit, the keys and their stable sort.  -> (origin, kept, keys int64 [N]
+    sorted, order int64 [N]); (None, 0, None, None) and no further launch without a finite row."""
+    N = points.shape[0]
+    lo, hi, kept = _cloud_bounds(points) if N else (None, None, 0)
+    if kept == 0:
+        return None, 0, None, None
+    org = origin(lo)
+    with np.errstate(over="ignore", invalid="ignore"):        # the largest cell index per axis in the kernel's fp32 arithmetic: monotone in x
+        top = np.floor((hi.astype(np.float32) - org) / np.float32(cell))
     if not np.all(np.isfinite(top)) or top.max() >= CLOUD_CELL_LIMIT:
         raise ValueError("%s: the cloud spans %s cells of %g on some axis; a grid key holds at most 2^21 = %d per axis"
-                         % (what, "%.0f" % np.nanmax(top + 1) if np.any(np.isfinite(top)) else "too many", cell, CLOUD_CELL_LIMIT))
-
-
-def _sorted_keys(points, origin, cell):
-    N = points.shape[0]
+                         % (who, "%.0f" % np.nanmax(top + 1) if np.any(np.isfinite(top)) else "too many", cell, CLOUD_CELL_LIMIT))
     keys = torch.empty((N,), dtype=torch.int64, device=points.device)
-    _lib.call("cmr_voxel_keys_f32", _p(points), 3, N, float(origin[0]), float(origin[1]), float(origin[2]), float(cell), _p(keys), _stream())
-    return torch.sort(keys, stable=True)                    # the one torch computation of this path: plumbing, like the allocator
+    _lib.call("cmr_voxel_keys_f32", _p(points), 3, N, float(org[0]), float(org[1]), float(org[2]), float(cell), _p(keys), _stream())
+    return (org, kept) + tuple(torch.sort(keys, stable=True))       # the one torch computation of this path: plumbing, like the allocator
+
+
+def _voxel_means(keys, order, n, kept, points, attr, want_inverse=False):
+    """The last `kept` of n sorted keys -> (runs S: one host read, offsets, means of points, of attr or None, count [kept], inverse or None)."""
+    dev = keys.device
+    order32 = torch.empty((kept,), dtype=torch.int32, device=dev)
+    offsets = torch.empty((kept + 1,), dtype=torch.int32, device=dev)
+    count = torch.empty((kept,), dtype=torch.int32, device=dev)
+    inverse = torch.empty((n,), dtype=torch.int64, device=dev) if want_inverse else None
+    nseg = torch.empty((1,), dtype=torch.int64, device=dev)
+    nb = _lib.load().cmr_segment_heads_workspace_bytes(n)
+    ws = torch.empty((nb,), dtype=torch.uint8, device=dev)
+    _lib.call("cmr_segment_heads_i64", _p(keys), _p(order), n, kept, _p(order32), _p(offsets), _p(count), _p(inverse), _p(nseg), _p(ws), nb, _stream())
+    S = int(nseg.item())
+    offsets = offsets[:S + 1]
+    means = segment_reduce(points, order32, offsets, S, "mean")
+    return S, offsets, means, segment_reduce(attr, order32, offsets, S, "mean") if attr is not None and attr.shape[1] else None, count, inverse
 
 
 def voxel_downsample(points, attr=None, voxel=0.1, origin=None, want_inverse=False):
-    """Voxel-grid downsample of one cloud (cmr_voxel_keys_f32 / cmr_segment_heads_i64 / cmr_segment_reduce_f32; the contract is the
+    """Voxel-grid downsample of one cloud (_cloud_grid's keys, _voxel_means' heads and cmr_segment_reduce_f32; the contract is the
     header's): one output row per occupied voxel in ascending key order, the fp32 mean of the voxel's rows summed in ascending input index.
     points float32 [N, 3], attr float32 [N, C] (C >= 0) or None -> VoxelCloud.  Rows with a non-finite coordinate are dropped.  The number
     of voxels is read back by the host: not capturable in a graph."""
@@ -2599,33 +2618,22 @@ def voxel_downsample(points, attr=None, voxel=0.1, origin=None, want_inverse=Fal
     def result(n, pts, att, cnt, inv, dropped, org):
         return VoxelCloud(pts, att if attr is not None else None, cnt, inv if want_inverse else None, dropped, tuple(float(v) for v in org))
 
-    lo, hi, kept = _cloud_bounds(points) if N else (None, None, 0)
+    def grid_origin(lo):
+        v32 = np.float32(voxel)
+        org = np.asarray(origin, dtype=np.float32) if origin is not None else lo - v32 * np.float32(0.5)
+        if not np.all(np.isfinite(org)):
+            raise ValueError("voxel_downsample: the grid origin %r is not finite in float32" % (org,))
+        if np.any(np.floor((lo - org) / v32) < 0):
+            raise ValueError("voxel_downsample: origin %r lies above the cloud's minimum %r on some axis (cell indices start at 0)" % (org, lo))
+        return org
+
+    org, kept, keys, order = _cloud_grid(points, voxel, "voxel_downsample", grid_origin)
     if kept == 0:
         return result(0, torch.empty((0, 3), dtype=f32, device=dev), torch.empty((0, C), dtype=f32, device=dev),
                       torch.empty((0,), dtype=torch.int32, device=dev), torch.full((N,), -1, dtype=torch.int64, device=dev), N,
                       origin if origin is not None else (0.0, 0.0, 0.0))
-    v32 = np.float32(voxel)
-    org = np.asarray(origin, dtype=np.float32) if origin is not None else lo - v32 * np.float32(0.5)
-    if not np.all(np.isfinite(org)):
-        raise ValueError("voxel_downsample: the grid origin %r is not finite in float32" % (org,))
-    if np.any(np.floor((lo - org) / v32) < 0):
-        raise ValueError("voxel_downsample: origin %r lies above the cloud's minimum %r on some axis (cell indices start at 0)" % (org, lo))
-    _cloud_cells(hi, org, voxel, "voxel_downsample")
-    keys, order = _sorted_keys(points, org, voxel)
-    order32 = torch.empty((kept,), dtype=torch.int32, device=dev)
-    offsets = torch.empty((kept + 1,), dtype=torch.int32, device=dev)
-    count = torch.empty((kept,), dtype=torch.int32, device=dev)
-    inverse = torch.empty((N,), dtype=torch.int64, device=dev) if want_inverse else None
-    nseg = torch.empty((1,), dtype=torch.int64, device=dev)
-    nb = _lib.load().cmr_segment_heads_workspace_bytes(N)
-    ws = torch.empty((nb,), dtype=torch.uint8, device=dev)
-    _lib.call("cmr_segment_heads_i64", _p(keys), _p(order), N, kept, _p(order32), _p(offsets), _p(count), _p(inverse), _p(nseg), _p(ws), nb,
-              _stream())
-    n = int(nseg.item())
-    offsets = offsets[:n + 1]
-    out = segment_reduce(points, order32, offsets, n, "mean")
-    att = segment_reduce(attr, order32, offsets, n, "mean") if C else torch.empty((n, C), dtype=f32, device=dev)
-    return result(n, out, att, count[:n], inverse, N - kept, org)
+    n, _, out, att, count, inverse = _voxel_means(keys, order, N, kept, points, attr, want_inverse)
+    return result(n, out, att if C else torch.empty((n, C), dtype=f32, device=dev), count[:n], inverse, N - kept, org)
 
 
 def point_normals(points, radius=0.6, viewpoint=(0, 0, 0), min_neighbors=3, want_eigenvalues=False):
@@ -2641,11 +2649,9 @@ def point_normals(points, radius=0.6, viewpoint=(0, 0, 0), min_neighbors=3, want
     normals = torch.zeros((N, 3), dtype=f32, device=dev)
     count = torch.zeros((N,), dtype=torch.int32, device=dev)
     eig = torch.zeros((N, 3), dtype=f32, device=dev) if want_eigenvalues else None
-    lo, hi, kept = _cloud_bounds(points) if N else (None, None, 0)
+    lo, kept, keys, order = _cloud_grid(points, radius, "point_normals")
     if kept == 0:
         return PointNormals(normals, count, eig)
-    _cloud_cells(hi, lo, radius, "point_normals")
-    keys, order = _sorted_keys(points, lo, radius)
     pts4 = torch.empty((N, 4), dtype=f32, device=dev)
     _lib.call("cmr_point_normals_f32", _p(points), 3, _p(keys), _p(order), N, kept, float(lo[0]), float(lo[1]), float(lo[2]), radius,
               viewpoint[0], viewpoint[1], viewpoint[2], min(max(min_neighbors, 3), CLOUD_MAX_ROWS), _p(pts4), _p(normals), _p(count), _p(eig),
@@ -2675,16 +2681,31 @@ class IcpResult(collections.namedtuple("IcpResult", "pose pairs rmse iterations 
     system float64 [iters, 28] = H upper, g, cost per iteration (host; None unless asked for)."""
 
 
-def _cloud_index_arg(index, max_dist, who):
+def _cloud_index_arg(index, reach, who, name="max_dist", why="a match must lie in the query's cell or one next to it"):
     if not isinstance(index, CloudIndex):
         raise ValueError("%s: index must be a CloudIndex (ops.cloud_index), got %s" % (who, type(index).__name__))
-    if max_dist is None:
+    if reach is None:
         return index.cell
-    max_dist = _cloud_scalar(max_dist, "max_dist")
-    if np.float32(max_dist) > np.float32(index.cell):
-        raise ValueError("%s: max_dist %g exceeds the index's cell %g (a match must lie in the query's cell or one next to it)"
-                         % (who, max_dist, index.cell))
-    return max_dist
+    reach = _cloud_scalar(reach, name)
+    if np.float32(reach) > np.float32(index.cell):
+        raise ValueError("%s: %s %g exceeds the index's cell %g (%s)" % (who, name, reach, index.cell, why))
+    return reach
+
+
+def _cloud_family(who, dev, index, one_device, rows=None):
+    """rows = (words, first or None, name, second): one row each per row of the index's cloud -> that number; all of them on dev.  Else ValueError."""
+    words, first, name, second = rows or ("", None, "", None)
+    n = index.n if index is not None else first.shape[0]
+    if rows and (second.shape[0] != n or (first is not None and first.shape[0] != n)):
+        raise ValueError("%s: %s %d rows, %s %d%s" % (who, words, first.shape[0] if first is not None else n, name, second.shape[0],
+                                                    "" if index is None else ", the index %d" % n))
+    if any(t is not None and t.device != dev for t in (first, second)) or (index is not None and index.pts4.device != dev):
+        raise ValueError("%s: %s" % (who, one_device))
+    return n
+
+
+def _none_found(M, dev):
+    return torch.full((M,), -1, dtype=torch.int32, device=dev), torch.full((M,), float("nan"), dtype=f32, device=dev)
 
 
 def _cloud_pose(pose, dev, who):
@@ -2702,12 +2723,10 @@ def cloud_index(points, cell):
     cell = _cloud_scalar(cell, "cell")
     points = _cloud_points(points)
     n, dev = points.shape[0], points.device
-    lo, hi, kept = _cloud_bounds(points) if n else (None, None, 0)
+    lo, kept, keys, order = _cloud_grid(points, cell, "cloud_index")
     if kept == 0:
         return CloudIndex(torch.empty((0, 4), dtype=f32, device=dev), torch.empty((0,), dtype=torch.int64, device=dev),
                           torch.empty((0,), dtype=torch.int64, device=dev), (0.0, 0.0, 0.0), cell, 0, n)
-    _cloud_cells(hi, lo, cell, "cloud_index")
-    keys, order = _sorted_keys(points, lo, cell)
     pts4 = torch.empty((kept, 4), dtype=f32, device=dev)
     _lib.call("cmr_cloud_gather4_f32", _p(points), 3, _p(order), kept, _p(pts4), _stream())
     return CloudIndex(pts4, keys, order, tuple(float(v) for v in lo), cell, kept, n)
@@ -2722,10 +2741,9 @@ def cloud_nearest(index, queries, max_dist=None, pose=None):
     queries = _cloud_points(queries, "queries")
     M, dev = queries.shape[0], queries.device
     pose = _cloud_pose(pose, dev, who)
-    if index.pts4.device != dev:
-        raise ValueError("%s: queries must be on the device of the index" % who)
+    _cloud_family(who, dev, index, "queries must be on the device of the index")
     if M == 0 or index.kept == 0:
-        return CloudNearest(torch.full((M,), -1, dtype=torch.int32, device=dev), torch.full((M,), float("nan"), dtype=f32, device=dev))
+        return CloudNearest(*_none_found(M, dev))
     idx = torch.empty((M,), dtype=torch.int32, device=dev)
     dist2 = torch.empty((M,), dtype=f32, device=dev)
     o = index.origin
@@ -2758,13 +2776,9 @@ def icp_point_to_plane(source, target, target_normals, pose=None, max_dist=1.0, 
     target_normals = _cloud_points(target_normals, "target_normals")
     if target is not None:
         target = _cloud_points(target, "target")
-    n = index.n if index is not None else target.shape[0]
-    if target_normals.shape[0] != n or (target is not None and target.shape[0] != n):
-        raise ValueError("%s: the target has %d rows, target_normals %d%s" % (
-            who, target.shape[0] if target is not None else n, target_normals.shape[0], "" if index is None else ", the index %d" % n))
+    n = _cloud_family(who, dev, index, "source, target, target_normals and the index must be on one device",
+                      ("the target has", target, "target_normals", target_normals))
     pose = _cloud_pose(pose, dev, who)
-    if target_normals.device != dev or (target is not None and target.device != dev) or (index is not None and index.pts4.device != dev):
-        raise ValueError("%s: source, target, target_normals and the index must be on one device" % who)
     if pose is None:
         pose = torch.eye(4, dtype=f32, device=dev)
     M = source.shape[0]
@@ -2823,18 +2837,11 @@ def point_fpfh(points, normals, radius, index=None, want_spfh=False):
     who = "point_fpfh"
     radius = _cloud_scalar(radius, "radius")
     if index is not None:
-        if not isinstance(index, CloudIndex):
-            raise ValueError("%s: index must be a CloudIndex (ops.cloud_index), got %s" % (who, type(index).__name__))
-        if np.float32(index.cell) < np.float32(radius):
-            raise ValueError("%s: radius %g exceeds the index's cell %g (a neighbour must lie in the row's cell or one next to it)"
-                             % (who, radius, index.cell))
+        _cloud_index_arg(index, radius, who, "radius", "a neighbour must lie in the row's cell or one next to it")
     points = _cloud_points(points)
     normals = _cloud_points(normals, "normals")
     N, dev = points.shape[0], points.device
-    if normals.shape[0] != N or (index is not None and index.n != N):
-        raise ValueError("%s: points has %d rows, normals %d%s" % (who, N, normals.shape[0], "" if index is None else ", the index %d" % index.n))
-    if normals.device != dev or (index is not None and index.pts4.device != dev):
-        raise ValueError("%s: points, normals and the index must be on one device" % who)
+    _cloud_family(who, dev, index, "points, normals and the index must be on one device", ("points has", points, "normals", normals))
     if index is None and N:
         index = cloud_index(points, radius)
     if N == 0 or index.kept == 0:
@@ -2891,7 +2898,7 @@ def descriptor_nearest(queries, targets, query_mask=None, target_mask=None):
     _on_one_gpu(who, queries, targets, query_mask, target_mask)
     dev = queries.device
     if M == 0 or N == 0:
-        return DescriptorNearest(torch.full((M,), -1, dtype=torch.int32, device=dev), torch.full((M,), float("nan"), dtype=f32, device=dev))
+        return DescriptorNearest(*_none_found(M, dev))
     idx = torch.empty((M,), dtype=torch.int32, device=dev)
     dist2 = torch.empty((M,), dtype=f32, device=dev)
     _lib.call("cmr_descriptor_nearest_f32", _p(queries), M, _p(targets), N, C, _p(query_mask), _p(target_mask), _p(idx), _p(dist2), _stream())
@@ -3021,7 +3028,7 @@ def _voxel_map_arg(map, who):
 
 
 def voxel_map_insert(map, points=None, attr=None, pose=None, stamp=0, min_stamp=None):
-    """One scan into a voxel map (cmr_voxel_map_keys_f32 / cmr_segment_heads_i64 / cmr_segment_reduce_f32 / cmr_voxel_map_plan_i64 /
+    """One scan into a voxel map (cmr_voxel_map_keys_f32 / _voxel_means' heads and cmr_segment_reduce_f32 / cmr_voxel_map_plan_i64 /
     cmr_voxel_map_write_f32; the contract is the header's) -> MapInsert with a NEW map; `map` is not changed.  points float32 [N, 3] in
     the scan's frame, attr float32 [N, C] with the map's C channels (None when C = 0), pose float32 [4, 4] or None: the scan's pose in the
     map's frame, applied in fp32.  Rows with a non-finite coordinate are dropped and rows off the grid counted as outside; neither is an
@@ -3076,18 +3083,7 @@ def voxel_map_insert(map, points=None, attr=None, pose=None, stamp=0, min_stamp=
         kept = N - dropped - outside
         keys, order = keys[N - kept:], order[N - kept:]           # both marks sort in front of every cell
         if kept:
-            order32 = torch.empty((kept,), dtype=i32, device=dev)
-            offsets = torch.empty((kept + 1,), dtype=i32, device=dev)
-            scan_count = torch.empty((kept,), dtype=i32, device=dev)
-            nseg = torch.empty((1,), dtype=i64, device=dev)
-            nb = lib.cmr_segment_heads_workspace_bytes(kept)
-            ws = torch.empty((nb,), dtype=torch.uint8, device=dev)
-            _lib.call("cmr_segment_heads_i64", _p(keys), _p(order), kept, kept, _p(order32), _p(offsets), _p(scan_count), None, _p(nseg), _p(ws),
-                      nb, _stream())
-            S = int(nseg.item())                                  # host read 2
-            offsets = offsets[:S + 1]
-            scan_points = segment_reduce(moved, order32, offsets, S, "mean")
-            scan_attr = segment_reduce(attr, order32, offsets, S, "mean") if C else None
+            S, offsets, scan_points, scan_attr, scan_count, _ = _voxel_means(keys, order, kept, kept, moved, attr)      # host read 2
     if M + S == 0:
         return MapInsert(VoxelMap(*(t.clone() for t in map[:5]), map.origin, map.voxel), 0, 0, 0, dropped, outside)
     low = 0 if min_stamp is None else min_stamp

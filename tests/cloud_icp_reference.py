@@ -235,3 +235,30 @@ def ops_icp_point_to_plane(source, target, target_normals, pose=None, max_dist=1
     return ops.IcpResult(torch.from_numpy(d["pose32"].copy()), d["pairs"], d["rmse"], d["iterations"], d["status"], torch.from_numpy(d["trace"]),
                          torch.from_numpy(d["system"]) if want_system else None)
 
+
+
+# ---- a folder of prepared frames, as dataset/prepare.py lays it out: the one writer of the tests -----------------------------------------
+def chained_frames(truths):
+    """len(truths) + 1 prepared clouds float32 [7, n] from every fourth row of pair_case()'s target: frame j + 1 is frame j moved by the
+    inverse of truths[j], in float64 all the way, reflectance zero."""
+    case = pair_case()
+    xyz, nrm = case["target"][::4].astype(np.float64), case["normals"][::4].astype(np.float64)
+    frames = []
+    for j in range(len(truths) + 1):
+        frames.append(np.concatenate([xyz.T, np.zeros((1, xyz.shape[0])), nrm.T]).astype(F32))
+        if j < len(truths):
+            inv = np.linalg.inv(truths[j])
+            xyz, nrm = xyz @ inv[:3, :3].T + inv[:3, 3], nrm @ inv[:3, :3].T
+    return frames
+
+
+def write_frames(root, frames, seq=9, first=3):
+    """frames[j] -> <root>/vel/sequences/<seq>/<prepare.subdir()>/<first + j>.npy.  -> the folder"""
+    import os
+
+    from cmr_agent_amd.dataset import prepare
+    folder = os.path.join(root, "vel", "sequences", "%02d" % seq, prepare.subdir())
+    os.makedirs(folder)
+    for j, f in enumerate(frames):
+        np.save(os.path.join(folder, "%06d.npy" % (first + j)), f)
+    return folder

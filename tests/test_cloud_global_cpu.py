@@ -9,7 +9,7 @@ import torch
 import cloud_global_reference as G
 import cloud_icp_reference as I
 from cmr_agent_amd import _lib, ops
-from cmr_agent_amd.dataset import align, prepare
+from cmr_agent_amd.dataset import align
 
 
 # ---- hand-computed cases ----------------------------------------------------------------------------------------------------------------
@@ -323,21 +323,6 @@ def test_header_and_work_model_know_the_entry_points():
 
 
 # ---- align --init -------------------------------------------------------------------------------------------------------------------------
-def _write_sequence(root, truths, seq=9, first=3, far=()):
-    """Prepared files of len(truths) + 1 frames: frame j + 1 is frame j moved by the inverse of truths[j].  -> the folder"""
-    case = I.pair_case()
-    folder = os.path.join(root, "vel", "sequences", "%02d" % seq, prepare.subdir())
-    os.makedirs(folder)
-    xyz, nrm = case["target"][::4].astype(np.float64), case["normals"][::4].astype(np.float64)
-    for j in range(len(truths) + 1):
-        cloud = np.concatenate([xyz.T, np.zeros((1, xyz.shape[0])), nrm.T]).astype(np.float32)
-        np.save(os.path.join(folder, "%06d.npy" % (first + j)), cloud)
-        if j < len(truths):
-            inv = np.linalg.inv(truths[j])
-            xyz, nrm = xyz @ inv[:3, :3].T + inv[:3, 3], nrm @ inv[:3, :3].T
-    return folder
-
-
 def test_align_init_recovers_a_broken_chain(tmp_path, monkeypatch, capsys):
     """The file layer with the restatement in the ops' place: no GPU.  Frame 5 lies 10 m from where its neighbours are."""
     used = []
@@ -347,7 +332,7 @@ def test_align_init_recovers_a_broken_chain(tmp_path, monkeypatch, capsys):
     jump = I.pose_matrix((0.0, 0.0, 0.5), (0.0, 0.0, 10.0))                                   # straight up: no row within max_dist
     truths = [step, jump, np.linalg.inv(jump) @ step]
     root = str(tmp_path)
-    _write_sequence(root, truths)
+    I.write_frames(root, I.chained_frames(truths))
     base = ["--root", root, "--data-velodyne", "vel", "--sequence", "9", "--huber", "0"]
     out = str(tmp_path / "poses.txt")
     # today's behaviour: the default, and --init previous, byte for byte -- the jump ends with status 2 and poisons the pair after it

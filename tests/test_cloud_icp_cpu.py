@@ -9,7 +9,7 @@ import torch
 
 import cloud_icp_reference as R
 from cmr_agent_amd import _lib, ops
-from cmr_agent_amd.dataset import align, prepare
+from cmr_agent_amd.dataset import align
 
 
 # ---- the restatement on hand-checked inputs ---------------------------------------------------------------------------------------------
@@ -262,21 +262,6 @@ def test_header_and_work_model_know_the_entry_points():
 
 
 # ---- align.py ---------------------------------------------------------------------------------------------------------------------------
-def _write_sequence(root, truths, seq=9, first=3, rows=7):
-    """Prepared files of len(truths) + 1 frames: frame j + 1 is frame j moved by the inverse of truths[j].  -> the folder"""
-    case = R.pair_case()
-    folder = os.path.join(root, "vel", "sequences", "%02d" % seq, prepare.subdir())
-    os.makedirs(folder)
-    xyz, nrm = case["target"][::4].astype(np.float64), case["normals"][::4].astype(np.float64)
-    for j in range(len(truths) + 1):
-        cloud = np.concatenate([xyz.T, np.zeros((1, xyz.shape[0])), nrm.T]).astype(np.float32)
-        np.save(os.path.join(folder, "%06d.npy" % (first + j)), cloud[:rows])
-        if j < len(truths):
-            inv = np.linalg.inv(truths[j])
-            xyz, nrm = xyz @ inv[:3, :3].T + inv[:3, 3], nrm @ inv[:3, :3].T
-    return folder
-
-
 def test_align_registers_consecutive_frames_and_chains_the_poses(tmp_path, monkeypatch, capsys):
     """The file layer with the restatement in the op's place: no GPU."""
     calls = []
@@ -288,7 +273,7 @@ def test_align_registers_consecutive_frames_and_chains_the_poses(tmp_path, monke
     monkeypatch.setattr(ops, "icp_point_to_plane", stand_in)
     truths = [R.pose_matrix((0.0, 0.0, 0.02), (0.3, 0.02, 0.0)), R.pose_matrix((0.0, 0.005, 0.025), (0.32, 0.0, 0.01))]
     root = str(tmp_path)
-    _write_sequence(root, truths)
+    R.write_frames(root, R.chained_frames(truths))
     out = str(tmp_path / "poses.txt")
     argv = ["--root", root, "--data-velodyne", "vel", "--sequence", "9", "--huber", "0", "--out", out]
     align.main(argv, device="cpu")
@@ -317,7 +302,7 @@ def test_align_registers_consecutive_frames_and_chains_the_poses(tmp_path, monke
 
 def test_align_flag_rules(tmp_path, capsys):
     root = str(tmp_path)
-    folder = _write_sequence(root, [np.eye(4)], rows=4)
+    folder = R.write_frames(root, [f[:4] for f in R.chained_frames([np.eye(4)])])
     base = ["--root", root, "--data-velodyne", "vel", "--sequence", "9"]
     with pytest.raises(SystemExit):
         align.main(base, device="cpu")                                                   # [4, n] files: no normals

@@ -230,7 +230,7 @@ def _thin_frames():
 
 def test_align_map_registers_against_the_map(tmp_path, stand_ins, capsys):
     frames = _thin_frames()
-    V.write_frames(str(tmp_path), frames)
+    R.write_frames(str(tmp_path), frames)
     out = str(tmp_path / "poses.txt")
     base = ["--root", str(tmp_path), "--data-velodyne", "vel", "--sequence", "9", "--iters", "8"]
     align.main(base + ["--map", "2", "--out", out], device="cpu")
@@ -269,7 +269,7 @@ def test_align_map_falls_back_to_a_global_start(tmp_path, stand_ins, monkeypatch
     """--init global / auto with --map: the global registration is frame j against frame i FROM THE FILES, its pose is moved into frame A
     by frame i's pose, and ICP then runs against the map from there."""
     frames = _thin_frames()[:3]
-    V.write_frames(str(tmp_path), frames)
+    R.write_frames(str(tmp_path), frames)
     truth = V.chain_truth()
     seen = []
 
@@ -324,7 +324,7 @@ def test_align_without_a_map_is_what_it_was(tmp_path, stand_ins, monkeypatch, ca
     monkeypatch.setattr(ops, "voxel_map", _touched)
     monkeypatch.setattr(ops, "point_normals", _touched)
     frames = _thin_frames()[:3]
-    V.write_frames(str(tmp_path), frames)
+    R.write_frames(str(tmp_path), frames)
     outs = [str(tmp_path / "a.txt"), str(tmp_path / "b.txt")]
     base = ["--root", str(tmp_path), "--data-velodyne", "vel", "--sequence", "9", "--iters", "6", "--out"]
     align.main(base + outs[:1], device="cpu")
@@ -349,12 +349,10 @@ def test_align_without_a_map_is_what_it_was(tmp_path, stand_ins, monkeypatch, ca
 
 def test_accumulate_writes_a_prepared_cloud(tmp_path, stand_ins, capsys):
     frames = _thin_frames()
-    folder = V.write_frames(str(tmp_path), frames)
+    folder = R.write_frames(str(tmp_path), frames)
     poses = V.chain_truth()
     pfile, out = str(tmp_path / "poses.txt"), str(tmp_path / "map.npy")
-    with open(pfile, "w") as fh:
-        for T in poses:
-            fh.write(" ".join("%.9e" % v for v in T[:3].reshape(-1)) + "\n")
+    align.write_poses(pfile, poses)
     base = ["--root", str(tmp_path), "--data-velodyne", "vel", "--sequence", "9", "--poses", pfile]
     accumulate.main(base + ["--out", out, "--voxel", "0.4"], device="cpu")
     lines = capsys.readouterr().out.splitlines()

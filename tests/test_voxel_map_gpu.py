@@ -301,7 +301,7 @@ def test_align_to_a_map_and_accumulate(tmp_path, capsys):
     the restatement's, each pose within 10 % of the restatement's own error of the restatement's pose.  Then accumulate on the written
     poses: keys and counts equal the restatement's map, means within the bound."""
     case = V.chain_case()
-    V.write_frames(str(tmp_path), case["frames"])
+    R.write_frames(str(tmp_path), case["frames"])
     out, cloud = str(tmp_path / "poses.txt"), str(tmp_path / "map.npy")
     base = ["--root", str(tmp_path), "--data-velodyne", "vel", "--sequence", "9"]
     align.main(base + ["--map", "2", "--huber", "0.1", "--max-dist", "1.0", "--iters", "40", "--out", out])

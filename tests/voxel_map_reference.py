@@ -188,14 +188,3 @@ def accumulate(frames, poses, first=0, voxel=MAP_VOXEL, extent=MAP_EXTENT):
     for j, (f, T) in enumerate(zip(frames, poses)):
         m, _ = insert(m, f[:3].T, f[3:4].T, np.asarray(T, dtype=F32), stamp=first + j)
     return m
-
-
-def write_frames(root, frames, seq=9, first=CHAIN_FIRST):
-    import os
-
-    from cmr_agent_amd.dataset import prepare
-    folder = os.path.join(root, "vel", "sequences", "%02d" % seq, prepare.subdir())
-    os.makedirs(folder)
-    for j, f in enumerate(frames):
-        np.save(os.path.join(folder, "%06d.npy" % (first + j)), f)
-    return folder
