@@ -11,7 +11,7 @@ ARCH  ?= gfx950
 SRC   := $(wildcard cmr_agent_amd/csrc/*.hip)
 OBJ   := $(patsubst cmr_agent_amd/csrc/%.hip,build/%.o,$(SRC))
 # sources that hold an A/B switch: compiled a second time for the A/B library, every other object is shared
-ABSRC := linear conv_wino conv_bf16 attention wgrad
+ABSRC := linear conv_wino conv_bf16 attention wgrad voxel_map_rays
 ABOBJ := $(patsubst %,build/ab_%.o,$(ABSRC))
 LIB   := cmr_agent_amd/lib/libcmr_hip.so
 LIBAB := cmr_agent_amd/lib/libcmr_hip_ab.so

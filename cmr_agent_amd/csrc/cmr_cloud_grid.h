@@ -24,6 +24,14 @@ __device__ __forceinline__ int64_t cell_index(float x, float origin, float cell)
   return c >= 0.f ? (c <= (float)CELL_MAX ? (int64_t)c : CELL_MAX) : 0;          // NaN -> 0
 }
 __device__ __forceinline__ int64_t pack_key(int64_t cx, int64_t cy, int64_t cz) { return cz << (2 * CELL_BITS) | cy << CELL_BITS | cx; }
+// the cell of a cell coordinate t = cell_coord(..), and whether the grid has it: the test is on the float, so +-inf and 3e38 are outside
+// like cell -1 (voxel_map.hip: a row's key; voxel_map_rays.hip: both ends of a ray)
+__device__ __forceinline__ bool grid_cell(float t, int64_t& c) {
+  const float f = floorf(t);
+  const bool inside = f >= 0.f && f <= (float)CELL_MAX;
+  c = inside ? (int64_t)f : 0;
+  return inside;
+}
 
 // the cells a query searches along one axis: its own and one to either side -- and a second one on the side whose face the query sits on to
 // within the rounding of cell_coord (a neighbour at distance radius there may round into the cell after next)

@@ -23,13 +23,8 @@ constexpr int64_t ROW_LIMIT = (int64_t)1 << 31;
 inline int64_t align16(int64_t bytes) { return (bytes + 15) & ~(int64_t)15; }
 
 // ---------------------------------------------------------------------------------------------------------------------------- keys
-// the cell of a coordinate as a float, and whether the grid has it: the test is on the float, so +-inf and 3e38 are outside like cell -1
-__device__ __forceinline__ bool cell_of(float x, float origin, float cell, int64_t& c) {
-  const float f = floorf(cell_coord(x, origin, cell));
-  const bool inside = f >= 0.f && f <= (float)CELL_MAX;
-  c = inside ? (int64_t)f : 0;
-  return inside;
-}
+// the cell of a coordinate, and whether the grid has it (grid_cell: the test is on the float)
+__device__ __forceinline__ bool cell_of(float x, float origin, float cell, int64_t& c) { return grid_cell(cell_coord(x, origin, cell), c); }
 
 // dropped rows in the low half of the word, outside rows in the high half: a workgroup has at most 256 of either
 __global__ __launch_bounds__(256) void map_keys_kernel(const float* __restrict__ pts, int64_t ld, int64_t N, const float* __restrict__ pose,

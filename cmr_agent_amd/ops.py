@@ -3099,3 +3099,54 @@ def voxel_map_insert(map, points=None, attr=None, pose=None, stamp=0, min_stamp=
               _p(scan_points), _p(scan_attr), _p(scan_count), S, C, stamp, low, _p(ws), nb, rows, _p(out.keys), _p(out.points), _p(out.attr),
               _p(out.count), _p(out.stamp), _stream())
     return MapInsert(out, new, merged, removed, dropped, outside)
+
+
+# ---- free space in a voxel map: the rays of a scan cast through it (csrc/voxel_map_rays.hip) -----------------------------------
+MAP_RAYS_MAX_CELLS = 1 << 16        # the longest walk a ray may be asked for
+
+
+class MapRays(collections.namedtuple("MapRays", "crossed hits cast dropped outside long")):
+    """voxel_map_rays' result: crossed int32 [n] = the rays that passed through each of the map's voxels, hits int32 [n] = the rays that
+    ended in it, both aligned with the map's rows; cast = rays walked, dropped = rows with a non-finite coordinate before or after the
+    pose, outside = finite rows whose sensor or end lies off the grid, long = rays of more than max_cells steps, which are not walked."""
+
+
+def voxel_map_rays(map, points, pose=None, start_margin=2, end_margin=1, max_cells=4096):
+    """The rays of one scan cast through a voxel map (cmr_voxel_map_rays_f32; the contract is the header's) -> MapRays; `map` is not
+    changed.  points float32 [N, 3] in the scan's frame: row i is a beam from the sensor -- the pose's translation, the origin without a
+    pose -- to the row moved by the pose, in fp32 as ops.voxel_map_insert moves it.  A voxel within start_margin cells of the ray's first
+    cell or within end_margin cells of its last (Chebyshev distances, on any axis) is not counted as crossed.  One host read: the four
+    counts."""
+    who = "voxel_map_rays"
+    M, _, dev = _voxel_map_arg(map, who)
+    start_margin = _int_arg(who, "start_margin", start_margin, 0, CLOUD_CELL_LIMIT - 1)
+    end_margin = _int_arg(who, "end_margin", end_margin, 0, CLOUD_CELL_LIMIT - 1)
+    max_cells = _int_arg(who, "max_cells", max_cells, 1, MAP_RAYS_MAX_CELLS)
+    pose = _cloud_pose(pose, dev, who)
+    points = _cloud_points(points)
+    if points.device != dev:
+        raise ValueError("%s: points must be on the map's device" % who)
+    if not map.keys.is_cuda:
+        raise ValueError("%s: the map must hold device tensors (there is no CPU path)" % who)
+    N = points.shape[0]
+    crossed = torch.empty((M,), dtype=torch.int32, device=dev)
+    hits = torch.empty((M,), dtype=torch.int32, device=dev)
+    if N == 0:
+        return MapRays(crossed.zero_(), hits.zero_(), 0, 0, 0, 0)
+    counts = torch.empty((4,), dtype=torch.int64, device=dev)
+    nb = _lib.load().cmr_voxel_map_rays_workspace_bytes(N)
+    ws = _ws(nb, dev)
+    o = map.origin
+    _lib.call("cmr_voxel_map_rays_f32", _p(map.keys) if M else None, M, o[0], o[1], o[2], map.voxel, _p(points), 3, N, _p(pose), start_margin,
+              end_margin, max_cells, _p(crossed) if M else None, _p(hits) if M else None, _p(counts), _p(ws), nb, _stream())
+    return MapRays(crossed, hits, *(int(v) for v in counts.cpu()))
+
+
+def voxel_map_keep(map, mask):
+    """The rows of a voxel map where mask (bool [n], on the map's device) is true, as a NEW map on the same grid: torch indexing."""
+    who = "voxel_map_keep"
+    M, _, dev = _voxel_map_arg(map, who)
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or tuple(mask.shape) != (M,) or mask.device != dev:
+        raise ValueError("%s: mask must be a bool [%d] tensor on the map's device, got %s %s%s" % (
+            (who, M) + _got(mask) + (" on %s" % mask.device if torch.is_tensor(mask) else "",)))
+    return VoxelMap(*(t[mask] for t in map[:5]), map.origin, map.voxel)

@@ -305,6 +305,10 @@ WORK = {
     "cmr_voxel_map_plan_i64": lambda a: (0, a["M"] * 24 + a["S"] * 28),
     "cmr_voxel_map_write_f32": lambda a: (3.0 * (3 + a["C"]) * min(a["M"], a["S"]),
                                           (a["M"] + a["S"]) * (8 + 28 + 4 * a["C"]) + a["rows"] * (28 + 4 * a["C"])),
+    # DESIGN.md 4aj, latency-class and priced on compulsory bytes: a row read (12 B), the map's keys once (8 B) and its two counters zeroed
+    # (8 B).  The walk is not counted: the number of cells a ray steps through and of lookups it makes is data (20 to 800 per ray on a
+    # driving scan), each lookup a binary search whose reads hit the cache, each count found one 4-byte atomic.
+    "cmr_voxel_map_rays_f32": lambda a: (0, a["N"] * 12 + a["M"] * 16),
 }
 
 # Multiplies the kernel ISSUES on the matrix cores per algorithmic multiply: F(2x2,3x3) Winograd computes 2x2 outputs with 16

@@ -1523,6 +1523,39 @@ int cmr_voxel_map_write_f32(const int64_t* map_keys, const float* map_points, co
                             int64_t S, int C, int stamp, int min_stamp, const void* workspace, int64_t workspace_bytes, int64_t rows,
                             int64_t* keys, float* points, float* attr, int32_t* count, int32_t* stamps, hipStream_t stream);
 
+/* ---- free space in a voxel map: the rays of a scan cast through it (csrc/voxel_map_rays.hip) ---------------------------
+ * Port extension.  Row i of points [N][ld >= 3], 0 < N < 2^31, is a beam from the sensor to its return; the cells of the map's grid
+ * (origin (ox, oy, oz), voxel) between the two were empty when the scan was taken.  keys int64 [M], M >= 0: a map's keys, ascending and
+ * unique.  Nothing in the map changes and the library keeps no state.  Everything below is fp32, every operation rounded on its own
+ * (no fused operation), so that every integer is exact.
+ *   ends      with pose (fp32 [4][4], row-major, upper 3 x 4 read) the sensor is o = t and the end q = R p + t, the moved row of
+ *             cmr_voxel_map_keys_f32;  with pose = null  o = (0, 0, 0), q = p;
+ *   dropped   p or q has a non-finite coordinate;
+ *   outside   else, o or q lies off the grid on some axis: cmr_voxel_map_keys_f32's test, floorf((x - origin) / voxel) below 0 or above
+ *             2^21 - 1, the comparison made on the float;
+ *   per axis  a = (o - origin) / voxel,  b = (q - origin) / voxel,  start cell s = floorf(a),  end cell e = floorf(b),  d = b - a,
+ *             left = |e - s|,  step = sign(e - s);
+ *   long      else, left_x + left_y + left_z > max_cells (1 <= max_cells <= 65 536): the ray is not cast.  The cap bounds every
+ *             lane's loop whatever the input;
+ *   cast      else.  The walk starts in s and makes exactly left_x + left_y + left_z steps of one cell along one axis: the axis with the
+ *             least tmax, ties going to x before y before z, where  tmax_i = +inf  once left_i = 0 and otherwise
+ *             tmax_i = ((float) (c_i + (step_i > 0 ? 1 : 0)) - a_i) / d_i  of the cell c the walk is in -- recomputed from the integer
+ *             cell after every step on axis i, never accumulated;  an axis with left_i = 0 is never divided on (d_i = 0 never divides,
+ *             a ray of length zero makes no step).  The walk therefore ends in e whatever the rounding did on the way, and the key of e
+ *             is, bit for bit, the key cmr_voxel_map_keys_f32 gives the row;
+ *   hits      the map holds the key of e at row r:  hits[r] += 1;
+ *   crossed   every cell c the walk visits other than e (s included) with  max_i |c_i - s_i| > start_margin  and
+ *             max_i |c_i - e_i| > end_margin  (Chebyshev distances in cells; both margins >= 0) whose key the map holds at row r:
+ *             crossed[r] += 1.
+ * crossed, hits int32 [M] (may be null when M = 0): zeroed by the call, then integer sums by atomic add -- order free, two calls agree
+ * exactly.  counts int64 [4] = {cast, dropped, outside, long}, per-workgroup totals added by one workgroup; they sum to N.  A row index
+ * only ever comes out of a search over [0, M) that found an equal key there: whatever keys are handed over, no store leaves
+ * crossed[0, M), hits[0, M) and counts.  Workspace of cmr_voxel_map_rays_workspace_bytes(N). */
+int64_t cmr_voxel_map_rays_workspace_bytes(int64_t N);
+int cmr_voxel_map_rays_f32(const int64_t* keys, int64_t M, float ox, float oy, float oz, float voxel, const float* points, int64_t ld,
+                           int64_t N, const float* pose, int start_margin, int end_margin, int max_cells, int32_t* crossed, int32_t* hits,
+                           int64_t* counts, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,11 @@ int cmr_set_wgrad_bf16_variant(int transposed_reads);
  * another order; returns the previous on / off setting. */
 int cmr_set_linear_wgrad_variant(int lds_staged);
 
+/* A/B switch of cmr_voxel_map_rays_f32's lookup: 0 (default, the product library's only choice) = every lookup is a binary search over all
+ * M keys, nonzero = the run of sorted keys behind a ray's (y, z) pair is found once per pair and searched alone while the ray steps along x
+ * (it measured slower; kept for tools/voxel_map_rays_bench.py).  Same integers either way; returns the previous setting. */
+int cmr_set_voxel_map_rays_variant(int runs);
+
 #ifdef __cplusplus
 }
 #endif
