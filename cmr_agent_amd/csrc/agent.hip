@@ -91,11 +91,12 @@ __global__ __launch_bounds__(256) void observation_finalize_kernel(const float* 
 // hipGraph replays; cells hit by nobody stay zero from the initial fill.
 // Tile reach of an occupied cell (cmr_observation_proj_reach_f32): map[b][ty][tx] = 1 for every 8 x 16 tile of the h x w grid (ceil at the
 // borders) whose area dilated by r pixels holds (yi, xi) -- at most 2 x 2 tiles for r < 8.  Every writer stores the same byte, so the
-// races between points are benign.
-__device__ __forceinline__ void obs_mark_reach(uint8_t* __restrict__ map, int r, int b, int yi, int xi, int h, int w) {
-  const int tiles_y = (h + 7) >> 3, tiles_x = (w + 15) >> 4;
-  const int ya = (yi - r > 0 ? yi - r : 0) >> 3, yb = (yi + r) >> 3 < tiles_y ? (yi + r) >> 3 : tiles_y - 1;
-  const int xa = (xi - r > 0 ? xi - r : 0) >> 4, xb = (xi + r) >> 4 < tiles_x ? (xi + r) >> 4 : tiles_x - 1;
+// races between points are benign.  sy / sx: log2 of the tile's height / width in observation cells (3 / 4: the full-resolution stage;
+// 4 / 5: the 8 x 16 tiles of the half-resolution stage, a 16 x 32 footprint, r < 16); tiles_y / tiles_x: that stage's tile grid.
+__device__ __forceinline__ void obs_mark_reach(uint8_t* __restrict__ map, int r, int sy, int sx, int tiles_y, int tiles_x, int b, int yi,
+                                               int xi) {
+  const int ya = (yi - r > 0 ? yi - r : 0) >> sy, yb = (yi + r) >> sy < tiles_y ? (yi + r) >> sy : tiles_y - 1;
+  const int xa = (xi - r > 0 ? xi - r : 0) >> sx, xb = (xi + r) >> sx < tiles_x ? (xi + r) >> sx : tiles_x - 1;
   uint8_t* m = map + (int64_t)b * tiles_y * tiles_x;
   m[ya * tiles_x + xa] = 1;
   m[ya * tiles_x + xb] = 1;
@@ -107,7 +108,8 @@ __global__ __launch_bounds__(256) void obs_project_kernel(const float* __restric
                                                           const float* __restrict__ pose, const float* __restrict__ Kmat,
                                                           const float* __restrict__ mean4, float* __restrict__ proj, float* __restrict__ cnt,
                                                           int32_t* __restrict__ cell, float* __restrict__ state3d, int B, int N, int h, int w,
-                                                          uint8_t* __restrict__ reach1, uint8_t* __restrict__ reach2) {
+                                                          uint8_t* __restrict__ reach1, uint8_t* __restrict__ reach2,
+                                                          uint8_t* __restrict__ reach3, uint8_t* __restrict__ reach4) {
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= (int64_t)B * N) return;
   const int32_t prev = cell[p];
@@ -141,8 +143,14 @@ __global__ __launch_bounds__(256) void obs_project_kernel(const float* __restric
     const int xi = (int)rintf(u), yi = (int)rintf(v);            // torch.round = half to even
     c = (int32_t)((int64_t)b * h * w + (int64_t)yi * w + xi);
     if (reach1) {                                                // (uniform) the convolutions' 8 x 16 tiles this cell can reach
-      obs_mark_reach(reach1, 1, b, yi, xi, h, w);
-      obs_mark_reach(reach2, 2, b, yi, xi, h, w);
+      const int tiles_y = (h + 7) >> 3, tiles_x = (w + 15) >> 4;
+      obs_mark_reach(reach1, 1, 3, 4, tiles_y, tiles_x, b, yi, xi);
+      obs_mark_reach(reach2, 2, 3, 4, tiles_y, tiles_x, b, yi, xi);
+    }
+    if (reach3) {                                                // (uniform) ... and the 8 x 16 tiles of the half-resolution stage (h, w even)
+      const int tiles_y = ((h >> 1) + 7) >> 3, tiles_x = ((w >> 1) + 15) >> 4;
+      obs_mark_reach(reach3, 4, 4, 5, tiles_y, tiles_x, b, yi, xi);
+      obs_mark_reach(reach4, 6, 4, 5, tiles_y, tiles_x, b, yi, xi);
     }
   }
   cell[p] = c;
@@ -289,20 +297,34 @@ extern "C" int cmr_project_scatter_f32(const float* pc4, const float* feat, cons
 
 // reach1 / reach2 (both or neither): byte maps [B][ceil(h / 8)][ceil(w / 16)] that receive a 1 for every tile within 1 / 2 pixels of a cell
 // hit now (see obs_mark_reach); never cleared here -- their consumer (cmr_wino_tile_lists) does that.
-extern "C" int cmr_observation_proj_reach_f32(const float* pc4, const float* feat, const uint8_t* overlap, const float* pose, const float* Kmat,
-                                              const float* mean4, float* proj, float* cnt, int32_t* cell, float* state3d, int B, int N, int h,
-                                              int w, uint8_t* reach1, uint8_t* reach2, hipStream_t stream) {
+// reach3 / reach4 (both or neither; with reach1 / reach2 only; h, w, h / 2 and w / 2 even): byte maps [B][ceil(h / 16)][ceil(w / 32)] on the
+// tile grid of the half-resolution stage that follows (two 3x3 convolutions on the 2 x 2 pooled map, 8 x 16 tiles of it = 16 x 32 cells):
+// a conv-1 output depends on the cells within 2, pooled pixel q on the cells 2q - 2 .. 2q + 3, and every further 3x3 convolution at half
+// resolution adds one pooled pixel = 2 cells on either side, so its first convolution can tell a cell within 4 cells of the tile's
+// footprint (reach3) and its second one within 6 (reach4).  Cleared by cmr_wino_tile_lists_staged.
+extern "C" int cmr_observation_proj_reach_staged_f32(const float* pc4, const float* feat, const uint8_t* overlap, const float* pose,
+                                                     const float* Kmat, const float* mean4, float* proj, float* cnt, int32_t* cell,
+                                                     float* state3d, int B, int N, int h, int w, uint8_t* reach1, uint8_t* reach2,
+                                                     uint8_t* reach3, uint8_t* reach4, hipStream_t stream) {
   CMR_REQUIRE(pc4 && feat && overlap && pose && Kmat && mean4 && proj && cnt && cell && state3d && B > 0 && N > 0 && h > 0 && w > 0);
   CMR_REQUIRE((int64_t)B * h * w < 0x7fffffff && cmr_aligned16(proj) && cmr_aligned16(state3d) && cmr_aligned16(pc4));
-  CMR_REQUIRE((reach1 == nullptr) == (reach2 == nullptr));
+  CMR_REQUIRE((reach1 == nullptr) == (reach2 == nullptr) && (reach3 == nullptr) == (reach4 == nullptr));
+  CMR_REQUIRE(!reach3 || (reach1 && h % 4 == 0 && w % 4 == 0));
   const int64_t total = (int64_t)B * N;
   const unsigned per_point = (unsigned)((total + 255) / 256);
   hipLaunchKernelGGL(obs_project_kernel, dim3(per_point), dim3(256), 0, stream, pc4, overlap, pose, Kmat, mean4, proj, cnt, cell, state3d, B, N,
-                     h, w, reach1, reach2);
+                     h, w, reach1, reach2, reach3, reach4);
   hipLaunchKernelGGL(obs_count_kernel, dim3(per_point), dim3(256), 0, stream, (const int32_t*)cell, cnt, total);
   hipLaunchKernelGGL(obs_scatter_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, stream, feat, (const int32_t*)cell,
                      (const float*)cnt, proj, total);
   return cmr_launch_status();
+}
+
+extern "C" int cmr_observation_proj_reach_f32(const float* pc4, const float* feat, const uint8_t* overlap, const float* pose, const float* Kmat,
+                                              const float* mean4, float* proj, float* cnt, int32_t* cell, float* state3d, int B, int N, int h,
+                                              int w, uint8_t* reach1, uint8_t* reach2, hipStream_t stream) {
+  return cmr_observation_proj_reach_staged_f32(pc4, feat, overlap, pose, Kmat, mean4, proj, cnt, cell, state3d, B, N, h, w, reach1, reach2,
+                                               nullptr, nullptr, stream);
 }
 
 extern "C" int cmr_observation_proj_f32(const float* pc4, const float* feat, const uint8_t* overlap, const float* pose, const float* Kmat,

@@ -406,8 +406,9 @@ constexpr bool WS_STATS = CMR_WS_STATS != 0, WS_BNBWD = CMR_WS_STATS != 0 && CMR
 // LIST instantiation (cmr_conv3x3_wino_list_nhwc_f32): only the tiles order[0 .. *nlive) are multiplied -- the workgroups walk the COMPACTED
 // index range in the same XCD-banded order and look the tile up in order[] -- and the tiles order[*nlive .. ntiles) are copied from y0, a
 // map of y's geometry (null: the ordinary epilogue on a zero product).  The dense instantiation never reads a WsList and compiles to the
-// program it was without it.
-struct WsList { const int* order; const int* nlive; const float* y0; };
+// program it was without it.  nend (cmr_conv3x3_wino_list_nend_nhwc_f32; null: ntiles): only order[*nlive .. *nend) are copied and the
+// tiles behind are NOT WRITTEN -- for an output whose only reader is a list launch that needs no pixel of them.
+struct WsList { const int* order; const int* nlive; const float* y0; const int* nend; };
 template <int dbg, bool LIST>
 __global__ __launch_bounds__(512, 1) void conv3x3_wino_ws_kernel(const WinoArgs a, const int tiles_x, const int tiles_y, const int ntiles, const WsList l) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -864,7 +865,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino_ws_kernel(const WinoArgs 
     const int pw = a.pool == 2 ? WT_TW / 2 : WT_TW, pn = a.pool == 2 ? WT_TH * WT_TW / 4 : WT_TH * WT_TW;
     const int Hy = a.pool == 2 ? a.H >> 1 : a.H, Wy = a.pool == 2 ? a.W >> 1 : a.W;
     const int c4 = tid & 15;
-    for (int s = nt + (int)blockIdx.x; s < ntiles; s += (int)gridDim.x) {
+    int ne = ntiles;                                   // end of the tiles to copy
+    if (l.nend) {
+      ne = __builtin_amdgcn_readfirstlane(*l.nend);
+      ne = ne < nt ? nt : (ne < ntiles ? ne : ntiles);
+    }
+    for (int s = nt + (int)blockIdx.x; s < ne; s += (int)gridDim.x) {
       int t = l.order[s];
       t = (unsigned)t < (unsigned)ntiles ? t : ntiles - 1;
       const int co0 = (t % nco) * 64; t /= nco;
@@ -1062,6 +1068,81 @@ __global__ __launch_bounds__(1024) void wino_tile_lists_kernel(uint8_t* __restri
   if (tid == 0) *(blockIdx.x ? nlive2 : nlive1) = total * nco;
 }
 
+// Two chained convolutions per stage, where the first one's output is read by the second one alone (cmr_wino_tile_lists_staged).
+// Workgroup g serves stage g: the maps ra / rb [B][ty][tx] of its first / second convolution become
+//   order_a = the tiles with ra set ("live"), then those without whose 3 x 3 tile neighbourhood in the same sample (itself included)
+//             holds a tile with rb set ("copy": the second convolution reads a one-pixel halo around its live tiles), then the rest,
+//             each part ascending;  cnt[0] = live, cnt[1] = live + copy, in virtual tiles
+//   order_b = the tiles with rb set, then the others;  cnt[2] = live virtual tiles
+// and both maps are cleared.  The classes are parked in ra between the two passes: a thread reads its neighbours' rb in the first pass
+// and clears only its own tiles in the second, after the barrier of the scan.
+struct WsStage { uint8_t* ra; uint8_t* rb; int B, ty, tx, nco; int* order_a; int* order_b; int* cnt; };
+__global__ __launch_bounds__(1024) void wino_tile_lists_staged_kernel(const WsStage s0, const WsStage s1) {
+  __shared__ int wsum[3][16];
+  const WsStage& s = blockIdx.x ? s1 : s0;
+  const int ntile = s.B * s.ty * s.tx;
+  const int tid = threadIdx.x;
+  const int per = (ntile + 1023) / 1024;                       // consecutive tiles per thread
+  const int lo = tid * per < ntile ? tid * per : ntile, hi = lo + per < ntile ? lo + per : ntile;
+  int n[3] = {0, 0, 0};                                        // live a, copy a, live b
+  for (int i = lo; i < hi; ++i) {
+    const int x = i % s.tx, y = (i / s.tx) % s.ty;
+    int cls = s.ra[i] != 0 ? 1 : 0;
+    if (!cls) {
+      for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx)
+          if ((unsigned)(y + dy) < (unsigned)s.ty && (unsigned)(x + dx) < (unsigned)s.tx && s.rb[i + dy * s.tx + dx] != 0) cls = 2;
+    }
+    s.ra[i] = (uint8_t)cls;
+    n[0] += cls == 1;
+    n[1] += cls == 2;
+    n[2] += s.rb[i] != 0;
+  }
+  // inclusive scans: inside the wave by shuffles, then over the 16 wave totals (one barrier instead of the twenty of the two-map kernel:
+  // this launch sits on every agent step's serial chain)
+  const int lane = tid & 63, wave = tid >> 6;
+  int inc[3], tot[3], pre[3];
+  for (int k = 0; k < 3; ++k) {
+    int v = n[k];
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(v, d, 64);
+      if (lane >= d) v += up;
+    }
+    inc[k] = v;
+    if (lane == 63) wsum[k][wave] = v;
+  }
+  __syncthreads();
+  for (int k = 0; k < 3; ++k) {
+    tot[k] = 0;
+    pre[k] = inc[k] - n[k];
+    for (int q = 0; q < 16; ++q) {
+      const int v = wsum[k][q];
+      tot[k] += v;
+      pre[k] += q < wave ? v : 0;
+    }
+  }
+  const int live_a = tot[0], copy_a = tot[1], live_b = tot[2];
+  int la = pre[0], ca = pre[1], lb = pre[2];
+  int ra = live_a + copy_a + (lo - la - ca), db = live_b + (lo - lb);
+  ca += live_a;
+  for (int i = lo; i < hi; ++i) {
+    const int cls = s.ra[i];
+    const int slot_a = cls == 1 ? la++ : (cls == 2 ? ca++ : ra++);
+    const int slot_b = s.rb[i] != 0 ? lb++ : db++;
+    s.ra[i] = 0;
+    s.rb[i] = 0;
+    for (int c = 0; c < s.nco; ++c) {
+      s.order_a[slot_a * s.nco + c] = i * s.nco + c;
+      s.order_b[slot_b * s.nco + c] = i * s.nco + c;
+    }
+  }
+  if (tid == 0) {
+    s.cnt[0] = live_a * s.nco;
+    s.cnt[1] = (live_a + copy_a) * s.nco;
+    s.cnt[2] = live_b * s.nco;
+  }
+}
+
 }  // namespace
 
 extern "C" int cmr_wino_tile_lists(uint8_t* reach1, uint8_t* reach2, int B, int H, int W, int Cout1, int Cout2, int* order1, int* nlive1,
@@ -1075,14 +1156,39 @@ extern "C" int cmr_wino_tile_lists(uint8_t* reach1, uint8_t* reach2, int B, int 
   return cmr_launch_status();
 }
 
+// The lists of two stages of two chained convolutions each: stage 0 on H x W maps with Cout0 channels, stage 1 on H / 2 x W / 2 maps with
+// Cout1 channels (H, W even).  reach1 .. reach4 = the byte maps of stage 0's first and second convolution, then stage 1's
+// (cmr_observation_proj_reach_staged_f32); order1 .. order4 likewise; counts [6] = live, live + copy of stage 0's first list, live of its
+// second, then the same three of stage 1 (wino_tile_lists_staged_kernel).  One launch; the four maps are cleared.
+extern "C" int cmr_wino_tile_lists_staged(uint8_t* reach1, uint8_t* reach2, uint8_t* reach3, uint8_t* reach4, int B, int H, int W, int Cout0,
+                                          int Cout1, int* order1, int* order2, int* order3, int* order4, int* counts, hipStream_t stream) {
+  CMR_REQUIRE(counts && B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0);
+  CMR_REQUIRE(Cout0 >= 64 && Cout0 % 64 == 0 && Cout1 >= 64 && Cout1 % 64 == 0);
+  uint8_t* const reach[4] = {reach1, reach2, reach3, reach4};
+  int* const order[4] = {order1, order2, order3, order4};
+  for (int k = 0; k < 4; ++k) CMR_REQUIRE(reach[k] && order[k]);
+  WsStage s[2];
+  for (int g = 0; g < 2; ++g) {
+    const int h = g ? H / 2 : H, w = g ? W / 2 : W, cout = g ? Cout1 : Cout0;
+    const int tx = (w + WT_TW - 1) / WT_TW, ty = (h + WT_TH - 1) / WT_TH;
+    CMR_REQUIRE((int64_t)tx * ty * B * (cout / 64) < 0x3fffffff);
+    s[g] = WsStage{reach[2 * g], reach[2 * g + 1], B, ty, tx, cout / 64, order[2 * g], order[2 * g + 1], counts + 3 * g};
+  }
+  hipLaunchKernelGGL(wino_tile_lists_staged_kernel, dim3(2), dim3(1024), 0, stream, s[0], s[1]);
+  return cmr_launch_status();
+}
+
 // cmr_conv3x3_wino_nhwc_f32 (no table operand) on the tiles order[0 .. *nlive) only; the tiles order[*nlive .. ntiles) of y are copied
 // from y0 [B][H / pool][W / pool][Cout], or, with y0 null (pool 1), receive the epilogue of a zero product: act(bias + res).  order is a
 // permutation of the ntiles = B ceil(H / 8) ceil(W / 16) Cout / 64 virtual tiles as cmr_wino_tile_lists writes it; order and nlive are
 // read on the device.  Bit-identical to the dense call wherever the live tiles cover every tile whose input halo (the tile dilated by one
 // pixel) is not all zero and y0 is the dense result on an all-zero x.  Served where the dense call runs the wave-specialised kernel.
-extern "C" int cmr_conv3x3_wino_list_nhwc_f32(const float* x, int B, int H, int W, int Cin, const float* u, const float* bias, const float* res,
-                                              float* y, int Cout, float slope, int pool, const int* order, const int* nlive, const float* y0,
-                                              int cu_budget, int slices, hipStream_t stream) {
+// nend (device, may be null = every tile): the tiles order[*nend .. ntiles) of y are NOT WRITTEN (cmr_wino_tile_lists_staged: the tiles no
+// live tile of the next list launch reads).
+extern "C" int cmr_conv3x3_wino_list_nend_nhwc_f32(const float* x, int B, int H, int W, int Cin, const float* u, const float* bias,
+                                                   const float* res, float* y, int Cout, float slope, int pool, const int* order,
+                                                   const int* nlive, const int* nend, const float* y0, int cu_budget, int slices,
+                                                   hipStream_t stream) {
   CMR_REQUIRE(x && u && y && order && nlive && B > 0 && H > 0 && W > 0 && Cin % 32 == 0 && Cin >= 32 && Cout % 64 == 0 && Cout >= 64);
   CMR_REQUIRE(cmr_aligned16(x) && cmr_aligned16(u) && cmr_aligned16(y) && (!bias || cmr_aligned16(bias)) && (!res || cmr_aligned16(res)) &&
               (!y0 || cmr_aligned16(y0)));
@@ -1092,5 +1198,12 @@ extern "C" int cmr_conv3x3_wino_list_nhwc_f32(const float* x, int B, int H, int 
   CMR_REQUIRE(2 * ntiles64 < 0x7fffffff);
   if (!(CMR_WINO_WS && Cin >= 64 && ntiles64 >= 200 && slope >= 0.f && slope <= 1.f)) return CMR_EUNSUPPORTED;
   const WinoArgs a{x, B, H, W, Cin, u, bias, res, nullptr, y, Cout, slope, pool};
-  return launch_wino_ws_t<0, true>(a, tiles_x, tiles_y, ntiles64, cu_budget, slices, stream, WsList{order, nlive, y0});
+  return launch_wino_ws_t<0, true>(a, tiles_x, tiles_y, ntiles64, cu_budget, slices, stream, WsList{order, nlive, y0, nend});
+}
+
+extern "C" int cmr_conv3x3_wino_list_nhwc_f32(const float* x, int B, int H, int W, int Cin, const float* u, const float* bias, const float* res,
+                                              float* y, int Cout, float slope, int pool, const int* order, const int* nlive, const float* y0,
+                                              int cu_budget, int slices, hipStream_t stream) {
+  return cmr_conv3x3_wino_list_nend_nhwc_f32(x, B, H, W, Cin, u, bias, res, y, Cout, slope, pool, order, nlive, nullptr, y0, cu_budget, slices,
+                                             stream);
 }

@@ -48,7 +48,7 @@ class _ObsContext:
         # state of the direct projected-half path (materialize_state_2d=False): the map itself, its counts and every point's cell of the
         # previous observation; created on first use
         self.proj = self.proj_cnt = self.proj_cell = None
-        self.reach, self.obs_serial = None, 0     # tile marks of the direct path's observations (zeroed once, cleared by their consumer)
+        self.reach, self.obs_serial = None, 0     # tile marks of the direct path's observations, two or four maps (zeroed once, cleared by their consumer)
         self.agent_cache = {}     # CMRAgent keeps the image half of its first conv here (constant over the steps of THIS registration)
         self.dirty = False        # True between a scatter and its finalize: an interrupted call must not leak accumulators
 
@@ -125,7 +125,10 @@ def observation_from_a_pose(data, RT, materialize_state_2d=True):
             ctx.proj_cell = torch.full((B * N,), -1, dtype=torch.int32, device=dev)
         sparse = CMRAgent.sparse_obs()
         if sparse and ctx.reach is None:
-            ctx.reach = torch.zeros((2, B, (h + 7) // 8, (w + 15) // 16), dtype=torch.uint8, device=dev)
+            # two maps on the tile grid of the agent's full-resolution stage and, where that grid halves evenly (h, w, h / 2, w / 2 even),
+            # two more on the half-resolution stage's behind them: four maps in one flat buffer (ops.observation_proj)
+            nt, nt1 = ops.reach_tiles(B, h, w)
+            ctx.reach = torch.zeros((2 * nt + (2 * nt1 if h % 4 == 0 and w % 4 == 0 else 0),), dtype=torch.uint8, device=dev)
         ops.observation_proj(ctx.pc4, ctx.feat, ctx.overlap, RT.contiguous(), ctx.K, ctx.mean4, B, N, h, w, ctx.proj, ctx.proj_cnt,
                              ctx.proj_cell, state3d, reach=ctx.reach if sparse else None)
         # which convolution tiles the points of THIS observation can reach (CMRAgent.SPARSE_OBS): the agent turns the marks into tile

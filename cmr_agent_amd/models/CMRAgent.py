@@ -122,13 +122,18 @@ class CMRAgent(Planned):
     # per registration next to the image half of conv 0 ("Sparse observation").  fp32 evaluation only: the bf16 chain and
     # the training engine run the dense calls.  False: every call is the dense one.
     SPARSE_OBS = True
+    # 2: stage 1 (the two convolutions on the pooled map) runs on lists too, where it has the tiles for it: a tile of its first / second
+    # convolution no point comes within 4 / 6 cells of is that of the empty projection as well, and the first convolution of either stage
+    # stops copying the tiles its successor does not read (ops.wino_tile_lists_staged).  1: stage 0 only, every skipped tile copied.
+    SPARSE_OBS_STAGES = 2
 
     @classmethod
     def sparse_obs(cls):
         return cls.SPARSE_OBS and ops.WINOGRAD and not ops.CONV_BF16
 
     def _tile_lists(self, cache, proj, c, u0, u1):
-        """-> ((order, nlive) of conv 0, of conv 1) of stage 0 for the observation `proj` belongs to, or None where stage 0 runs dense."""
+        """-> ((order, nlive) of conv 0, of conv 1) of stage 0 for the observation `proj` belongs to, or None where stage 0 runs dense.
+        cache["lists_staged"]: the four lists of ops.wino_tile_lists_staged where stage 1 is served too, else None."""
         mark = cache.get("reach")
         if mark is None or not self.sparse_obs() or self.training or mark[1] is not proj or u0 is None or u1 is None:
             return None
@@ -136,7 +141,16 @@ class CMRAgent(Planned):
         if h % 2 or w % 2 or not (ops.wino_list_served(B, h, w, cin, c) and ops.wino_list_served(B, h, w, c, c)):
             return None
         if cache.get("lists_of") != mark[2]:                  # once per observation: the list kernel clears the marks
-            cache["lists"] = (c, ops.wino_tile_lists(mark[0], B, h, w, c, c))
+            nt, nt1 = ops.reach_tiles(B, h, w)
+            staged = (self.SPARSE_OBS_STAGES >= 2 and mark[0].numel() == 2 * nt + 2 * nt1 and h % 4 == 0 and w % 4 == 0
+                      and ops.wino_list_served(B, h // 2, w // 2, c, c))
+            if staged:
+                l4 = ops.wino_tile_lists_staged(mark[0], B, h, w, c, c)
+                cache["lists"] = (c, (l4[0][:2], l4[1]))
+                cache["lists_staged"] = l4
+            else:
+                cache["lists"] = (c, ops.wino_tile_lists(mark[0].view(-1)[:2 * nt], B, h, w, c, c))
+                cache["lists_staged"] = None
             cache["lists_of"] = mark[2]
         width, lists = cache["lists"]
         return lists if width == c else None
@@ -145,6 +159,7 @@ class CMRAgent(Planned):
         p = self.plan()
         c = 2 * self.config.embed_dim
         x = state2d
+        staged = None                                        # stage 1 on lists: its two lists, from stage 0
         for stage, ((wa, ba, ua), (wb, bb, ub)) in enumerate(p["convs"]):
             if stage == 0 and split is not None:
                 # split = (image half, projected half, per-registration cache): the cache dict belongs to the
@@ -167,10 +182,25 @@ class CMRAgent(Planned):
                         cache["x2_0"] = ops.conv3x3(cache["x1_0"], wb, bb, c, 1, SLOPE, pool=2, u=ub)
                         cache["tag0"] = tag
                     (o1, n1), (o2, n2) = lists
-                    x = ops.conv3x3_wino_list(proj, up, None, c, SLOPE, o1, n1, cache["x1_0"], res=cache["val"])
+                    l4 = cache.get("lists_staged") if self.SPARSE_OBS_STAGES >= 2 else None
+                    if l4 is not None and p["convs"][1][0][2] is not None and p["convs"][1][1][2] is not None:
+                        if cache.get("tag1") != tag:           # the image-only maps of stage 1, next to those of stage 0
+                            (w2, b2, u2), (w3, b3, u3) = p["convs"][1]
+                            cache["x3_0"] = ops.conv3x3(cache["x2_0"], w2, b2, c, 1, SLOPE, u=u2)
+                            cache["x4_0"] = ops.conv3x3(cache["x3_0"], w3, b3, c, 1, SLOPE, pool=2, u=u3)
+                            cache["tag1"] = tag
+                        staged = (l4[2], l4[3], cache["x3_0"], cache["x4_0"])
+                    # x1 is read by the next launch alone, on its live tiles and their halo: with the staged lists the rest is not written
+                    x = ops.conv3x3_wino_list(proj, up, None, c, SLOPE, o1, n1, cache["x1_0"], res=cache["val"],
+                                              nend=l4[0][2] if l4 is not None else None)
                     x = ops.conv3x3_wino_list(x, ub, bb, c, SLOPE, o2, n2, cache["x2_0"], pool=2)
                     continue
                 x = ops.conv3x3(proj, wp, None, c, 1, SLOPE, res=cache["val"], u=up, out_bf16=True)
+            elif stage == 1 and staged is not None:
+                (o3, n3, e3), (o4, n4), x3_0, x4_0 = staged
+                x = ops.conv3x3_wino_list(x, ua, ba, c, SLOPE, o3, n3, x3_0, nend=e3)
+                x = ops.conv3x3_wino_list(x, ub, bb, c, SLOPE, o4, n4, x4_0, pool=2)
+                continue
             else:
                 x = ops.conv3x3(x, wa, ba, c, 1, SLOPE, u=ua, out_bf16=True)
             # every map of the chain only feeds the next convolution (bf16 mode: stored as bf16); the last one goes to the heads in fp32

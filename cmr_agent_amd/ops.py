@@ -247,9 +247,10 @@ def wino_list_served(B, H, W, cin, cout):
     return WINOGRAD and cin >= 64 and cin % 32 == 0 and cout % 64 == 0 and ((W + 15) // 16) * ((H + 7) // 8) * B * (cout // 64) >= max(200, WINO_MIN_TILES)
 
 
-def conv3x3_wino_list(x, u, bias, cout, slope, order, nlive, y0, res=None, pool=1):
+def conv3x3_wino_list(x, u, bias, cout, slope, order, nlive, y0, res=None, pool=1, nend=None):
     """conv3x3_wino on the virtual tiles order[:nlive] (device tensors, see wino_tile_lists); the other tiles are copied from y0, the result
-    on an all-zero x -- or, with y0 None (pool 1), computed as act(bias + res), which IS that result."""
+    on an all-zero x -- or, with y0 None (pool 1), computed as act(bias + res), which IS that result.  nend (device int32 [1], see
+    wino_tile_lists_staged): only order[nlive:nend] are copied; the tiles behind are left as torch.empty made them."""
     B, H, W, cin = x.shape
     hp, wp = (H // 2, W // 2) if pool == 2 else (H, W)
     ntiles = ((W + 15) // 16) * ((H + 7) // 8) * B * (cout // 64)
@@ -257,10 +258,16 @@ def conv3x3_wino_list(x, u, bias, cout, slope, order, nlive, y0, res=None, pool=
         raise ValueError("conv3x3_wino_list: bad operand layout")
     if order.dtype != torch.int32 or nlive.dtype != torch.int32 or order.numel() != ntiles or nlive.numel() != 1 or not order.is_contiguous():
         raise ValueError("conv3x3_wino_list: order must be int32 [%d] and nlive int32 [1]" % ntiles)
+    if nend is not None and (nend.dtype != torch.int32 or nend.numel() != 1):
+        raise ValueError("conv3x3_wino_list: nend must be int32 [1]")
     if (y0 is not None and (tuple(y0.shape) != (B, hp, wp, cout) or not y0.is_contiguous() or y0.dtype != f32)) or (
             res is not None and (tuple(res.shape) != (B, H, W, cout) or not res.is_contiguous() or res.dtype != f32)):
         raise ValueError("conv3x3_wino_list: y0 / res of the wrong shape")
     y = torch.empty((B, hp, wp, cout), dtype=f32, device=x.device)
+    if nend is not None:
+        _lib.call("cmr_conv3x3_wino_list_nend_nhwc_f32", _p(x), B, H, W, cin, _p(u), _p(bias), _p(res), _p(y), cout, float(slope), pool,
+                  _p(order), _p(nlive), _p(nend), _p(y0), _cu_budget(), _slices(), _stream())
+        return y
     _lib.call("cmr_conv3x3_wino_list_nhwc_f32", _p(x), B, H, W, cin, _p(u), _p(bias), _p(res), _p(y), cout, float(slope), pool, _p(order),
               _p(nlive), _p(y0), _cu_budget(), _slices(), _stream())
     return y
@@ -277,6 +284,23 @@ def wino_tile_lists(reach, B, H, W, cout1, cout2):
     o1, o2, l1, l2 = buf[:n1], buf[n1:n1 + n2], buf[n1 + n2:n1 + n2 + 1], buf[n1 + n2 + 4:n1 + n2 + 5]
     _lib.call("cmr_wino_tile_lists", _p(reach), reach.data_ptr() + nt, B, H, W, cout1, cout2, _p(o1), _p(l1), _p(o2), _p(l2), _stream())
     return (o1, l1), (o2, l2)
+
+
+def wino_tile_lists_staged(reach, B, H, W, cout0, cout1):
+    """reach: the four maps observation_proj marks, flat uint8 (2 full-resolution maps, then 2 of the half-resolution stage; cleared here)
+    -> ((order, nlive, nend) of stage 0's first convolution, (order, nlive) of its second, the same two of stage 1).  A first list is
+    live | copy | rest (see cmr_wino_tile_lists_staged): nend = live + copy ends what its convolution has to write."""
+    nt, nt1 = reach_tiles(B, H, W)
+    if reach.dtype != torch.uint8 or reach.numel() != 2 * nt + 2 * nt1 or not reach.is_contiguous() or H % 2 or W % 2:
+        raise ValueError("wino_tile_lists_staged: reach must be uint8 [2 * %d + 2 * %d] and H, W even" % (nt, nt1))
+    n0, n1 = nt * (cout0 // 64), nt1 * (cout1 // 64)
+    buf = torch.empty((2 * n0 + 2 * n1 + 8,), dtype=torch.int32, device=reach.device)
+    o = [buf[:n0], buf[n0:2 * n0], buf[2 * n0:2 * n0 + n1], buf[2 * n0 + n1:2 * n0 + 2 * n1]]
+    c = buf[2 * n0 + 2 * n1:]
+    a = reach.data_ptr()
+    _lib.call("cmr_wino_tile_lists_staged", a, a + nt, a + 2 * nt, a + 2 * nt + nt1, B, H, W, cout0, cout1, _p(o[0]), _p(o[1]), _p(o[2]),
+              _p(o[3]), _p(c), _stream())
+    return (o[0], c[0:1], c[1:2]), (o[1], c[2:3]), (o[2], c[3:4], c[4:5]), (o[3], c[5:6])
 
 
 def conv3x3_wino_stats(x, u, bias, cout):
@@ -886,16 +910,28 @@ def observation_finalize(img_feat, acc, cnt, state2d, proj, B, h, w, write_img, 
               int(write_img), int(clear), _stream())
 
 
+def reach_tiles(B, h, w):
+    """(tiles of the full-resolution stage, tiles of the half-resolution stage) of the observation's reach maps"""
+    return B * ((h + 7) // 8) * ((w + 15) // 16), B * ((h // 2 + 7) // 8) * ((w // 2 + 15) // 16)
+
+
 def observation_proj(pc4, feat, overlap_u8, pose, K, mean4, B, N, h, w, proj, cnt, cell, state3d, reach=None):
     """The projected half of the observation maintained in place (see cmr_observation_proj_f32): proj / cnt / cell are the caller's state.
     reach (uint8 [2, B, ceil(h/8), ceil(w/16)], zero before the first call): the tiles within 1 / 2 pixels of a cell hit now are marked in
-    reach[0] / reach[1], for wino_tile_lists."""
+    reach[0] / reach[1], for wino_tile_lists.  With 2 B ceil(h/16) ceil(w/32) more bytes behind them (flat; h, w multiples of 4): the two
+    maps of the half-resolution stage too (footprints dilated by 4 / 6 cells), for wino_tile_lists_staged."""
     if cell.dtype != torch.int32 or cell.numel() != B * N or proj.numel() != B * h * w * 64 or cnt.numel() != B * h * w:
         raise ValueError("observation_proj: state buffers of the wrong shape / dtype")
     if reach is not None:
-        nt = B * ((h + 7) // 8) * ((w + 15) // 16)
-        if reach.dtype != torch.uint8 or reach.numel() != 2 * nt or not reach.is_contiguous():
-            raise ValueError("observation_proj: reach must be uint8 [2, %d]" % nt)
+        nt, nt1 = reach_tiles(B, h, w)
+        staged = reach.numel() == 2 * nt + 2 * nt1 and h % 4 == 0 and w % 4 == 0
+        if reach.dtype != torch.uint8 or not (reach.numel() == 2 * nt or staged) or not reach.is_contiguous():
+            raise ValueError("observation_proj: reach must be uint8 [2, %d] (+ [2, %d])" % (nt, nt1))
+        if staged:
+            a = reach.data_ptr()
+            _lib.call("cmr_observation_proj_reach_staged_f32", _p(pc4), _p(feat), _p(overlap_u8), _p(pose), _p(K), _p(mean4), _p(proj), _p(cnt),
+                      _p(cell), _p(state3d), B, N, h, w, a, a + nt, a + 2 * nt, a + 2 * nt + nt1, _stream())
+            return
         _lib.call("cmr_observation_proj_reach_f32", _p(pc4), _p(feat), _p(overlap_u8), _p(pose), _p(K), _p(mean4), _p(proj), _p(cnt), _p(cell),
                   _p(state3d), B, N, h, w, _p(reach), reach.data_ptr() + nt, _stream())
         return

@@ -113,6 +113,20 @@ int cmr_conv3x3_wino_list_nhwc_f32(const float* x, int B, int H, int W, int Cin,
  * tiles; *nlive_m = live virtual tiles.  Both maps are cleared for the next observation.  One launch. */
 int cmr_wino_tile_lists(uint8_t* reach1, uint8_t* reach2, int B, int H, int W, int Cout1, int Cout2, int* order1, int* nlive1,
                         int* order2, int* nlive2, hipStream_t stream);
+/* cmr_conv3x3_wino_list_nhwc_f32 that copies only the tiles order[*nlive .. *nend) (nend on the device; null: every tile) and leaves the
+ * tiles order[*nend .. ntiles) of y UNWRITTEN: for a map whose only reader is a list launch that reads none of their pixels. */
+int cmr_conv3x3_wino_list_nend_nhwc_f32(const float* x, int B, int H, int W, int Cin, const float* u, const float* bias, const float* res,
+                                        float* y, int Cout, float slope, int pool, const int* order, const int* nlive, const int* nend,
+                                        const float* y0, int cu_budget, int slices, hipStream_t stream);
+/* The lists of two STAGES of two chained convolutions each -- stage 0 on H x W maps with Cout0 channels, stage 1 on its 2 x 2 pooled output
+ * (H / 2 x W / 2, Cout1 channels; H, W even) -- from the four byte maps cmr_observation_proj_reach_staged_f32 marks (reach1 / reach2: stage
+ * 0's first / second convolution, reach3 / reach4: stage 1's).  The second convolution's list of a stage (order2, order4) is
+ * cmr_wino_tile_lists's: marked tiles ascending, then the others.  The first one's (order1, order3) has three parts, each ascending: the
+ * marked tiles ("live"), the unmarked ones with a tile marked for the SECOND convolution in their 3 x 3 tile neighbourhood of the same
+ * sample ("copy": the second convolution reads a one-pixel halo around its live tiles), the rest (read by nobody).  counts [6] = live,
+ * live + copy of order1 and live of order2, then the same of order3 / order4, in virtual tiles.  The four maps are cleared.  One launch. */
+int cmr_wino_tile_lists_staged(uint8_t* reach1, uint8_t* reach2, uint8_t* reach3, uint8_t* reach4, int B, int H, int W, int Cout0, int Cout1,
+                               int* order1, int* order2, int* order3, int* order4, int* counts, hipStream_t stream);
 /* Training forward of a 3x3 convolution that feeds a batch-statistics BatchNorm (models/ImageResNet.py:5-40 under Train_Geo.py:166-174):
  * y = conv(x) + bias as the call above with slope 1, no residual / table / pool, AND the sums the BatchNorm needs, accumulated by the helper
  * waves of the wave-specialised kernel while they finish the output tiles (they wait 25 - 50 % of a launch): part [parts][2][64] = per helper
@@ -846,6 +860,13 @@ int cmr_observation_proj_f32(const float* pc4, const float* feat, const uint8_t*
 int cmr_observation_proj_reach_f32(const float* pc4, const float* feat, const uint8_t* overlap, const float* pose, const float* Kmat,
                                    const float* mean4, float* proj, float* cnt, int32_t* cell, float* state3d, int B, int N, int h, int w,
                                    uint8_t* reach1, uint8_t* reach2, hipStream_t stream);
+/* ... and the reach on the tile grid of the half-resolution stage behind them (two more 3x3 convolutions on the 2 x 2 pooled map; its 8x16
+ * tiles cover 16 x 32 cells): reach3 / reach4 [B][ceil(h / 16)][ceil(w / 32)] (both or neither, with reach1 / reach2; h, w, h / 2, w / 2
+ * even) receive a 1 for every tile whose 16 x 32 footprint dilated by 4 / 6 cells holds a cell hit now.  cmr_wino_tile_lists_staged
+ * consumes and clears all four. */
+int cmr_observation_proj_reach_staged_f32(const float* pc4, const float* feat, const uint8_t* overlap, const float* pose, const float* Kmat,
+                                          const float* mean4, float* proj, float* cnt, int32_t* cell, float* state3d, int B, int N, int h,
+                                          int w, uint8_t* reach1, uint8_t* reach2, uint8_t* reach3, uint8_t* reach4, hipStream_t stream);
 /* environment.py:179-260 (step + euler_angles_to_matrix 'XYZ'), :14-21 (to_disentangled). */
 int cmr_pose_step_f32(float* pose, const int64_t* act_r, const int64_t* act_t, const double* r_steps,
                       const double* t_steps, int B, int six_dof, hipStream_t stream);
