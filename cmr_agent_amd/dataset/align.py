@@ -68,6 +68,35 @@ def write_poses(path, poses):
     np.savetxt(path, np.asarray(poses)[:, :3].reshape(-1, 12), fmt="%.9e")
 
 
+def write_edges(path, edges):
+    """Loop edges (dataset/loops.py) as (i, j, pose [4, 4], dist, rmse, pairs) -> one line each: i j, the upper 3 x 4 of the pose that maps
+    frame i into frame j (row-major, %.9e as write_poses), then dist rmse pairs."""
+    with open(path, "w") as fh:
+        for i, j, pose, dist, rmse, pairs in edges:
+            fh.write("%d %d %s %.9e %.9e %d\n" % (i, j, " ".join("%.9e" % v for v in np.asarray(pose, np.float64)[:3].reshape(-1)), dist, rmse, pairs))
+
+
+def read_edges(path):
+    """The file write_edges writes -> a list of (i, j, pose float64 [4, 4], dist, rmse, pairs); ValueError for anything else."""
+    edges = []
+    with open(path) as fh:
+        for n, line in enumerate(fh):
+            words = line.split()
+            try:
+                if len(words) != 17:
+                    raise ValueError
+                i, j, pairs = int(words[0]), int(words[1]), int(words[16])
+                nums = np.array([float(w) for w in words[2:16]])
+                if not np.isfinite(nums).all() or min(i, j, pairs) < 0:
+                    raise ValueError
+            except ValueError:
+                raise ValueError("%s line %d: need `i j`, 12 numbers of a pose, `dist rmse pairs`" % (path, n + 1))
+            pose = np.eye(4)
+            pose[:3] = nums[:12].reshape(3, 4)
+            edges.append((i, j, pose, float(nums[12]), float(nums[13]), pairs))
+    return edges
+
+
 def on_device(device):
     return torch.device("cuda", torch.cuda.current_device()) if device is None else device
 

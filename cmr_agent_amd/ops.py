@@ -3186,3 +3186,113 @@ def voxel_map_keep(map, mask):
         raise ValueError("%s: mask must be a bool [%d] tensor on the map's device, got %s %s%s" % (
             (who, M) + _got(mask) + (" on %s" % mask.device if torch.is_tensor(mask) else "",)))
     return VoxelMap(*(t[mask] for t in map[:5]), map.origin, map.voxel)
+
+
+# ---- place recognition between scans: ring-and-sector descriptors and their ring-shift match (csrc/scan_descriptor.hip) -----
+SCAN_MAX_RINGS = 64
+SCAN_MAX_SECTORS = 256
+SCAN_MAX_CELLS = 4096               # rings x sectors: the image a workgroup keeps in LDS is 16 KiB at most
+SCAN_MATCH_CALL_BYTES = 1 << 28     # dist and shift of ONE cmr_scan_match_f32 call stay under this; scan_match splits its queries to keep it
+
+
+class ScanDescriptor(collections.namedtuple("ScanDescriptor", "desc binned dropped outside")):
+    """scan_descriptor's result: desc float32 [rings, sectors] = per cell the largest z + height over its rows, 0 when none is above 0;
+    binned = rows that fell into a cell, dropped = rows with a non-finite coordinate, outside = finite rows nearer than min_range or at
+    or beyond max_range.  The three sum to the cloud's rows."""
+
+
+class ScanMatch(collections.namedtuple("ScanMatch", "dist shift")):
+    """scan_match's result: dist float32 [Q, N] = the least column-cosine distance over the ring shifts that count, shift int32 [Q, N] = the
+    lowest shift that reaches it; NaN and -1 where no shift counts and for every candidate at or beyond the query's limit."""
+
+
+def _scan_shape(who, rings, sectors):
+    rings = _int_arg(who, "rings", rings, 1, SCAN_MAX_RINGS)
+    sectors = _int_arg(who, "sectors", sectors, 4, SCAN_MAX_SECTORS)
+    if sectors % 4 or rings * sectors > SCAN_MAX_CELLS:
+        raise ValueError("%s: sectors must be a multiple of 4 and rings x sectors at most %d, got %d x %d" % (who, SCAN_MAX_CELLS, rings, sectors))
+    return rings, sectors
+
+
+def scan_tables(rings, sectors, min_range, max_range):
+    """The two tables cmr_scan_descriptor_f32 reads, computed in float64 and rounded to float32 (numpy): ring_edge2 [rings + 1] = the squared
+    ring edges, sector_dir [sectors / 4 - 1, 2] = (cos, sin) of the sector edges inside the first quadrant."""
+    j = np.arange(rings + 1, dtype=np.float64)
+    k = np.arange(1, sectors // 4, dtype=np.float64) * (2.0 * np.pi / sectors)
+    return ((min_range + (max_range - min_range) * j / rings) ** 2).astype(np.float32), np.stack([np.cos(k), np.sin(k)], 1).astype(np.float32)
+
+
+def scan_descriptor(points, rings=20, sectors=60, max_range=80.0, min_range=0.0, height=2.0):
+    """The ring-and-sector descriptor of one scan (cmr_scan_descriptor_f32; the contract is the header's): the cloud seen from above, cut
+    into `rings` rings between min_range and max_range and `sectors` sectors from the x axis towards y, each cell holding the largest
+    z + height of its rows.  points float32 [N, 3] in the sensor's frame -> ScanDescriptor.  One host read: the three counts."""
+    who = "scan_descriptor"
+    rings, sectors = _scan_shape(who, rings, sectors)
+    max_range = _cloud_scalar(max_range, "max_range")
+    min_range = _f32_arg(who, "min_range", min_range, "be a number in [0, max_range)", 0.0)
+    if not np.float32(min_range) < np.float32(max_range):
+        raise ValueError("%s: min_range must be a number in [0, max_range), got %r with max_range %r" % (who, min_range, max_range))
+    height = _f32_arg(who, "height", height, "be a finite number", -math.inf)
+    points = _cloud_points(points)
+    N, dev = points.shape[0], points.device
+    desc = torch.empty((rings, sectors), dtype=f32, device=dev)
+    if N == 0:
+        return ScanDescriptor(desc.zero_(), 0, 0, 0)
+    edge2, dirs = (torch.from_numpy(t).to(dev) for t in scan_tables(rings, sectors, min_range, max_range))
+    counts = torch.empty((3,), dtype=torch.int64, device=dev)
+    _lib.call("cmr_scan_descriptor_f32", _p(points), 3, N, rings, sectors, _p(edge2), _p(dirs) if sectors > 4 else None, height, _p(desc),
+              _p(counts), _stream())
+    return ScanDescriptor(desc, *(int(v) for v in counts.cpu()))
+
+
+def _scan_batch(who, name, t):
+    if not isinstance(t, torch.Tensor) or t.dtype != f32 or t.dim() != 3:
+        raise ValueError("%s: %s must be a float32 [n, rings, sectors] tensor, got %s %s" % ((who, name) + _got(t)))
+    if not 0 < t.shape[0] <= CLOUD_MAX_ROWS:
+        raise ValueError("%s: %s holds %d descriptors; need 1 to 2^31 - 1" % (who, name, t.shape[0]))
+    if not t.is_cuda:
+        raise ValueError("%s: %s must be a device tensor (there is no CPU path)" % (who, name))
+    return t.contiguous()
+
+
+def scan_match(queries, cands, limit=None, min_cols=None):
+    """Every query descriptor against every candidate at every ring shift (cmr_scan_match_f32; the contract is the header's) -> ScanMatch.
+    queries float32 [Q, R, S], cands float32 [N, R, S]; limit int32 [Q] or None: query q meets the candidates [0, limit[q]) only (a loop
+    search passes the earlier frames); min_cols: a shift counts when that many column pairs are non-empty on both sides (default S // 4).
+    The queries are split so that one call's outputs stay under SCAN_MATCH_CALL_BYTES; the result does not depend on the split."""
+    who = "scan_match"
+    queries, cands = _scan_batch(who, "queries", queries), _scan_batch(who, "cands", cands)
+    if queries.shape[1:] != cands.shape[1:]:
+        raise ValueError("%s: queries are %d x %d, cands %d x %d" % ((who,) + tuple(queries.shape[1:]) + tuple(cands.shape[1:])))
+    R, S = _scan_shape(who, queries.shape[1], queries.shape[2])
+    min_cols = _int_arg(who, "min_cols", S // 4 if min_cols is None else min_cols, 1, S)
+    Q, N, dev = queries.shape[0], cands.shape[0], queries.device
+    if cands.device != dev:
+        raise ValueError("%s: queries and cands must be on one device" % who)
+    if limit is not None:
+        if not isinstance(limit, torch.Tensor) or limit.dtype != torch.int32 or limit.dim() != 1:
+            raise ValueError("%s: limit must be an int32 [Q] tensor or None, got %s %s" % ((who,) + _got(limit)))
+        _cloud_family(who, dev, None, "limit must be on the device of queries", ("queries hold", queries, "limit", limit))
+        limit = limit.contiguous()
+        if Q and (int(limit.min()) < 0 or int(limit.max()) > N):
+            raise ValueError("%s: limit must lie in [0, %d] (the candidates), got [%d, %d]" % (who, N, int(limit.min()), int(limit.max())))
+    dist = torch.empty((Q, N), dtype=f32, device=dev)
+    shift = torch.empty((Q, N), dtype=torch.int32, device=dev)
+    step = max(1, SCAN_MATCH_CALL_BYTES // (8 * N))
+    lib = _lib.load()
+    for a in range(0, Q, step):
+        b = min(Q, a + step)
+        nb = lib.cmr_scan_match_workspace_bytes(b - a, N, R, S)
+        ws = _ws(nb, dev)
+        _lib.call("cmr_scan_match_f32", _p(queries[a:b]), b - a, _p(cands), N, R, S, _p(limit[a:b]) if limit is not None else None, min_cols,
+                  _p(dist[a:b]), _p(shift[a:b]), _p(ws), nb, _stream())
+    return ScanMatch(dist, shift)
+
+
+def scan_shift_yaw(shift, sectors):
+    """The heading a ring shift stands for: -shift 2 pi / sectors wrapped into (-pi, pi] (python float, or numpy float64 for an array of
+    shifts).  Turning the candidate's points by it about z brings them onto the query's: p_query ~ Rz(yaw) p_candidate."""
+    sectors = _int_arg("scan_shift_yaw", "sectors", sectors, 1, 1 << 30)
+    k = np.mod(-np.asarray(shift, dtype=np.int64), sectors)
+    yaw = np.where(2 * k > sectors, k - sectors, k) * (2.0 * np.pi / sectors)
+    return float(yaw) if yaw.ndim == 0 else yaw

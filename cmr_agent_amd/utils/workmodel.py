@@ -309,6 +309,13 @@ WORK = {
     # (8 B).  The walk is not counted: the number of cells a ray steps through and of lookups it makes is data (20 to 800 per ray on a
     # driving scan), each lookup a binary search whose reads hit the cache, each count found one 4-byte atomic.
     "cmr_voxel_map_rays_f32": lambda a: (0, a["N"] * 12 + a["M"] * 16),
+    # DESIGN.md 4ak.  Descriptor: latency-class, a row read (12 B) and the image written (4 B per cell); the comparisons are not counted.
+    # Match: per (query, candidate) and shift S columns of R products and R sums and one sum per column -- unfused by contract, so a
+    # multiply-add is two operations here as on the device; a `limit` that halves the pairs is not seen (the model prices all Q x N).
+    # Bytes: both sides read once, their unit columns written and read once (tiles re-read from cache are not counted), 8 B per output.
+    "cmr_scan_descriptor_f32": lambda a: (0, a["N"] * 12 + a["R"] * a["S"] * 4),
+    "cmr_scan_match_f32": lambda a: (float(a["Q"]) * a["N"] * (2 * a["R"] * a["S"] * a["S"] + a["S"] * a["S"]),
+                                     3 * F * (a["Q"] + a["N"]) * a["R"] * a["S"] + 8 * a["Q"] * a["N"]),
 }
 
 # Multiplies the kernel ISSUES on the matrix cores per algorithmic multiply: F(2x2,3x3) Winograd computes 2x2 outputs with 16

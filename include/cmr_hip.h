@@ -1577,6 +1577,49 @@ int cmr_voxel_map_rays_f32(const int64_t* keys, int64_t M, float ox, float oy, f
                            int64_t N, const float* pose, int start_margin, int end_margin, int max_cells, int32_t* crossed, int32_t* hits,
                            int64_t* counts, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+/* ---- place recognition between scans: ring-and-sector descriptors and their ring-shift match (csrc/scan_descriptor.hip) ----
+ * Port extension.  Scan Context (Kim & Kim, IROS 2018) restated so that every integer follows from stated fp32 operations: no atan2, and
+ * every operation below is rounded on its own (no fused operation).  1 <= R <= 64 rings, 4 <= S <= 256 sectors, S % 4 = 0, R S <= 4096;
+ * any other (R, S) returns CMR_EUNSUPPORTED (-3).  The library keeps no state.
+ *
+ * cmr_scan_descriptor_f32: points [N][ld >= 3], 0 < N < 2^31 -> desc float [R][S] and counts int64 [3] = {binned, dropped, outside}, which
+ * sum to N.  Two device tables, which the caller computes in fp64 and rounds to fp32:
+ *   ring_edge2  float [R + 1]:        ring_edge2[j] = (min_range + (max_range - min_range) j / R)^2;
+ *   sector_dir  float [S / 4 - 1][2]: sector_dir[k - 1] = (c_k, s_k) = (cos, sin)(k 2 pi / S), k = 1 .. S / 4 - 1 (may be null when S = 4).
+ * Per row (x, y, z):
+ *   dropped   x, y or z is not finite;
+ *   ring      else r2 = fp32(fp32(x x) + fp32(y y));  the row is OUTSIDE when r2 < ring_edge2[0] or r2 >= ring_edge2[R];  otherwise its ring
+ *             is the number of j in 1 .. R - 1 with r2 >= ring_edge2[j];
+ *   quadrant  (u, v) = the row turned into the first quadrant by exact swaps and negations:  q = 0: x > 0 and y >= 0, (x, y);
+ *             q = 1: x <= 0 and y > 0, (y, -x);  q = 2: x < 0 and y <= 0, (-x, -y);  q = 3: x >= 0 and y < 0, (-y, x);  x = y = 0: q = 0, (0, 0);
+ *   sector    q S / 4 + m,  m = the number of k in 1 .. S / 4 - 1 with fp32(v c_k) >= fp32(u s_k);
+ *   value     fp32(z + height)  (height: the sensor's height above the ground, finite);
+ *   binned    every row that is neither dropped nor outside.
+ * A cell of desc holds the largest value over its binned rows, and 0 when none of them is above 0: desc is zeroed by the call, then an
+ * integer atomic max of the values' bit patterns (those of floats above 0 order like integers), per workgroup in LDS and then into desc;
+ * the counts are integer atomic sums.  All of it is order free: two calls agree bit for bit.  Ring and sector are counts of comparisons:
+ * they lie in [0, R) and [0, S) whatever the rows and the tables hold, and no store leaves desc[0, R S) and counts[0, 3).
+ *
+ * cmr_scan_match_f32: queries float [Q][R][S] against cands float [N][R][S] (0 < Q, N < 2^31; values taken as finite) -> dist float [Q][N],
+ * shift int32 [Q][N].  limit int32 [Q] or null: query q is compared with the candidates [0, limit[q]) only, 0 <= limit[q] <= N (null: all N;
+ * a value outside that range acts as the nearer end of it).  1 <= min_cols <= S.
+ *   unit columns  per descriptor and column  n2 = sum over r of fp32(a_r a_r),  from 0 in ring order, every sum rounded;  the column is EMPTY
+ *                 when n2 == 0;  otherwise e_r = fp32(a_r / sqrtf(n2)),  square root and division correctly rounded;
+ *   shift k       0 .. S - 1: over j = 0 .. S - 1 in order, query column j meets candidate column (j + k) mod S;  when neither is empty
+ *                 dot = sum over r of fp32(eq_r ec_r)  from 0 in ring order, every sum rounded, then  sum = fp32(sum + dot)  and  cnt += 1;
+ *                 the shift COUNTS when cnt >= min_cols, and its distance is then  fp32(1 - fp32(sum / fp32(cnt)));
+ *   outputs       the least distance over the shifts that count and the lowest such shift on equal distances (a distance that is NaN, which
+ *                 finite descriptors never give, is passed over);  NaN and -1 when no shift counts, and for every candidate at or beyond
+ *                 limit[q].
+ * Every output is written once, by the thread that owns it, with a plain store, and the order of every sum is the one above whatever the
+ * tiling: two calls agree bit for bit.  Query and candidate indices are guarded at the stores: no store leaves dist, shift and the
+ * workspace.  Workspace of cmr_scan_match_workspace_bytes(Q, N, R, S) (the unit columns and the empty flags of both sides), 16-byte aligned. */
+int cmr_scan_descriptor_f32(const float* points, int64_t ld, int64_t N, int R, int S, const float* ring_edge2, const float* sector_dir,
+                            float height, float* desc, int64_t* counts, hipStream_t stream);
+int64_t cmr_scan_match_workspace_bytes(int64_t Q, int64_t N, int R, int S);
+int cmr_scan_match_f32(const float* queries, int64_t Q, const float* cands, int64_t N, int R, int S, const int32_t* limit, int min_cols,
+                       float* dist, int32_t* shift, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,361 @@
+"""CPU tier of place recognition between scans (ops.scan_descriptor / ops.scan_match / ops.scan_shift_yaw, csrc/scan_descriptor.hip,
+dataset/loops.py): the numpy restatement of scan_descriptor_reference.py against an independent float64 statement and
+against properties that hold exactly, the boundary behaviour of the match, the host logic of the wrappers and of the command, and the
+synthetic drive the loop search is tested on.  No GPU."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import cloud_icp_reference as I
+import scan_descriptor_reference as D
+from cmr_agent_amd import _lib, ops
+from cmr_agent_amd.dataset import align, loops
+
+F32 = np.float32
+SEED = D.DRIVE_SEED
+RS = ((1, 4), (3, 4), (2, 8), (8, 24), (20, 60), (64, 64), (16, 256))
+
+
+def cloud(seed, n=4000, reach=30.0):
+    rng = np.random.default_rng(seed)
+    return np.concatenate([rng.uniform(-reach, reach, (n, 2)), rng.uniform(-3, 6, (n, 1))], 1).astype(F32)
+
+
+# ---- the restatement against float64 ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("R,S", RS)
+def test_bins_agree_with_float64_away_from_the_edges(R, S):
+    scenes = [cloud(1), cloud(2, reach=1.0), D.drive(SEED)["frames"][0][:3].T, D.drive(SEED)["frames"][17][:3].T]
+    for pts in scenes:
+        a, b = D.rows(pts, R, S, 0.5, 25.0), D.rows64(pts, R, S, 0.5, 25.0)
+        ok = ~b["near"]
+        assert b["near"].mean() <= 0.01, b["near"].mean()
+        assert np.array_equal(a["state"][ok], b["state"][ok])
+        binned = ok & (a["state"] == D.BINNED)
+        assert binned.sum() > 100 and np.array_equal(a["ring"][binned], b["ring"][binned]) and np.array_equal(a["sector"][binned], b["sector"][binned])
+        assert a["ring"].min() >= 0 and a["ring"].max() < R and a["sector"].min() >= 0 and a["sector"].max() < S
+    # rows ON an edge are where the two may differ, and they are flagged
+    on = F32([[5.0, 0.0, 0.0], [0.0, 7.0, 0.0], [-3.0, 0.0, 0.0], [0.0, 0.0, 1.0], [25.0, 0.0, 0.0]])
+    assert D.rows64(on, 8, 24, 0.0, 25.0)["near"].all()
+
+
+def test_tables_are_float64_rounded_once():
+    e2, dirs = D.tables(20, 60, 0.0, 80.0)
+    assert e2.dtype == dirs.dtype == F32 and e2.shape == (21,) and dirs.shape == (14, 2) and e2[0] == 0 and e2[20] == 6400 and e2[1] == 16
+    assert dirs[0, 0] == F32(np.cos(2 * np.pi / 60)) and dirs[13, 1] == F32(np.sin(14 * 2 * np.pi / 60))
+    assert D.tables(3, 4, 0.0, 10.0)[1].shape == (0, 2)
+    a, b = ops.scan_tables(20, 60, 0.0, 80.0)                        # the wrapper's tables are the restatement's, bit for bit
+    assert np.array_equal(a, e2) and np.array_equal(b, dirs) and a.dtype == b.dtype == F32
+    a, b = ops.scan_tables(64, 64, 1.5, 33.3)
+    assert np.array_equal(a, D.tables(64, 64, 1.5, 33.3)[0]) and np.array_equal(b, D.tables(64, 64, 1.5, 33.3)[1])
+
+
+# ---- exact properties --------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("R,S", RS)
+def test_a_quarter_turn_rolls_the_descriptor_by_a_quarter(R, S):
+    pts = np.concatenate([cloud(5), F32([[3, 0, 1], [0, 3, 1], [-3, 0, 1], [0, -3, 1], [2, 2, 1], [-2, 2, 1]])])      # rows on the axes too
+    turned = np.stack([-pts[:, 1], pts[:, 0], pts[:, 2]], 1)           # (x, y) -> (-y, x): exact
+    a, ca = D.describe(pts, R, S, 0.0, 25.0)
+    b, cb = D.describe(turned, R, S, 0.0, 25.0)
+    assert ca == cb and ca[0] > 1000 and a.any() and np.array_equal(np.roll(a, S // 4, 1), b)
+    # the row at the origin does not turn: q = 0, (u, v) = (0, 0), every comparison true
+    w = D.rows(F32([[0, 0, 2], [-0.0, 0.0, 2]]), R, S, 0.0, 25.0)
+    assert w["sector"].tolist() == [S // 4 - 1] * 2 and w["ring"].tolist() == [0, 0] and w["state"].tolist() == [D.BINNED] * 2
+
+
+def test_descriptor_by_hand():
+    pts = F32([[1, 0, 0], [0, 1, 1], [-1, 0, 2], [0, -1, 3], [0, 0, 5]])
+    desc, counts = D.describe(pts, 3, 4, 0.0, 10.0, 0.5)
+    assert desc[0].tolist() == [5.5, 1.5, 2.5, 3.5] and not desc[1:].any() and counts == (5, 0, 0)
+    # dropped and outside rows, a ring edge (r2 >= edge goes up), values at or below 0, the largest value wins
+    pts = F32([[np.nan, 0, 0], [0, np.inf, 0], [0, 0, -np.inf], [10, 0, 1], [0, -12, 1], [2e19, 2e19, 1], [5, 0, -2.0], [5, 0, -0.5], [-5, 0, 1], [-5.5, -0.1, 3],
+               [-5.2, -0.1, 2]])
+    desc, counts = D.describe(pts, 2, 4, 0.0, 10.0, 0.5)
+    assert counts == (5, 3, 3) and desc[1].tolist() == [0.0, 0.0, 3.5, 0.0] and not desc[0].any()
+    desc, counts = D.describe(pts, 2, 4, 6.0, 10.0, 0.5)              # an inner radius: the rows at 5 m are outside too
+    assert counts == (0, 3, 8) and not desc.any()
+
+
+def test_match_of_a_descriptor_with_itself_and_with_its_rolls():
+    for R, S in ((3, 4), (8, 24), (20, 60)):
+        d, _ = D.describe(cloud(7), R, S, 0.0, 30.0)
+        assert (np.count_nonzero(d, axis=0) > 0).all()
+        rolls = np.stack([np.roll(d, k, 1) for k in range(S)])          # candidate k: column j of it is the query's column j - k
+        dist, shift = D.match(d[None], rolls)
+        assert shift[0].tolist() == list(range(S)) and (np.abs(dist) <= 2.0 ** -20).all()
+        dist, shift = D.match(rolls, d[None])                           # the query rolled by k: shift (S - k) mod S
+        assert shift[:, 0].tolist() == [(S - k) % S for k in range(S)] and (np.abs(dist) <= 2.0 ** -20).all()
+
+
+def test_shift_and_yaw_of_a_turned_scan():
+    assert abs(np.degrees(ops.scan_shift_yaw(57, 60)) - 18.0) < 1e-12
+    assert ops.scan_shift_yaw(0, 60) == 0.0 and ops.scan_shift_yaw(30, 60) == np.pi and ops.scan_shift_yaw(29, 60) < 0 < ops.scan_shift_yaw(31, 60)
+    assert np.allclose(np.degrees(ops.scan_shift_yaw(np.array([1, 59, 15, 45]), 60)), [-6, 6, -90, 90])
+    for bad in (0, -4, 2.5, None):
+        with pytest.raises(ValueError, match="sectors must be an integer"):
+            ops.scan_shift_yaw(3, bad)
+    # the candidate is the query's scan from a sensor turned by +18 degrees about its own z: its rows are the query's turned by -18
+    query = D.drive(SEED)["frames"][2][:3].T.astype(np.float64)
+    cand = (query @ D.rz(np.radians(-18.0))[:3, :3].T).astype(F32)
+    a, b = (D.describe(p, 20, 60, 0.0, 25.0)[0] for p in (query, cand))
+    dist, shift = D.match(a[None], b[None])
+    assert shift[0, 0] == 57 and dist[0, 0] < 0.02
+    back = cand.astype(np.float64) @ D.rz(ops.scan_shift_yaw(57, 60))[:3, :3].T              # p_query ~ Rz(yaw) p_candidate
+    assert np.abs(back - query).max() < 1e-4
+    assert np.allclose(loops.shift_start(57, 60), D.rz(np.radians(-18.0)))
+
+
+# ---- boundary behaviour of the match ------------------------------------------------------------------------------------------------------------
+def test_match_boundaries():
+    R, S = 2, 8
+    rng = np.random.default_rng(2)
+    q = rng.uniform(0.5, 2, (R, S)).astype(F32)
+    c = q.copy()
+    c[:, 5:] = 0                                                        # three empty columns in the candidate
+    dist, shift, every = D.match(q[None], c[None], min_cols=5, all_shifts=True)
+    assert shift[0, 0] == 0 and abs(dist[0, 0]) <= 2.0 ** -20 and not np.isnan(every).any()       # every shift pairs the 5 full columns
+    assert np.isnan(D.match(q[None], c[None], min_cols=6)[0]).all() and D.match(q[None], c[None], min_cols=6)[1][0, 0] == -1
+    q2 = q.copy()
+    q2[:, :4] = 0                                                       # query columns 4-7, candidate columns 0-4
+    _, _, every = D.match(q2[None], c[None], min_cols=1, all_shifts=True)
+    pairs = [sum(1 for j in range(4, 8) if (j + k) % S < 5) for k in range(S)]
+    assert pairs == [1, 1, 2, 3, 4, 4, 3, 2]
+    for m in range(1, 6):
+        _, _, every = D.match(q2[None], c[None], min_cols=m, all_shifts=True)
+        assert [not np.isnan(every[k, 0, 0]) for k in range(S)] == [p >= m for p in pairs]
+    # nothing counts: an all-empty side
+    z = np.zeros((R, S), F32)
+    for a, b in ((z, q), (q, z), (z, z)):
+        dist, shift = D.match(a[None], b[None], min_cols=1)
+        assert np.isnan(dist[0, 0]) and shift[0, 0] == -1
+    # equal distances go to the lowest shift: every column the same, and a pattern of period 4 in 8 columns
+    same = np.tile(q[:, :1], (1, S))
+    assert D.match(same[None], same[None])[1][0, 0] == 0
+    period = np.tile(q[:, :4], (1, 2))
+    dist, shift, every = D.match(period[None], np.roll(period, 1, 1)[None], all_shifts=True)
+    assert shift[0, 0] == 1 and D.bits(every[1, 0, 0]) == D.bits(every[5, 0, 0])
+    # limit: candidates at or beyond it are NaN and -1, those before it what they are without
+    qs = rng.uniform(0.5, 2, (4, R, S)).astype(F32)
+    full = D.match(qs, qs)
+    cut = D.match(qs, qs, np.array([0, 4, 2, 1]))
+    for i, lim in enumerate((0, 4, 2, 1)):
+        assert np.isnan(cut[0][i, lim:]).all() and (cut[1][i, lim:] == -1).all()
+        assert np.array_equal(D.bits(cut[0][i, :lim]), D.bits(full[0][i, :lim])) and np.array_equal(cut[1][i, :lim], full[1][i, :lim])
+    assert np.array_equal(np.diag(full[1]), np.zeros(4)) and (np.abs(np.diag(full[0])) <= 2.0 ** -20).all()
+
+
+# ---- host logic -----------------------------------------------------------------------------------------------------------------------------------
+def _touched(*a, **k):
+    raise AssertionError("the library was reached")
+
+
+def test_argument_checks(monkeypatch):
+    monkeypatch.setattr(_lib, "load", _touched)
+    monkeypatch.setattr(_lib, "call", _touched)
+    p = torch.zeros((8, 3))
+    for bad in (torch.zeros((8, 2)), torch.zeros((8,)), torch.zeros((8, 3), dtype=torch.float64), None, np.zeros((8, 3), F32)):
+        with pytest.raises(ValueError, match="points must be a float32"):
+            ops.scan_descriptor(bad)
+    with pytest.raises(ValueError, match="device tensor"):
+        ops.scan_descriptor(p)
+    for bad in (0, 65, 2.5, None, True):
+        with pytest.raises(ValueError, match="rings must be an integer"):
+            ops.scan_descriptor(p, rings=bad)
+    for bad in (0, 3, 257, 2.5, None):
+        with pytest.raises(ValueError, match="sectors must be an integer"):
+            ops.scan_descriptor(p, sectors=bad)
+    for r, s in ((20, 62), (64, 68), (17, 256), (1, 6)):
+        with pytest.raises(ValueError, match="multiple of 4 and rings x sectors at most 4096"):
+            ops.scan_descriptor(p, rings=r, sectors=s)
+    for bad in (0.0, -1.0, float("inf"), float("nan"), 1e39):
+        with pytest.raises(ValueError, match="max_range must be a finite number > 0"):
+            ops.scan_descriptor(p, max_range=bad)
+    for bad in (-0.1, 80.0, 90.0, float("nan"), "x"):
+        with pytest.raises(ValueError, match="min_range must be a number in \\[0, max_range\\)"):
+            ops.scan_descriptor(p, min_range=bad)
+    for bad in (float("inf"), float("nan"), 1e39, None):
+        with pytest.raises(ValueError, match="height must be a finite number"):
+            ops.scan_descriptor(p, height=bad)
+    assert (ops.SCAN_MAX_RINGS, ops.SCAN_MAX_SECTORS, ops.SCAN_MAX_CELLS) == (64, 256, 4096)
+    # scan_match
+    d = torch.zeros((3, 8, 24))
+    for bad in (torch.zeros((8, 24)), torch.zeros((3, 8, 24), dtype=torch.float64), None, np.zeros((3, 8, 24), F32)):
+        with pytest.raises(ValueError, match="queries must be a float32 \\[n, rings, sectors\\]"):
+            ops.scan_match(bad, d)
+    with pytest.raises(ValueError, match="queries must be a device tensor"):
+        ops.scan_match(d, d)
+
+
+def test_checks_behind_the_device_check(monkeypatch):
+    monkeypatch.setattr(_lib, "load", _touched)
+    monkeypatch.setattr(_lib, "call", _touched)
+    real = ops._scan_batch
+
+    def shape_only(who, name, t):
+        try:
+            return real(who, name, t)
+        except ValueError as e:
+            if "device tensor" not in str(e):
+                raise
+            return t
+
+    monkeypatch.setattr(ops, "_scan_batch", shape_only)
+    d = torch.zeros((3, 8, 24))
+    with pytest.raises(ValueError, match="cands must be a float32"):
+        ops.scan_match(d, torch.zeros((8, 24)))
+    with pytest.raises(ValueError, match="holds 0 descriptors"):
+        ops.scan_match(d[:0], d)
+    with pytest.raises(ValueError, match="queries are 8 x 24, cands 8 x 20"):
+        ops.scan_match(d, torch.zeros((3, 8, 20)))
+    with pytest.raises(ValueError, match="multiple of 4"):
+        ops.scan_match(torch.zeros((3, 8, 22)), torch.zeros((3, 8, 22)))
+    with pytest.raises(ValueError, match="rings must be an integer"):
+        ops.scan_match(torch.zeros((3, 65, 4)), torch.zeros((3, 65, 4)))
+    for bad in (0, 25, 2.5, True):
+        with pytest.raises(ValueError, match="min_cols must be an integer in \\[1, 24\\]"):
+            ops.scan_match(d, d, min_cols=bad)
+    for bad in (torch.zeros((3,), dtype=torch.int64), torch.zeros((3, 1), dtype=torch.int32), [0, 1, 2], np.zeros(3, np.int32)):
+        with pytest.raises(ValueError, match="limit must be an int32 \\[Q\\]"):
+            ops.scan_match(d, d, limit=bad)
+    with pytest.raises(ValueError, match="queries hold 3 rows, limit 2"):
+        ops.scan_match(d, d, limit=torch.zeros((2,), dtype=torch.int32))
+    for bad in ([0, -1, 2], [0, 4, 2]):
+        with pytest.raises(ValueError, match="limit must lie in \\[0, 3\\]"):
+            ops.scan_match(d, d, limit=torch.tensor(bad, dtype=torch.int32))
+    # an empty cloud: no launch, an all-zero descriptor
+    monkeypatch.setattr(ops, "_cloud_points", lambda t, name="points": t)
+    e = ops.scan_descriptor(torch.zeros((0, 3)), 3, 4)
+    assert e.desc.shape == (3, 4) and not e.desc.any() and e[1:] == (0, 0, 0)
+
+
+def test_header_and_work_model_know_the_entry_points():
+    from cmr_agent_amd.utils import workmodel
+    protos = _lib.parse_header()
+    assert protos["cmr_scan_descriptor_f32"][2] == ["points", "ld", "N", "R", "S", "ring_edge2", "sector_dir", "height", "desc", "counts", "stream"]
+    assert protos["cmr_scan_match_f32"][2] == ["queries", "Q", "cands", "N", "R", "S", "limit", "min_cols", "dist", "shift", "workspace",
+                                               "workspace_bytes", "stream"]
+    fl, by = workmodel.WORK["cmr_scan_match_f32"](dict(Q=10, N=20, R=20, S=60))
+    assert fl == 10 * 20 * (2 * 20 * 60 * 60 + 60 * 60) and by > 0
+    assert workmodel.WORK["cmr_scan_descriptor_f32"](dict(N=1000, R=20, S=60))[1] == 1000 * 12 + 20 * 60 * 4
+    lib = _lib.load()
+    assert lib.cmr_scan_match_workspace_bytes(3, 5, 8, 24) == 8 * (8 * 24 + 24) * 4
+    assert lib.cmr_scan_match_workspace_bytes(3, 5, 8, 22) == 0 and lib.cmr_scan_match_workspace_bytes(0, 5, 8, 24) == 0
+
+
+def test_selection_and_acceptance_rules():
+    assert loops.gap_limits(8, 3).tolist() == [0, 0, 0, 1, 2, 3, 4, 5] and loops.gap_limits(8, 3).dtype == np.int32
+    assert loops.gap_limits(3, 50).tolist() == [0, 0, 0] and loops.gap_limits(4, 1).tolist() == [0, 1, 2, 3]
+    nan = float("nan")
+    dist = torch.tensor([[nan, nan, nan, nan], [0.5, nan, nan, nan], [0.2, 0.1, nan, nan], [0.25, 0.1, 0.1, nan], [0.1, 0.3, 0.2, 0.3]])
+    pick = lambda top, thr: [t.tolist() for t in loops.select_candidates(dist, top, thr)]                    # noqa: E731
+    q, c, d = pick(1, 0.3)
+    assert (q, c) == ([2, 3, 4], [1, 1, 0]) and np.allclose(d, [0.1, 0.1, 0.1])                       # a tie goes to the lower frame
+    q, c, d = pick(2, 0.3)
+    assert list(zip(q, c)) == [(2, 1), (2, 0), (3, 1), (3, 2), (4, 0), (4, 2)]
+    q, c, d = pick(9, 0.25)
+    assert list(zip(q, c)) == [(2, 1), (2, 0), (3, 1), (3, 2), (3, 0), (4, 0), (4, 2)]
+    assert pick(1, 0.05) == [[], [], []] and pick(1, 0.5)[0] == [1, 2, 3, 4]                          # the threshold is inclusive
+    res = lambda status, pairs, rmse: ops.IcpResult(None, pairs, rmse, 3, status, None, None)              # noqa: E731
+    ok = lambda r: loops.accepted(r, 1000, 0.2, 0.3)                                                       # noqa: E731
+    assert ok(res(0, 300, 0.2)) and ok(res(1, 1000, 0.0)) and not ok(res(0, 299, 0.1)) and not ok(res(0, 500, 0.2001))
+    assert not ok(res(2, 500, 0.1)) and not ok(res(3, 500, 0.1)) and not ok(res(0, 500, float("nan")))
+    m, deg = loops.drift(np.stack([np.eye(4), D.rz(0.1)]), 1, 0, D.rz(0.1))
+    assert m == 0 and deg < 1e-6
+    T = D.rz(0.1)
+    T[0, 3] = 3.0
+    m, deg = loops.drift(np.stack([np.eye(4), T]), 1, 0, np.eye(4))
+    assert abs(m - 3.0) < 1e-12 and abs(deg - np.degrees(0.1)) < 1e-6
+
+
+def test_edges_round_trip(tmp_path):
+    path = str(tmp_path / "edges.txt")
+    rng = np.random.default_rng(0)
+    edges = [(17, 3, I.pose_matrix(rng.normal(size=3), rng.normal(size=3)).astype(F32).astype(np.float64), float(F32(0.123)), float(F32(0.0456)), 2100),
+             (250, 0, np.eye(4), 0.0, 0.0, 6)]
+    align.write_edges(path, edges)
+    back = align.read_edges(path)
+    assert len(back) == 2 and all(len(open(path).read().splitlines()[n].split()) == 17 for n in range(2))
+    for a, b in zip(edges, back):
+        assert a[:2] == b[:2] and a[5] == b[5] and np.array_equal(D.bits(a[2]), D.bits(b[2])) and D.bits(a[3:5]).tolist() == D.bits(b[3:5]).tolist()     # %.9e carries a float32 exactly
+    align.write_edges(path, [])
+    assert align.read_edges(path) == []
+    for bad in ("1 2 3\n", "1 2 " + "0 " * 12 + "0.1 0.2 x\n", "1 2 " + "nan " * 12 + "0.1 0.2 3\n", "-1 2 " + "0 " * 12 + "0.1 0.2 3\n"):
+        open(path, "w").write(bad)
+        with pytest.raises(ValueError, match="line 1: need `i j`"):
+            align.read_edges(path)
+
+
+def test_loops_flag_rules(tmp_path, capsys):
+    root = str(tmp_path)
+    I.write_frames(root, [f[:, :50] for f in D.drive(SEED)["frames"][:2]])
+    base = ["--root", root, "--data-velodyne", "vel", "--sequence", "9"]
+    for extra in (["--rings", "0"], ["--rings", "65"], ["--sectors", "62"], ["--rings", "64", "--sectors", "68"], ["--max-range", "0"],
+                  ["--min-range", "-1"], ["--min-range", "80"], ["--height", "nan"], ["--gap", "0"], ["--top", "0"], ["--max-desc-dist", "-0.1"],
+                  ["--max-desc-dist", "nan"], ["--min-cols", "0"], ["--min-cols", "61"], ["--init", "previous"], ["--max-dist", "0"], ["--huber", "-1"],
+                  ["--iters", "1001"], ["--max-rmse", "0"], ["--min-overlap", "1.5"], ["--min-overlap", "-0.1"], ["--ransac-hyp", "0"], ["--seed", "-1"],
+                  ["--frames", "6:2"], ["--poses", os.path.join(root, "none.txt")]):
+        with pytest.raises(SystemExit):
+            loops.main(base + extra, device="cpu")
+    capsys.readouterr()
+    align.write_poses(os.path.join(root, "three.txt"), np.tile(np.eye(4), (3, 1, 1)))
+    with pytest.raises(SystemExit):
+        loops.main(base + ["--poses", os.path.join(root, "three.txt")], device="cpu")
+    assert "holds 3 poses, --frames names 2 frames" in capsys.readouterr().err
+    _, args = loops.parse_args(base)
+    assert (args.rings, args.sectors, args.max_range, args.min_range, args.height, args.gap, args.top, args.max_desc_dist, args.min_cols) == \
+        (20, 60, 80.0, 0.0, 2.0, 50, 1, 0.3, None)
+    assert (args.init, args.max_dist, args.huber, args.iters, args.max_rmse, args.min_overlap, args.poses, args.out) == \
+        ("auto", 1.0, 0.1, 30, 0.2, 0.3, None, None)
+    ap, _ = loops.parse_args(base)
+    assert "not tuned on real data" in ap.format_help()
+
+
+# ---- the synthetic drive ----------------------------------------------------------------------------------------------------------------------------
+def test_every_planted_revisit_lies_below_every_other_pair():
+    d = D.drive(SEED)
+    assert len(d["frames"]) == 20 and all(2000 <= f.shape[1] <= 3500 and f.dtype == F32 and f.shape[0] == 7 for f in d["frames"])
+    assert d["revisits"] == ((16, 0), (17, 1), (18, 2), (19, 3))
+    hi, lo = D.drive_margin(SEED)
+    assert hi <= 0.7 * lo, (hi, lo)
+    dist, shift = D.drive_match(SEED)
+    assert np.isnan(dist[:6]).all() and not np.isnan(dist[19, :14]).any() and np.isnan(dist[19, 14:]).all()       # gap 6
+    for i, j in d["revisits"]:                                           # the shift gives the heading to half a sector
+        truth = np.linalg.inv(d["poses"][j]) @ d["poses"][i]
+        rot, _ = I.pose_error(loops.shift_start(shift[i, j], D.DRIVE["sectors"]), truth)
+        assert rot <= np.pi / D.DRIVE["sectors"] + 1e-9, (i, j, np.degrees(rot))
+    assert [int(shift[i, j]) for i, j in d["revisits"]] == [0, 9, 0, 9]
+
+
+def test_loops_command_on_stand_ins(tmp_path, monkeypatch, capsys):
+    """The file layer with the restatements in the ops' places: no GPU.  The tolerance on the measured poses is twice the error of the same
+    ICP on the same pairs started from the truth (the scans overlap, they are not identical)."""
+    matches = []
+    monkeypatch.setattr(ops, "scan_descriptor", D.ops_scan_descriptor)
+    monkeypatch.setattr(ops, "scan_match", lambda *a, **k: matches.append(a) or D.ops_scan_match(*a, **k))
+    monkeypatch.setattr(ops, "icp_point_to_plane", I.ops_icp_point_to_plane)
+    monkeypatch.setattr(ops, "register_global", _touched)
+    rot, trans = D.drive_icp_error(lambda t, s, start: align.register_pair(t, s, align.device_pose(start, "cpu"), device="cpu").pose.numpy())
+    root, out = str(tmp_path), str(tmp_path / "edges.txt")
+    for init in ("shift", "auto"):                                       # accepted from the shift: auto asks for no global start
+        loops.main(D.drive_argv(root, "--init", init, "--out", out), device="cpu")
+        D.check_drive_run(capsys.readouterr().out.splitlines(), ["shift"] * 4, 2 * rot, 2 * trans, out)
+    assert len(matches) == 2 and matches[0][2].tolist() == loops.gap_limits(20, 6).tolist() and matches[0][3] is None
+    assert matches[0][0].shape == (20, 8, 24) and matches[0][0] is matches[0][1]
+    # a threshold below every pair: no candidate, no edge
+    loops.main(D.drive_argv(root, "--max-desc-dist", "0.01", "--out", out), device="cpu")
+    assert capsys.readouterr().out.splitlines() == ["loops: 0 accepted of 0 candidates of 20 frames"] and align.read_edges(out) == []
+    # an acceptance rule nothing meets: auto goes on to the global start, and the line says which start it ended with
+    asked = []
+
+    def fake_global(*a, **k):
+        asked.append(k.get("refine"))
+        return ops.GlobalResult(torch.eye(4), 0, 0, 1, None)
+
+    monkeypatch.setattr(ops, "register_global", fake_global)
+    argv = [a for a in D.drive_argv(root, "--frames", ":20", "--max-rmse", "1e-9")]
+    at = argv.index("--poses")
+    loops.main(argv[:at] + argv[at + 2:], device="cpu")                  # 17 frames: the poses file of 20 does not go with them
+    lines = capsys.readouterr().out.splitlines()
+    assert len(lines) == 2 and lines[0].startswith("loop 19 3: ") and lines[0].endswith("start global -> rejected") and asked == [False]
+    assert lines[1] == "loops: 0 accepted of 1 candidates of 17 frames"
