@@ -19,6 +19,7 @@
 // 8 TB/s at ~75 % matrix occupancy; three workgroups per CU (51 KB of LDS each).  rows must be a multiple of 32 (every map this serves is
 // B x a power of two); no predicated access anywhere.  Partials [workgroups][n][k] are summed in double in a fixed order.
 #include "cmr_common.h"
+#include "cmr_reduce.h"
 #include "cmr_mfma16.h"
 
 namespace {
@@ -337,64 +338,8 @@ __global__ __launch_bounds__(256) void bn_linear_bwd_kernel(const BlbArgs a) {
   }
 }
 
-// coef[0][c] = sum d / rows, coef[1][c] = sum d xhat / rows, dgamma = sum d xhat, dbeta = sum d: one wave per channel over the workgroups'
-// partials, in double (train.hip: bn_bwd_final_kernel's arithmetic)
-__global__ __launch_bounds__(64) void blb_coef_final_kernel(const float* __restrict__ part, int nblk, int64_t rows, int C, float* __restrict__ coef,
-                                                            float* __restrict__ dgamma, float* __restrict__ dbeta) {
-  const int c = blockIdx.x, lane = threadIdx.x;
-  double s = 0.0, sx = 0.0;
-  for (int b = lane; b < nblk; b += 64) {
-    s += (double)part[(int64_t)b * 2 * C + c];
-    sx += (double)part[(int64_t)b * 2 * C + C + c];
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    s += __shfl_xor(s, o, 64);
-    sx += __shfl_xor(sx, o, 64);
-  }
-  if (lane != 0) return;
-  coef[c] = (float)(s / (double)rows);
-  coef[C + c] = (float)(sx / (double)rows);
-  if (dbeta) dbeta[c] = (float)s;
-  if (dgamma) dgamma[c] = (float)sx;
-}
-
-// dw[i] (+)= sum over the workgroups' partials, in double, fixed order (32 slice groups x 8 loads in flight)
-constexpr int BR_OUT = 32, BR_GRP = 32, BR_U = 8;
-// outputs [0, n k): dw entries; [n k, n k + n): db entries (when part_b)
-__global__ __launch_bounds__(BR_OUT * BR_GRP) void blb_reduce_kernel(const float* __restrict__ part, const float* __restrict__ part_b, int nslices,
-                                                                     int n, int k, float* __restrict__ dw, int64_t lddw, int accumulate,
-                                                                     float* __restrict__ db, int accumulate_db) {
-  __shared__ double sm[BR_GRP][BR_OUT];
-  const int o = threadIdx.x % BR_OUT, gq = threadIdx.x / BR_OUT;
-  const int64_t nk = (int64_t)n * k, total = nk + (part_b ? n : 0);
-  const int64_t i = (int64_t)blockIdx.x * BR_OUT + o;
-  const float* p = i < nk ? part + i : (i < total ? part_b + (i - nk) : part);
-  const int64_t stride = i < nk ? nk : n;
-  double s = 0.0;
-  for (int j0 = gq; j0 < nslices; j0 += BR_GRP * BR_U) {
-    float v[BR_U];
-#pragma unroll
-    for (int u = 0; u < BR_U; ++u) {
-      const int j = j0 + u * BR_GRP;
-      v[u] = p[(int64_t)(j < nslices ? j : j0) * stride];
-    }
-#pragma unroll
-    for (int u = 0; u < BR_U; ++u) s += j0 + u * BR_GRP < nslices ? (double)v[u] : 0.0;
-  }
-  sm[gq][o] = s;
-  __syncthreads();
-  if (gq == 0 && i < total) {
-#pragma unroll
-    for (int j = 1; j < BR_GRP; ++j) s += sm[j][o];
-    if (i < nk) {
-      float* d = dw + (i / k) * lddw + (i % k);
-      *d = accumulate ? *d + (float)s : (float)s;
-    } else {
-      db[i - nk] = accumulate_db ? db[i - nk] + (float)s : (float)s;
-    }
-  }
-}
+// The second stages are in cmr_reduce.h: bn_bwd_final_kernel (coef, dgamma, dbeta of the lazy operand from xpart) and
+// linear_wgrad_reduce_kernel (dw, db from the workgroups' whole-gradient partials: nblk = 1, npad = n, kpad = k).
 
 // ------------------------------------------------------------------------------------------------------------------
 // Forward of the same layer: h = x W^T + b for 64 output channels WITH the BatchNorm statistics of h from the same pass (the separate
@@ -555,9 +500,7 @@ __global__ __launch_bounds__(64) void bn_stats_merge_kernel(const float* __restr
                                                             const float* __restrict__ beta, float* __restrict__ running_mean,
                                                             float* __restrict__ running_var, float* __restrict__ stat) {
   const int c = blockIdx.x, lane = threadIdx.x;
-  // ONE pass over the partials: with d_w = mean - p_w,  M2 = sum_w [ss_w - 2 d_w s_w + n_w d_w^2]
-  //   = sum ss - 2 mean sum s + 2 sum p s + mean^2 sum n - 2 mean sum n p + sum n p^2   (double: the terms are <= rows * mean^2 ~ 1e8, M2 ~ 1e6)
-  double s_s = 0.0, s_ss = 0.0, s_ps = 0.0, s_np = 0.0, s_npp = 0.0;
+  double s_s = 0.0, s_ss = 0.0, s_ps = 0.0, s_np = 0.0, s_npp = 0.0;      // ONE pass over the partials: the five sums of cmr_bn_merge5
   for (int w = lane; w < G; w += 64) {
     const double n = 32.0 * (double)((seg_blocks - w % seg_groups + seg_groups - 1) / seg_groups);
     const double p = (double)part[(int64_t)w * 3 * C + c], s = (double)part[(int64_t)w * 3 * C + C + c];
@@ -573,23 +516,9 @@ __global__ __launch_bounds__(64) void bn_stats_merge_kernel(const float* __restr
   s_np = cmr_wave_sum_d(s_np);
   s_npp = cmr_wave_sum_d(s_npp);
   if (lane != 0) return;
-  const double n = (double)rows;
-  const double mean = (s_np + s_s) / n;
-  const double m2 = s_ss - 2.0 * mean * s_s + 2.0 * s_ps + mean * mean * n - 2.0 * mean * s_np + s_npp;
-  double var = m2 / n;
-  var = var > 0.0 ? var : 0.0;
-  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-  const float gm = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
-  const float scale = gm * rstd;
-  stat[c] = (float)mean;
-  stat[C + c] = rstd;
-  stat[2 * C + c] = scale;
-  stat[3 * C + c] = bt - (float)mean * scale;
-  if (running_mean) {
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-    const double unbiased = rows > 1 ? var * n / (n - 1.0) : var;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-  }
+  double mean;
+  const double var = cmr_bn_merge5(s_s, s_ss, s_ps, s_np, s_npp, rows, mean);
+  cmr_bn_stat_tail(mean, var, rows, c, C, eps, momentum, gamma, beta, running_mean, running_var, stat);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -785,23 +714,9 @@ __global__ __launch_bounds__(256) void bn_stats_merge_cnt_kernel(const float* __
   s_ps = sm[0][2] + sm[1][2] + sm[2][2] + sm[3][2];
   s_np = sm[0][3] + sm[1][3] + sm[2][3] + sm[3][3];
   s_npp = sm[0][4] + sm[1][4] + sm[2][4] + sm[3][4];
-  const double n = (double)rows;
-  const double mean = (s_np + s_s) / n;
-  const double m2 = s_ss - 2.0 * mean * s_s + 2.0 * s_ps + mean * mean * n - 2.0 * mean * s_np + s_npp;
-  double var = m2 / n;
-  var = var > 0.0 ? var : 0.0;
-  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-  const float gm = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
-  const float scale = gm * rstd;
-  stat[c] = (float)mean;
-  stat[C + c] = rstd;
-  stat[2 * C + c] = scale;
-  stat[3 * C + c] = bt - (float)mean * scale;
-  if (running_mean) {
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-    const double unbiased = rows > 1 ? var * n / (n - 1.0) : var;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-  }
+  double mean;
+  const double var = cmr_bn_merge5(s_s, s_ss, s_ps, s_np, s_npp, rows, mean);
+  cmr_bn_stat_tail(mean, var, rows, c, C, eps, momentum, gamma, beta, running_mean, running_var, stat);
 }
 
 #ifndef CMR_BLG_WG_PER_CU
@@ -836,17 +751,8 @@ __global__ __launch_bounds__(64) void blb_seg_reduce_kernel(const float* __restr
   const int seg = blockIdx.x, c = blockIdx.y * 64 + threadIdx.x;
   if (c >= n) return;
   const float* p = part_b + (int64_t)seg * seg_groups * n + c;
-  double s = 0.0;
-  int w = 0;
-  for (; w + 8 <= seg_groups; w += 8) {          // eight independent loads in flight (one dependent load per workgroup took 18 us for 76)
-    float v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = p[(int64_t)(w + u) * n];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += (double)v[u];
-  }
-  for (; w < seg_groups; ++w) s += (double)p[(int64_t)w * n];
-  cs[(int64_t)seg * n + c] = (float)s;
+  // one thread per output: eight independent loads in flight (one dependent load per workgroup took 18 us for 76)
+  cs[(int64_t)seg * n + c] = (float)cmr_slice_sum<1, 8>(p, n, seg_groups, 0);
 }
 
 inline int blb_groups(int64_t rows, int n, int k) {
@@ -1204,6 +1110,24 @@ int blh_dispatch(const BlbArgs& a, bool bn, bool zh, bool xl, int groups, hipStr
 
 inline bool blb_shape_ok(int64_t rows, int n, int k) { return (n == 64 || n == 128) && (k == 64 || k == 128) && rows >= 32 && rows % 32 == 0; }
 
+// Workgroup plan over a map of R-row blocks cut into seg_rows-row segments (seg_rows = 0: one segment): a whole number of workgroups per
+// segment, >= 4 blocks each.  groups in: what the unsegmented launch would take; out: the grid (at most 256 more -- the workspace sizes
+// allow for that; false when it would take more).
+inline bool seg_plan(int64_t rows, int64_t seg_rows, int R, int& groups, int& seg_groups, int64_t& seg_blocks) {
+  seg_blocks = rows / R;
+  seg_groups = groups;
+  if (seg_rows <= 0) return true;
+  const int64_t nseg = rows / seg_rows;
+  seg_blocks = seg_rows / R;
+  int64_t gps = (groups + nseg - 1) / nseg;
+  if (gps > seg_blocks / 4) gps = seg_blocks / 4;
+  if (gps < 1) gps = 1;
+  if (nseg * gps > groups + 256) return false;
+  seg_groups = (int)gps;
+  groups = (int)(nseg * gps);
+  return true;
+}
+
 }  // namespace
 
 // dW partials [groups][n][k] + (lazy x operand) the previous layer's BatchNorm-backward partials [groups][2][k]
@@ -1244,18 +1168,9 @@ static int blb_entry(bool bf16, const float* dz, int64_t lddz, const float* z, i
   if (xl && bf16) CMR_REQUIRE(xslope >= 0.f && ldx % 4 == 0);
   int groups = bf16 ? blh_groups(rows) : blb_groups(rows, n, k);
   const int R = bf16 ? BLH_R : blb_rows_per_block(rows, n);
-  int64_t seg_blocks = rows / R;
-  int seg_groups = groups;
-  if (seg_db) {                                  // per-segment column sums: a whole number of workgroups per segment, >= 4 blocks each
-    const int64_t nseg = rows / seg_rows;
-    seg_blocks = seg_rows / R;
-    int64_t gps = (groups + nseg - 1) / nseg;
-    if (gps > seg_blocks / 4) gps = seg_blocks / 4;
-    if (gps < 1) gps = 1;
-    CMR_REQUIRE(nseg * gps <= groups + 256);
-    seg_groups = (int)gps;
-    groups = (int)(nseg * gps);
-  }
+  int64_t seg_blocks;
+  int seg_groups;
+  CMR_REQUIRE(seg_plan(rows, seg_db ? seg_rows : 0, R, groups, seg_groups, seg_blocks));      // per-segment column sums
   CMR_REQUIRE(ws_bytes >= (int64_t)groups * ((int64_t)n * k + 2 * k + n) * (int64_t)sizeof(float));
   float* xpart = (float*)ws + (int64_t)groups * n * k;
   float* part_b = (db || seg_db) ? xpart + (int64_t)groups * 2 * k : nullptr;
@@ -1274,13 +1189,11 @@ static int blb_entry(bool bf16, const float* dz, int64_t lddz, const float* z, i
   else if (n == 128 && k == 64) rc = blb_dispatch<4, 2>(a, bn, zh, xl, groups, stream);
   else rc = blb_dispatch<4, 4>(a, bn, zh, xl, groups, stream);
   if (rc != CMR_OK) return rc;
-  const int64_t outs = (int64_t)n * k + (db ? n : 0);
-  hipLaunchKernelGGL(blb_reduce_kernel, dim3((unsigned)((outs + BR_OUT - 1) / BR_OUT)), dim3(BR_OUT * BR_GRP), 0, stream, (const float*)ws,
-                     (const float*)(db ? part_b : nullptr), groups, n, k, dw, lddw, accumulate, db, accumulate_db);
+  cmr_linear_wgrad_reduce((const float*)ws, db ? part_b : nullptr, groups, n, k, 1, n, k, dw, lddw, accumulate, db, accumulate_db, stream);
   if (seg_db)
     hipLaunchKernelGGL(blb_seg_reduce_kernel, dim3((unsigned)(rows / seg_rows), (unsigned)((n + 63) / 64)), dim3(64), 0, stream, (const float*)part_b,
                        seg_groups, n, seg_db);
-  if (xl) hipLaunchKernelGGL(blb_coef_final_kernel, dim3(k), dim3(64), 0, stream, (const float*)xpart, groups, rows, k, xcoef, xdgamma, xdbeta);
+  if (xl) hipLaunchKernelGGL(bn_bwd_final_kernel<1>, dim3(k), dim3(64), 0, stream, (const float*)xpart, groups, rows, k, xcoef, xdgamma, xdbeta);
   return cmr_launch_status();
 }
 
@@ -1353,18 +1266,9 @@ static int blf_entry(bool bf16, const float* x, int64_t ldx, int k, const float*
     return cmr_launch_status();
   }
   int groups = blf_groups(rows, n, k);
-  int64_t seg_blocks = rows / 32;
-  int seg_groups = groups;
-  if (bias_seg_rows > 0) {
-    const int64_t nseg = rows / bias_seg_rows;
-    seg_blocks = bias_seg_rows / 32;
-    int64_t gps = (groups + nseg - 1) / nseg;
-    if (gps > seg_blocks / 4) gps = seg_blocks / 4;
-    if (gps < 1) gps = 1;
-    CMR_REQUIRE(nseg * gps <= groups + 256);
-    seg_groups = (int)gps;
-    groups = (int)(nseg * gps);
-  }
+  int64_t seg_blocks;
+  int seg_groups;
+  CMR_REQUIRE(seg_plan(rows, bias_seg_rows, 32, groups, seg_groups, seg_blocks));
   CMR_REQUIRE(ws_bytes >= (int64_t)groups * 3 * n * (int64_t)sizeof(float));
   const BlfArgs a{x, ldx, pro_stat, pro_slope, w, ldw, bias, bias_seg_rows > 0 ? bias_stride : 0, h, ldh, (float*)ws, rows, seg_blocks, seg_groups};
   if (n == 64 && k == 64) {

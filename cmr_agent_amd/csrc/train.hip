@@ -10,6 +10,7 @@
 // combined in double in a fixed order (so a result never depends on scheduling, and the data-parallel ranks of
 // utils/flatbucket.py stay bit-identical after the all-reduce).
 #include "cmr_common.h"
+#include "cmr_reduce.h"
 
 namespace {
 
@@ -78,31 +79,12 @@ __global__ __launch_bounds__(64) void bn_stats_final_kernel(const float* __restr
                                                             const float* __restrict__ beta, float* __restrict__ running_mean,
                                                             float* __restrict__ running_var, float* __restrict__ stat) {
   const int c = blockIdx.x, lane = threadIdx.x;
-  double s = 0.0, ss = 0.0;
-  for (int b = lane; b < nblk; b += 64) {
-    s += (double)part[(int64_t)b * 2 * C + c];
-    ss += (double)part[(int64_t)b * 2 * C + C + c];
-  }
-  s = cmr_wave_sum_d(s);
-  ss = cmr_wave_sum_d(ss);
+  double s[2];                                     // sums of (x - pivot) and (x - pivot)^2
+  cmr_wave_partials_sum<1, 2>(part + c, 2 * C, C, nblk, lane, s);
   if (lane != 0) return;
   const double n = (double)rows;
-  const double pm = s / n;
-  double var = ss / n - pm * pm;
-  var = var > 0.0 ? var : 0.0;
-  const double mean = (double)x[c] + pm;
-  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-  const float g = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
-  const float scale = g * rstd;
-  stat[c] = (float)mean;
-  stat[C + c] = rstd;
-  stat[2 * C + c] = scale;
-  stat[3 * C + c] = bt - (float)mean * scale;
-  if (running_mean) {
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-    const double unbiased = rows > 1 ? var * n / (n - 1.0) : var;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-  }
+  const double pm = s[0] / n;
+  cmr_bn_stat_tail((double)x[c] + pm, s[1] / n - pm * pm, rows, c, C, eps, momentum, gamma, beta, running_mean, running_var, stat);
 }
 
 // y = lrelu(x * scale + shift + [res * rscale + rshift | res]).  scale / shift null -> identity on x.
@@ -236,23 +218,7 @@ __global__ __launch_bounds__(RED_THREADS) void bn_bwd_partial_kernel(const float
   }
 }
 
-// coef[0][c] = sum dy / n, coef[1][c] = sum dy xhat / n;  dgamma / dbeta written (or accumulated) into the gradient bucket
-__global__ __launch_bounds__(64) void bn_bwd_final_kernel(const float* __restrict__ part, int nblk, int64_t rows, int C, float* __restrict__ coef,
-                                                          float* __restrict__ dgamma, float* __restrict__ dbeta) {
-  const int c = blockIdx.x, lane = threadIdx.x;
-  double s = 0.0, sx = 0.0;
-  for (int b = lane; b < nblk; b += 64) {
-    s += (double)part[(int64_t)b * 2 * C + c];
-    sx += (double)part[(int64_t)b * 2 * C + C + c];
-  }
-  s = cmr_wave_sum_d(s);
-  sx = cmr_wave_sum_d(sx);
-  if (lane != 0) return;
-  coef[c] = (float)(s / (double)rows);
-  coef[C + c] = (float)(sx / (double)rows);
-  if (dbeta) dbeta[c] = (float)s;
-  if (dgamma) dgamma[c] = (float)sx;
-}
+// (the final step, bn_bwd_final_kernel, is in cmr_reduce.h: bn_linear.hip launches it too)
 
 // dx = scale * (dy - c1 - xhat * c2) (+ add),  scale = gamma * rstd = stat[2]
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dz, int64_t lddz, const float* __restrict__ z, int64_t ldz,
@@ -404,9 +370,7 @@ __global__ __launch_bounds__(64) void col_final_kernel(const float* __restrict__
       arg[(int64_t)b * C + c] = ia;
     }
   } else {
-    double a = 0.0;
-    for (int k = lane; k < nblk; k += 64) a += (double)pv[((int64_t)b * nblk + k) * C + c];
-    a = cmr_wave_sum_d(a);
+    const double a = cmr_wave_partials_sum<1>(pv + (int64_t)b * nblk * C + c, C, nblk, lane);
     if (lane == 0) out[(int64_t)b * C + c] = (float)a;
   }
 }
@@ -695,42 +659,13 @@ static __global__ __launch_bounds__(64) void bn_stats_from_sums_kernel(const flo
                                                                 float* __restrict__ running_mean, float* __restrict__ running_var,
                                                                 float* __restrict__ stat) {
   const int c = blockIdx.x, lane = threadIdx.x;
-  double s = 0.0, ss = 0.0;
-  for (int64_t b0 = lane; b0 < parts; b0 += 64 * 8) {
-    float v0[8], v1[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int64_t b = b0 + 64 * u < parts ? b0 + 64 * u : b0;
-      v0[u] = part[b * 2 * C + c];
-      v1[u] = part[b * 2 * C + C + c];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (b0 + 64 * u < parts) {
-        s += (double)v0[u];
-        ss += (double)v1[u];
-      }
-  }
-  s = cmr_wave_sum_d(s);
-  ss = cmr_wave_sum_d(ss);
+  double s[2];
+  cmr_wave_partials_sum<8, 2>(part + c, 2 * C, C, parts, lane, s);      // a producer may leave thousands of parts: 8 loads in flight
   if (lane != 0) return;
   const double n = (double)rows;
-  const double pm = s / n;
-  double var = ss / n - pm * pm;
-  var = var > 0.0 ? var : 0.0;
-  const double mean = (pivot ? (double)pivot[c] : 0.0) + pm;
-  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-  const float g = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
-  const float scale = g * rstd;
-  stat[c] = (float)mean;
-  stat[C + c] = rstd;
-  stat[2 * C + c] = scale;
-  stat[3 * C + c] = bt - (float)mean * scale;
-  if (running_mean) {
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-    const double unbiased = rows > 1 ? var * n / (n - 1.0) : var;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-  }
+  const double pm = s[0] / n;
+  cmr_bn_stat_tail((pivot ? (double)pivot[c] : 0.0) + pm, s[1] / n - pm * pm, rows, c, C, eps, momentum, gamma, beta, running_mean, running_var,
+                   stat);
 }
 
 extern "C" int cmr_bn_stats_from_sums_f32(const float* part, int64_t parts, int64_t rows, int C, const float* pivot, float eps, float momentum,
@@ -769,7 +704,7 @@ extern "C" int cmr_bn_bwd_f32(const float* dz, int64_t lddz, const float* z, int
   float* part = (float*)ws;
   float* coef = part + (int64_t)nb * 2 * C;
   hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(nb), dim3(RED_THREADS), 0, stream, dz, lddz, z, ldz, slope, x, ldx, stat, rows, C, part);
-  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C), dim3(64), 0, stream, (const float*)part, nb, rows, C, coef, dgamma, dbeta);
+  hipLaunchKernelGGL(bn_bwd_final_kernel<1>, dim3(C), dim3(64), 0, stream, (const float*)part, nb, rows, C, coef, dgamma, dbeta);
   hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid(rows * (C / 4))), dim3(256), 0, stream, dz, lddz, z, ldz, slope, x, ldx, stat,
                      (const float*)coef, add, ldadd, dx, lddx, dzm, lddzm, rows, C);
   return cmr_launch_status();
@@ -785,7 +720,7 @@ extern "C" int cmr_bn_bwd_from_sums_f32(const float* dz, int64_t lddz, float slo
   CMR_REQUIRE(lddz % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0 && cmr_aligned16(dz) && cmr_aligned16(x) && cmr_aligned16(dx));
   CMR_REQUIRE(ws_bytes >= (int64_t)2 * C * (int64_t)sizeof(float));
   float* coef = (float*)ws;
-  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C), dim3(64), 0, stream, part, (int)parts, rows, C, coef, dgamma, dbeta);
+  hipLaunchKernelGGL(bn_bwd_final_kernel<1>, dim3(C), dim3(64), 0, stream, part, (int)parts, rows, C, coef, dgamma, dbeta);
   hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid(rows * (C / 4))), dim3(256), 0, stream, dz, lddz, (const float*)nullptr, (int64_t)0, slope, x, ldx,
                      stat, (const float*)coef, (const float*)nullptr, (int64_t)0, dx, lddx, (float*)nullptr, (int64_t)0, rows, C);
   return cmr_launch_status();
@@ -804,7 +739,7 @@ extern "C" int cmr_bn_bwd_coef_f32(const float* dz, int64_t lddz, const float* z
   CMR_REQUIRE(ws_bytes >= (int64_t)nb * 2 * C * (int64_t)sizeof(float));
   float* part = (float*)ws;
   hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(nb), dim3(RED_THREADS), 0, stream, dz, lddz, z, ldz, slope, x, ldx, stat, rows, C, part);
-  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C), dim3(64), 0, stream, (const float*)part, nb, rows, C, coef, dgamma, dbeta);
+  hipLaunchKernelGGL(bn_bwd_final_kernel<1>, dim3(C), dim3(64), 0, stream, (const float*)part, nb, rows, C, coef, dgamma, dbeta);
   return cmr_launch_status();
 }
 

@@ -5,6 +5,7 @@
 // streaming kernels below (or a contraction of csrc/wgrad.hip / a forward kernel on transposed weights).  All of it is
 // HBM- or latency-class row work over [rows, 64]-shaped maps; reductions are two-stage with a fixed combination order.
 #include "cmr_common.h"
+#include "cmr_reduce.h"
 
 namespace {
 
@@ -120,9 +121,7 @@ __global__ __launch_bounds__(256) void ln64_bwd_kernel(const float* __restrict__
 __global__ __launch_bounds__(64) void reduce_partials_kernel(const float* __restrict__ part, int nblk, int n, float* __restrict__ out,
                                                              const int32_t* __restrict__ out_map, int accumulate) {
   const int i = blockIdx.x, lane = threadIdx.x;
-  double s = 0.0;
-  for (int b = lane; b < nblk; b += 64) s += (double)part[(int64_t)b * n + i];
-  s = cmr_wave_sum_d(s);
+  const double s = cmr_wave_partials_sum<1>(part + i, n, nblk, lane);
   if (lane == 0) {
     float* d = out + (out_map ? out_map[i] : i);
     *d = accumulate ? *d + (float)s : (float)s;
@@ -133,9 +132,7 @@ __global__ __launch_bounds__(64) void reduce_partials_kernel(const float* __rest
 __global__ __launch_bounds__(64) void reduce_partials2_kernel(const float* __restrict__ part, int nblk, int n, float* __restrict__ out0,
                                                               float* __restrict__ out1, int accumulate) {
   const int i = blockIdx.x, lane = threadIdx.x;
-  double s = 0.0;
-  for (int b = lane; b < nblk; b += 64) s += (double)part[(int64_t)b * 2 * n + i];
-  s = cmr_wave_sum_d(s);
+  const double s = cmr_wave_partials_sum<1>(part + i, 2 * n, nblk, lane);
   if (lane == 0) {
     float* d = i < n ? out0 + i : out1 + (i - n);
     *d = accumulate ? *d + (float)s : (float)s;

@@ -9,6 +9,7 @@
 // per-wave partial outputs go to a workspace and a second kernel sums them in a fixed order (deterministic: the
 // data-parallel ranks must produce bit-identical buckets from identical inputs).
 #include "cmr_common.h"
+#include "cmr_reduce.h"
 
 namespace {
 
@@ -840,21 +841,13 @@ __global__ __launch_bounds__(1024) void conv_bias_reduce_kernel(const float* __r
   __shared__ double sm[32][32];
   const int o = threadIdx.x & 31, g = threadIdx.x >> 5;
   const int c = blockIdx.x * 32 + o;
-  double s = 0.0;
-  if (c < Cout)
-    for (int j = g; j < nslices; j += 32) s += (double)part_b[(int64_t)j * Cout + c];
-  sm[g][o] = s;
-  __syncthreads();
-  if (g == 0 && c < Cout) {
-#pragma unroll
-    for (int j = 1; j < 32; ++j) s += sm[j][o];
-    db[c] = (float)s;
-  }
+  const double s = cmr_group_sum(sm, c < Cout ? cmr_slice_sum<32, 1>(part_b + c, Cout, nslices, g) : 0.0, g, o, c < Cout);
+  if (g == 0 && c < Cout) db[c] = (float)s;
 }
 
 // Sum of the per-wave partial outputs.  Workgroup = 32 consecutive outputs x 8 slice groups: thread (o, g) adds slices
-// g, g + 8, ... in double (coalesced over o), the 8 group sums are combined through LDS in a fixed order.
-constexpr int RED_OUT = 32, RED_GRP = 8;
+// g, g + 8, ... in double (coalesced over o, eight slices in flight per thread), the 8 group sums are combined through LDS in a fixed order.
+constexpr int RED_GRP = 8;
 
 __global__ __launch_bounds__(256) void conv3x3_wgrad_reduce_kernel(const float* __restrict__ part, int nslices, int Cout, int Cin,
                                                                    float* __restrict__ dw) {
@@ -862,26 +855,18 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_reduce_kernel(const float* 
   const int total = 9 * Cout * Cin;
   const int o = threadIdx.x % RED_OUT, g = threadIdx.x / RED_OUT;
   const int i = blockIdx.x * RED_OUT + o;
-  double s = 0.0;
-  if (i < total) {
-    int k = g;
-    for (; k + 7 * RED_GRP < nslices; k += 8 * RED_GRP) {         // eight slices in flight per thread, added in slice order
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = part[(int64_t)(k + u * RED_GRP) * total + i];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += (double)v[u];
-    }
-    for (; k < nslices; k += RED_GRP) s += (double)part[(int64_t)k * total + i];
-  }
-  sm[g][o] = s;
-  __syncthreads();
+  const double s = cmr_group_sum(sm, i < total ? cmr_slice_sum<RED_GRP, 8>(part + i, total, nslices, g) : 0.0, g, o, i < total);
   if (g == 0 && i < total) {
-#pragma unroll
-    for (int k = 1; k < RED_GRP; ++k) s += sm[k][o];
     const int ci = i % Cin, co = (i / Cin) % Cout, tap = i / (Cin * Cout);
     dw[((int64_t)co * Cin + ci) * 9 + tap] = (float)s;
   }
+}
+
+// dw = the sum of the nslices partial gradients at part; db likewise from part_b when asked
+static int conv3x3_wgrad_reduce(const float* part, const float* part_b, int nslices, int Cout, int Cin, float* dw, float* db, hipStream_t stream) {
+  hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3((9 * Cout * Cin + RED_OUT - 1) / RED_OUT), dim3(256), 0, stream, part, nslices, Cout, Cin, dw);
+  if (db) hipLaunchKernelGGL(conv_bias_reduce_kernel, dim3((Cout + 31) / 32), dim3(1024), 0, stream, part_b, nslices, Cout, db);
+  return cmr_launch_status();
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1117,57 +1102,7 @@ __global__ __launch_bounds__(256) void linear_wgrad_lds_kernel(const float* __re
   }
 }
 
-// outputs [0, n k): dW entries; [n k, n k + n): db entries (when part_b)
-// (round 3) A thread used to walk its 96 slices of a 768-slice sum one dependent load at a time: 130 workgroups of 256 threads took 30-35 us
-// for 12.8 MB (profiles/r03_pmc_lwgrad.txt: 92 % of the wave cycles waiting on memory) -- more than a third of the weight gradient of a
-// 524 288-row map.  Now 32 slice groups (1 024 threads) and LRED_U independent loads in flight per thread; sums still in double, fixed order.
-constexpr int LRED_GRP = 32, LRED_U = 8;
-__global__ __launch_bounds__(RED_OUT * LRED_GRP) void linear_wgrad_reduce_kernel(const float* __restrict__ part, const float* __restrict__ part_b, int nslices,
-                                                                  int npad, int kpad, int nblk, int n, int k, float* __restrict__ dw,
-                                                                  int64_t lddw, int accumulate, float* __restrict__ db, int acc_db) {
-  __shared__ double sm[LRED_GRP][RED_OUT];
-  const int o = threadIdx.x % RED_OUT, g = threadIdx.x / RED_OUT;
-  const int64_t i = (int64_t)blockIdx.x * RED_OUT + o;
-  const int64_t nk = (int64_t)n * k, total = nk + (part_b ? n : 0);
-  double s = 0.0;
-  int row = 0, col = 0;
-  const float* p = part;
-  int64_t stride = 0;
-  if (i < nk) {
-    row = (int)(i / k), col = (int)(i - (int64_t)row * k);
-    const int nb = row / npad, kb = col / kpad;
-    p = part + ((int64_t)kb * nblk + nb) * nslices * npad * kpad + (int64_t)(row - nb * npad) * kpad + (col - kb * kpad);
-    stride = (int64_t)npad * kpad;
-  } else if (i < total) {
-    row = (int)(i - nk);
-    const int nb = row / npad;
-    p = part_b + (int64_t)nb * nslices * npad + (row - nb * npad);
-    stride = npad;
-  }
-  if (i < total)
-    for (int j0 = g; j0 < nslices; j0 += LRED_GRP * LRED_U) {
-      float v[LRED_U];
-#pragma unroll
-      for (int u = 0; u < LRED_U; ++u) {
-        const int j = j0 + u * LRED_GRP;
-        v[u] = p[(int64_t)(j < nslices ? j : j0) * stride];          // (branch-free: a slice past the end re-reads j0 and is dropped below)
-      }
-#pragma unroll
-      for (int u = 0; u < LRED_U; ++u) s += j0 + u * LRED_GRP < nslices ? (double)v[u] : 0.0;
-    }
-  sm[g][o] = s;
-  __syncthreads();
-  if (g == 0 && i < total) {
-#pragma unroll
-    for (int j = 1; j < LRED_GRP; ++j) s += sm[j][o];
-    if (i < nk) {
-      float* d = dw + (int64_t)row * lddw + col;
-      *d = accumulate ? *d + (float)s : (float)s;
-    } else {
-      db[row] = acc_db ? db[row] + (float)s : (float)s;
-    }
-  }
-}
+// (the slices are summed by linear_wgrad_reduce_kernel, cmr_reduce.h: bn_linear.hip launches it too)
 
 // ------------------------------------------------------------------------------------------------------------------
 // conv3x3 weights [Co][Ci][3][3] (the nn.Conv2d parameter, read straight from the flat bucket) -> the operand layouts
@@ -1353,9 +1288,7 @@ extern "C" int cmr_conv3x3_wgrad_f32(const float* x, const float* dy, int B, int
     const int rc = nci == 4 ? wgrad_launch_lds<conv3x3_wgrad_lds_kernel<4>>(grid, dim3(256), smem, stream, x, dy, B, H, W, Cout, lp.rps, part)
                             : wgrad_launch_lds<conv3x3_wgrad_lds_kernel<2>>(grid, dim3(256), smem, stream, x, dy, B, H, W, Cout, lp.rps, part);
     if (rc != CMR_OK) return rc;
-    hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3((9 * Cout * Cin + RED_OUT - 1) / RED_OUT), dim3(256), 0, stream, (const float*)part,
-                       lp.groups * nsplit, Cout, Cin, dw);
-    return cmr_launch_status();
+    return conv3x3_wgrad_reduce(part, nullptr, lp.groups * nsplit, Cout, Cin, dw, nullptr, stream);
   }
   const int slices = wgrad_slices(((int64_t)B * H * W + 1) / 2);
   CMR_REQUIRE(ws_bytes >= (int64_t)slices * nsplit * 9 * Cout * Cin * (int64_t)sizeof(float));
@@ -1366,9 +1299,7 @@ extern "C" int cmr_conv3x3_wgrad_f32(const float* x, const float* dy, int B, int
     hipLaunchKernelGGL(conv3x3_wgrad_kernel<2>, grid, dim3(256), 0, stream, x, dy, B, H, W, Cin, Cout, part);
   else
     hipLaunchKernelGGL(conv3x3_wgrad_kernel<1>, grid, dim3(256), 0, stream, x, dy, B, H, W, Cin, Cout, part);
-  hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3((9 * Cout * Cin + RED_OUT - 1) / RED_OUT), dim3(256), 0, stream, (const float*)part,
-                     slices * nsplit, Cout, Cin, dw);
-  return cmr_launch_status();
+  return conv3x3_wgrad_reduce(part, nullptr, slices * nsplit, Cout, Cin, dw, nullptr, stream);
 }
 
 // stride-2 convolution: x [B][H][W][Cin] (H, W even), dy [B][H/2][W/2][Cout]; workspace = cmr_conv3x3_wgrad_workspace_bytes(B, H/2, W/2, ...)
@@ -1385,9 +1316,7 @@ extern "C" int cmr_conv3x3_wgrad_s2_f32(const float* x, const float* dy, int B, 
   if (nci == 4) hipLaunchKernelGGL(conv3x3_wgrad_s2_kernel<4>, grid, dim3(256), 0, stream, x, dy, B, H, W, Cin, Cout, part);
   else if (nci == 2) hipLaunchKernelGGL(conv3x3_wgrad_s2_kernel<2>, grid, dim3(256), 0, stream, x, dy, B, H, W, Cin, Cout, part);
   else hipLaunchKernelGGL(conv3x3_wgrad_s2_kernel<1>, grid, dim3(256), 0, stream, x, dy, B, H, W, Cin, Cout, part);
-  hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3((9 * Cout * Cin + RED_OUT - 1) / RED_OUT), dim3(256), 0, stream, (const float*)part,
-                     slices * nsplit, Cout, Cin, dw);
-  return cmr_launch_status();
+  return conv3x3_wgrad_reduce(part, nullptr, slices * nsplit, Cout, Cin, dw, nullptr, stream);
 }
 
 extern "C" int cmr_conv3x3_wgrad_bias_bf16_f32(const float* x, const float* dy, int B, int H, int W, int Cin, int Cout, float* dw, float* db,
@@ -1437,9 +1366,7 @@ static int wgrad_bias_bf16(const float* x, const float* xscale, const float* xsh
     const int rc = xscale ? (db ? CMR_WT2(true, true) : CMR_WT2(false, true)) : (db ? CMR_WT2(true, false) : CMR_WT2(false, false));
 #undef CMR_WT2
     if (rc != CMR_OK) return rc;
-    hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3((9 * Cout * Cin + RED_OUT - 1) / RED_OUT), dim3(256), 0, stream, (const float*)part, groups, Cout, Cin, dw);
-    if (db) hipLaunchKernelGGL(conv_bias_reduce_kernel, dim3((Cout + 31) / 32), dim3(1024), 0, stream, (const float*)part_b, groups, Cout, db);
-    return cmr_launch_status();
+    return conv3x3_wgrad_reduce(part, part_b, groups, Cout, Cin, dw, db, stream);
   }
   // persistent workgroups, one per CU (288 accumulator registers per wave at two cout tiles), over all cout groups; ~8 column strips
   // of >= 4 rows per workgroup
@@ -1472,10 +1399,7 @@ static int wgrad_bias_bf16(const float* x, const float* xscale, const float* xsh
   else CMR_WGB_LAUNCH(2, 1, 32, false, 1);
 #undef CMR_WGB_LAUNCH
   if (rc != CMR_OK) return rc;
-  hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3((9 * Cout * Cin + RED_OUT - 1) / RED_OUT), dim3(256), 0, stream, (const float*)part,
-                     groups * nsplit, Cout, Cin, dw);
-  if (db) hipLaunchKernelGGL(conv_bias_reduce_kernel, dim3((Cout + 31) / 32), dim3(1024), 0, stream, (const float*)part_b, groups * nsplit, Cout, db);
-  return cmr_launch_status();
+  return conv3x3_wgrad_reduce(part, part_b, groups * nsplit, Cout, Cin, dw, db, stream);
 }
 
 namespace {
@@ -1546,9 +1470,7 @@ extern "C" int cmr_linear_wgrad_f32(const float* dy, int64_t lddy, int n, const 
         else CMR_LWL(4, 1);
 #undef CMR_LWL
         if (rc != CMR_OK) return rc;
-        const int64_t outs = (int64_t)n * k + (db ? n : 0);
-        hipLaunchKernelGGL(linear_wgrad_reduce_kernel, dim3((unsigned)((outs + RED_OUT - 1) / RED_OUT)), dim3(RED_OUT * LRED_GRP), 0, stream, (const float*)part,
-                           (const float*)pb, groups, n, k, 1, n, k, dw, lddw, accumulate, db, accumulate_db);
+        cmr_linear_wgrad_reduce(part, pb, groups, n, k, 1, n, k, dw, lddw, accumulate, db, accumulate_db, stream);
         return cmr_launch_status();
       }
     }
@@ -1566,9 +1488,7 @@ extern "C" int cmr_linear_wgrad_f32(const float* dy, int64_t lddy, int n, const 
   else if (p.ntp == 4 && p.ktp == 2) CMR_LW(4, 2);
   else CMR_LW(4, 4);
 #undef CMR_LW
-  const int64_t outs = (int64_t)n * k + (db ? n : 0);
-  hipLaunchKernelGGL(linear_wgrad_reduce_kernel, dim3((unsigned)((outs + RED_OUT - 1) / RED_OUT)), dim3(RED_OUT * LRED_GRP), 0, stream, (const float*)part,
-                     (const float*)part_b, p.slices * (4 / p.ntp), p.ntp * 32, p.ktp * 32, p.nblk, n, k, dw, lddw, accumulate, db, accumulate_db);
+  cmr_linear_wgrad_reduce(part, part_b, p.slices * (4 / p.ntp), p.ntp * 32, p.ktp * 32, p.nblk, n, k, dw, lddw, accumulate, db, accumulate_db, stream);
   return cmr_launch_status();
 }
 

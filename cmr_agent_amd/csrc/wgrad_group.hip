@@ -10,6 +10,7 @@
 //             kernels (vit_train.hip) left behind.
 // Deterministic: no atomics.  Problems / jobs are passed BY VALUE (host descriptor array -> kernel arguments): nothing to upload.
 #include "cmr_common.h"
+#include "cmr_reduce.h"
 
 namespace {
 
@@ -142,7 +143,6 @@ __global__ __launch_bounds__(WR_OUT * WR_GRP) void wgrad_group_reduce_kernel(con
     for (int i = 1; i < WG_MAXP; ++i)
       if (i < a.nprob && b >= a.p[i].red0) pi = i;
   }
-  double s = 0.0;
   const float* p = a.ws;
   int64_t stride = 0, total = 0, i = 0;
   int nsl = 0;
@@ -171,22 +171,10 @@ __global__ __launch_bounds__(WR_OUT * WR_GRP) void wgrad_group_reduce_kernel(con
       stride = WG_T;
     }
   }
-  if (i < total)
-    for (int j0 = grp; j0 < nsl; j0 += WR_GRP * WR_U) {       // WR_U loads in flight per thread (one dependent load per iteration left the
-      float v[WR_U];                                             // reduction a chain of memory round trips: 28 us for a transformer block)
-#pragma unroll
-      for (int u = 0; u < WR_U; ++u) {
-        const int j = j0 + u * WR_GRP;
-        v[u] = p[(int64_t)(j < nsl ? j : j0) * stride];          // branch-free: a slice past the end re-reads j0 and is dropped below
-      }
-#pragma unroll
-      for (int u = 0; u < WR_U; ++u) s += j0 + u * WR_GRP < nsl ? (double)v[u] : 0.0;
-    }
-  sm[grp][o] = s;
-  __syncthreads();
+  // WR_U loads in flight per thread (one dependent load per iteration left the reduction a chain of memory round trips: 28 us for a
+  // transformer block)
+  const double s = cmr_group_sum(sm, i < total ? cmr_slice_sum<WR_GRP, WR_U>(p, stride, nsl, grp) : 0.0, grp, o, i < total);
   if (grp != 0 || i >= total) return;
-#pragma unroll
-  for (int j = 1; j < WR_GRP; ++j) s += sm[j][o];
   if (vi >= 0) {
     const WgVector& V = a.v[vi];
     float* d = i < V.len ? V.out_a + i : V.out_b + (i - V.len);
