@@ -18,7 +18,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "cmr_hip.h")
 AB_LIB_PATH = os.path.join(_PKG, "lib", "libcmr_hip_ab.so")
 AB_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "cmr_hip_ab.h")
 
-_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32, "float": ctypes.c_float, "hipStream_t": ctypes.c_void_p}
+_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32, "float": ctypes.c_float, "double": ctypes.c_double, "hipStream_t": ctypes.c_void_p}
 _RET = {"int": ctypes.c_int, "int64_t": ctypes.c_int64}
 
 

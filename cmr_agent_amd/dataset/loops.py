@@ -20,7 +20,8 @@ how far the file's inv(P_j) P_i lies from the measured pose.  The closing line i
     loops: <a> accepted of <c> candidates of <F> frames
 
 --out FILE writes one line per accepted edge (`align.write_edges`): i j, the 12 numbers of the pose that maps frame i into frame j, then
-dist rmse pairs.  No default of this command is tuned on real data.  A pose-graph solve over the chain and these edges is not part of it.
+dist rmse pairs.  No default of this command is tuned on real data.  The pose-graph solve over the chain and these edges is
+`python -m cmr_agent_amd.dataset.posegraph`, which reads this file.
 
     python -m cmr_agent_amd.dataset.loops --root DIR --sequence S [--frames A:B --rings 20 --sectors 60 --max-range 80 --min-range 0
                                           --height 2.0 --gap 50 --top 1 --max-desc-dist 0.3 --min-cols S/4]

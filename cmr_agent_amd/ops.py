@@ -3296,3 +3296,150 @@ def scan_shift_yaw(shift, sectors):
     k = np.mod(-np.asarray(shift, dtype=np.int64), sectors)
     yaw = np.where(2 * k > sectors, k - sectors, k) * (2.0 * np.pi / sectors)
     return float(yaw) if yaw.ndim == 0 else yaw
+
+
+# ---- a pose-graph solve over a chain of poses and its loop edges (csrc/pose_graph.hip) ------------------------------------------
+PG_MAX_ITERS = 100
+PG_MAX_CG_ITERS = 4096
+PG_STATUS = ("converged", "iterations exhausted", "singular block or non-finite value", "wide edges at the start")
+
+
+class PoseGraphTerms(collections.namedtuple("PoseGraphTerms", "r chi scale A b cost wide")):
+    """pose_graph_linearize's result, float64 on the device: r [E, 6] = (phi, rho), chi [E], scale [E] = the Huber factor s_e, A [E, 21] =
+    s_e J^T W J (upper triangle, row by row), b [E, 6] = s_e J^T W r; cost (python float) and wide (int, edges turned by more than 3 rad)."""
+
+
+class PoseGraphResult(collections.namedtuple("PoseGraphResult", "poses cost iterations status trace")):
+    """pose_graph_optimize's result: poses float64 [F, 4, 4] on the device; cost at them; iterations = steps executed (an undone one
+    counts); status 0 .. 3 (PG_STATUS); trace float64 [iters, 5] = cost the step started from, CG iterations used, sqrt(r.z / r0.z0) at
+    the end of CG, max |dw|, max |dv| per executed step (host)."""
+
+
+def _pg_edges(who, edges):
+    if not isinstance(edges, torch.Tensor) or edges.dtype != torch.int32 or edges.dim() != 2 or edges.shape[1] != 2:
+        raise ValueError("%s: edges must be an int32 [E, 2] tensor, got %s %s" % ((who,) + _got(edges)))
+    return edges.contiguous()
+
+
+def _pg_f64(who, name, t, *shape):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+        raise ValueError("%s: %s must be a float64 tensor, got %s %s" % ((who, name) + _got(t)))
+    _shaped(who, name, t, *shape)
+    return t.contiguous()
+
+
+def _pg_graph(who, poses, edges, meas, weights, fixed=None):
+    """The tensors of a graph, checked: types, shapes, one device, sizes, and -- in ONE host read -- indices, weights and finiteness.
+    -> poses, edges, meas, weights, fixed (uint8 [F]; None in, None out), F, E."""
+    poses = _pg_f64(who, "poses", poses, "F", 4, 4)
+    edges = _pg_edges(who, edges)
+    F, E = poses.shape[0], edges.shape[0]
+    meas = _pg_f64(who, "meas", meas, E, 4, 4)
+    weights = _pg_f64(who, "weights", weights, E, 2)
+    if F < 1:
+        raise ValueError("%s: need at least one pose" % who)
+    if 6 * F >= 1 << 31 or 28 * E >= 1 << 31:
+        raise ValueError("%s: %d poses and %d edges: 6 F and 28 E must stay below 2^31" % (who, F, E))
+    ts = [poses, edges, meas, weights]
+    if fixed is not None:
+        if not isinstance(fixed, torch.Tensor) or fixed.dtype != torch.bool or tuple(fixed.shape) != (F,):
+            raise ValueError("%s: fixed must be a bool [%d] tensor or None, got %s %s" % ((who, F) + _got(fixed)))
+        ts.append(fixed)
+    if any(t.device != poses.device for t in ts):
+        raise ValueError("%s: poses, edges, meas, weights and fixed must be on one device" % who)
+    flags = [(edges[:, 0] == edges[:, 1]).any(), ((edges < 0) | (edges >= F)).any(), (~torch.isfinite(weights) | (weights < 0)).any(),
+             (~torch.isfinite(poses)).any(), (~torch.isfinite(meas)).any(),
+             fixed.all() if fixed is not None else torch.zeros((), dtype=torch.bool, device=poses.device)]
+    same, outside, weight, pose, measured, none_free = torch.stack(flags).cpu().tolist()                  # the one host read
+    if same:
+        raise ValueError("%s: an edge joins a pose to itself" % who)
+    if outside:
+        raise ValueError("%s: an edge names a pose outside [0, %d)" % (who, F))
+    if weight:
+        raise ValueError("%s: weights must be finite and >= 0" % who)
+    if pose or measured:
+        raise ValueError("%s: %s must be finite" % (who, "poses" if pose else "meas"))
+    if none_free:
+        raise ValueError("%s: every pose is fixed: there is nothing to solve" % who)
+    return poses, edges, meas, weights, (fixed.to(torch.uint8).contiguous() if fixed is not None else None), F, E
+
+
+def _pg_on_gpu(who, t):
+    if not t.is_cuda:
+        raise ValueError("%s: the tensors must be on a GPU (there is no CPU path)" % who)
+
+
+def pose_graph_incidence(edges, F):
+    """The incidence of a graph's F nodes as a CSR, on edges' device (pure torch; runs on the CPU too): offsets int32 [F + 1], edge numbers
+    int32 [2 E] -- a node's edges ascending, by a STABLE sort, a duplicate edge once per copy -- and signs int32 [2 E]: +1 where the node
+    is the edge's i, -1 where it is its j.  edges int32 [E, 2] with every index in [0, F) (pose_graph_optimize checks that; here an index
+    outside raises from torch or is a ValueError)."""
+    who = "pose_graph_incidence"
+    edges = _pg_edges(who, edges)
+    F = _int_arg(who, "F", F, 1, (1 << 31) // 6)
+    nodes = edges.reshape(-1).to(torch.int64)                          # entry 2 e is edge e's i, 2 e + 1 its j
+    if nodes.numel() and (int(nodes.min()) < 0 or int(nodes.max()) >= F):
+        raise ValueError("%s: an edge names a pose outside [0, %d)" % (who, F))
+    order = torch.sort(nodes, stable=True).indices
+    counts = torch.bincount(nodes, minlength=F)
+    offsets = torch.zeros((F + 1,), dtype=torch.int64, device=edges.device)
+    offsets[1:] = torch.cumsum(counts, 0)
+    return offsets.to(torch.int32), (order // 2).to(torch.int32), (1 - 2 * (order % 2)).to(torch.int32)
+
+
+def pose_graph_linearize(poses, edges, meas, weights, huber=0.0):
+    """Every edge's residual, weight and Gauss-Newton terms at the given poses (cmr_pose_graph_linearize_f64; the contract is the
+    header's).  poses float64 [F, 4, 4] (X_n maps frame n into the first frame), edges int32 [E, 2] = (i, j), meas float64 [E, 4, 4] (Z_e
+    maps frame i into frame j), weights float64 [E, 2] = (w_rot, w_trans).  -> PoseGraphTerms.  chi before and after a solve is how a wrong
+    loop shows.  E = 0 gives empty terms and no launch."""
+    who = "pose_graph_linearize"
+    huber = _f32_arg(who, "huber", huber, "be a finite number >= 0", as_f32=False, bools=False)
+    poses, edges, meas, weights, _, F, E = _pg_graph(who, poses, edges, meas, weights)
+    dev = poses.device
+    r, chi, scale, A, b = (torch.empty((E,) + s, dtype=torch.float64, device=dev) for s in ((6,), (), (), (21,), (6,)))
+    if E == 0:
+        return PoseGraphTerms(r, chi, scale, A, b, 0.0, 0)
+    _pg_on_gpu(who, poses)
+    cost = torch.empty((1,), dtype=torch.float64, device=dev)
+    wide = torch.empty((1,), dtype=torch.int32, device=dev)
+    nb = _lib.load().cmr_pose_graph_linearize_workspace_bytes(E)
+    ws = _ws(nb, dev)
+    _lib.call("cmr_pose_graph_linearize_f64", _p(poses), F, _p(edges), _p(meas), _p(weights), E, huber, _p(r), _p(chi), _p(scale), _p(A), _p(b),
+              _p(cost), _p(wide), _p(ws), nb, _stream())
+    return PoseGraphTerms(r, chi, scale, A, b, float(cost.cpu()[0]), int(wide.cpu()[0]))
+
+
+def pose_graph_optimize(poses, edges, meas, weights, fixed=None, huber=0.0, iters=20, cg_iters=200, cg_tol=1e-8, damping=0.0, tol_rot=1e-9,
+                        tol_trans=1e-9):
+    """Gauss-Newton over a pose graph, the linear system by matrix-free preconditioned conjugate gradients, the whole loop on the device
+    (cmr_pose_graph_optimize_f64; the contract is the header's).  Tensors as pose_graph_linearize's; fixed bool [F]: the poses that do not
+    move (default: pose 0 alone).  huber: edges with chi above it are down-weighted by huber / chi (0: off); damping is added to H's
+    diagonal.  The launch count depends on (iters, cg_iters) alone; the result is read once at the end.  -> PoseGraphResult.  E = 0 or
+    F = 1 returns the poses unchanged with status 0 and no launch."""
+    who = "pose_graph_optimize"
+    huber = _f32_arg(who, "huber", huber, "be a finite number >= 0", as_f32=False, bools=False)
+    iters = _int_arg(who, "iters", iters, 0, PG_MAX_ITERS)
+    cg_iters = _int_arg(who, "cg_iters", cg_iters, 0, PG_MAX_CG_ITERS)
+    cg_tol = _f32_arg(who, "cg_tol", cg_tol, "be a finite number >= 0", as_f32=False, bools=False)
+    damping = _f32_arg(who, "damping", damping, "be a finite number >= 0", as_f32=False, bools=False)
+    tol_rot = _f32_arg(who, "tol_rot", tol_rot, "be a finite number >= 0", as_f32=False, bools=False)
+    tol_trans = _f32_arg(who, "tol_trans", tol_trans, "be a finite number >= 0", as_f32=False, bools=False)
+    if fixed is None and torch.is_tensor(poses) and poses.dim() == 3 and poses.shape[0] > 1:
+        fixed = torch.zeros((poses.shape[0],), dtype=torch.bool, device=poses.device)
+        fixed[0] = True
+    poses, edges, meas, weights, fixed, F, E = _pg_graph(who, poses, edges, meas, weights, fixed)
+    dev = poses.device
+    if E == 0 or F == 1:
+        return PoseGraphResult(poses.clone(), 0.0, 0, 0, torch.zeros((iters, 5), dtype=torch.float64))
+    _pg_on_gpu(who, poses)
+    offsets, numbers, _ = pose_graph_incidence(edges, F)
+    out = torch.empty((F, 4, 4), dtype=torch.float64, device=dev)
+    cost = torch.empty((1,), dtype=torch.float64, device=dev)
+    trace = torch.empty((iters, 5), dtype=torch.float64, device=dev)
+    status = torch.empty((3,), dtype=torch.int32, device=dev)
+    nb = _lib.load().cmr_pose_graph_optimize_workspace_bytes(F, E)
+    ws = _ws(nb, dev)
+    _lib.call("cmr_pose_graph_optimize_f64", _p(poses), F, _p(edges), _p(meas), _p(weights), E, _p(offsets), _p(numbers), _p(fixed), huber, iters,
+              cg_iters, cg_tol, damping, tol_rot, tol_trans, _p(out), _p(cost), _p(trace), _p(status), _p(ws), nb, _stream())
+    code, executed, _ = (int(v) for v in status.cpu())                  # the one host read (cost and trace ride behind it)
+    return PoseGraphResult(out, float(cost.cpu()[0]), executed, code, trace.cpu())

@@ -316,6 +316,16 @@ WORK = {
     "cmr_scan_descriptor_f32": lambda a: (0, a["N"] * 12 + a["R"] * a["S"] * 4),
     "cmr_scan_match_f32": lambda a: (float(a["Q"]) * a["N"] * (2 * a["R"] * a["S"] * a["S"] + a["S"] * a["S"]),
                                      3 * F * (a["Q"] + a["N"]) * a["R"] * a["S"] + 8 * a["Q"] * a["N"]),
+    # DESIGN.md 4am, all float64.  Linearise: ~600 FLOP per edge (three 3 x 3 products, Log, the Jacobian, 21 + 6 weighted sums); two
+    # poses, the measurement and the weights read (2 x 128 + 128 + 16 B), 35 doubles written.  Optimize: per outer iteration one
+    # linearisation and the node blocks (every edge's 27 doubles twice, ~700 FLOP per node for the six solves), per CG iteration every
+    # edge's A and the neighbour's z and p from both ends (2 x (21 + 12) doubles, 2 x 84 FLOP) and ~20 doubles and ~100 FLOP per node.
+    # The launch floor that decides its time at a few thousand nodes is not work and is not priced.
+    "cmr_pose_graph_linearize_f64": lambda a: (600.0 * a["E"], a["E"] * (400 + 35 * 8)),
+    "cmr_pose_graph_optimize_f64": lambda a: (
+        (a["iters"] + 1) * 600.0 * a["E"] + a["iters"] * (700.0 * a["F"] + a["cg_iters"] * (168.0 * a["E"] + 100.0 * a["F"])),
+        (a["iters"] + 1) * a["E"] * (400 + 27 * 8) + a["iters"] * (a["E"] * 2 * 27 * 8 + a["F"] * 40 * 8
+                                                                   + a["cg_iters"] * (a["E"] * 2 * 33 * 8 + a["F"] * 20 * 8))),
 }
 
 # Multiplies the kernel ISSUES on the matrix cores per algorithmic multiply: F(2x2,3x3) Winograd computes 2x2 outputs with 16

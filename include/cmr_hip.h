@@ -1620,6 +1620,64 @@ int64_t cmr_scan_match_workspace_bytes(int64_t Q, int64_t N, int R, int S);
 int cmr_scan_match_f32(const float* queries, int64_t Q, const float* cands, int64_t N, int R, int S, const int32_t* limit, int min_cols,
                        float* dist, int32_t* shift, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+/* ---- a pose-graph solve over a chain of poses and its loop edges (csrc/pose_graph.hip) ----------------------------------
+ * Port extension: the reference has no counterpart.  Everything is float64.
+ *
+ * NODES   poses [F][4][4] row-major, X_n = (R_n, t_n) maps frame n into the first frame; the upper 3 x 4 is read.
+ * EDGES   edges int32 [E][2] = (i, j), meas [E][4][4] = Z_e, which maps frame i into frame j (Z ~ inv(X_j) X_i), weights [E][2] =
+ *         (w_rot, w_trans), finite and >= 0.  An edge whose indices do not name two different nodes has zero terms.
+ * RESIDUAL  R_D = R_Z^T R_j^T R_i,  t_D = R_Z^T (R_j^T (t_i - t_j) - t_Z);  r = (phi, rho), rho = t_D, phi = Log(R_D) from the
+ *         antisymmetric part:  a = 1/2 (R32 - R23, R13 - R31, R21 - R12), s = |a|, c = (trace - 1) / 2, theta = atan2(s, c),
+ *         phi = (theta / s) a, with theta / s = 1 + s^2 / 6 for s < 1e-8.  An edge with theta > 3 is WIDE: Log loses its digits near pi
+ *         and such an edge is a wrong loop, not a measurement; wide edges are counted.
+ * JACOBIAN  for the left increment X <- [Exp(w) | v] X, xi = (w, v):
+ *           d r / d xi_i = J = [[Jr^-1(phi) R_i^T, 0], [-R_Z^T R_j^T [t_i]x, R_Z^T R_j^T]],  d r / d xi_j = -J,
+ *         Jr^-1(phi) = I + 1/2 [phi]x + k [phi]x^2,  k = 1 / theta^2 - (1 + cos theta) / (2 theta sin theta),  k = 1/12 for theta < 1e-4.
+ * WEIGHT  chi^2 = w_rot |phi|^2 + w_trans |rho|^2.  huber = k > 0:  s_e = 1 and cost 1/2 chi^2 for chi <= k, s_e = k / chi and cost
+ *         k chi - 1/2 k^2 above;  huber = 0: s_e = 1 always.  The cost is formed from the ROUNDED chi, every operation rounded on its
+ *         own, as (0.5 chi) chi and k chi - (0.5 k) k: an edge's cost follows from its chi bit for bit.  A_e = s_e J^T W J (21 upper entries, row by row), b_e = s_e J^T W r,
+ *         W = diag(w_rot x 3, w_trans x 3).
+ *
+ * cmr_pose_graph_linearize_f64: per edge r [E][6], chi [E], scale [E] = s_e, A [E][21], b [E][6]; cost [1] = the sum of the edges' costs
+ * (the lanes of a workgroup of 256 consecutive edges by the wave butterfly and then in wave order, the workgroups' slots in slot order);
+ * wide int32 [1].  0 < F, E with 6 F < 2^31 and 28 E < 2^31.  Workspace of cmr_pose_graph_linearize_workspace_bytes(E), 16-byte aligned.
+ *
+ * cmr_pose_graph_optimize_f64: Gauss-Newton from poses_in, the whole loop on the device and on the caller's stream, in
+ * 2 (iters + 1) + iters (2 + 2 cg_iters) + 2 launches whatever the data (0 <= iters <= 100, 0 <= cg_iters <= 4096).
+ *   system  J_j = -J_i, so H = sum_e (E_i - E_j) A_e (E_i - E_j)^T + damping I and g = sum_e (E_i - E_j) b_e: a graph Laplacian with 6 x 6
+ *           weights.  Nodes with fixed[n] != 0 (bytes [F]) are removed: their rows of every vector are 0 and they do not move.
+ *   sums    a node's incident edges are added in INCIDENCE order: inc_offsets int32 [F + 1] and inc_edges int32 [2 E] are the CSR of the
+ *           incidence, a node's edge numbers ascending (which end of the edge the node is, is read from edges).  A dot product is six
+ *           components in order per node, the nodes of a workgroup of 256 by the wave butterfly and then in wave order, the workgroups'
+ *           slots in slot order.  No atomics, one writer per slot: two calls agree bit for bit.
+ *   solve   H delta = -g by preconditioned conjugate gradients, matrix-free.  Preconditioner: M_n = sum_{e at n} A_e + damping I, inverted
+ *           once per outer iteration (the 6 x 6 Cholesky of the pose refinement against the six unit vectors; a pivot must exceed 1e-13 of
+ *           its diagonal entry).  x_0 = 0, r_0 = -g, z = M^-1 r, p = z; then q = H p (q_n = sum_{e at n} +- A_e (p_i - p_j), then
+ *           + damping p_n), alpha = r.z / p.q, x += alpha p, r -= alpha q, z = M^-1 r, beta = r.z / (previous r.z), p = z + beta p.
+ *           It stops before iteration c when r.z <= cg_tol^2 (r_0.z_0), after cg_iters, or at a p.q that is not positive and finite.
+ *   step    X_n <- [Exp(dw_n) | dv_n] X_n, delta_n = (dw_n, dv_n).
+ *   rules   the cost is evaluated at the stepped poses.  A step with max_n |dw_n| <= tol_rot and max_n |dv_n| <= tol_trans stands and ends
+ *           the loop (status 0) -- it changes the cost by less than the cost's rounding, so the costs are not compared.  Any other step
+ *           whose cost is not below the cost before it is undone and ends the loop (status 0); else it stands and the loop goes on.  The
+ *           last step's cost is evaluated too, so iters steps take iters + 1 linearisations.
+ * Outputs: poses [F][4][4];  cost [1] = the cost at them;  trace [iters][5] = {cost the step started from, CG iterations used,
+ * sqrt(r.z / r_0.z_0) at the end of CG, max |dw|, max |dv|} per executed step, zero rows after;  status int32 [3] = {code, steps executed
+ * (an undone one counts), wide edges at the start}:
+ *   0 converged, by either rule;  1 iterations exhausted;  2 a free node's block does not factor (a free node without edges at damping = 0
+ *   is one), or a cost or an update is not finite: the poses are those the failing step started from;  3 wide edges at the start: nothing
+ *   is solved, poses = poses_in.
+ * Indices are guarded at every load and store that depends on them: whatever edges, inc_offsets and inc_edges hold, nothing outside the
+ * arrays is touched.  Workspace of cmr_pose_graph_optimize_workspace_bytes(F, E), 16-byte aligned. */
+int64_t cmr_pose_graph_linearize_workspace_bytes(int64_t E);
+int cmr_pose_graph_linearize_f64(const double* poses, int64_t F, const int32_t* edges, const double* meas, const double* weights, int64_t E,
+                                 double huber, double* r, double* chi, double* scale, double* A, double* b, double* cost, int32_t* wide,
+                                 void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int64_t cmr_pose_graph_optimize_workspace_bytes(int64_t F, int64_t E);
+int cmr_pose_graph_optimize_f64(const double* poses_in, int64_t F, const int32_t* edges, const double* meas, const double* weights, int64_t E,
+                                const int32_t* inc_offsets, const int32_t* inc_edges, const uint8_t* fixed, double huber, int iters,
+                                int cg_iters, double cg_tol, double damping, double tol_rot, double tol_trans, double* poses, double* cost,
+                                double* trace, int32_t* status, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
