@@ -77,6 +77,10 @@ Without these flags the output is unchanged.
 (<seq>/velodyne/*.bin) and voxel-downsampled on the device as it is loaded (FrameDataset(..., from_raw=True));
 `python -m cmr_agent_amd.dataset.prepare --root DIR` writes the folder once instead.  Without the flag nothing changes.
 
+--pc-subdir NAME (with --data-root): the clouds are read from <seq>/NAME instead of the prepared folder
+(FrameDataset(..., pc_subdir=NAME)) -- the views of a map that `python -m cmr_agent_amd.dataset.view` wrote, so that the images are
+registered against the map as a sensor at the frame's pose would see it.  Without the flag nothing changes.
+
 Pairs come from the synthetic generator (cmr_agent_amd.utils.synthetic) unless --data-root names a dataset in the reference's layout
 (its 'test' split), and the weights are the deterministic hash fill unless --geo-ckpt points at a reference-format state_dict."""
 import argparse
@@ -99,9 +103,9 @@ from cmr_agent_amd.models import MultiHeadModel  # noqa: E402
 from cmr_agent_amd.models.MultiHeadModel import match_features  # noqa: E402
 from cmr_agent_amd.utils import hashfill, synthetic  # noqa: E402
 from cmr_agent_amd.utils.checkpoint import load_checked  # noqa: E402
-from cmr_agent_amd.utils.evalcli import (add_dense_flags, add_mi_flags, add_paint_flags, add_raw_flag, add_surfel_flags,  # noqa: E402
+from cmr_agent_amd.utils.evalcli import (add_dense_flags, add_mi_flags, add_paint_flags, add_pc_subdir_flag, add_raw_flag, add_surfel_flags,  # noqa: E402
                                          add_visible_flags, dense_option, dense_pairs, guided_rounds, mi_option, paint_option, paint_pairs,
-                                         print_mi, print_recall, print_visible, raw_option, surfel_option, visible_option)
+                                         pc_subdir_option, print_mi, print_recall, print_visible, raw_option, surfel_option, visible_option)
 
 
 def _ratios(counts):
@@ -144,12 +148,14 @@ def main():
     add_dense_flags(ap, "--pnp")
     add_mi_flags(ap, "--pnp")
     add_raw_flag(ap)
+    add_pc_subdir_flag(ap)
     add_surfel_flags(ap)
     args = ap.parse_args()
     paint = paint_option(ap, args, "--pnp", args.pnp)
     dense = dense_option(ap, args, ops.DENSIFY_MAX_RADIUS, "--pnp", args.pnp)
     mi_bins = mi_option(ap, args, ops.POSE_MI_MAX_BINS, "--pnp", args.pnp)
     raw_kw = raw_option(ap, args)
+    raw_kw.update(pc_subdir_option(ap, args))
     if args.verify and not args.pnp:
         ap.error("--verify scores the PnP pose (and the --guided one): give --pnp as well")
     filtered = args.mutual or args.ratio is not None

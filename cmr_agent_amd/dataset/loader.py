@@ -122,12 +122,14 @@ class FrameDataset:
     (port extension; off by default, and then the sample dict is unchanged): the sample gains 'pc_normal' float32 [3, N], the
     surface normals (rows 4 - 6 of the cloud on disk) of the down-sampled points in the frame and the order of 'pc': turned by the rotation of
     P_random P_Tr, both rigid, the 3 x 3 product formed on the host in float64 and applied in fp32.  A file without those rows is a
-    ValueError naming the frame; with from_raw the scan is prepared with normals."""
+    ValueError naming the frame; with from_raw the scan is prepared with normals.  pc_subdir (port extension; None by
+    default, and then the folder is PC_SUBDIR as before): the clouds are read from that folder of every sequence instead, files of the same
+    layout -- the views of a map that `python -m cmr_agent_amd.dataset.view` writes, for one."""
 
     SEQUENCES = {"train": (0, 1, 2, 3, 4, 5, 6, 7, 8), "val": (9, 10), "test": (9, 10)}
     PC_SUBDIR = "voxel0.1-SNr0.6"
 
-    def __init__(self, root, config, mode, device=None, n_circle=512, with_intensity=False, from_raw=False, with_normals=False):
+    def __init__(self, root, config, mode, device=None, n_circle=512, with_intensity=False, from_raw=False, with_normals=False, pc_subdir=None):
         if mode not in self.SEQUENCES:
             raise Exception("Invalid mode...")                                     # KittiDataset.py:162
         self.root, self.config, self.mode = root, config, mode
@@ -138,6 +140,7 @@ class FrameDataset:
         self.with_intensity = bool(with_intensity)
         self.from_raw = bool(from_raw)
         self.with_normals = bool(with_normals)
+        self.pc_subdir = self.PC_SUBDIR if pc_subdir is None else str(pc_subdir)
         self.amp_t = (config.P_Tx_amplitude, config.P_Ty_amplitude, config.P_Tz_amplitude)
         self.amp_r = (config.P_Rx_amplitude, config.P_Ry_amplitude, config.P_Rz_amplitude)
         self.calib = read_calib(root)
@@ -151,7 +154,7 @@ class FrameDataset:
         for seq in self.SEQUENCES[self.mode]:
             img2 = os.path.join(self.root, cfg.data_color, "sequences", "%02d" % seq, "image_2")
             img3 = os.path.join(self.root, cfg.data_color, "sequences", "%02d" % seq, "image_3")
-            pcs = os.path.join(self.root, cfg.data_velodyne, "sequences", "%02d" % seq, self.PC_SUBDIR)
+            pcs = os.path.join(self.root, cfg.data_velodyne, "sequences", "%02d" % seq, self.pc_subdir)
             if self.from_raw and not os.path.isdir(pcs) and os.path.isdir(os.path.join(os.path.dirname(pcs), "velodyne")):
                 pcs = os.path.join(os.path.dirname(pcs), "velodyne")                # raw scans: read_frame prepares them
             if not (os.path.isdir(img2) and os.path.isdir(pcs)) or seq not in self.calib:

@@ -3443,3 +3443,143 @@ def pose_graph_optimize(poses, edges, meas, weights, fixed=None, huber=0.0, iter
               cg_iters, cg_tol, damping, tol_rot, tol_trans, _p(out), _p(cost), _p(trace), _p(status), _p(ws), nb, _stream())
     code, executed, _ = (int(v) for v in status.cpu())                  # the one host read (cost and trace ride behind it)
     return PoseGraphResult(out, float(cost.cpu()[0]), executed, code, trace.cpu())
+
+
+# ---- range images and virtual scans of a cloud from a sensor pose (csrc/range_image.hip) --------------------------------------
+RANGE_MAX_ROWS = 128
+RANGE_MAX_COLS = 4096
+RANGE_MAX_CELLS = 1 << 19           # rows x cols of a range image
+RANGE_MAX_WINDOW = 1024             # cells range_visible reads round one cell, after clipping to the image
+
+
+class RangeImage(collections.namedtuple("RangeImage", "index dist2 binned dropped outside")):
+    """range_image's result: index int32 [rows, cols] = per cell the input row nearest to the sensor, -1 where the cell is empty; dist2
+    float32 [rows, cols] = its squared distance, NaN where empty; binned = rows that fell into a cell, dropped = rows with a non-finite
+    coordinate before or after the pose, outside = finite rows out of range or out of the field of elevation.  The three sum to the
+    cloud's rows.  Image row 0 is the lowest elevation; column 0 starts at the x axis and the columns turn towards y."""
+
+
+class VirtualScan(collections.namedtuple("VirtualScan", "rows image visible")):
+    """virtual_scan's result: rows int64 [k] = the input row numbers of the visible winners, ascending; image = the RangeImage;
+    visible bool [rows, cols] = range_visible of it."""
+
+
+def _range_shape(who, rows, cols):
+    rows = _int_arg(who, "rows", rows, 1, RANGE_MAX_ROWS)
+    cols = _int_arg(who, "cols", cols, 4, RANGE_MAX_COLS)
+    if cols % 4 or rows * cols > RANGE_MAX_CELLS:
+        raise ValueError("%s: cols must be a multiple of 4 and rows x cols at most %d, got %d x %d" % (who, RANGE_MAX_CELLS, rows, cols))
+    return rows, cols
+
+
+def range_tables(rows, cols, elev_lo, elev_hi):
+    """The two tables cmr_range_image_f32 reads, computed in float64 and rounded to float32 (numpy): elev [rows + 1, 2] = (sign(tan e_j),
+    tan^2 e_j) of the edge angles e_j = elev_lo + (elev_hi - elev_lo) j / rows, col_dir [cols / 4 - 1, 2] = (cos, sin) of the column edges
+    inside the first quadrant (scan_tables' sector_dir).  Angles in radians, -pi/2 < elev_lo < elev_hi < pi/2."""
+    who = "range_tables"
+    rows, cols = _range_shape(who, rows, cols)
+    try:
+        lo, hi = float(elev_lo), float(elev_hi)
+        ok = not isinstance(elev_lo, bool) and not isinstance(elev_hi, bool) and -math.pi / 2 < lo < hi < math.pi / 2
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("%s: need -pi/2 < elev_lo < elev_hi < pi/2 in radians, got %r and %r" % (who, elev_lo, elev_hi))
+    t = np.tan(lo + (hi - lo) * np.arange(rows + 1, dtype=np.float64) / rows)
+    k = np.arange(1, cols // 4, dtype=np.float64) * (2.0 * np.pi / cols)
+    with np.errstate(over="ignore"):
+        elev = np.stack([np.sign(t), t * t], 1).astype(np.float32)
+    if not np.isfinite(elev).all():
+        raise ValueError("%s: tan^2 of an edge angle is not finite in float32; keep elev_lo and elev_hi away from +-pi/2, got %r and %r" % (who, elev_lo, elev_hi))
+    return elev, np.stack([np.cos(k), np.sin(k)], 1).astype(np.float32)
+
+
+def _range_ranges(who, min_range, max_range):
+    """-> (min_range2, max_range2): the squares formed in float64, with 0 < min_range2 < max_range2 < inf as float32"""
+    max_range = _cloud_scalar(max_range, "max_range")
+    min_range = _f32_arg(who, "min_range", min_range, "be a number in (0, max_range)", 0.0, lo_open=True, bools=False)
+    with np.errstate(over="ignore", under="ignore"):
+        lo2, hi2 = np.float32(min_range * min_range), np.float32(max_range * max_range)
+    if not np.isfinite(hi2):
+        raise ValueError("max_range must be a finite number > 0 whose square is finite in float32, got %r" % max_range)
+    if not 0.0 < lo2 < hi2:
+        raise ValueError("%s: min_range must be a number in (0, max_range), got %r with max_range %r" % (who, min_range, max_range))
+    return float(lo2), float(hi2)
+
+
+def range_image(points, pose=None, rows=64, cols=1024, elev_lo=-0.4363, elev_hi=0.0524, min_range=1.0, max_range=80.0):
+    """The range image of a cloud seen from a sensor (cmr_range_image_f32; the contract is the header's): a spherical z-buffer of `rows`
+    elevation rows between elev_lo and elev_hi (radians) and `cols` azimuth columns, each cell keeping the row nearest to the sensor among
+    those between min_range and max_range.  points float32 [N, 3]; pose float32 [4, 4] or None: the rows are moved by it first, in fp32 --
+    it maps the cloud's frame into the sensor's, whose origin is where the sensor stands.  -> RangeImage.  One host read: the three
+    counts.  N = 0 gives the empty image and no launch.  The defaults (a 64-beam sensor's field, 1 m to 80 m) are not tuned on real data."""
+    who = "range_image"
+    rows, cols = _range_shape(who, rows, cols)
+    elev, dirs = range_tables(rows, cols, elev_lo, elev_hi)
+    min2, max2 = _range_ranges(who, min_range, max_range)
+    points = _cloud_points(points)
+    N, dev = points.shape[0], points.device
+    pose = _cloud_pose(pose, dev, who)
+    index = torch.empty((rows, cols), dtype=torch.int32, device=dev)
+    dist2 = torch.empty((rows, cols), dtype=f32, device=dev)
+    if N == 0:
+        return RangeImage(index.fill_(-1), dist2.fill_(float("nan")), 0, 0, 0)
+    elev, dirs = torch.from_numpy(elev).to(dev), torch.from_numpy(dirs).to(dev)
+    counts = torch.empty((3,), dtype=torch.int64, device=dev)
+    nb = _lib.load().cmr_range_image_workspace_bytes(rows, cols)
+    ws = _ws(nb, dev)
+    _lib.call("cmr_range_image_f32", _p(points), 3, N, _p(pose), rows, cols, _p(elev), _p(dirs) if cols > 4 else None, min2, max2, _p(index),
+              _p(dist2), _p(counts), _p(ws), nb, _stream())
+    return RangeImage(index, dist2, *(int(v) for v in counts.cpu()))
+
+
+def _range_window(who, radius, rel_tol, rows, cols):
+    """-> (radius_rows, radius_cols, factor): the window's reach, clipped to the image, and fp32((1 + rel_tol)^2) formed in float64"""
+    try:
+        rr, rc = radius
+    except (TypeError, ValueError):
+        raise ValueError("%s: radius must be two integers (rows, cols), got %r" % (who, radius))
+    rr = min(_int_arg(who, "radius[0]", rr, 0, 1 << 30), rows)
+    rc = min(_int_arg(who, "radius[1]", rc, 0, 1 << 30), cols)
+    if min(2 * rr + 1, rows) * min(2 * rc + 1, cols) > RANGE_MAX_WINDOW:
+        raise ValueError("%s: the window of radius %r holds more than %d cells of a %d x %d image" % (who, tuple(radius), RANGE_MAX_WINDOW, rows, cols))
+    rel_tol = _f32_arg(who, "rel_tol", rel_tol, "be a finite number >= 0", as_f32=False, bools=False)
+    with np.errstate(over="ignore"):
+        factor = float(np.float32((1.0 + rel_tol) ** 2)) if rel_tol < 1e150 else math.inf
+    if not factor < math.inf:
+        raise ValueError("%s: rel_tol must be a finite number >= 0 with (1 + rel_tol)^2 finite in float32, got %r" % (who, rel_tol))
+    return rr, rc, factor
+
+
+def range_visible(dist2, radius=(1, 1), rel_tol=0.05):
+    """Which cells of a range image a sensor sees (cmr_range_visible_f32; the contract is the header's): a cell with a winner is visible
+    when its squared distance is at most (1 + rel_tol)^2 times the least one in the window of `radius` = (rows, cols) cells round it --
+    image rows clipped at the border, columns wrapped -- which stops far surfaces leaking through the gaps between near rows.  dist2
+    float32 [rows, cols] as range_image gives it (NaN = empty) -> bool [rows, cols].  radius (0, 0) keeps every winner.  The defaults are
+    not tuned on real data."""
+    who = "range_visible"
+    if not isinstance(dist2, torch.Tensor) or dist2.dtype != f32 or dist2.dim() != 2:
+        raise ValueError("%s: dist2 must be a float32 [rows, cols] tensor, got %s %s" % ((who,) + _got(dist2)))
+    rows, cols = _range_shape(who, dist2.shape[0], dist2.shape[1])
+    rr, rc, factor = _range_window(who, radius, rel_tol, rows, cols)
+    if not dist2.is_cuda:
+        raise ValueError("%s: dist2 must be a device tensor (there is no CPU path)" % who)
+    dist2 = dist2.contiguous()
+    visible = torch.empty((rows, cols), dtype=torch.uint8, device=dist2.device)
+    _lib.call("cmr_range_visible_f32", _p(dist2), rows, cols, rr, rc, factor, _p(visible), _stream())
+    return visible.view(torch.bool)
+
+
+def virtual_scan(points, pose=None, rows=64, cols=1024, elev_lo=-0.4363, elev_hi=0.0524, min_range=1.0, max_range=80.0, radius=(1, 1),
+                 rel_tol=0.05):
+    """What a spinning LiDAR standing at `pose` would see of a cloud: range_image, then range_visible of it, then the visible winners'
+    row numbers in ascending order (torch glue over the two ops) -> VirtualScan.  It depends on where the sensor stands, not on its heading,
+    save for which rows sit on a cell edge.  Arguments as the two ops'; every default is untuned on real data."""
+    who = "virtual_scan"
+    rows, cols = _range_shape(who, rows, cols)
+    _range_window(who, radius, rel_tol, rows, cols)                     # ahead of the first launch
+    image = range_image(points, pose, rows, cols, elev_lo, elev_hi, min_range, max_range)
+    if image.binned == 0:                                               # an empty image: nothing is visible, and no second launch
+        return VirtualScan(torch.empty((0,), dtype=torch.int64, device=image.index.device), image, torch.zeros_like(image.index, dtype=torch.bool))
+    visible = range_visible(image.dist2, radius, rel_tol)
+    return VirtualScan(torch.sort(image.index[visible].to(torch.int64)).values, image, visible)

@@ -1,6 +1,8 @@
 """Command-line helpers shared by Test_Geo.py and Test_Agent.py: the round lists of --guided / --refine, the --visible flags, the --paint flags
 with the per-pair PLY output, the --dense-depth flags with the per-pair PFM output, the surfel flags that extend --dense-depth and --visible,
 the --verify-mi flags, the --from-raw flag, and the closing recall block."""
+import os
+
 import numpy as np
 
 
@@ -214,6 +216,23 @@ def raw_option(ap, args):
     if not args.data_root:
         ap.error("--from-raw reads raw scans of real frames: give --data-root as well (synthetic pairs have no files)")
     return dict(from_raw=True)
+
+
+def add_pc_subdir_flag(ap):
+    """--pc-subdir: the loader reads another cloud folder of every sequence (FrameDataset(..., pc_subdir=NAME))."""
+    ap.add_argument('--pc-subdir', default=None, metavar='NAME', help="with --data-root: read the clouds from <seq>/NAME instead of the prepared "
+                    "folder, e.g. the views of a map that python -m cmr_agent_amd.dataset.view wrote")
+
+
+def pc_subdir_option(ap, args):
+    """-> the keyword arguments --pc-subdir adds to FrameDataset; ap.error on a misplaced flag."""
+    if args.pc_subdir is None:
+        return {}
+    if not args.data_root:
+        ap.error("--pc-subdir names a cloud folder of real frames: give --data-root as well (synthetic pairs have no files)")
+    if not args.pc_subdir or os.path.basename(args.pc_subdir) != args.pc_subdir or args.pc_subdir in (".", ".."):
+        ap.error("--pc-subdir must be a folder name, got %r" % args.pc_subdir)
+    return dict(pc_subdir=args.pc_subdir)
 
 
 def print_mi(names, values, chosen):

@@ -326,6 +326,11 @@ WORK = {
         (a["iters"] + 1) * 600.0 * a["E"] + a["iters"] * (700.0 * a["F"] + a["cg_iters"] * (168.0 * a["E"] + 100.0 * a["F"])),
         (a["iters"] + 1) * a["E"] * (400 + 27 * 8) + a["iters"] * (a["E"] * 2 * 27 * 8 + a["F"] * 40 * 8
                                                                    + a["cg_iters"] * (a["E"] * 2 * 33 * 8 + a["F"] * 20 * 8))),
+    # DESIGN.md 4an.  Range image: latency-class, a row read (12 B; most rows of a map fail the range test and cost no more), the packed
+    # image written, read and unpacked (8 + 8 + 8 B per cell); comparisons, searches and atomics are not counted.  Visible: a cell's
+    # window is read from cache, so one read of the image and one byte out per cell; the window's comparisons are not counted.
+    "cmr_range_image_f32": lambda a: (0, a["N"] * 12 + a["rows"] * a["cols"] * 24),
+    "cmr_range_visible_f32": lambda a: (0, a["rows"] * a["cols"] * 5),
 }
 
 # Multiplies the kernel ISSUES on the matrix cores per algorithmic multiply: F(2x2,3x3) Winograd computes 2x2 outputs with 16

@@ -1678,6 +1678,52 @@ int cmr_pose_graph_optimize_f64(const double* poses_in, int64_t F, const int32_t
                                 int cg_iters, double cg_tol, double damping, double tol_rot, double tol_trans, double* poses, double* cost,
                                 double* trace, int32_t* status, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+/* ---- range images and virtual scans of a cloud from a sensor pose (csrc/range_image.hip) ---------------------------------
+ * Port extension: what a spinning LiDAR standing at a pose would see of a cloud, as a spherical z-buffer.  Every integer follows from
+ * stated fp32 operations: no atan2, no sqrt, and every operation below is rounded on its own (no fused operation).  1 <= rows <= 128,
+ * 4 <= cols <= 4096, cols % 4 = 0, rows cols <= 2^19; any other shape returns CMR_EUNSUPPORTED (-3).  The library keeps no state.
+ *
+ * cmr_range_image_f32: points [N][ld >= 3], 0 < N < 2^31; pose float [4][4] row-major or null -> index int32 [rows][cols] (-1 where
+ * empty), dist2 float [rows][cols] (the quiet NaN 0x7fc00000 where empty) and counts int64 [3] = {binned, dropped, outside}, which sum to
+ * N.  min_range2 and max_range2 are the squared ranges, 0 < min_range2 < max_range2 < inf.  Two device tables, which the caller computes in
+ * fp64 and rounds to fp32 (R = rows, C = cols):
+ *   elev     float [R + 1][2]:     elev[j] = (s_j, q_j) = (sign(tan e_j) as -1, 0 or 1, tan^2 e_j) of the edge angle
+ *                                  e_j = elev_lo + (elev_hi - elev_lo) j / R,  -pi/2 < elev_lo < elev_hi < pi/2;
+ *   col_dir  float [C / 4 - 1][2]: col_dir[k - 1] = (c_k, s_k) = (cos, sin)(k 2 pi / C), k = 1 .. C / 4 - 1 (may be null when C = 4).
+ * Per row (px, py, pz):
+ *   pose      with a pose, (x, y, z) = R p + t as the cloud kernels move a row:  x = fp32(fp32(fp32(fp32(R00 px) + fp32(R01 py)) +
+ *             fp32(R02 pz)) + t0), y and z alike;  without one, (x, y, z) = (px, py, pz);
+ *   dropped   a coordinate that is not finite, before or after the pose;
+ *   range     xx = fp32(x x), yy = fp32(y y), zz = fp32(z z), r2 = fp32(xx + yy), d2 = fp32(r2 + zz);  the row is OUTSIDE when
+ *             d2 < min_range2 or d2 >= max_range2 (an infinite d2 is).  This test comes before any table is read;
+ *   above(j)  "the elevation is at or above e_j", with rhs = fp32(r2 q_j):   s_j > 0:  z >= 0 and zz >= rhs;   s_j = 0:  z >= 0;
+ *             s_j < 0:  z >= 0 or zz <= rhs;
+ *   row       the row is OUTSIDE when above(0) fails or above(R) holds;  otherwise its image row is the number of j in 1 .. R - 1 for
+ *             which above(j) holds: image row 0 is the lowest elevation;
+ *   column    (u, v) and the quadrant q of (x, y) exactly as cmr_scan_descriptor_f32 takes them, x = y = 0 included;  m = the number of k
+ *             in 1 .. C / 4 - 1 with fp32(v c_k) >= fp32(u s_k);  the column is q C / 4 + m;
+ *   binned    every row that is neither dropped nor outside falls into the cell (image row, column).
+ * A cell's winner is its binned row with the least d2, the lowest input row on equal d2: a 64-bit unsigned atomic minimum of
+ * (bits of d2) << 32 | row, the bits of a float above 0 ordering like the float, over an image initialised to all ones; the counts are
+ * integer atomic sums.  All of it is order free: two calls agree bit for bit, whatever the launch shape.  Both families of comparisons
+ * are monotone in the table index for tables made as above (an fp32 product is monotone in each factor, q_j and c_k descend where they
+ * are used, s_k ascends, u, v >= 0), so the kernel finds the two counts by binary search; either way they are bounded by R - 1 and
+ * C / 4 - 1 whatever the rows and the tables hold, and no store leaves index, dist2, counts and the workspace.
+ * Workspace of cmr_range_image_workspace_bytes(rows, cols) = 8 rows cols bytes (the packed image; 0 for a shape not served), 16-byte aligned.
+ *
+ * cmr_range_visible_f32: dist2 float [rows][cols] as above -> visible uint8 [rows][cols].  A cell that has a winner is visible iff
+ * d2 <= fp32(m2 factor), m2 = the least dist2 over the cells (r + dr, (c + dc) mod cols) with |dr| <= radius_rows, |dc| <= radius_cols:
+ * image rows are clipped at the border, columns wrap, empty cells (NaN) are passed over and the cell itself is included.  An empty cell is
+ * not visible.  factor = fp32((1 + rel_tol)^2), formed by the caller in fp64, finite and >= 1.  The window a cell reads, after clipping
+ * (min(2 radius_rows + 1, rows) rows of min(2 radius_cols + 1, cols) columns), holds at most 1024 cells.  One cell per thread, plain
+ * stores by the owner. */
+int64_t cmr_range_image_workspace_bytes(int rows, int cols);
+int cmr_range_image_f32(const float* points, int64_t ld, int64_t N, const float* pose, int rows, int cols, const float* elev,
+                        const float* col_dir, float min_range2, float max_range2, int32_t* index, float* dist2, int64_t* counts,
+                        void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int cmr_range_visible_f32(const float* dist2, int rows, int cols, int radius_rows, int radius_cols, float factor, uint8_t* visible,
+                          hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

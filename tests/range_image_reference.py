@@ -1,0 +1,292 @@
+"""numpy restatement of the range image and its visibility test (csrc/range_image.hip), written from include/cmr_hip.h:
+every operation on float32 arrays, so every product and sum is rounded on its own, in the order the header states; the image row and the
+column are the COUNTS of comparisons the header states (the kernel finds them by binary search).  The kernels are compared with it
+EXACTLY: index, counts and visible as integers, dist2 as bits.
+
+Also here: the same two integers by the search, an independent float64 statement of the cells (arctan2, arctan, floor) with the rows
+near a cell edge flagged, the ops' interface on the restatement (CPU stand-ins for tests of the file layer), the occlusion scene and the
+synthetic sequence the command is tested on."""
+import os
+
+import numpy as np
+
+F32 = np.float32
+BINNED, DROPPED, OUTSIDE = 0, 1, 2
+QUIET = dict(invalid="ignore", over="ignore", divide="ignore", under="ignore")
+DEFAULTS = dict(rows=64, cols=1024, elev_lo=-0.4363, elev_hi=0.0524, min_range=1.0, max_range=80.0)
+
+
+def tables(R, C, elev_lo, elev_hi):
+    """-> (elev float32 [R + 1, 2] = (sign(tan e_j), tan^2 e_j), col_dir float32 [C / 4 - 1, 2] = (cos, sin)), float64 rounded once"""
+    t = np.array([np.tan(elev_lo + (elev_hi - elev_lo) * j / R) for j in range(R + 1)], dtype=np.float64)
+    ang = np.array([k * 2.0 * np.pi / C for k in range(1, C // 4)], dtype=np.float64)
+    return np.stack([np.sign(t), t * t], 1).astype(F32), np.stack([np.cos(ang), np.sin(ang)], 1).astype(F32).reshape(-1, 2)
+
+
+def range2(min_range, max_range):
+    return F32(float(min_range) ** 2), F32(float(max_range) ** 2)
+
+
+def pose_apply(points, pose):
+    """q = R p + t as cmr_cloud_grid.h's pose_apply: fp32, every operation rounded on its own, left to right -> float32 [N, 3]"""
+    p = np.asarray(points, dtype=F32)
+    if pose is None:
+        return p[:, :3].copy()
+    T = np.asarray(pose, dtype=F32)
+    with np.errstate(**QUIET):
+        return np.stack([((T[r, 0] * p[:, 0] + T[r, 1] * p[:, 1]) + T[r, 2] * p[:, 2]) + T[r, 3] for r in range(3)], 1).astype(F32)
+
+
+def above(tab, j, z, zz, r2):
+    """elevation >= edge j, per row; j an int or an int array of the rows' shape"""
+    s, q = tab[j, 0], tab[j, 1]
+    with np.errstate(**QUIET):
+        rhs = (r2 * q).astype(F32)
+    return np.where(s > 0, (z >= 0) & (zz >= rhs), np.where(s < 0, (z >= 0) | (zz <= rhs), z >= 0))
+
+
+def quadrant(x, y):
+    q = np.zeros(x.shape, np.int64)
+    u, v = np.zeros_like(x), np.zeros_like(y)                          # x = y = 0 keeps q = 0, (0, 0)
+    for k, mask, uu, vv in ((0, (x > 0) & (y >= 0), x, y), (1, (x <= 0) & (y > 0), y, -x), (2, (x < 0) & (y <= 0), -x, -y),
+                            (3, (x >= 0) & (y < 0), -y, x)):
+        q[mask], u[mask], v[mask] = k, uu[mask], vv[mask]
+    return q, u, v
+
+
+def rows(points, R, C, pose=None, elev_lo=-0.4363, elev_hi=0.0524, min_range=1.0, max_range=80.0, search=False):
+    """Per row of points [N, >= 3]: -> dict(state, row, col, d2, xyz); row and col mean something where state is BINNED.  search=True
+    finds row and col by the kernel's binary searches instead of the counts."""
+    p = np.asarray(points, dtype=F32)
+    xyz = pose_apply(p, pose)
+    x, y, z = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    tab, dirs = tables(R, C, elev_lo, elev_hi)
+    lo2, hi2 = range2(min_range, max_range)
+    with np.errstate(**QUIET):
+        dropped = ~(np.isfinite(p[:, :3]).all(1) & np.isfinite(xyz).all(1))
+        xx, yy, zz = x * x, y * y, z * z
+        r2 = xx + yy
+        d2 = r2 + zz
+        outside = ~dropped & ((d2 < lo2) | (d2 >= hi2))
+        outside |= ~dropped & ~outside & (~above(tab, 0, z, zz, r2) | above(tab, R, z, zz, r2))
+        q, u, v = quadrant(x, y)
+        if search:
+            row, top = np.zeros(x.shape, np.int64), np.full(x.shape, R, np.int64)
+            while (top - row > 1).any():
+                mid = (row + top) >> 1
+                go, up = top - row > 1, above(tab, np.minimum(mid, R), z, zz, r2)
+                row, top = np.where(go & up, mid, row), np.where(go & ~up, mid, top)
+            m, end = np.zeros(x.shape, np.int64), np.full(x.shape, C // 4 - 1, np.int64)
+            while (m < end).any():
+                mid = np.minimum((m + end) >> 1, max(C // 4 - 2, 0))
+                go = m < end
+                holds = (v * dirs[mid, 0] >= u * dirs[mid, 1]) if len(dirs) else np.zeros(x.shape, bool)
+                m, end = np.where(go & holds, mid + 1, m), np.where(go & ~holds, mid, end)
+        else:
+            row = np.stack([above(tab, j, z, zz, r2) for j in range(1, R)], 1).sum(1) if R > 1 else np.zeros(x.shape, np.int64)
+            m = (v[:, None] * dirs[None, :, 0] >= u[:, None] * dirs[None, :, 1]).sum(1)
+    state = np.where(dropped, DROPPED, np.where(outside, OUTSIDE, BINNED))
+    return dict(state=state, row=row, col=q * (C // 4) + m, d2=d2.astype(F32), xyz=xyz)
+
+
+def image(points, R, C, pose=None, elev_lo=-0.4363, elev_hi=0.0524, min_range=1.0, max_range=80.0):
+    """-> (index int32 [R, C], dist2 float32 [R, C], (binned, dropped, outside))"""
+    w = rows(points, R, C, pose, elev_lo, elev_hi, min_range, max_range)
+    sel = np.flatnonzero(w["state"] == BINNED)
+    key = np.full(R * C, np.iinfo(np.uint64).max, np.uint64)
+    packed = (w["d2"][sel].view(np.uint32).astype(np.uint64) << np.uint64(32)) | sel.astype(np.uint64)
+    np.minimum.at(key, w["row"][sel] * C + w["col"][sel], packed)
+    empty = key == np.iinfo(np.uint64).max
+    index = np.where(empty, -1, (key & np.uint64(0xffffffff)).astype(np.int64)).astype(np.int32)
+    dist2 = np.where(empty, np.uint32(0x7fc00000), (key >> np.uint64(32)).astype(np.uint32)).astype(np.uint32).view(F32)
+    return index.reshape(R, C), dist2.reshape(R, C), tuple(int((w["state"] == s).sum()) for s in (BINNED, DROPPED, OUTSIDE))
+
+
+def factor(rel_tol):
+    return F32((1.0 + float(rel_tol)) ** 2)
+
+
+def visible(dist2, radius=(1, 1), rel_tol=0.05):
+    """dist2 float32 [R, C] -> bool [R, C]: a winner no farther than fp32(m2 factor), m2 the least dist2 of its window"""
+    d = np.asarray(dist2, dtype=F32)
+    R, C = d.shape
+    big = np.where(np.isnan(d), F32(np.inf), d)
+    m2 = np.full((R, C), F32(np.inf), F32)
+    rr, rc = min(radius[0], R), radius[1]
+    cols = range(C) if 2 * rc + 1 >= C else range(-rc, rc + 1)
+    for dr in range(-rr, rr + 1):
+        src = np.full((R, C), F32(np.inf), F32)
+        a, b = max(0, -dr), min(R, R - dr)                             # rows r with 0 <= r + dr < R
+        if a < b:
+            src[a:b] = big[a + dr:b + dr]
+        for dc in cols:
+            m2 = np.minimum(m2, np.roll(src, -dc, 1))                  # column c reads (c + dc) mod C
+    with np.errstate(**QUIET):
+        bound = (m2 * factor(rel_tol)).astype(F32)
+    return ~np.isnan(d) & (d <= bound)
+
+
+def virtual_scan(points, R, C, pose=None, radius=(1, 1), rel_tol=0.05, **kw):
+    """-> (rows int64 [k] ascending, index, dist2, counts, visible)"""
+    index, dist2, counts = image(points, R, C, pose, **kw)
+    vis = visible(dist2, radius, rel_tol)
+    return np.sort(index[vis].astype(np.int64)), index, dist2, counts, vis
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=F32).view(np.int32)
+
+
+# ---- the cells stated independently in float64 ------------------------------------------------------------------------------------------------
+def rows64(points, R, C, elev_lo=-0.4363, elev_hi=0.0524, min_range=1.0, max_range=80.0, margin=4 * 2.0 ** -10):
+    """image row = floor of the elevation's share of the field, column = floor of arctan2's share of the circle.  near = rows within
+    `margin` cell widths of a cell edge (either direction) or within that share of a range limit, and rows on the z axis, whose azimuth is
+    undefined: there the two statements may differ.  Finite rows only."""
+    p = np.asarray(points, dtype=F32).astype(np.float64)
+    rho = np.hypot(p[:, 0], p[:, 1])
+    d = np.sqrt(rho * rho + p[:, 2] ** 2)
+    el = np.arctan2(p[:, 2], rho)
+    fr = (el - elev_lo) / (elev_hi - elev_lo) * R
+    turn = np.mod(np.arctan2(p[:, 1], p[:, 0]), 2.0 * np.pi) / (2.0 * np.pi / C)
+    outside = (d < min_range) | (d >= max_range) | (fr < 0) | (fr >= R)
+    near = (np.abs(fr - np.round(fr)) <= margin) | (np.abs(turn - np.round(turn)) <= margin) | (rho == 0)
+    near |= (np.abs(d - min_range) <= margin * min_range) | (np.abs(d - max_range) <= margin * max_range)
+    return dict(state=np.where(outside, OUTSIDE, BINNED), row=np.clip(np.floor(fr), 0, R - 1).astype(np.int64),
+                col=np.floor(turn).astype(np.int64) % C, near=near)
+
+
+# ---- the ops' interface on the restatement (CPU stand-ins for tests of the file layer) -------------------------------------------------------
+def ops_range_image(points, pose=None, rows=64, cols=1024, elev_lo=-0.4363, elev_hi=0.0524, min_range=1.0, max_range=80.0):
+    import torch
+    from cmr_agent_amd import ops
+    index, dist2, counts = image(points.cpu().numpy(), rows, cols, None if pose is None else pose.cpu().numpy(), elev_lo, elev_hi, min_range,
+                                 max_range)
+    return ops.RangeImage(torch.from_numpy(index), torch.from_numpy(dist2), *counts)
+
+
+def ops_range_visible(dist2, radius=(1, 1), rel_tol=0.05):
+    import torch
+    return torch.from_numpy(visible(dist2.cpu().numpy(), radius, rel_tol))
+
+
+# ---- scenes ---------------------------------------------------------------------------------------------------------------------------------------
+def scene(N, seed=1):
+    """N rows with xy within +-60 m and z in [-8, 4], one of them no number from 16 rows on"""
+    rng = np.random.default_rng(seed)
+    pts = np.concatenate([rng.uniform(-60, 60, (1025, 2)), rng.uniform(-8, 4, (1025, 1))], 1).astype(F32)[:N]
+    if N >= 16:
+        pts[7, 1] = np.nan
+    return pts
+
+
+def a_pose(seed=0, shift=(3.0, -2.0, 0.5)):
+    """a non-trivial rigid pose, float32 [4, 4]: a rotation about a skew axis and a shift"""
+    rng = np.random.default_rng(seed)
+    axis = rng.normal(size=3)
+    axis /= np.linalg.norm(axis)
+    a = 0.7
+    K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+    T = np.eye(4)
+    T[:3, :3] = np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * K @ K
+    T[:3, 3] = shift
+    return T.astype(F32)
+
+
+OCCLUSION = dict(rows=32, cols=512, elev_lo=np.radians(-25.0), elev_hi=np.radians(15.0), min_range=1.0, max_range=80.0)
+
+
+def occlusion_scene():
+    """A near wall at x = 5 (y in [-4, 4), z in [-1.5, 1.0)) in front of a far wall at x = 20 (y in [-30, 30), z in [-1.5, 4.0)), both
+    on a 0.1 m lattice.  -> (points float32 [n, 3], near bool [n], hidden bool [n]): hidden = far rows whose ray to the sensor meets
+    x = 5 with |y| < 3.7 and z in (-1.4, 0.8), well inside the near wall."""
+    def wall(x, y0, y1, z0, z1):
+        y, z = np.meshgrid(np.arange(round((y1 - y0) * 10)) * 0.1 + y0, np.arange(round((z1 - z0) * 10)) * 0.1 + z0, indexing="ij")
+        return np.stack([np.full(y.size, x), y.ravel(), z.ravel()], 1)
+
+    a, b = wall(5.0, -4.0, 4.0, -1.5, 1.0), wall(20.0, -30.0, 30.0, -1.5, 4.0)
+    pts = np.concatenate([a, b]).astype(F32)
+    near = np.arange(len(pts)) < len(a)
+    at5 = pts.astype(np.float64) * (5.0 / 20.0)
+    hidden = ~near & (np.abs(at5[:, 1]) < 3.7) & (at5[:, 2] > -1.4) & (at5[:, 2] < 0.8)
+    return pts, near, hidden
+
+
+# ---- a synthetic sequence for the command: a box room seen from three positions -----------------------------------------------------------------
+VIEW = dict(rows=16, cols=128, elev_lo_deg=-30.0, elev_hi_deg=30.0, min_range=0.5, max_range=40.0, first=3)
+
+
+def room(seed=4, n=6000):
+    """-> the map float32 [7, n]: the walls, floor and ceiling of a 20 x 12 x 5 m room and a pillar in it, with unit normals and a reflectance"""
+    rng = np.random.default_rng(seed)
+    half = np.array([10.0, 6.0, 2.5])
+    face = rng.integers(0, 6, n)
+    p = rng.uniform(-1, 1, (n, 3)) * half
+    nrm = np.zeros((n, 3))
+    axis, sign = face // 2, np.where(face % 2 == 0, 1.0, -1.0)
+    p[np.arange(n), axis] = sign * half[axis]
+    nrm[np.arange(n), axis] = -sign
+    ang, zed = rng.uniform(0, 2 * np.pi, 800), rng.uniform(-2.5, 2.5, 800)
+    pillar = np.stack([3.0 + 0.5 * np.cos(ang), 1.0 + 0.5 * np.sin(ang), zed], 1)
+    pn = np.stack([np.cos(ang), np.sin(ang), np.zeros(800)], 1)
+    pts, nrm = np.concatenate([p, pillar]), np.concatenate([nrm, pn])
+    return np.concatenate([pts.T, rng.uniform(0, 1, (1, len(pts))), nrm.T]).astype(F32)
+
+
+def room_poses():
+    """float64 [3, 4, 4]: frame j in the map's frame -- three positions inside the room, turned about z"""
+    out = []
+    for a, t in ((0.0, (0.0, 0.0, 0.0)), (0.4, (1.5, -0.5, 0.1)), (-1.1, (-4.0, 2.0, -0.2))):
+        T = np.eye(4)
+        T[:2, :2] = [[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]]
+        T[:3, 3] = t
+        out.append(T)
+    return np.stack(out)
+
+
+def view_argv(root, *extra):
+    """Writes the room as a map, three poses and three (empty-shelled) prepared frames 3, 4, 5 under root once -> the command's arguments"""
+    from cmr_agent_amd.dataset import align, prepare
+    folder = os.path.join(root, "vel", "sequences", "09", prepare.subdir())
+    if not os.path.isdir(folder):
+        os.makedirs(folder)
+        for i in range(3):
+            np.save(os.path.join(folder, "%06d.npy" % (VIEW["first"] + i)), room()[:, :40 + i])
+        with open(os.path.join(root, "map.npy"), "wb") as fh:
+            np.save(fh, room())
+        align.write_poses(os.path.join(root, "poses.txt"), room_poses())
+    return ["--root", root, "--data-velodyne", "vel", "--sequence", "9", "--map", os.path.join(root, "map.npy"), "--poses",
+            os.path.join(root, "poses.txt"), "--rows", str(VIEW["rows"]), "--cols", str(VIEW["cols"]), "--elev-lo", str(VIEW["elev_lo_deg"]),
+            "--elev-hi", str(VIEW["elev_hi_deg"]), "--min-range", str(VIEW["min_range"]), "--max-range", str(VIEW["max_range"])] + list(extra)
+
+
+def inverse_pose(T):
+    """(R, t) -> (R^T, -R^T t) in float64, rounded to float32: the map's frame into frame j"""
+    T = np.asarray(T, dtype=np.float64)
+    inv = np.eye(4)
+    inv[:3, :3] = T[:3, :3].T
+    inv[:3, 3] = -T[:3, :3].T @ T[:3, 3]
+    return inv.astype(F32)
+
+
+def expected_view(j, radius=(1, 1), rel_tol=0.05):
+    """What the command writes for frame j of view_argv's files, by the restatement -> (float32 [4, k]: x, y, z, reflectance; normals
+    float64 [3, k] by the float64 rotation; counts)"""
+    cloud, inv = room(), inverse_pose(room_poses()[j])
+    kw = dict(elev_lo=np.radians(VIEW["elev_lo_deg"]), elev_hi=np.radians(VIEW["elev_hi_deg"]), min_range=VIEW["min_range"], max_range=VIEW["max_range"])
+    keep, _, _, counts, _ = virtual_scan(cloud[:3].T, VIEW["rows"], VIEW["cols"], inv, radius, rel_tol, **kw)
+    xyz = pose_apply(cloud[:3].T[keep], inv)
+    normals = inv[:3, :3].astype(np.float64) @ cloud[4:7, keep].astype(np.float64)
+    return np.concatenate([xyz.T, cloud[3:4, keep]]), normals, counts
+
+
+def check_view_files(root, subdir="map-view", radius=(1, 1), rel_tol=0.05):
+    """The three files of a run on view_argv's inputs against the restatement -> the rows per file"""
+    ks = []
+    for j in range(3):
+        got = np.load(os.path.join(root, "vel", "sequences", "09", subdir, "%06d.npy" % (VIEW["first"] + j)))
+        want, normals, _ = expected_view(j, radius, rel_tol)
+        assert got.dtype == F32 and got.shape == (7, want.shape[1]) and want.shape[1] > 200
+        assert np.array_equal(bits(got[:4]), bits(want))
+        assert np.abs(got[4:7].astype(np.float64) - normals).max() <= 2.0 ** -21
+        ks.append(got.shape[1])
+    return ks
