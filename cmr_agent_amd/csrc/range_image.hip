@@ -2,25 +2,25 @@
 // include/cmr_hip.h so that every integer follows from stated fp32 operations -- no atan2, no sqrt, no fused multiply-add.
 //
 //   range_fill_kernel      the packed image = all ones and the three counts = 0, one 64-bit word per lane
-//   range_scatter_kernel   1 024 rows per workgroup, one row per lane and pass: the pose step, the squares and the range test first (a row
-//                          out of range costs its load and three products), then the image row and the column by binary search in the two
-//                          tables (LDS, 9 KiB) -- the comparisons are monotone in the table index, so the search gives the counts the
-//                          header states -- and the winner by ONE 64-bit unsigned atomic min on (bits(d2) << 32 | row index), skipped when
-//                          a plain load of the cell already shows a key at or below the lane's (a cell only ever decreases); the three
-//                          counts by per-wave shuffle sums and at most one integer atomic add per workgroup and count
+//   range_scatter_kernel   1 024 rows per workgroup, one row per lane and pass, the pose loaded once ahead of the passes: the row's intake
+//                          (cmr_scan_rows.h), the squares and the range test first (a row out of range costs its load and three
+//                          products), then the image row by binary search in its table and the column as cmr_scan_rows.h's azimuth bin
+//                          (both tables in LDS, 9 KiB) -- the comparisons are monotone in the table index, so a search gives the count
+//                          the header states -- and the winner by ONE 64-bit unsigned atomic min on (bits(d2) << 32 | row index), skipped
+//                          when a plain load of the cell already shows a key at or below the lane's (a cell only ever decreases); the
+//                          three counts by cmr_scan_rows.h's shuffle sums and at most one integer atomic add per workgroup and count
 //   range_unpack_kernel    index and dist2 of a packed cell, one cell per lane
 //   range_visible_kernel   the windowed minimum of dist2 round a cell and the test against it, one cell per lane, plain stores
 // A minimum of packed integers and an integer sum are order free, and every other output is a plain store by its owner: two calls agree
 // bit for bit.  The image row is the lower end of a search interval inside [0, R] that never reaches R, the column q C / 4 + m with
 // q <= 3 and m the lower end of a search over [0, C / 4 - 1], so the cell lies in [0, R C) whatever the rows and the tables hold; the
 // window of the visible kernel is clipped to [0, R) and wrapped into [0, C): no store and no load leaves the arrays.
-#include "cmr_cloud_grid.h"
+#include "cmr_scan_rows.h"
 
 #include <math.h>
 
 namespace {
 
-constexpr int64_t ROW_LIMIT = (int64_t)1 << 31;
 constexpr int MAX_ROWS = 128, MAX_COLS = 4096, MAX_CELLS = 1 << 19;
 constexpr int MAX_WINDOW = 1024;                                  // cells the visible kernel reads per cell at most
 constexpr int SCATTER_ROWS = 1024;                                // rows per workgroup of the scatter kernel: four per lane
@@ -56,10 +56,7 @@ __global__ __launch_bounds__(256) void range_scatter_kernel(const float* __restr
     elev[j][0] = elev_tab[2 * j];
     elev[j][1] = elev_tab[2 * j + 1];
   }
-  for (int k = threadIdx.x; k < quarter - 1; k += 256) {
-    dirs[k][0] = col_dir[2 * k];
-    dirs[k][1] = col_dir[2 * k + 1];
-  }
+  azimuth_load(col_dir, quarter, dirs);
   float T[12];
   if (pose) pose_load(pose, T);
   __syncthreads();
@@ -68,15 +65,8 @@ __global__ __launch_bounds__(256) void range_scatter_kernel(const float* __restr
   for (int p = 0; p < SCATTER_ROWS / 256; ++p) {
     const int64_t i = first + p * 256 + threadIdx.x;
     if (i >= N) break;
-    float x = pts[i * ld], y = pts[i * ld + 1], z = pts[i * ld + 2];
-    bool finite = cmr_finite3(x, y, z);
-    if (pose) {
-      float qx, qy, qz;
-      pose_apply(T, x, y, z, qx, qy, qz);
-      x = qx, y = qy, z = qz;
-      finite = finite && cmr_finite3(x, y, z);
-    }
-    if (!finite) {
+    float x, y, z;
+    if (!scan_row(pts, ld, i, pose != nullptr, T, x, y, z)) {
       ++dropped;
       continue;
     }
@@ -96,47 +86,11 @@ __global__ __launch_bounds__(256) void range_scatter_kernel(const float* __restr
       const int mid = (row + top) >> 1;
       if (above(elev[mid][0], elev[mid][1], z, zz, r2)) row = mid; else top = mid;
     }
-    int q;
-    float u, v;
-    if (x > 0.f && y >= 0.f) {
-      q = 0, u = x, v = y;
-    } else if (x <= 0.f && y > 0.f) {
-      q = 1, u = y, v = -x;
-    } else if (x < 0.f && y <= 0.f) {
-      q = 2, u = -x, v = -y;
-    } else if (x >= 0.f && y < 0.f) {
-      q = 3, u = -y, v = x;
-    } else {
-      q = 0, u = 0.f, v = 0.f;                                    // x = y = 0
-    }
-    int m = 0, end = quarter - 1;                                 // the comparisons below m hold, those from `end` on do not
-    while (m < end) {
-      const int mid = (m + end) >> 1;
-      const float vc = v * dirs[mid][0], us = u * dirs[mid][1];
-      if (vc >= us) m = mid + 1; else end = mid;
-    }
-    const int cell = row * C + q * quarter + m;
+    const int cell = row * C + azimuth_bin(x, y, dirs, quarter);
     const unsigned long long key = (unsigned long long)__builtin_bit_cast(unsigned, d2) << 32 | (unsigned long long)i;      // d2 > 0: its bits order like it
     if (key < image[cell]) atomicMin(&image[cell], key);
   }
-  // the workgroup's counts: a sum per wave by shuffles, the four waves' by thread 0
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    dropped += __shfl_xor(dropped, o, 64);
-    outside += __shfl_xor(outside, o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    part[0][threadIdx.x >> 6] = dropped;
-    part[1][threadIdx.x >> 6] = outside;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int64_t rows = N - first < SCATTER_ROWS ? N - first : SCATTER_ROWS;
-    const int d = part[0][0] + part[0][1] + part[0][2] + part[0][3], o = part[1][0] + part[1][1] + part[1][2] + part[1][3];
-    if (rows - d - o) atomicAdd(&counts[0], (unsigned long long)(rows - d - o));
-    if (d) atomicAdd(&counts[1], (unsigned long long)d);
-    if (o) atomicAdd(&counts[2], (unsigned long long)o);
-  }
+  scan_counts_add(dropped, outside, (int)(N - first < SCATTER_ROWS ? N - first : SCATTER_ROWS), part, counts);
 }
 
 __global__ __launch_bounds__(256) void range_unpack_kernel(const unsigned long long* __restrict__ image, int cells, int32_t* __restrict__ index,

@@ -1,9 +1,10 @@
 // Place recognition between scans (port extension): Scan Context (Kim & Kim, IROS 2018) restated in include/cmr_hip.h so
 // that every integer follows from stated fp32 operations -- no atan2, no fused multiply-add.
 //
-//   scan_descriptor_kernel   1 024 rows per workgroup, one row per lane and pass: ring and sector as counts of comparisons against the two
-//                            tables (LDS), the value into the workgroup's image (LDS, <= 16 KiB) by integer atomic max, the image's
-//                            cells above 0 into desc by integer atomic max, the three counts by integer atomic add
+//   scan_descriptor_kernel   1 024 rows per workgroup, one row per lane and pass: the ring as a count of comparisons against its table, the
+//                            sector as cmr_scan_rows.h's azimuth bin (that count, by bisection; both tables in LDS), the value into the
+//                            workgroup's image (LDS, <= 16 KiB) by integer atomic max, the image's cells above 0 into desc by integer
+//                            atomic max, the three counts by cmr_scan_rows.h's integer atomic adds
 //   scan_unit_kernel         the unit columns of a batch of descriptors and their empty flags, one (descriptor, column) per lane
 //   scan_match_kernel        a tile of candidates (as many as 256 lanes hold shifts of, at most 16) stays in LDS while the workgroup walks
 //                            its queries four at a time: lane (candidate, shift) runs the S columns in order with the four queries'
@@ -12,16 +13,15 @@
 //                            loop; the S distances of a pair go through LDS to the one lane that takes the least in
 //                            shift order and stores it
 // A maximum and an integer sum are order free and every output of the match is a plain store by its owner: two calls agree bit for bit.
-// Ring and sector are counts of at most R - 1 and S / 4 - 1 true comparisons plus q S / 4 with q <= 3, so they lie in [0, R) and [0, S)
-// whatever the rows and the tables hold; a candidate index is below N and a query index below Q by the guards at the stores: no store
-// leaves desc, counts, dist and shift.
-#include "cmr_common.h"
+// The ring is a count of at most R - 1 true comparisons, the sector q S / 4 + m with q <= 3 and m the lower end of a search over
+// [0, S / 4 - 1], so they lie in [0, R) and [0, S) whatever the rows and the tables hold; a candidate index is below N and a query index
+// below Q by the guards at the stores: no store leaves desc, counts, dist and shift.
+#include "cmr_scan_rows.h"
 
 #include <math.h>
 
 namespace {
 
-constexpr int64_t ROW_LIMIT = (int64_t)1 << 31;
 constexpr int MAX_RINGS = 64, MAX_SECTORS = 256, MAX_CELLS = 4096;
 constexpr int DESC_ROWS = 1024;                                   // rows per workgroup of the descriptor kernel: four per lane
 constexpr int QT = 4;                                             // queries a lane of the match kernel carries at once
@@ -42,18 +42,15 @@ __global__ __launch_bounds__(256) void scan_descriptor_kernel(const float* __res
   const int cells = R * S, quarter = S / 4;
   for (int c = threadIdx.x; c < cells; c += 256) image[c] = 0;
   for (int j = threadIdx.x; j <= R; j += 256) edge[j] = ring_edge2[j];
-  for (int k = threadIdx.x; k < quarter - 1; k += 256) {
-    dirs[k][0] = sector_dir[2 * k];
-    dirs[k][1] = sector_dir[2 * k + 1];
-  }
+  azimuth_load(sector_dir, quarter, dirs);
   __syncthreads();
   int dropped = 0, outside = 0;
   const int64_t first = (int64_t)blockIdx.x * DESC_ROWS;
   for (int p = 0; p < DESC_ROWS / 256; ++p) {
     const int64_t i = first + p * 256 + threadIdx.x;
     if (i >= N) break;
-    const float x = pts[i * ld], y = pts[i * ld + 1], z = pts[i * ld + 2];
-    if (!cmr_finite3(x, y, z)) {
+    float x, y, z;
+    if (!scan_row(pts, ld, i, x, y, z)) {
       ++dropped;
       continue;
     }
@@ -65,50 +62,16 @@ __global__ __launch_bounds__(256) void scan_descriptor_kernel(const float* __res
     }
     int ring = 0;
     for (int j = 1; j < R; ++j) ring += r2 >= edge[j] ? 1 : 0;
-    int q;
-    float u, v;
-    if (x > 0.f && y >= 0.f) {
-      q = 0, u = x, v = y;
-    } else if (x <= 0.f && y > 0.f) {
-      q = 1, u = y, v = -x;
-    } else if (x < 0.f && y <= 0.f) {
-      q = 2, u = -x, v = -y;
-    } else if (x >= 0.f && y < 0.f) {
-      q = 3, u = -y, v = x;
-    } else {
-      q = 0, u = 0.f, v = 0.f;                                    // x = y = 0
-    }
-    int m = 0;
-    for (int k = 0; k < quarter - 1; ++k) {
-      const float vc = v * dirs[k][0], us = u * dirs[k][1];
-      m += vc >= us ? 1 : 0;
-    }
+    const int sector = azimuth_bin(x, y, dirs, quarter);
     const float value = z + height;
-    if (value > 0.f) atomicMax(&image[ring * S + q * quarter + m], __builtin_bit_cast(int, value));      // bits of floats > 0 order like ints
+    if (value > 0.f) atomicMax(&image[ring * S + sector], __builtin_bit_cast(int, value));      // bits of floats > 0 order like ints
   }
   __syncthreads();
   for (int c = threadIdx.x; c < cells; c += 256) {
     const int v = image[c];
     if (v > 0) atomicMax(&desc[c], v);
   }
-  // the workgroup's counts: a sum per wave by shuffles, the four waves' by thread 0
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    dropped += __shfl_xor(dropped, o, 64);
-    outside += __shfl_xor(outside, o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    part[0][threadIdx.x >> 6] = dropped;
-    part[1][threadIdx.x >> 6] = outside;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int64_t rows = N - first < DESC_ROWS ? N - first : DESC_ROWS;
-    const int d = part[0][0] + part[0][1] + part[0][2] + part[0][3], o = part[1][0] + part[1][1] + part[1][2] + part[1][3];
-    atomicAdd(&counts[0], (unsigned long long)(rows - d - o));
-    if (d) atomicAdd(&counts[1], (unsigned long long)d);
-    if (o) atomicAdd(&counts[2], (unsigned long long)o);
-  }
+  scan_counts_add(dropped, outside, (int)(N - first < DESC_ROWS ? N - first : DESC_ROWS), part, counts);
 }
 
 // unit [D][R][S] and full [D][S] (1 = the column is not empty) of descriptors [D][R][S]

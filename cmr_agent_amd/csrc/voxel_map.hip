@@ -3,7 +3,8 @@
 // is a sorted unique key list; a scan becomes one too (the keys below, the caller's stable sort, cmr_segment_heads_i64 and
 // cmr_segment_reduce_f32, as for the voxel downsample), and the merge is two sorted unique lists in and one out.
 //
-//   cmr_voxel_map_keys_f32    one pass over the scan's rows: q = R p + t, the flags dropped / outside, the key, the moved row; their counts
+//   cmr_voxel_map_keys_f32    one pass over the scan's rows: the row's intake (cmr_scan_rows.h: q = R p + t, dropped or not), outside or
+//                             the key, the moved row; the two counts from the workgroups' packed flags (cmr_scan_rows.h)
 //   cmr_voxel_map_plan_i64    where every row of both sides goes: every scan voxel is located in the map's keys and every map row in the scan's
 //                             by binary search, keep / miss / hit flags, their exclusive prefix sums (the tile scan of cloud_prepare.hip), sizes
 //   (the caller reads the sizes back and allocates the new map)
@@ -11,6 +12,7 @@
 //                             a scan voxel the map lacks is copied in
 // No re-sort of the map, no atomics, plain stores; every float result follows from operations stated one by one in include/cmr_hip.h.
 #include "cmr_cloud_grid.h"
+#include "cmr_scan_rows.h"
 
 namespace {
 
@@ -18,7 +20,6 @@ constexpr int64_t KEY_DROPPED = -1;                             // a non-finite 
 constexpr int64_t KEY_OUTSIDE = -2;                             // finite, but off the grid on some axis; both sort in front of every cell
                                                                 // (a key takes all 63 bits: 2^63 - 1 is the last cell's)
 constexpr int SCAN_TILE = 1024;                                 // items per workgroup of the prefix sums: 256 threads x 4
-constexpr int64_t ROW_LIMIT = (int64_t)1 << 31;
 
 inline int64_t align16(int64_t bytes) { return (bytes + 15) & ~(int64_t)15; }
 
@@ -26,7 +27,7 @@ inline int64_t align16(int64_t bytes) { return (bytes + 15) & ~(int64_t)15; }
 // the cell of a coordinate, and whether the grid has it (grid_cell: the test is on the float)
 __device__ __forceinline__ bool cell_of(float x, float origin, float cell, int64_t& c) { return grid_cell(cell_coord(x, origin, cell), c); }
 
-// dropped rows in the low half of the word, outside rows in the high half: a workgroup has at most 256 of either
+// the moved row is stored whatever its key; the workgroup's flag word (cmr_scan_rows.h) goes to flag_counts_kernel<2, KEYS_FLAG_BITS, false>
 __global__ __launch_bounds__(256) void map_keys_kernel(const float* __restrict__ pts, int64_t ld, int64_t N, const float* __restrict__ pose,
                                                        float ox, float oy, float oz, float cell, int64_t* __restrict__ keys,
                                                        float* __restrict__ moved, int32_t* __restrict__ part) {
@@ -34,15 +35,10 @@ __global__ __launch_bounds__(256) void map_keys_kernel(const float* __restrict__
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   int flag = 0;
   if (i < N) {
-    const float px = pts[i * ld], py = pts[i * ld + 1], pz = pts[i * ld + 2];
-    float qx = px, qy = py, qz = pz;
-    if (pose) {
-      float T[12];
-      pose_load(pose, T);
-      pose_apply(T, px, py, pz, qx, qy, qz);
-    }
+    float T[12], qx, qy, qz;
+    if (pose) pose_load(pose, T);
     int64_t key = KEY_DROPPED;
-    if (cmr_finite3(px, py, pz) && cmr_finite3(qx, qy, qz)) {
+    if (scan_row(pts, ld, i, pose != nullptr, T, qx, qy, qz)) {
       int64_t cx, cy, cz;
       const bool ix = cell_of(qx, ox, cell, cx), iy = cell_of(qy, oy, cell, cy), iz = cell_of(qz, oz, cell, cz);
       key = ix && iy && iz ? pack_key(cx, cy, cz) : KEY_OUTSIDE;
@@ -51,33 +47,11 @@ __global__ __launch_bounds__(256) void map_keys_kernel(const float* __restrict__
     moved[i * 3] = qx;
     moved[i * 3 + 1] = qy;
     moved[i * 3 + 2] = qz;
-    flag = key == KEY_DROPPED ? 1 : key == KEY_OUTSIDE ? 1 << 16 : 0;
+    flag = key == KEY_DROPPED ? row_flag<KEYS_FLAG_BITS>(ROW_DROPPED) : key == KEY_OUTSIDE ? row_flag<KEYS_FLAG_BITS>(ROW_OUTSIDE) : 0;
   }
   int total;
   scan256(flag, buf, total);
   if (threadIdx.x == 0) part[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(256) void map_keys_count_kernel(const int32_t* __restrict__ part, int64_t blocks, int64_t* __restrict__ counts) {
-  __shared__ int64_t sh[2][256];
-  int64_t dropped = 0, outside = 0;
-  for (int64_t b = threadIdx.x; b < blocks; b += 256) {
-    dropped += part[b] & 0xFFFF;
-    outside += part[b] >> 16;
-  }
-  sh[0][threadIdx.x] = dropped;
-  sh[1][threadIdx.x] = outside;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) {
-      sh[0][threadIdx.x] += sh[0][threadIdx.x + off];
-      sh[1][threadIdx.x] += sh[1][threadIdx.x + off];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    counts[0] = sh[0][0];
-    counts[1] = sh[1][0];
-  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------- plan
@@ -275,7 +249,8 @@ extern "C" int cmr_voxel_map_keys_f32(const float* points, int64_t ld, int64_t N
   const unsigned blocks = blocks_of(N, 256);
   hipLaunchKernelGGL(map_keys_kernel, dim3(blocks), dim3(256), 0, stream, points, ld, N, pose, ox, oy, oz, voxel, keys, moved,
                      (int32_t*)workspace);
-  hipLaunchKernelGGL(map_keys_count_kernel, dim3(1), dim3(256), 0, stream, (const int32_t*)workspace, (int64_t)blocks, counts);
+  hipLaunchKernelGGL((flag_counts_kernel<2, KEYS_FLAG_BITS, false>), dim3(1), dim3(256), 0, stream, (const int32_t*)workspace, (int64_t)blocks, N,
+                     counts);
   return cmr_launch_status();
 }
 

@@ -7,16 +7,18 @@
 //                            build only; it measured slower): while a ray steps along x its (y, z) pair stands still, and the cells of one
 //                            pair are ONE run of the sorted keys -- the run behind the x cells the ray still has ahead of it is found once
 //                            per pair and searched alone
-//   map_rays_count_kernel    the per-workgroup flag totals -> counts, by one workgroup (as cmr_voxel_map_keys_f32 sums its two)
+// A row comes in by the operations cmr_scan_rows.h's scan_row states, written out here: the pose is loaded next to its use and the
+// sensor taken from its shift in one branch, and the intake function in its place -- the same walk loop, laid out otherwise by the
+// compiler -- measured 5 % slower.  The per-workgroup flag totals (that header's row_flag) become counts by its
+// flag_counts_kernel<3, RAYS_FLAG_BITS, true>, one workgroup, as cmr_voxel_map_keys_f32 sums its two.
 // crossed and hits are int32 sums by atomicAdd: order free, two calls agree exactly.  An index only ever comes out of a search over
 // [0, M) that found an equal key there, so no store leaves crossed[0, M), hits[0, M) and counts whatever keys are handed over.
 #include "cmr_cloud_grid.h"
+#include "cmr_scan_rows.h"
 
 namespace {
 
-constexpr int64_t ROW_LIMIT = (int64_t)1 << 31;
 constexpr int MAX_CELLS_LIMIT = 65536;                          // the longest walk a lane can be asked for: bounds every lane's loop
-constexpr int FLAG_DROPPED = 1, FLAG_OUTSIDE = 1 << 10, FLAG_LONG = 1 << 20;      // a workgroup has at most 256 of each: 10 bits apiece
 
 // one axis of a ray: the cell coordinates of its ends, the cells they lie in, the steps still to make
 struct RayAxis {
@@ -90,11 +92,11 @@ __global__ __launch_bounds__(256) void map_rays_kernel(const float* __restrict__
     }
     RayAxis x, y, z;
     if (!(cmr_finite3(px, py, pz) && cmr_finite3(qx, qy, qz))) {
-      flag = FLAG_DROPPED;
+      flag = row_flag<RAYS_FLAG_BITS>(ROW_DROPPED);
     } else if (!(ray_axis(sx, qx, ox, cell, x) & ray_axis(sy, qy, oy, cell, y) & ray_axis(sz, qz, oz, cell, z))) {
-      flag = FLAG_OUTSIDE;
+      flag = row_flag<RAYS_FLAG_BITS>(ROW_OUTSIDE);
     } else if (x.left + y.left + z.left > max_cells) {          // at most 3 (2^21 - 1): no overflow
-      flag = FLAG_LONG;
+      flag = row_flag<RAYS_FLAG_BITS>(ROW_LONG);
     } else {
       const int steps = x.left + y.left + z.left, lx = x.left, ly = y.left, lz = z.left;
       const int xlo = x.c < x.end ? x.c : x.end, xhi = x.c < x.end ? x.end : x.c;
@@ -137,32 +139,6 @@ __global__ __launch_bounds__(256) void map_rays_kernel(const float* __restrict__
   if (threadIdx.x == 0) part[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(256) void map_rays_count_kernel(const int32_t* __restrict__ part, int64_t blocks, int64_t N,
-                                                             int64_t* __restrict__ counts) {
-  __shared__ int64_t sh[3][256];
-  int64_t c[3] = {0, 0, 0};
-  for (int64_t b = threadIdx.x; b < blocks; b += 256) {
-#pragma unroll
-    for (int f = 0; f < 3; ++f) c[f] += part[b] >> (10 * f) & 0x3FF;
-  }
-#pragma unroll
-  for (int f = 0; f < 3; ++f) sh[f][threadIdx.x] = c[f];
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) {
-#pragma unroll
-      for (int f = 0; f < 3; ++f) sh[f][threadIdx.x] += sh[f][threadIdx.x + off];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    counts[0] = N - sh[0][0] - sh[1][0] - sh[2][0];               // cast
-    counts[1] = sh[0][0];
-    counts[2] = sh[1][0];
-    counts[3] = sh[2][0];
-  }
-}
-
 }  // namespace
 
 // The product library searches the whole list: on the scan of tools/voxel_map_rays_bench.py the run-restricted lookup measured 0.67 x
@@ -197,6 +173,7 @@ extern "C" int cmr_voxel_map_rays_f32(const int64_t* keys, int64_t M, float ox, 
 #endif
   hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, points, ld, N, pose, ox, oy, oz, voxel, keys, M, start_margin, end_margin,
                      max_cells, crossed, hits, (int32_t*)workspace);
-  hipLaunchKernelGGL(map_rays_count_kernel, dim3(1), dim3(256), 0, stream, (const int32_t*)workspace, (int64_t)blocks, N, counts);
+  hipLaunchKernelGGL((flag_counts_kernel<3, RAYS_FLAG_BITS, true>), dim3(1), dim3(256), 0, stream, (const int32_t*)workspace, (int64_t)blocks, N,
+                     counts);
   return cmr_launch_status();
 }

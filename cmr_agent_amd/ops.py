@@ -3206,20 +3206,32 @@ class ScanMatch(collections.namedtuple("ScanMatch", "dist shift")):
     lowest shift that reaches it; NaN and -1 where no shift counts and for every candidate at or beyond the query's limit."""
 
 
+def _azimuth_shape(who, names, shape, most):
+    """The shape of an image whose second axis goes round the circle in quarters (a scan descriptor, a range image): names = what the
+    caller calls the two axes, most = (the first axis', the second's, the cells') upper bounds -> the two as ints"""
+    a = _int_arg(who, names[0], shape[0], 1, most[0])
+    b = _int_arg(who, names[1], shape[1], 4, most[1])
+    if b % 4 or a * b > most[2]:
+        raise ValueError("%s: %s must be a multiple of 4 and %s x %s at most %d, got %d x %d" % (who, names[1], names[0], names[1], most[2], a, b))
+    return a, b
+
+
+def _azimuth_dirs(bins):
+    """float32 [bins / 4 - 1, 2] = (cos, sin) of the edges inside the first quadrant of a circle cut into `bins`, computed in float64 and
+    rounded: the table csrc/cmr_scan_rows.h bisects"""
+    k = np.arange(1, bins // 4, dtype=np.float64) * (2.0 * np.pi / bins)
+    return np.stack([np.cos(k), np.sin(k)], 1).astype(np.float32)
+
+
 def _scan_shape(who, rings, sectors):
-    rings = _int_arg(who, "rings", rings, 1, SCAN_MAX_RINGS)
-    sectors = _int_arg(who, "sectors", sectors, 4, SCAN_MAX_SECTORS)
-    if sectors % 4 or rings * sectors > SCAN_MAX_CELLS:
-        raise ValueError("%s: sectors must be a multiple of 4 and rings x sectors at most %d, got %d x %d" % (who, SCAN_MAX_CELLS, rings, sectors))
-    return rings, sectors
+    return _azimuth_shape(who, ("rings", "sectors"), (rings, sectors), (SCAN_MAX_RINGS, SCAN_MAX_SECTORS, SCAN_MAX_CELLS))
 
 
 def scan_tables(rings, sectors, min_range, max_range):
     """The two tables cmr_scan_descriptor_f32 reads, computed in float64 and rounded to float32 (numpy): ring_edge2 [rings + 1] = the squared
     ring edges, sector_dir [sectors / 4 - 1, 2] = (cos, sin) of the sector edges inside the first quadrant."""
     j = np.arange(rings + 1, dtype=np.float64)
-    k = np.arange(1, sectors // 4, dtype=np.float64) * (2.0 * np.pi / sectors)
-    return ((min_range + (max_range - min_range) * j / rings) ** 2).astype(np.float32), np.stack([np.cos(k), np.sin(k)], 1).astype(np.float32)
+    return ((min_range + (max_range - min_range) * j / rings) ** 2).astype(np.float32), _azimuth_dirs(sectors)
 
 
 def scan_descriptor(points, rings=20, sectors=60, max_range=80.0, min_range=0.0, height=2.0):
@@ -3465,11 +3477,7 @@ class VirtualScan(collections.namedtuple("VirtualScan", "rows image visible")):
 
 
 def _range_shape(who, rows, cols):
-    rows = _int_arg(who, "rows", rows, 1, RANGE_MAX_ROWS)
-    cols = _int_arg(who, "cols", cols, 4, RANGE_MAX_COLS)
-    if cols % 4 or rows * cols > RANGE_MAX_CELLS:
-        raise ValueError("%s: cols must be a multiple of 4 and rows x cols at most %d, got %d x %d" % (who, RANGE_MAX_CELLS, rows, cols))
-    return rows, cols
+    return _azimuth_shape(who, ("rows", "cols"), (rows, cols), (RANGE_MAX_ROWS, RANGE_MAX_COLS, RANGE_MAX_CELLS))
 
 
 def range_tables(rows, cols, elev_lo, elev_hi):
@@ -3486,12 +3494,11 @@ def range_tables(rows, cols, elev_lo, elev_hi):
     if not ok:
         raise ValueError("%s: need -pi/2 < elev_lo < elev_hi < pi/2 in radians, got %r and %r" % (who, elev_lo, elev_hi))
     t = np.tan(lo + (hi - lo) * np.arange(rows + 1, dtype=np.float64) / rows)
-    k = np.arange(1, cols // 4, dtype=np.float64) * (2.0 * np.pi / cols)
     with np.errstate(over="ignore"):
         elev = np.stack([np.sign(t), t * t], 1).astype(np.float32)
     if not np.isfinite(elev).all():
         raise ValueError("%s: tan^2 of an edge angle is not finite in float32; keep elev_lo and elev_hi away from +-pi/2, got %r and %r" % (who, elev_lo, elev_hi))
-    return elev, np.stack([np.cos(k), np.sin(k)], 1).astype(np.float32)
+    return elev, _azimuth_dirs(cols)
 
 
 def _range_ranges(who, min_range, max_range):

@@ -1592,13 +1592,17 @@ int cmr_voxel_map_rays_f32(const int64_t* keys, int64_t M, float ox, float oy, f
  *             is the number of j in 1 .. R - 1 with r2 >= ring_edge2[j];
  *   quadrant  (u, v) = the row turned into the first quadrant by exact swaps and negations:  q = 0: x > 0 and y >= 0, (x, y);
  *             q = 1: x <= 0 and y > 0, (y, -x);  q = 2: x < 0 and y <= 0, (-x, -y);  q = 3: x >= 0 and y < 0, (-y, x);  x = y = 0: q = 0, (0, 0);
- *   sector    q S / 4 + m,  m = the number of k in 1 .. S / 4 - 1 with fp32(v c_k) >= fp32(u s_k);
+ *   sector    q S / 4 + m,  m = the number of k in 1 .. S / 4 - 1 with fp32(v c_k) >= fp32(u s_k); the value is that count, found by
+ *             binary search (below);
  *   value     fp32(z + height)  (height: the sensor's height above the ground, finite);
  *   binned    every row that is neither dropped nor outside.
  * A cell of desc holds the largest value over its binned rows, and 0 when none of them is above 0: desc is zeroed by the call, then an
  * integer atomic max of the values' bit patterns (those of floats above 0 order like integers), per workgroup in LDS and then into desc;
- * the counts are integer atomic sums.  All of it is order free: two calls agree bit for bit.  Ring and sector are counts of comparisons:
- * they lie in [0, R) and [0, S) whatever the rows and the tables hold, and no store leaves desc[0, R S) and counts[0, 3).
+ * the counts are integer atomic sums.  All of it is order free: two calls agree bit for bit.  The azimuth comparisons -- the sector's
+ * here, the column's of cmr_range_image_f32 -- are monotone in the table index for a table made as above (an fp32 product is monotone in
+ * each factor, c_k descends, s_k ascends, u, v >= 0): those that hold are the first m, so both entry points find m by bisecting the table
+ * (csrc/cmr_scan_rows.h) instead of counting.  The ring is a count of at most R - 1 comparisons and m the lower end of a search over
+ * [0, S / 4 - 1]: they lie in [0, R) and [0, S) whatever the rows and the tables hold, and no store leaves desc[0, R S) and counts[0, 3).
  *
  * cmr_scan_match_f32: queries float [Q][R][S] against cands float [N][R][S] (0 < Q, N < 2^31; values taken as finite) -> dist float [Q][N],
  * shift int32 [Q][N].  limit int32 [Q] or null: query q is compared with the candidates [0, limit[q]) only, 0 <= limit[q] <= N (null: all N;
@@ -1705,10 +1709,11 @@ int cmr_pose_graph_optimize_f64(const double* poses_in, int64_t F, const int32_t
  *   binned    every row that is neither dropped nor outside falls into the cell (image row, column).
  * A cell's winner is its binned row with the least d2, the lowest input row on equal d2: a 64-bit unsigned atomic minimum of
  * (bits of d2) << 32 | row, the bits of a float above 0 ordering like the float, over an image initialised to all ones; the counts are
- * integer atomic sums.  All of it is order free: two calls agree bit for bit, whatever the launch shape.  Both families of comparisons
- * are monotone in the table index for tables made as above (an fp32 product is monotone in each factor, q_j and c_k descend where they
- * are used, s_k ascends, u, v >= 0), so the kernel finds the two counts by binary search; either way they are bounded by R - 1 and
- * C / 4 - 1 whatever the rows and the tables hold, and no store leaves index, dist2, counts and the workspace.
+ * integer atomic sums.  All of it is order free: two calls agree bit for bit, whatever the launch shape.  The column's comparisons are
+ * monotone in the table index as cmr_scan_descriptor_f32's paragraph argues, and so are above(j) for a table made as above (an fp32
+ * product is monotone in each factor, q_j descends where it is used), so the kernel finds the two counts by binary search; either way
+ * they are bounded by R - 1 and C / 4 - 1 whatever the rows and the tables hold, and no store leaves index, dist2, counts and the
+ * workspace.
  * Workspace of cmr_range_image_workspace_bytes(rows, cols) = 8 rows cols bytes (the packed image; 0 for a shape not served), 16-byte aligned.
  *
  * cmr_range_visible_f32: dist2 float [rows][cols] as above -> visible uint8 [rows][cols].  A cell that has a winner is visible iff

@@ -10,17 +10,16 @@ import os
 
 import numpy as np
 
-F32 = np.float32
-BINNED, DROPPED, OUTSIDE = 0, 1, 2
-QUIET = dict(invalid="ignore", over="ignore", divide="ignore", under="ignore")
+# the row states, the quadrant fold, the direction table and the column by count or by search are the scan descriptor's
+from scan_descriptor_reference import BINNED, DROPPED, F32, OUTSIDE, QUIET, bits, column, directions, quadrant  # noqa: F401
+
 DEFAULTS = dict(rows=64, cols=1024, elev_lo=-0.4363, elev_hi=0.0524, min_range=1.0, max_range=80.0)
 
 
 def tables(R, C, elev_lo, elev_hi):
     """-> (elev float32 [R + 1, 2] = (sign(tan e_j), tan^2 e_j), col_dir float32 [C / 4 - 1, 2] = (cos, sin)), float64 rounded once"""
     t = np.array([np.tan(elev_lo + (elev_hi - elev_lo) * j / R) for j in range(R + 1)], dtype=np.float64)
-    ang = np.array([k * 2.0 * np.pi / C for k in range(1, C // 4)], dtype=np.float64)
-    return np.stack([np.sign(t), t * t], 1).astype(F32), np.stack([np.cos(ang), np.sin(ang)], 1).astype(F32).reshape(-1, 2)
+    return np.stack([np.sign(t), t * t], 1).astype(F32), directions(C)
 
 
 def range2(min_range, max_range):
@@ -45,15 +44,6 @@ def above(tab, j, z, zz, r2):
     return np.where(s > 0, (z >= 0) & (zz >= rhs), np.where(s < 0, (z >= 0) | (zz <= rhs), z >= 0))
 
 
-def quadrant(x, y):
-    q = np.zeros(x.shape, np.int64)
-    u, v = np.zeros_like(x), np.zeros_like(y)                          # x = y = 0 keeps q = 0, (0, 0)
-    for k, mask, uu, vv in ((0, (x > 0) & (y >= 0), x, y), (1, (x <= 0) & (y > 0), y, -x), (2, (x < 0) & (y <= 0), -x, -y),
-                            (3, (x >= 0) & (y < 0), -y, x)):
-        q[mask], u[mask], v[mask] = k, uu[mask], vv[mask]
-    return q, u, v
-
-
 def rows(points, R, C, pose=None, elev_lo=-0.4363, elev_hi=0.0524, min_range=1.0, max_range=80.0, search=False):
     """Per row of points [N, >= 3]: -> dict(state, row, col, d2, xyz); row and col mean something where state is BINNED.  search=True
     finds row and col by the kernel's binary searches instead of the counts."""
@@ -69,24 +59,16 @@ def rows(points, R, C, pose=None, elev_lo=-0.4363, elev_hi=0.0524, min_range=1.0
         d2 = r2 + zz
         outside = ~dropped & ((d2 < lo2) | (d2 >= hi2))
         outside |= ~dropped & ~outside & (~above(tab, 0, z, zz, r2) | above(tab, R, z, zz, r2))
-        q, u, v = quadrant(x, y)
         if search:
             row, top = np.zeros(x.shape, np.int64), np.full(x.shape, R, np.int64)
             while (top - row > 1).any():
                 mid = (row + top) >> 1
                 go, up = top - row > 1, above(tab, np.minimum(mid, R), z, zz, r2)
                 row, top = np.where(go & up, mid, row), np.where(go & ~up, mid, top)
-            m, end = np.zeros(x.shape, np.int64), np.full(x.shape, C // 4 - 1, np.int64)
-            while (m < end).any():
-                mid = np.minimum((m + end) >> 1, max(C // 4 - 2, 0))
-                go = m < end
-                holds = (v * dirs[mid, 0] >= u * dirs[mid, 1]) if len(dirs) else np.zeros(x.shape, bool)
-                m, end = np.where(go & holds, mid + 1, m), np.where(go & ~holds, mid, end)
         else:
             row = np.stack([above(tab, j, z, zz, r2) for j in range(1, R)], 1).sum(1) if R > 1 else np.zeros(x.shape, np.int64)
-            m = (v[:, None] * dirs[None, :, 0] >= u[:, None] * dirs[None, :, 1]).sum(1)
     state = np.where(dropped, DROPPED, np.where(outside, OUTSIDE, BINNED))
-    return dict(state=state, row=row, col=q * (C // 4) + m, d2=d2.astype(F32), xyz=xyz)
+    return dict(state=state, row=row, col=column(x, y, dirs, search), d2=d2.astype(F32), xyz=xyz)
 
 
 def image(points, R, C, pose=None, elev_lo=-0.4363, elev_hi=0.0524, min_range=1.0, max_range=80.0):
@@ -131,10 +113,6 @@ def virtual_scan(points, R, C, pose=None, radius=(1, 1), rel_tol=0.05, **kw):
     index, dist2, counts = image(points, R, C, pose, **kw)
     vis = visible(dist2, radius, rel_tol)
     return np.sort(index[vis].astype(np.int64)), index, dist2, counts, vis
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=F32).view(np.int32)
 
 
 # ---- the cells stated independently in float64 ------------------------------------------------------------------------------------------------

@@ -13,15 +13,49 @@ BINNED, DROPPED, OUTSIDE = 0, 1, 2
 QUIET = dict(invalid="ignore", over="ignore", divide="ignore", under="ignore")
 
 
+def directions(bins):
+    """-> float32 [bins / 4 - 1, 2] = (cos, sin) of the edges inside the first quadrant of a circle cut into `bins`, float64 rounded once"""
+    ang = np.array([k * 2.0 * np.pi / bins for k in range(1, bins // 4)], dtype=np.float64)
+    return np.stack([np.cos(ang), np.sin(ang)], 1).astype(F32).reshape(-1, 2)
+
+
+def quadrant(x, y):
+    """-> (q, u, v): the quadrant of (x, y) and the direction turned into the first one, by exact swaps and negations"""
+    q = np.zeros(x.shape, np.int64)
+    u, v = np.zeros_like(x), np.zeros_like(y)                          # x = y = 0 keeps q = 0, (0, 0)
+    for k, mask, uu, vv in ((0, (x > 0) & (y >= 0), x, y), (1, (x <= 0) & (y > 0), y, -x), (2, (x < 0) & (y <= 0), -x, -y),
+                            (3, (x >= 0) & (y < 0), -y, x)):
+        q[mask], u[mask], v[mask] = k, uu[mask], vv[mask]
+    return q, u, v
+
+
+def column(x, y, dirs, search=False):
+    """The azimuth bin of every (x, y) on the table `dirs` of 4 (len(dirs) + 1) bins: q quarter + m, m the COUNT of table entries with
+    fp32(v c_k) >= fp32(u s_k) as the header states it, or with search=True the lower end of the kernels' bisection (csrc/cmr_scan_rows.h)."""
+    quarter = len(dirs) + 1
+    q, u, v = quadrant(x, y)
+    with np.errstate(**QUIET):
+        if search:
+            m, end = np.zeros(x.shape, np.int64), np.full(x.shape, quarter - 1, np.int64)
+            while (m < end).any():
+                go = m < end
+                mid = np.minimum((m + end) >> 1, quarter - 2)          # a row that is done may point past the table
+                holds = v * dirs[mid, 0] >= u * dirs[mid, 1]
+                m, end = np.where(go & holds, mid + 1, m), np.where(go & ~holds, mid, end)
+        else:
+            m = (v[:, None] * dirs[None, :, 0] >= u[:, None] * dirs[None, :, 1]).sum(1)
+    return q * quarter + m
+
+
 def tables(R, S, min_range, max_range):
     """-> (ring_edge2 float32 [R + 1], sector_dir float32 [S / 4 - 1, 2]), computed in float64 and rounded"""
     edge = np.array([(min_range + (max_range - min_range) * j / R) ** 2 for j in range(R + 1)], dtype=np.float64)
-    ang = np.array([k * 2.0 * np.pi / S for k in range(1, S // 4)], dtype=np.float64)
-    return edge.astype(F32), np.stack([np.cos(ang), np.sin(ang)], 1).astype(F32).reshape(-1, 2)
+    return edge.astype(F32), directions(S)
 
 
-def rows(points, R, S, min_range=0.0, max_range=80.0, height=2.0):
-    """Per row of points [N, >= 3]: -> dict(state, ring, sector, value); ring and sector mean something where state is BINNED."""
+def rows(points, R, S, min_range=0.0, max_range=80.0, height=2.0, search=False):
+    """Per row of points [N, >= 3]: -> dict(state, ring, sector, value); ring and sector mean something where state is BINNED.
+    search=True finds the sector by the kernel's bisection instead of the count."""
     p = np.asarray(points, dtype=F32)
     x, y, z = p[:, 0], p[:, 1], p[:, 2]
     e2, dirs = tables(R, S, min_range, max_range)
@@ -30,15 +64,30 @@ def rows(points, R, S, min_range=0.0, max_range=80.0, height=2.0):
         r2 = x * x + y * y                                             # float32 arrays: three roundings
         outside = ~dropped & ((r2 < e2[0]) | (r2 >= e2[R]))
         ring = (r2[:, None] >= e2[None, 1:R]).sum(1)
-        q = np.zeros(x.shape, np.int64)
-        u, v = np.zeros_like(x), np.zeros_like(y)                      # x = y = 0 keeps q = 0, (0, 0)
-        for k, mask, uu, vv in ((0, (x > 0) & (y >= 0), x, y), (1, (x <= 0) & (y > 0), y, -x), (2, (x < 0) & (y <= 0), -x, -y),
-                                (3, (x >= 0) & (y < 0), -y, x)):
-            q[mask], u[mask], v[mask] = k, uu[mask], vv[mask]
-        m = (v[:, None] * dirs[None, :, 0] >= u[:, None] * dirs[None, :, 1]).sum(1)
         value = z + F32(height)
     state = np.where(dropped, DROPPED, np.where(outside, OUTSIDE, BINNED))
-    return dict(state=state, ring=ring, sector=q * (S // 4) + m, value=value)
+    return dict(state=state, ring=ring, sector=column(x, y, dirs, search), value=value)
+
+
+@functools.lru_cache(maxsize=None)
+def planted(bins):
+    """Directions (x, y) float32 [n, 2] on which a bin of a circle cut into `bins` is decided: in every quadrant, every table direction
+    (c_k, s_k) scaled by 2^-20, 1 and 2^20, each also one ulp to either side in either coordinate; the four axes and the origin (with
+    zeros of both signs); rows with a subnormal coordinate; rows at 1e19, whose squares overflow.  Read only."""
+    first = []
+    for scale in (2.0 ** -20, 1.0, 2.0 ** 20):
+        d = directions(bins) * F32(scale)                              # a power of two: exact
+        c, s = d[:, 0], d[:, 1]
+        for cc, ss in ((c, s), (np.nextafter(c, F32(np.inf)), s), (np.nextafter(c, F32(0)), s), (c, np.nextafter(s, F32(np.inf))),
+                       (c, np.nextafter(s, F32(0)))):
+            first.append(np.stack([cc, ss], 1))
+    tiny, huge = F32(1e-45), F32(1e19)
+    first.append(np.array([(1, 0), (0, 0), (tiny, 1), (1, tiny), (tiny, tiny), (tiny, 0), (huge, huge), (huge, 1), (1, huge), (huge, tiny), (huge, 0)], F32))
+    uv = np.concatenate(first).astype(F32)
+    u, v = uv[:, 0], uv[:, 1]
+    out = np.concatenate([np.stack([u, v], 1), np.stack([-v, u], 1), np.stack([-u, -v], 1), np.stack([v, -u], 1)]).astype(F32)
+    out.setflags(write=False)
+    return out
 
 
 def describe(points, R, S, min_range=0.0, max_range=80.0, height=2.0):

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import cloud_icp_reference as I
+import range_image_reference as G
 import scan_descriptor_reference as D
 from cmr_agent_amd import _lib, ops
 from cmr_agent_amd.dataset import align, loops
@@ -49,6 +50,29 @@ def test_tables_are_float64_rounded_once():
     assert np.array_equal(a, e2) and np.array_equal(b, dirs) and a.dtype == b.dtype == F32
     a, b = ops.scan_tables(64, 64, 1.5, 33.3)
     assert np.array_equal(a, D.tables(64, 64, 1.5, 33.3)[0]) and np.array_equal(b, D.tables(64, 64, 1.5, 33.3)[1])
+
+
+# ---- the azimuth bin: the header states a count, the kernels bisect (csrc/cmr_scan_rows.h) ------------------------------------------------------
+@pytest.mark.parametrize("bins", list(range(4, 257, 4)) + [1024, 4096])
+def test_the_column_by_count_is_the_column_by_search(bins):
+    """On the rows where a bin is decided (D.planted: every table direction at three scales and one ulp round it, the axes, the origin,
+    subnormal coordinates, 1e19; all four quadrants) the two forms give the same integer, in the descriptor's restatement for every legal
+    sector count and in the range image's for its column counts.  An equality of integers, every row compared."""
+    xy = D.planted(bins)
+    pts = np.concatenate([xy, np.zeros((len(xy), 1), F32)], 1)
+    assert len(xy) == 4 * (15 * (bins // 4 - 1) + 11)
+    seen = set()
+    for a in range(0, len(pts), 4096):                                   # the count form holds rows x table entries at once
+        part = pts[a:a + 4096]
+        if bins <= 256:
+            count, search = (D.rows(part, 1, bins, 0.0, 2.0 ** 21, search=s)["sector"] for s in (False, True))
+            assert np.array_equal(count, search), np.flatnonzero(count != search)[:8] + a
+        if bins in (4, 8, 12, 1024, 4096):
+            count, search = (G.rows(part, 1, bins, search=s)["col"] for s in (False, True))
+            assert np.array_equal(count, search), np.flatnonzero(count != search)[:8] + a
+        assert count.min() >= 0 and count.max() < bins
+        seen.update(count.tolist())
+    assert len(seen) == bins                                             # the planted rows reach every bin
 
 
 # ---- exact properties --------------------------------------------------------------------------------------------------------------------------

@@ -57,6 +57,26 @@ def test_descriptor_sizes(N):
     describe(pts, 8, 24, min_range=3.0, max_range=22.5, height=0.25)
 
 
+@pytest.mark.parametrize("last", (1023, 1024, 1025))
+@pytest.mark.parametrize("R,S", ((1, 4), (2, 8), (3, 12), (16, 256)))
+def test_descriptor_sector_where_it_is_decided(R, S, last):
+    """The kernel bisects the sector; the restatement compared with it COUNTS, as the header states it.  The rows are D.planted(S) -- every
+    table direction at three scales and one ulp round it, the axes, the origin, subnormal and 1e19 coordinates, in all four quadrants --
+    standing above random filler, each with a z of its own that rises along the planted order, so that a planted row in a wrong sector
+    shows wherever it is the largest of the cell it left or of the cell it reached.  The shapes: no table, one entry, an odd
+    quarter, the largest quarter.  N = 1 023, 1 024 and 1 025 (for 256 sectors, whose planted rows alone are 3 824, 3 072 more): the last
+    workgroup one row short of full, full, and one row past."""
+    xy = D.planted(S)
+    N = -(-len(xy) // 1024) * 1024 - 1024 + last
+    rng = np.random.default_rng(S)
+    fill = rng.uniform(-1, 1, (N - len(xy), 2)) * 2.0 ** rng.integers(-20, 21, (N - len(xy), 1))
+    rising = 1.0 + 3.0 * np.arange(1, len(xy) + 1) / (len(xy) + 1)        # every planted row its own z: no two of them tie in a cell
+    pts = np.concatenate([np.concatenate([xy, fill]), np.concatenate([rising, rng.uniform(-3, 1, len(fill))])[:, None]], 1)
+    pts = pts.astype(F32)[rng.permutation(N)]
+    got = describe(pts, R, S, max_range=2.0 ** 21)
+    assert got.dropped == 0 and got.outside == 20 and got.desc[0].count_nonzero() == S      # outside: the five rows at 1e19 of each quadrant
+
+
 def test_descriptor_rows_on_the_axes_the_origin_and_the_edges():
     pts = F32([[1, 0, 0], [0, 1, 1], [-1, 0, 2], [0, -1, 3], [0, 0, 5]])
     got = describe(pts, 3, 4, 0.0, 10.0, 0.5)
